@@ -10,7 +10,17 @@ A step = one full frame: every rank traces its interleaved row strips with the p
 kernel (scene already resident in HBM), the tiles meet on rank 0 in ONE gather over RCCL, and
 rank 0 de-interleaves.  The frame is fixed while N grows, so scaling is "strong".
 Rank 0 prints one JSON line.  `value` = rays of all ranks / max-over-ranks wall time of the K
-timed steps.
+timed steps; `ms_per_step` = that wall time / K.
+
+A plain run is lean: it sets up, renders the view's first frame (its dispatch-order pre-pass and
+tile-cost measurement), warms up, times the K steps, writes its outputs if asked and prints the
+line.  Everything else below (`roofline`, the extras, config 3 / 4 / 5 blocks, `cpu_baseline`)
+runs only with --full; the --no-* options trim a --full run.
+
+    --dump-outputs DIR   after the timed steps, rank 0 writes the frame the last timed step returned
+                         (the de-interleaved [H, W, 4] f32 frame, 33 MB) as DIR/frame.npy.  The inputs
+                         are fixed by the arguments (scene seed, camera, random seed), so two builds
+                         can be compared output for output.
 
 `roofline` names the resource that binds the trace kernel: the f32 vector pipes (VALU
 lane-cycles).  achieved = VALU instructions x average active lanes / kernel time, peak = 256 CUs
@@ -74,6 +84,9 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)   # the first ~7 frames after idle run 4 % slower (clock ramp)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure: roofline (live "
+                    "rocprofv3 --pmc passes), extras, config 3 / 4 / 5 blocks, CPU baseline; the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the frame of the last timed step as DIR/frame.npy (f32, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall-time target of the CPU baseline sample")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc pass (N = 1 only)")
@@ -235,8 +248,10 @@ def main():
             end_of_frame(tile)                  # the RCCL send / the copy kernel are done before `tile` is reused
             return st, frame
 
+        # the view's first frame (dispatch-order pre-pass, tile-cost measurement) runs before the warm-up, in the instantiation that
+        # counts the frame's work: the steady state of the timed steps does not depend on --full
         counted, frame = step(brt.FLAG_COUNTERS) if counters else (None, None)
-        if counted is not None and stub is None:
+        if counted is not None and stub is None and args.full:
             # lane-level iterations of the rejection sampler = active lanes summed over the executions of its section
             counted["ball_iterations"] = plugin.debug_profile()["ball"][1]
         for _ in range(warmup):
@@ -299,10 +314,12 @@ def main():
 
     head = run_workload(WORKLOAD, brt.SCENE_COVER, args.steps, args.warmup)
     W, H, spp = head["W"], head["H"], head["spp"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["frame"])
 
-    # ---- outside the timed region: what a frame costs when the view or the seed is new ----------------
+    # ---- outside the timed region (--full): what a frame costs when the view or the seed is new ----------------
     extras = {}
-    if not args.no_extras and stub is None:
+    if args.full and not args.no_extras and stub is None:
         step = head["step"]
         # (a) a new seed every frame, as the reference draws one (extract.rs:72-73); the dispatch order of the
         #     view is reused (it does not depend on the seed)
@@ -419,7 +436,7 @@ def main():
             except Exception as e:   # noqa: BLE001  (a measurement beside the contract line must never take it down)
                 extras["frames_in_flight"] = {"error": str(e)[:200]}
     cfg4 = None
-    if not args.no_extras and world > 1:
+    if args.full and not args.no_extras and world > 1:
         # config 2's longest pixel chains take ~5 ms whatever N is; BASELINE.json's own
         # multi-GPU config is 4K x 1024 spp, reported here beside the headline
         r4 = run_workload(WORKLOAD4, brt.SCENE_RTIOW_FINAL if stub is None else brt.SCENE_COVER, 2, 1, counters=False)
@@ -428,7 +445,7 @@ def main():
                 "steps": r4["steps"], "warmup": 1, "kernel_ms_per_rank": r4["kernel_ms_per_rank"], "gather_ms": r4["gather_ms"]}
 
     cfg_blocks = {}
-    if world == 1 and stub is None and not args.no_configs:
+    if args.full and world == 1 and stub is None and not args.no_configs:
         # BASELINE.json's other one-GPU configs under the driver's own run: a few frames each, kernel time from HIP events, own
         # counter pass for the roofline, sampled rows against the oracle (the -m gpu suite checks the WHOLE frames)
         for key, wl, kind, tag, name in (("config3", WORKLOAD3, brt.SCENE_RTIOW_FINAL, PMC_WORKLOAD3_TAG,
@@ -441,15 +458,18 @@ def main():
 
     if rank == 0:
         counted = head["counted"]
-        my_rows = int((frame_rows_of_part(H, 0, world) >= 0).sum())
-        alg = bytes_alg(counted, W, my_rows)
-        kernel_ms = max(head["kernel_ms_per_rank"])          # the slowest rank's kernel bounds the frame
-        roof = roofline_block(args, world, stub is not None, kernel_ms, alg, PMC_WORKLOAD_TAG, counted=counted, paths=W * H * spp)
+        roof = None
+        if args.full:
+            my_rows = int((frame_rows_of_part(H, 0, world) >= 0).sum())
+            alg = bytes_alg(counted, W, my_rows)
+            kernel_ms = max(head["kernel_ms_per_rank"])          # the slowest rank's kernel bounds the frame
+            roof = roofline_block(args, world, stub is not None, kernel_ms, alg, PMC_WORKLOAD_TAG, counted=counted, paths=W * H * spp)
         out = {
             "metric": "Mrays/s at 1920x1080, 64 spp, 8 bounces", "value": head["total_rays"] / head["elapsed"] / 1e6,
             "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": head["elapsed"] / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic" if stub is None else "synthetic (STUB tracer: no rays traced)",
+            "full": args.full,
             "config": {"workload": "README cover scene 1920x1080, 64 spp, 8 bounces (BASELINE.json configs[1])",
                        "spheres": int(len(head["buffers"].models)), "bvh_nodes": int(len(head["buffers"].bvh)),
                        "bvh": "built by the callee (brt_upload_scene without a BVH: binned SAH, INTEGRATION.md section 3); "
@@ -472,10 +492,11 @@ def main():
                              "submission": ("the K timed frames are enqueued on one stream (caller-stream form of brt_render_part_device, each followed by its "
                                             "gather / de-interleave), one synchronisation at the closing barrier; frames run one after the other, none overlaps "
                                             "(`frames_in_flight`)") if head["async_steps"] else "one synchronous call per frame (a host round trip each)"},
-            "roofline": roof,
             "kernel": {"lds_bytes": counted["lds_bytes"], "scene_in_lds": counted["scene_in_lds"],
                        "workgroups": counted["n_workgroups"], "threads": counted["threads_per_workgroup"]},
         }
+        if roof is not None:
+            out["roofline"] = roof
         out.update(extras)
         # both trees side by side in the contract's config block: `value` is measured in the tree the callee
         # builds; the same frame in the tree the reference's extract stage would hand over (PLOC, 0.1 pads):
@@ -497,7 +518,7 @@ def main():
                                               memory_side=(key == "config5")),
                    "sampled_rows_bit_exact": sampled_rows_exact(r)}
             out[key] = blk
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(head["buffers"], head["lvl"], head["cam"], head["win"], W, H, head["frame"],
                                                args.cpu_seconds, is_stub=stub is not None)
         print(json.dumps(out), flush=True)
@@ -508,6 +529,14 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     plugin.close()
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the de-interleaved frame, [H, W, 4] f32
+    (1920 x 1080 x 4 x 4 B = 33 MB, written whole) -- as out_dir/frame.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(frame.cpu().numpy(), dtype=np.float32))
 
 
 # ---- roofline ---------------------------------------------------------------------------------------------

@@ -6,12 +6,13 @@
 # Outputs under gpurun_out/TAG; copy the summaries into profiles/rNN afterwards.
 # A second argument selects a part (the whole takes ~20 minutes; a gpurun call is limited to 20):  pmc | rest | all (default)
 TAG=${1:-profiles}
+ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 PART=${2:-all}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != "rest" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -- python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-pmc --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -- python3 $ROOT/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-pmc --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
 find $OUT/ktrace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 rm -rf $OUT/ktrace
 cd $GRAFT_REPO_ROOT
@@ -38,7 +39,7 @@ PY
 fi
 cd $GRAFT_REPO_ROOT
 if [ "$PART" = "pmc" ]; then exit 0; fi
-python3 bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python3 bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 python3 scripts/run_configs.py > $OUT/configs.jsonl 2> $OUT/configs.err
 python3 scripts/gpu_time.py --reps 4 > $OUT/section_profile.txt 2>&1
 python3 scripts/gpu_time.py --scene 2 --reps 3 > $OUT/section_profile_config5.txt 2>&1

@@ -5,7 +5,7 @@
 TAG=${1:-r03}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python3 bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-pmc --no-extras > $OUT/bench.json 2> $OUT/bench.err &&
+python3 bench.py --full --steps 20 --warmup 10 --no-cpu-baseline --no-pmc --no-extras > $OUT/bench.json 2> $OUT/bench.err &&
 python3 scripts/gpu_parts.py > $OUT/parts_emulation.txt 2>&1 &&
 python3 scripts/run_configs.py 3 5 > $OUT/configs.jsonl 2> $OUT/configs.err &&
 python3 scripts/gpu_time.py --reps 4 > $OUT/section_profile.txt 2>&1

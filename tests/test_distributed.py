@@ -217,7 +217,7 @@ def _run_bench(extra_env, *argv):
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (the driver's command shape): the parent starts the
     two ranks itself (gloo + a stub tracer here), relays ONE JSON line and the line describes both ranks."""
-    out = _run_bench({}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1")
+    out = _run_bench({}, "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--full")
     assert out["n_gpus"] == 2 and out["n_ranks_seen"] == 2 and out["steps"] == 2
     assert out["scaling"] == "strong" and out["unit"] == "Mrays/s"
     assert len(out["kernel_ms_per_rank"]) == 2 and out["kernel_ms_per_rank"] == [1.0, 2.0]
@@ -238,10 +238,32 @@ def test_bench_launches_its_own_ranks():
 
 
 def test_bench_single_rank_line_has_the_contract_keys():
-    out = _run_bench({}, "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
+    out = _run_bench({}, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out, k
     assert out["n_gpus"] == 1 and out["n_ranks_seen"] == 1 and out["vs_baseline"] is None
     assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(out["roofline"])
     assert out["roofline"]["bound"] == "valu" and "workload" in out["config"] and "model" not in out["config"]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_the_last_frame(tmp_path, gpus):
+    """Without --full the line holds the headline figure only (no roofline, extras, config blocks or CPU baseline),
+    --steps sets the number of timed steps, and --dump-outputs writes the frame the last timed step returned on rank 0:
+    the stub fills every pixel of a frame row with the row's index, so the gathered frame is known exactly."""
+    out = _run_bench({}, "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["n_gpus"] == gpus and out["full"] is False and out["ms_per_step"] > 0
+    assert out["metric"] == "Mrays/s at 1920x1080, 64 spp, 8 bounces" and out["unit"] == "Mrays/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert abs(out["value"] - out["rays_per_frame"] / (out["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * out["value"]
+    for k in ("roofline", "cpu_baseline", "config3", "config5", "config4", "reseeded_ms", "first_frame_ms"):
+        assert k not in out, k
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == ["frame.npy"]
+    assert os.path.getsize(tmp_path / "out" / "frame.npy") <= 64 << 20
+    frame = np.load(tmp_path / "out" / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (1080, 1920, 4)
+    assert np.array_equal(frame, np.broadcast_to(np.arange(1080, dtype=np.float32)[:, None, None], frame.shape))

@@ -471,7 +471,7 @@ def test_rccl_not_found_is_an_error_code_not_a_crash():
     assert "librccl not found" in msg and "librccl_not_here" in msg
 
 
-def test_srgb_store_thresholds_and_the_oracle_formula_agree_at_every_decision_point(oracle):
+def test_srgb_store_thresholds_and_the_oracle_formula_agree_at_every_decision_point(oracle, tmp_path):
     """BRT_FLAG_OUT_RGBA8_UNORM_SRGB (the store into TextureFormat::bevy_default(), pipeline.rs:311-315): the product counts 255
     precomputed f32 thresholds (exact: scripts/gen_srgb_table.py evaluates them in 60-digit arithmetic), the oracle evaluates
     round(255 * OETF(c)) in double.  They must agree on every f32 -- it suffices to look where the code changes: at each threshold the
@@ -488,12 +488,20 @@ def test_srgb_store_thresholds_and_the_oracle_formula_agree_at_every_decision_po
         want = np.searchsorted(t, x, side="right")       # thresholds <= x  (NaN sorts last: fixed below)
     want[np.isnan(x)] = 0
     assert np.array_equal(enc(x), want)
-    # the regenerated table is the committed one
+    # the regenerated table is the committed one.  The generator writes into a scratch tree: rewriting the committed header, even
+    # with the same text, would make the library older than one of its sources and rebuild it on the next import
     import subprocess, sys
     header = os.path.join(ROOT, "bevyray_amd", "csrc", "brt_srgb_table.h")
-    before = open(header).read()
-    subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "gen_srgb_table.py")], check=True, capture_output=True)
-    assert open(header).read() == before
+    (tmp_path / "bevyray_amd" / "csrc").mkdir(parents=True)
+    gen = ("import importlib.util, sys\n"
+           "spec = importlib.util.spec_from_file_location('gen_srgb_table', sys.argv[1])\n"
+           "mod = importlib.util.module_from_spec(spec)\n"
+           "spec.loader.exec_module(mod)\n"
+           "mod.ROOT = sys.argv[2]\n"
+           "mod.main()\n")
+    subprocess.run([sys.executable, "-c", gen, os.path.join(ROOT, "scripts", "gen_srgb_table.py"), str(tmp_path)], check=True,
+                   capture_output=True)
+    assert (tmp_path / "bevyray_amd" / "csrc" / "brt_srgb_table.h").read_text() == open(header).read()
 
 
 _OOM_CHILD = r'''
