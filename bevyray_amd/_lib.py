@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BRT_LIB_PATH") or os.path.join(_HERE, "libbevyray_amd.so")   # BRT_LIB_PATH: A/B of builds
 _SOURCES = ["brt_api.cpp", "brt_interop.cpp", "brt_ctx.h", "brt_host.cpp", "brt_kernels.hip", "brt_trace_prod.hip", "brt_trace_tune.hip", "brt_trace.h",
-            "brt_host.h", "brt_kernels.h", "brt_layout.h", "brt_device.h", "brt_ploc.h", "brt_sah.h", "brt_srgb_table.h", "brt_bvh.hip", "brt_sah.hip", "brt_order.hip", "Makefile"]
+            "brt_host.h", "brt_kernels.h", "brt_layout.h", "brt_device.h", "brt_ploc.h", "brt_sah.h", "brt_srgb_table.h", "brt_bvh.hip", "brt_sah.hip", "brt_order.hip", "brt_denoise.hip",
+            "brt_denoise.h", "brt_store.h", "Makefile"]
 
 _lock = threading.Lock()
 _lib = None
@@ -89,6 +90,9 @@ _PROTOTYPES = {
     "brt_debug_export_frame_fd": (_I32, [_VP, C.c_uint64, C.POINTER(_I32), C.POINTER(_VP)]),
     "brt_debug_copy_to_host": (_I32, [_VP, _VP, _VP, C.c_uint64]),
     "brt_debug_eval": (_I32, [_VP, _U32, _VP, _VP, _U32]),
+    "brt_set_denoise": (_I32, [_VP, _U32, _F, _F, _F]),
+    "brt_denoise_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_debug_denoise_guides": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP]),
     "brt_debug_profile": (_I32, [_VP, C.POINTER(C.c_uint64)]),
     "brt_debug_tile_order": (_I32, [_VP, _VP, _VP, _U32, _U32, C.c_uint64, _U32, _U32, _U32, _VP, _VP]),
     "brt_build_bvh": (_I32, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),

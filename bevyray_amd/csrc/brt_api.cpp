@@ -800,6 +800,8 @@ void free_device(DeviceCtx& dc) {
     if (dc.d_slice_state) (void)hipFree(dc.d_slice_state);
     if (dc.d_record_hits) (void)hipFree(dc.d_record_hits);
     if (dc.d_bvh_models) (void)hipFree(dc.d_bvh_models);
+    if (dc.d_denoise) (void)hipFree(dc.d_denoise);
+    if (dc.ev_dn) (void)hipEventDestroy(dc.ev_dn);
     if (dc.ev0) (void)hipEventDestroy(dc.ev0);
     if (dc.ev1) (void)hipEventDestroy(dc.ev1);
     if (dc.ev_last) (void)hipEventDestroy(dc.ev_last);
@@ -933,10 +935,12 @@ int32_t brt_create(const int32_t* device_ids, int32_t n_devices, brt_ctx** out_c
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_asm, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_in, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_pack, hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_dn, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreate(&dc.ev_g0));
             HIP_TRY(ctx, hipEventCreate(&dc.ev_g1));
             HIP_TRY(ctx, hipEventRecord(dc.ev_asm, dc.stream));
             HIP_TRY(ctx, hipEventRecord(dc.ev_last, dc.stream));
+            HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
             HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dc.d_ctrl), 512));
             return BRT_OK;
         };
@@ -1282,6 +1286,36 @@ void drain_all_streams(brt_ctx* ctx) {
     g_last_error = keep;
 }
 
+// ---- denoiser (brt_denoise.hip) on the first device ----
+
+// the scratch of a width x height frame for work on `stream`: the stream first waits for the last denoise (on whichever stream), so
+// that what is enqueued next -- an assembled frame into ds->frame included -- finds the scratch free; a larger one is allocated only
+// once that denoise has finished
+int32_t denoise_scratch_of(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream, DenoiseScratch* ds) {
+    const size_t bytes = denoise_scratch_bytes(width, height);
+    if (dc.denoise_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
+    int32_t rc = ensure(ctx, &dc.d_denoise, &dc.denoise_cap, bytes);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_dn, 0));
+    *ds = denoise_scratch(dc.d_denoise, width, height);
+    return BRT_OK;
+}
+
+// guides of fp's frame on the resident scene, then the passes from d_in (RGBA32F) into d_out (out_format), on `stream` (which
+// denoise_scratch_of has ordered behind the previous denoise of the context)
+int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, void* d_out,
+                    uint32_t out_format, hipStream_t stream) {
+    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream));
+    HIP_TRY(ctx, launch_denoise(fp, ctx->denoise, ds, d_in, d_out, out_format, stream));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
+    return BRT_OK;
+}
+
+// the frame parameters the guides are cast with (one part, level 3)
+int32_t denoise_params(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, FrameParams* fp) {
+    return make_frame_params(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, 0u, 1u, fp);
+}
+
 int32_t render_part_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t width,
                                uint32_t height, uint32_t part, uint32_t n_parts, const float* d_raster_rgba,
                                const float* d_raster_depth, float* d_out_tile, void* hip_stream, uint32_t flags,
@@ -1358,6 +1392,7 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
     double prepass_ms = 0.0;
     std::vector<char> prepass_ran(n_parts, 0);
     const bool direct = is_pinned(ctx, out_rgba, frame_px * 16);
+    const bool denoise = (flags & BRT_FLAG_DENOISE) != 0u;
 
     // launch every device, then collect: the devices trace their strips concurrently
     for (uint32_t p = 0; p < n_parts; p++) {
@@ -1417,6 +1452,14 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
         if (rc != BRT_OK) return rc;
         rc = launch_part(ctx, dc, fps[p], d_rgba, d_depth, dc.d_tile, dc.stream, flags, true, &lp);
         if (rc != BRT_OK) return rc;
+        if (denoise && n_parts == 1) {     // the tile IS the frame: denoised in place before it is copied out
+            DenoiseScratch ds;
+            FrameParams gp;
+            rc = denoise_params(ctx, camera80, window16, width, height, &gp);
+            if (rc == BRT_OK) rc = denoise_scratch_of(ctx, dc, width, height, dc.stream, &ds);
+            if (rc == BRT_OK) rc = run_denoise(ctx, dc, gp, ds, dc.d_tile, dc.d_tile, BRT_FLAG_OUT_RGBA32F, dc.stream);
+            if (rc != BRT_OK) return rc;
+        }
         if (direct) {
             // page-locked destination: DMA every strip to its place in the frame, no CPU copy
             const uint32_t strips = (height + BRT_STRIP_ROWS - 1u) / BRT_STRIP_ROWS;
@@ -1462,6 +1505,21 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
         }
         gather_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
         st.paths += part_pixels(fps[p]) * (uint64_t)fps[p].sample_count;
+    }
+    if (denoise && n_parts > 1) {      // the strips of N devices: the assembled frame goes back to the first device to be denoised
+        DeviceCtx& d0 = ctx->devs[0];
+        HIP_TRY(ctx, hipSetDevice(d0.device));
+        DenoiseScratch ds;
+        FrameParams gp;
+        int32_t rc = denoise_params(ctx, camera80, window16, width, height, &gp);
+        if (rc == BRT_OK) rc = denoise_scratch_of(ctx, d0, width, height, d0.stream, &ds);
+        if (rc != BRT_OK) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ds.frame, out_rgba, frame_px * 16, hipMemcpyHostToDevice, d0.stream));
+        float4* result = denoise_result_plane(ds, ctx->denoise);      // (a plane the last pass does not read)
+        rc = run_denoise(ctx, d0, gp, ds, reinterpret_cast<float*>(ds.frame), result, BRT_FLAG_OUT_RGBA32F, d0.stream);
+        if (rc != BRT_OK) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(out_rgba, result, frame_px * 16, hipMemcpyDeviceToHost, d0.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(d0.stream));
     }
     if (stats) {
         *stats = st;
@@ -1597,8 +1655,25 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
     HIP_TRY(ctx, hipSetDevice(d0.device));
     HIP_TRY(ctx, hipEventRecord(d0.ev_g0, stream0));
     for (uint32_t p = 1; p < n_parts; p++) HIP_TRY(ctx, hipStreamWaitEvent(stream0, ctx->devs[p].ev_copy, 0));
-    HIP_TRY(ctx, launch_deinterleave(d0.d_gather, d_frame, width, height, n_parts, tile_rows, flags & BRT_FLAG_OUT_MASK, stream0));
-    HIP_TRY(ctx, hipEventRecord(d0.ev_g1, stream0));
+    if (flags & BRT_FLAG_DENOISE) {
+        // the assembled RGBA f32 frame (one device: its tile, row for row) is denoised into d_frame in the requested format
+        DenoiseScratch ds;
+        FrameParams gp;
+        rc = denoise_params(ctx, camera80, window16, width, height, &gp);
+        if (rc == BRT_OK) rc = denoise_scratch_of(ctx, d0, width, height, stream0, &ds);
+        if (rc != BRT_OK) return rc;
+        const float* assembled = d0.d_gather;
+        if (n_parts > 1) {
+            HIP_TRY(ctx, launch_deinterleave(d0.d_gather, ds.frame, width, height, n_parts, tile_rows, BRT_FLAG_OUT_RGBA32F, stream0));
+            assembled = reinterpret_cast<const float*>(ds.frame);
+        }
+        HIP_TRY(ctx, hipEventRecord(d0.ev_g1, stream0));
+        rc = run_denoise(ctx, d0, gp, ds, assembled, d_frame, flags & BRT_FLAG_OUT_MASK, stream0);
+        if (rc != BRT_OK) return rc;
+    } else {
+        HIP_TRY(ctx, launch_deinterleave(d0.d_gather, d_frame, width, height, n_parts, tile_rows, flags & BRT_FLAG_OUT_MASK, stream0));
+        HIP_TRY(ctx, hipEventRecord(d0.ev_g1, stream0));
+    }
     HIP_TRY(ctx, hipEventRecord(d0.ev_asm, stream0));
     HIP_TRY(ctx, hipEventRecord(d0.ev_last, stream0));
     brt_stats st{};
@@ -1654,6 +1729,8 @@ int32_t brt_render(brt_ctx* ctx, const void* camera80, const void* window16, uin
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!out_rgba) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_rgba is null");
+    if ((flags & BRT_FLAG_DENOISE) && level != BRT_LEVEL_PURE)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE needs level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_OUT_MASK) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "brt_render writes RGBA f32 (BRT_FLAG_OUT_* apply to the device frame of brt_render_device / brt_gather_rccl / brt_deinterleave_device)");
     uint32_t rebuilt = 0u;
@@ -1671,6 +1748,8 @@ int32_t brt_render_part_device(brt_ctx* ctx, const void* camera80, const void* w
                                brt_stats* stats) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (flags & BRT_FLAG_DENOISE)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's strips have no neighbours: denoise the assembled frame (brt_denoise_device)");
     if (!d_out_tile) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out_tile is null");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_OUT_MASK) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's tile is RGBA f32 (the format is applied where the frame is assembled: brt_gather_rccl / brt_deinterleave_device)");
@@ -1691,6 +1770,8 @@ int32_t brt_render_device(brt_ctx* ctx, const void* camera80, const void* window
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
+    if ((flags & BRT_FLAG_DENOISE) && level != BRT_LEVEL_PURE)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE needs level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_KERNEL_SIMPLE) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "brt_render_device runs the persistent kernel only");
     uint32_t rebuilt = 0u;
@@ -1760,6 +1841,8 @@ int32_t brt_deinterleave_device(brt_ctx* ctx, const float* d_tiles, uint32_t n_p
                                 void* d_frame, void* hip_stream, uint32_t flags) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (flags & BRT_FLAG_DENOISE)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the de-interleave does not denoise: brt_denoise_device on the assembled frame");
     if (!d_tiles || !d_frame || n_parts == 0) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null buffer / n_parts == 0");
     DeviceCtx& dc = ctx->devs[0];
     HIP_TRY(ctx, hipSetDevice(dc.device));
@@ -1870,6 +1953,77 @@ int32_t brt_debug_tile_order(brt_ctx* ctx, const uint32_t* ray_sum, const uint32
     if (d_meta) (void)hipFree(d_meta);
     if (d_scratch) (void)hipFree(d_scratch);
     return rc;
+    });
+}
+
+int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance, float sigma_normal, float sigma_depth) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (iterations < 1u || iterations > 6u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "iterations must be in [1, 6]");
+    for (float v : {sigma_luminance, sigma_normal, sigma_depth})
+        if (!std::isfinite(v) || !(v > 0.0f)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "the sigmas must be finite and > 0");
+    ctx->denoise.iterations = iterations;
+    ctx->denoise.sigma_l = sigma_luminance;
+    ctx->denoise.sigma_n = sigma_normal;
+    ctx->denoise.sigma_z = sigma_depth;
+    return BRT_OK;
+    });
+}
+
+int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                           const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!d_frame_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame_rgba / d_out is null");
+    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE))
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only");
+    if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
+    uint32_t rebuilt = 0u;
+    int32_t rc = ensure_tree_reach(ctx, camera80, &rebuilt);    // (the guides walk the tree the frame was traced in)
+    FrameParams fp;
+    if (rc == BRT_OK) rc = denoise_params(ctx, camera80, window16, width, height, &fp);
+    if (rc != BRT_OK) return rc;
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    const bool own_stream = (hip_stream == nullptr) && !(flags & BRT_FLAG_CALLER_STREAM);
+    hipStream_t stream = own_stream ? dc.stream : static_cast<hipStream_t>(hip_stream);
+    DenoiseScratch ds;
+    rc = denoise_scratch_of(ctx, dc, width, height, stream, &ds);
+    if (rc == BRT_OK) rc = run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, stream);
+    if (rc == BRT_OK && own_stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    if (stats) {
+        std::memset(stats, 0, sizeof *stats);
+        stats->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        tree_stats(ctx, rebuilt, stats);
+    }
+    return BRT_OK;
+    });
+}
+
+int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, float* out8) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out8 is null");
+    if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
+    uint32_t rebuilt = 0u;
+    int32_t rc = ensure_tree_reach(ctx, camera80, &rebuilt);
+    FrameParams fp;
+    if (rc == BRT_OK) rc = denoise_params(ctx, camera80, window16, width, height, &fp);
+    if (rc != BRT_OK) return rc;
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    DenoiseScratch ds;
+    rc = denoise_scratch_of(ctx, dc, width, height, dc.stream, &ds);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, dc.stream));
+    const size_t n = (size_t)width * height;
+    HIP_TRY(ctx, hipMemcpy2DAsync(out8, 32, ds.g0, 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(out8 + 4, 32, ds.g1, 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
+    return BRT_OK;
     });
 }
 

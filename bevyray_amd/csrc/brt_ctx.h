@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "brt_denoise.h"
 #include "brt_host.h"
 #include "brt_kernels.h"
 
@@ -91,6 +92,10 @@ struct DeviceCtx {
     std::vector<float> h_spheres_cur, h_sphmats_cur;
     std::vector<uint32_t> h_sphmat_cur;
     std::vector<float> h_pairs_hot, h_pairs_cur;          // scratch / the records as they are on the device (when hot_tree matches)
+    // denoiser scratch (brt_denoise.h DenoiseScratch), first device only
+    char* d_denoise = nullptr;
+    size_t denoise_cap = 0;
+    hipEvent_t ev_dn = nullptr;     // end of the last denoise (any stream): the scratch is free again
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;
@@ -162,6 +167,7 @@ struct brt_ctx {
     uint32_t tree_rebuilds = 0;          // rebuilds since brt_create (diagnostic)
     brt::Knobs knobs;           // tuning knobs (brt_set_tuning; environment once at brt_create under BRT_ENABLE_TUNING=1)
     uint32_t policy_flags = 0;  // brt_set_policy
+    brt::DenoiseSettings denoise;   // brt_set_denoise
     std::string last_error;
 };
 

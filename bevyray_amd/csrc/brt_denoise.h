@@ -1,0 +1,49 @@
+// brt_denoise.h -- host-callable launchers of the guide-buffer a-trous denoiser (brt_denoise.hip).  The formulas: DESIGN.md "Denoiser".
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "brt_layout.h"
+
+namespace brt {
+
+struct DenoiseSettings {
+    uint32_t iterations = 5;           // a-trous passes, step 2^i in pass i (1 .. 6)
+    float sigma_l = 4.0f, sigma_n = 128.0f, sigma_z = 1.0f;
+};
+
+// Above this many samples per pixel the filter's strength falls as the noise std does: sigma_l and the blend weight
+// of the filtered result both scale by k = sqrt(kStrengthSpp / spp)
+constexpr uint32_t kStrengthSpp = 4;
+
+// The context-owned scratch of one width x height frame, carved out of one allocation (denoise_scratch_bytes): 88 bytes per pixel, every
+// plane read by every denoise.
+//   g0    float4 {normal.xyz, t}                  first hit of the pixel-centre ray (t = +INF: sky)
+//   g1    float4 {a.rgb, material id as bits}     demodulation factor (1, 1, 1 and 0xFFFFFFFF for sky)
+//   cv    float4 {c'.rgb, var} x 2                the ping-pong planes of the passes (var < 0: the pixel passes through)
+//   dm    float4 {c'.rgb, 0 or -1}                the demodulated input, kept for the last pass's blend
+//   aux   float2 {alpha, depth scale}             the input's alpha; t * theta_px / max(|n . dir|, 0.1)
+// `frame` is cv[1] under another name: room for an assembled RGBA32F frame (brt_render_device / brt_render on N devices) -- only the
+// demodulation reads it, and pass 0 is the first kernel that writes cv[1].
+struct DenoiseScratch {
+    float4* g0;
+    float4* g1;
+    float4* cv[2];
+    float4* dm;
+    float2* aux;
+    float4* frame;
+};
+size_t denoise_scratch_bytes(uint32_t width, uint32_t height);
+// a plane of the scratch the last of st.iterations passes does not read: room for the RGBA32F result of a denoise of ds.frame
+inline float4* denoise_result_plane(const DenoiseScratch& ds, const DenoiseSettings& st) { return ds.cv[st.iterations & 1u]; }
+DenoiseScratch denoise_scratch(char* base, uint32_t width, uint32_t height);
+
+// the guide buffer of fp's frame (fp: level 3, one part) on the resident scene
+hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& fp, const DenoiseScratch& ds, hipStream_t stream);
+// guides must be in ds; d_in: RGBA32F width x height (may be ds.frame); d_out: out_format (BRT_FLAG_OUT_*), may equal d_in
+hipError_t launch_denoise(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, const float* d_in, void* d_out,
+                          uint32_t out_format, hipStream_t stream);
+
+}  // namespace brt

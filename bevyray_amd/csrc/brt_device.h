@@ -1868,6 +1868,18 @@ BRT_DEV f3 camera_dir_raw(const FrameParams& fp, float ndc0x, float ndc0y, uint3
 BRT_DEV f3 camera_ray_dir(const FrameParams& fp, float ndc0x, float ndc0y, uint32_t& rng) {
     return normalize3(camera_dir_raw(fp, ndc0x, ndc0y, rng));
 }
+// The pixel-centre ray: camera_ray_dir's arithmetic with rand_square = (0, 0) instead of the two RNG draws (no jitter; the
+// denoiser's guide buffer, brt_denoise.hip)
+BRT_DEV f3 camera_ray_dir_center(const FrameParams& fp, float ndc0x, float ndc0y) {
+    const float ndc_x = ndc0x + fp.inv_width * 0.0f;
+    const float ndc_y = ndc0y + fp.inv_height * 0.0f;
+    const float sx = (ndc_x * fp.aspect) * fp.tan_half_fov;
+    const float sy = ndc_y * fp.tan_half_fov;
+    const f3 cd = mk3(fp.cam_dir[0], fp.cam_dir[1], fp.cam_dir[2]);
+    const f3 cr = mk3(fp.cam_right[0], fp.cam_right[1], fp.cam_right[2]);
+    const f3 cu = mk3(fp.cam_up[0], fp.cam_up[1], fp.cam_up[2]);
+    return normalize3((cd + sx * cr) + sy * cu);
+}
 
 // raytrace.wgsl:104-122: final colour of a pixel from the averaged sample colour/depth.
 BRT_DEV float4 resolve_pixel(const FrameParams& fp, f3 avg, float avg_depth, const float* raster_rgba,

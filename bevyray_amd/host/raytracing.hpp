@@ -155,7 +155,7 @@ public:
     // empty buffers: pipeline.rs:82-151); throws Error for real failures.
     bool run(const std::optional<std::pair<RaytraceLevelExtract, CameraExtract>>& view, const WindowExtract& window,
              uint32_t width, uint32_t height, const Buffers* buffers, const float* raster_rgba, const float* raster_depth,
-             std::vector<float>& destination, brt_stats* stats = nullptr, uint32_t flags = 0) {
+             std::vector<float>& destination, brt_stats* stats = nullptr, uint32_t flags = 0, bool denoise = false) {
         if (!view) return false;
         if (buffers) {
             const int32_t rc = brt_upload_scene(ctx_, buffers->models.data(), static_cast<uint32_t>(buffers->models.size()),
@@ -166,8 +166,15 @@ public:
         }
         destination.resize(static_cast<size_t>(width) * height * 4);
         check(brt_render(ctx_, &view->second, &window, view->first.level, width, height, raster_rgba, raster_depth,
-                         destination.data(), flags, stats), ctx_);
+                         destination.data(), flags | (denoise ? BRT_FLAG_DENOISE : 0u), stats), ctx_);
         return true;
+    }
+    // The context's denoiser (RaytracePlugin::set_denoise) on an RGBA f32 device frame the caller holds -- e.g. the root's frame after
+    // gather() -- into d_out in the BRT_FLAG_OUT_* format of `flags` (d_out may be d_frame).  run / run_device denoise with
+    // denoise = true / BRT_FLAG_DENOISE (level 3 only).
+    void denoise_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, const float* d_frame,
+                        void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_denoise_device(ctx_, &camera, &window, width, height, d_frame, d_out, hip_stream, flags, stats), ctx_);
     }
     // The same pass on an N-device context with the frame assembled ON THE FIRST DEVICE (brt_render_device: tiles by peer
     // copy over xGMI, one de-interleave kernel): `d_destination` is a device pointer, e.g. the mapped colour target
@@ -216,6 +223,10 @@ public:
     // the reading of `||` in raytrace.wgsl:269 (BRT_POLICY_OR_SHORT_CIRCUIT or 0); scheduling knobs (never change a pixel)
     void set_policy(uint32_t flags) { check(brt_set_policy(ctx_, flags), ctx_); }
     void set_tuning(const char* name, uint32_t value) { check(brt_set_tuning(ctx_, name, value), ctx_); }
+    // the denoiser's settings (brt_set_denoise; the defaults are the library's)
+    void set_denoise(uint32_t iterations = 5, float sigma_luminance = 4.0f, float sigma_normal = 128.0f, float sigma_depth = 1.0f) {
+        check(brt_set_denoise(ctx_, iterations, sigma_luminance, sigma_normal, sigma_depth), ctx_);
+    }
     // one process per GPU: the strips dealt out to the ranks by measured cost instead of s % world (brt_plan_strips: every rank computes
     // the same table from the same probe frame; an empty vector to set_strip_table: back to s % world)
     std::vector<uint32_t> plan_strips(const std::pair<RaytraceLevelExtract, CameraExtract>& view, const WindowExtract& window, uint32_t width,

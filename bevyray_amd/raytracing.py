@@ -52,6 +52,7 @@ POLICY_MINMAX_SELECT = 2      # ... min / max by compare-select (default: minNum
 POLICY_POW_EXP2_LOG2 = 4      # ... pow(x, 5) as exp2(5 log2 x) (default: multiplies)
 EXTMEM_OPAQUE_FD, EXTMEM_DMABUF_FD = 1, 2   # brt_import_frame_fd handle types
 FLAG_CALLER_STREAM = 4   # device entry points: `stream` is the caller's stream even when its handle is 0
+FLAG_DENOISE = 32        # brt_render / brt_render_device (level 3): the frame is denoised (RaytracePlugin.set_denoise) before it is written
 # format of an assembled DEVICE frame (render_device, gather_rccl, deinterleave_device): the colour target's own (pipeline.rs:311-315)
 FLAG_OUT_RGBA32F, FLAG_OUT_RGBA8_UNORM_SRGB, FLAG_OUT_RGBA16F, FLAG_OUT_RGBA8_UNORM = 0, 8, 16, 24
 OUT_PIXEL_BYTES = {FLAG_OUT_RGBA32F: 16, FLAG_OUT_RGBA8_UNORM_SRGB: 4, FLAG_OUT_RGBA16F: 8, FLAG_OUT_RGBA8_UNORM: 4}
@@ -337,6 +338,21 @@ class RaytracePlugin:
                     self.set_tuning(k, v)
         return cm()
 
+    def set_denoise(self, iterations: int = 5, sigma_luminance: float = 4.0, sigma_normal: float = 128.0,
+                    sigma_depth: float = 1.0) -> None:
+        """brt_set_denoise: the denoiser's settings (iterations 1..6, sigmas finite and > 0); applies to FLAG_DENOISE frames and
+        RayTracingNode.denoise_device.  Invalid values raise BrtError and leave the settings as they were."""
+        _lib.check(self._lib.brt_set_denoise(self._ctx, int(iterations), float(sigma_luminance), float(sigma_normal),
+                                             float(sigma_depth)), self._ctx)
+
+    def debug_denoise_guides(self, camera, window, width: int, height: int) -> np.ndarray:
+        """brt_debug_denoise_guides: (height, width, 8) f32 -- normal.xyz, t (inf: sky), a.rgb, material id as bits
+        (0xFFFFFFFF: sky) of every pixel-centre ray on the resident scene."""
+        out = np.empty((height, width, 8), np.float32)
+        _lib.check(self._lib.brt_debug_denoise_guides(self._ctx, camera.ctypes.data, window.ctypes.data, width, height,
+                                                      out.ctypes.data), self._ctx)
+        return out
+
     def alloc_frame(self, width: int, height: int) -> np.ndarray:
         """Page-locked (height, width, 4) f32 frame owned by the context (brt_host_alloc): passing it
         as `out` to RayTracingNode.run lets the library DMA straight into it."""
@@ -551,6 +567,17 @@ class RayTracingNode:
                                             C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
+
+    def denoise_device(self, camera, window, width: int, height: int, d_frame: int, d_out: int, stream: Optional[int] = None,
+                       out_format: int = FLAG_OUT_RGBA32F) -> dict:
+        """brt_denoise_device: the context's denoiser on the RGBA f32 device frame d_frame (rendered with camera / window on the
+        resident scene) into d_out (out_format: FLAG_OUT_*; may be d_frame).  Stream rule as for render_part_device."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_denoise_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_frame, d_out,
+                                             stream or None, (0 if stream is None else FLAG_CALLER_STREAM) | out_format,
+                                             C.byref(stats)), p._ctx)
+        return stats.as_dict()
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

@@ -96,7 +96,13 @@ enum {
     BRT_FLAG_OUT_RGBA8_UNORM_SRGB = 8u,
     BRT_FLAG_OUT_RGBA16F = 16u,
     BRT_FLAG_OUT_RGBA8_UNORM = 24u,
-    BRT_FLAG_OUT_MASK = 24u
+    BRT_FLAG_OUT_MASK = 24u,
+    /* brt_render / brt_render_device: the frame is traced exactly as without the flag (RGBA f32), then the context's denoiser
+     * (brt_set_denoise) runs on the assembled frame on the first device and its result is what is written, in the requested format.
+     * Level 3 (Pure) only: BRT_ERR_UNSUPPORTED at levels 0-2 (the raster blend of levels 1 / 2 leaves no mark of the pixels that took
+     * the raster colour) and on brt_render_part_device / brt_gather_rccl / brt_deinterleave_device (a rank's strips have no
+     * neighbours: denoise the assembled frame with brt_denoise_device).  The denoiser's time is part of brt_stats::total_ms only. */
+    BRT_FLAG_DENOISE = 32u
 };
 
 typedef struct brt_ctx brt_ctx;
@@ -326,6 +332,24 @@ enum {
                               (the store conversions of BRT_FLAG_OUT_*) */
 };
 int32_t brt_debug_eval(brt_ctx* ctx, uint32_t op, const float* in16, float* out8, uint32_t n);
+
+/* ---- denoiser ----------------------------------------------------------------------------------------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010, with the spatial edge-stopping and variance terms of SVGF) guided by the
+ * first hit of every pixel-centre ray: normal, distance, and the first bounce's base colour, which is divided out before the filter and
+ * multiplied back after it.  Formulas and kernels: DESIGN.md "Denoiser".  Deterministic: the same input gives the same output bits.
+ *   brt_set_denoise          the context's settings: iterations 1..6 (pass i has step 2^i), sigma_luminance, sigma_normal, sigma_depth
+ *                            finite and > 0.  Defaults 5, 4, 128, 1.  Anything else: BRT_ERR_INVALID_ARGUMENT, settings unchanged.
+ *   brt_denoise_device       denoises an RGBA f32 width x height DEVICE frame the caller holds (e.g. the root's frame after
+ *                            brt_gather_rccl) rendered with camera80 / window16 on the resident scene, into d_out (DEVICE, the
+ *                            BRT_FLAG_OUT_* format of `flags`; may equal d_frame_rgba).  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*
+ *                            (and BRT_FLAG_DENOISE, implied); other bits BRT_ERR_INVALID_ARGUMENT.  Stream rule as for
+ *                            brt_render_device; stats_or_null: total_ms only.  BRT_ERR_NO_SCENE before an upload.
+ *   brt_debug_denoise_guides diagnostic: the guide buffer of that frame, out8[(y * width + x) * 8 + k] = normal.xyz, t (+INF: no hit),
+ *                            a.rgb (the demodulation factor), material id as bits (0xFFFFFFFF: no hit).  Host memory, synchronous. */
+int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance, float sigma_normal, float sigma_depth);
+int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                           const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, float* out8);
 
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how
