@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -801,6 +802,8 @@ void free_device(DeviceCtx& dc) {
     if (dc.d_record_hits) (void)hipFree(dc.d_record_hits);
     if (dc.d_bvh_models) (void)hipFree(dc.d_bvh_models);
     if (dc.d_denoise) (void)hipFree(dc.d_denoise);
+    if (dc.d_temporal) (void)hipFree(dc.d_temporal);
+    if (dc.d_tsph) (void)hipFree(dc.d_tsph);
     if (dc.ev_dn) (void)hipEventDestroy(dc.ev_dn);
     if (dc.ev0) (void)hipEventDestroy(dc.ev0);
     if (dc.ev1) (void)hipEventDestroy(dc.ev1);
@@ -1170,6 +1173,7 @@ int32_t upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const 
             for (auto& dc : ctx->devs) if (dc.hot_tree != 0u) { dc.order_valid = false; dc.view_rays = 0; }
         return BRT_OK;
     }
+    if (n_models != ctx->last_n_models || tb != ctx->last_materials.size()) ctx->temporal.valid = false;   // another scene: no history
     ctx->last_models.assign(static_cast<const char*>(models), static_cast<const char*>(models) + mb);
     ctx->last_materials.assign(static_cast<const char*>(materials), static_cast<const char*>(materials) + tb);
     if (bb) ctx->last_bvh.assign(static_cast<const char*>(bvh_nodes), static_cast<const char*>(bvh_nodes) + bb);
@@ -1301,13 +1305,103 @@ int32_t denoise_scratch_of(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t
     return BRT_OK;
 }
 
-// guides of fp's frame on the resident scene, then the passes from d_in (RGBA32F) into d_out (out_format), on `stream` (which
-// denoise_scratch_of has ordered behind the previous denoise of the context)
+// ---- temporal accumulation (brt_temporal.hip) on the first device ----
+
+// the history of fp's frame and the arguments of its accumulation, for work on `stream` (which denoise_scratch_of has ordered behind the
+// previous denoise, temporal or not, of the context): the planes (a new size: a reset), the spheres of this frame and of the previous
+// temporal frame in the caller's order, and the map from the resident sphere numbering to the caller's
+int32_t temporal_begin(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, hipStream_t stream, TemporalHistory* th, TemporalArgs* ta,
+                       const uint32_t** rmap) {
+    auto& tp = ctx->temporal;
+    bool had = tp.valid && tp.width == fp.width && tp.height == fp.height;
+    tp.valid = false;                               // (until this frame is enqueued)
+    const size_t bytes = temporal_history_bytes(fp.width, fp.height);
+    if (dc.temporal_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
+    int32_t rc = ensure(ctx, &dc.d_temporal, &dc.temporal_cap, bytes);
+    if (rc != BRT_OK) return rc;
+    *th = temporal_history(dc.d_temporal, fp.width, fp.height);
+    const uint32_t m = dc.view.n_models;
+    const std::vector<float>& sph = ctx->enc.spheres;          // {centre, r^2} in the caller's order (validate_and_encode)
+    if (m == 0u || sph.size() != (size_t)m * 4u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "no resident spheres for the temporal history");
+    const size_t sb = (size_t)m * 36u;
+    if (dc.tsph_cap < sb) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
+    rc = ensure(ctx, &dc.d_tsph, &dc.tsph_cap, sb);
+    if (rc != BRT_OK) return rc;
+    if (tp.slot_models != m) {                       // (another layout: what the slots held is gone)
+        tp.slot_models = m;
+        tp.slot_epoch[0] = tp.slot_epoch[1] = -1;
+        tp.h_rmap.clear();
+    }
+    float4* slots[2] = {reinterpret_cast<float4*>(dc.d_tsph), reinterpret_cast<float4*>(dc.d_tsph) + m};
+    uint32_t* d_rmap = reinterpret_cast<uint32_t*>(slots[1] + m);
+    const int64_t epoch = ctx->scene_epoch;
+    const int old = !had ? -1 : tp.slot_epoch[0] == tp.prev_epoch ? 0 : tp.slot_epoch[1] == tp.prev_epoch ? 1 : -1;
+    int cur = tp.slot_epoch[0] == epoch ? 0 : tp.slot_epoch[1] == epoch ? 1 : -1;
+    bool copied = false;
+    if (cur < 0) {                                  // a new upload: into the slot the previous frame's spheres are not in
+        cur = old == 0 ? 1 : 0;
+        HIP_TRY(ctx, hipMemcpyAsync(slots[cur], sph.data(), (size_t)m * 16u, hipMemcpyHostToDevice, stream));
+        tp.slot_epoch[cur] = epoch;
+        copied = true;
+    }
+    // the hot order (apply_hot_order) renumbers the resident spheres: h_total_srank[caller index] = resident index
+    *rmap = nullptr;
+    if (dc.hot_tree == ctx->tree_epoch && dc.h_total_srank.size() == m) {
+        std::vector<uint32_t> map(m);
+        for (uint32_t i = 0; i < m; i++) map[dc.h_total_srank[i]] = i;
+        if (map != tp.h_rmap) {
+            tp.h_rmap.swap(map);
+            HIP_TRY(ctx, hipMemcpyAsync(d_rmap, tp.h_rmap.data(), (size_t)m * 4u, hipMemcpyHostToDevice, stream));
+            copied = true;
+        }
+        *rmap = d_rmap;
+    }
+    if (copied) HIP_TRY(ctx, hipStreamSynchronize(stream));     // (pageable sources; a frame after an upload or a renumbering only)
+    had = had && old >= 0;
+    const FrameParams& pp = tp.prev;
+    auto same = [](const float* a, const float* b, int n) { return std::memcmp(a, b, sizeof(float) * (size_t)n) == 0; };
+    ta->prev = tp.set;
+    ta->has_history = had ? 1u : 0u;
+    ta->same_camera = had && same(fp.cam_pos, pp.cam_pos, 3) && same(fp.cam_dir, pp.cam_dir, 3) && same(fp.cam_up, pp.cam_up, 3) &&
+                      same(fp.cam_right, pp.cam_right, 3) && same(&fp.aspect, &pp.aspect, 1) && same(&fp.tan_half_fov, &pp.tan_half_fov, 1);
+    ta->motion = had && tp.prev_models == m ? 1u : 0u;
+    ta->max_history = (float)tp.max_history;
+    ta->sph_new = slots[cur];
+    ta->sph_old = slots[old >= 0 ? old : cur];
+    if (!had) tp.prev = fp;                         // (no previous camera: the kernel reads none)
+    return BRT_OK;
+}
+
+// guides of fp's frame on the resident scene, then the passes (BRT_FLAG_DENOISE) and / or the temporal accumulation
+// (BRT_FLAG_TEMPORAL) from d_in (RGBA32F) into d_out (out_format), on `stream` (which denoise_scratch_of has ordered behind the
+// previous denoise of the context)
 int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, void* d_out,
-                    uint32_t out_format, hipStream_t stream) {
-    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream));
-    HIP_TRY(ctx, launch_denoise(fp, ctx->denoise, ds, d_in, d_out, out_format, stream));
+                    uint32_t out_format, hipStream_t stream, uint32_t flags = BRT_FLAG_DENOISE) {
+    if (!(flags & BRT_FLAG_TEMPORAL)) {
+        HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream));
+        HIP_TRY(ctx, launch_denoise(fp, ctx->denoise, ds, d_in, d_out, out_format, stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
+        return BRT_OK;
+    }
+    TemporalHistory th;
+    TemporalArgs ta;
+    const uint32_t* rmap = nullptr;
+    int32_t rc = temporal_begin(ctx, dc, fp, stream, &th, &ta, &rmap);
+    if (rc != BRT_OK) return rc;
+    const bool filter = (flags & BRT_FLAG_DENOISE) != 0u;
+    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream, rmap, th.sid));
+    HIP_TRY(ctx, launch_denoise_demod(fp, ds, d_in, !filter, stream));
+    HIP_TRY(ctx, launch_temporal(fp, ctx->temporal.prev, ta, ds, th, filter ? nullptr : d_out, out_format, stream));
+    if (filter) HIP_TRY(ctx, launch_denoise_filter(fp, ctx->denoise, ds, d_out, out_format, stream, th.c[ta.prev ^ 1u]));
     HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
+    auto& tp = ctx->temporal;
+    tp.valid = true;
+    tp.width = fp.width;
+    tp.height = fp.height;
+    tp.set = ta.prev ^ 1u;
+    tp.prev = fp;
+    tp.prev_models = dc.view.n_models;
+    tp.prev_epoch = ctx->scene_epoch;
     return BRT_OK;
 }
 
@@ -1392,7 +1486,8 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
     double prepass_ms = 0.0;
     std::vector<char> prepass_ran(n_parts, 0);
     const bool direct = is_pinned(ctx, out_rgba, frame_px * 16);
-    const bool denoise = (flags & BRT_FLAG_DENOISE) != 0u;
+    const bool denoise = (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) != 0u;
+    const uint32_t post = flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL);
 
     // launch every device, then collect: the devices trace their strips concurrently
     for (uint32_t p = 0; p < n_parts; p++) {
@@ -1457,7 +1552,7 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
             FrameParams gp;
             rc = denoise_params(ctx, camera80, window16, width, height, &gp);
             if (rc == BRT_OK) rc = denoise_scratch_of(ctx, dc, width, height, dc.stream, &ds);
-            if (rc == BRT_OK) rc = run_denoise(ctx, dc, gp, ds, dc.d_tile, dc.d_tile, BRT_FLAG_OUT_RGBA32F, dc.stream);
+            if (rc == BRT_OK) rc = run_denoise(ctx, dc, gp, ds, dc.d_tile, dc.d_tile, BRT_FLAG_OUT_RGBA32F, dc.stream, post);
             if (rc != BRT_OK) return rc;
         }
         if (direct) {
@@ -1516,7 +1611,7 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
         if (rc != BRT_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ds.frame, out_rgba, frame_px * 16, hipMemcpyHostToDevice, d0.stream));
         float4* result = denoise_result_plane(ds, ctx->denoise);      // (a plane the last pass does not read)
-        rc = run_denoise(ctx, d0, gp, ds, reinterpret_cast<float*>(ds.frame), result, BRT_FLAG_OUT_RGBA32F, d0.stream);
+        rc = run_denoise(ctx, d0, gp, ds, reinterpret_cast<float*>(ds.frame), result, BRT_FLAG_OUT_RGBA32F, d0.stream, post);
         if (rc != BRT_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(out_rgba, result, frame_px * 16, hipMemcpyDeviceToHost, d0.stream));
         HIP_TRY(ctx, hipStreamSynchronize(d0.stream));
@@ -1655,8 +1750,8 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
     HIP_TRY(ctx, hipSetDevice(d0.device));
     HIP_TRY(ctx, hipEventRecord(d0.ev_g0, stream0));
     for (uint32_t p = 1; p < n_parts; p++) HIP_TRY(ctx, hipStreamWaitEvent(stream0, ctx->devs[p].ev_copy, 0));
-    if (flags & BRT_FLAG_DENOISE) {
-        // the assembled RGBA f32 frame (one device: its tile, row for row) is denoised into d_frame in the requested format
+    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) {
+        // the assembled RGBA f32 frame (one device: its tile, row for row) is denoised / accumulated into d_frame in the requested format
         DenoiseScratch ds;
         FrameParams gp;
         rc = denoise_params(ctx, camera80, window16, width, height, &gp);
@@ -1668,7 +1763,7 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
             assembled = reinterpret_cast<const float*>(ds.frame);
         }
         HIP_TRY(ctx, hipEventRecord(d0.ev_g1, stream0));
-        rc = run_denoise(ctx, d0, gp, ds, assembled, d_frame, flags & BRT_FLAG_OUT_MASK, stream0);
+        rc = run_denoise(ctx, d0, gp, ds, assembled, d_frame, flags & BRT_FLAG_OUT_MASK, stream0, flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL));
         if (rc != BRT_OK) return rc;
     } else {
         HIP_TRY(ctx, launch_deinterleave(d0.d_gather, d_frame, width, height, n_parts, tile_rows, flags & BRT_FLAG_OUT_MASK, stream0));
@@ -1729,8 +1824,8 @@ int32_t brt_render(brt_ctx* ctx, const void* camera80, const void* window16, uin
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!out_rgba) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_rgba is null");
-    if ((flags & BRT_FLAG_DENOISE) && level != BRT_LEVEL_PURE)
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE needs level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
+    if ((flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) && level != BRT_LEVEL_PURE)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL need level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_OUT_MASK) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "brt_render writes RGBA f32 (BRT_FLAG_OUT_* apply to the device frame of brt_render_device / brt_gather_rccl / brt_deinterleave_device)");
     uint32_t rebuilt = 0u;
@@ -1748,8 +1843,8 @@ int32_t brt_render_part_device(brt_ctx* ctx, const void* camera80, const void* w
                                brt_stats* stats) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & BRT_FLAG_DENOISE)
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's strips have no neighbours: denoise the assembled frame (brt_denoise_device)");
+    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's strips have no neighbours: denoise / accumulate the assembled frame (brt_denoise_device)");
     if (!d_out_tile) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out_tile is null");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_OUT_MASK) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's tile is RGBA f32 (the format is applied where the frame is assembled: brt_gather_rccl / brt_deinterleave_device)");
@@ -1770,8 +1865,8 @@ int32_t brt_render_device(brt_ctx* ctx, const void* camera80, const void* window
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
-    if ((flags & BRT_FLAG_DENOISE) && level != BRT_LEVEL_PURE)
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE needs level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
+    if ((flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) && level != BRT_LEVEL_PURE)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL need level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_KERNEL_SIMPLE) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "brt_render_device runs the persistent kernel only");
     uint32_t rebuilt = 0u;
@@ -1841,8 +1936,8 @@ int32_t brt_deinterleave_device(brt_ctx* ctx, const float* d_tiles, uint32_t n_p
                                 void* d_frame, void* hip_stream, uint32_t flags) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & BRT_FLAG_DENOISE)
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the de-interleave does not denoise: brt_denoise_device on the assembled frame");
+    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the de-interleave does not denoise or accumulate: brt_denoise_device on the assembled frame");
     if (!d_tiles || !d_frame || n_parts == 0) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null buffer / n_parts == 0");
     DeviceCtx& dc = ctx->devs[0];
     HIP_TRY(ctx, hipSetDevice(dc.device));
@@ -1976,8 +2071,8 @@ int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* windo
     const auto t0 = std::chrono::steady_clock::now();
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!d_frame_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame_rgba / d_out is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only");
+    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only");
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     uint32_t rebuilt = 0u;
     int32_t rc = ensure_tree_reach(ctx, camera80, &rebuilt);    // (the guides walk the tree the frame was traced in)
@@ -1990,7 +2085,9 @@ int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* windo
     hipStream_t stream = own_stream ? dc.stream : static_cast<hipStream_t>(hip_stream);
     DenoiseScratch ds;
     rc = denoise_scratch_of(ctx, dc, width, height, stream, &ds);
-    if (rc == BRT_OK) rc = run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, stream);
+    // without BRT_FLAG_TEMPORAL the call denoises (BRT_FLAG_DENOISE implied); with it, it accumulates, and filters if BRT_FLAG_DENOISE is set too
+    const uint32_t post = (flags & BRT_FLAG_TEMPORAL) ? flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL) : (uint32_t)BRT_FLAG_DENOISE;
+    if (rc == BRT_OK) rc = run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, stream, post);
     if (rc == BRT_OK && own_stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
     if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
     if (stats) {
@@ -2021,6 +2118,55 @@ int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void*
     const size_t n = (size_t)width * height;
     HIP_TRY(ctx, hipMemcpy2DAsync(out8, 32, ds.g0, 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
     HIP_TRY(ctx, hipMemcpy2DAsync(out8 + 4, 32, ds.g1, 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
+    return BRT_OK;
+    });
+}
+
+int32_t brt_set_temporal(brt_ctx* ctx, uint32_t max_history) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (max_history < 1u || max_history > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "max_history must be in [1, 65535]");
+    ctx->temporal.max_history = max_history;
+    ctx->temporal.valid = false;
+    return BRT_OK;
+    });
+}
+
+int32_t brt_reset_temporal(brt_ctx* ctx) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    ctx->temporal.valid = false;
+    return BRT_OK;
+    });
+}
+
+int32_t brt_debug_temporal_state(brt_ctx* ctx, uint32_t width, uint32_t height, float* out8) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out8 is null");
+    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    const auto& tp = ctx->temporal;
+    const size_t n = (size_t)width * height;
+    if (!tp.valid) {                                 // an empty history: n = 0, nothing reprojected
+        const float nan = std::numeric_limits<float>::quiet_NaN();
+        for (size_t i = 0; i < n; i++) {
+            float* o = out8 + i * 8;
+            o[0] = o[1] = o[2] = o[3] = o[4] = o[5] = 0.0f;
+            o[6] = o[7] = nan;
+        }
+        return BRT_OK;
+    }
+    if (width != tp.width || height != tp.height) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "the history is of another size");
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    const TemporalHistory th = temporal_history(dc.d_temporal, width, height);
+    HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_dn, 0));
+    HIP_TRY(ctx, hipMemcpy2DAsync(out8, 32, th.b[tp.set], 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(out8 + 4, 32, th.c[tp.set], 16, 8, n, hipMemcpyDeviceToHost, dc.stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(out8 + 6, 32, th.xy, 8, 8, n, hipMemcpyDeviceToHost, dc.stream));
     HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
     HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
     return BRT_OK;

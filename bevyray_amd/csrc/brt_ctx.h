@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "brt_denoise.h"
+#include "brt_temporal.h"
 #include "brt_host.h"
 #include "brt_kernels.h"
 
@@ -96,6 +97,12 @@ struct DeviceCtx {
     char* d_denoise = nullptr;
     size_t denoise_cap = 0;
     hipEvent_t ev_dn = nullptr;     // end of the last denoise (any stream): the scratch is free again
+    // temporal history (brt_temporal.h TemporalHistory), first device only; ordered by ev_dn like the scratch (every temporal frame
+    // runs the denoiser's guides and demodulation)
+    char* d_temporal = nullptr;
+    size_t temporal_cap = 0;
+    char* d_tsph = nullptr;         // two slots of float4[n_models] {centre, r^2} in the caller's order, then u32[n_models] resident -> caller
+    size_t tsph_cap = 0;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;
@@ -168,6 +175,17 @@ struct brt_ctx {
     brt::Knobs knobs;           // tuning knobs (brt_set_tuning; environment once at brt_create under BRT_ENABLE_TUNING=1)
     uint32_t policy_flags = 0;  // brt_set_policy
     brt::DenoiseSettings denoise;   // brt_set_denoise
+    struct Temporal {               // BRT_FLAG_TEMPORAL
+        uint32_t max_history = 32;  // brt_set_temporal
+        bool valid = false;         // the history holds a frame (false: n = 0 everywhere)
+        uint32_t width = 0, height = 0, set = 0;   // that frame's size and the plane set it wrote
+        brt::FrameParams prev{};    // its parameters (camera)
+        uint32_t prev_models = 0;   // its sphere count ...
+        int64_t prev_epoch = -1;    // ... and the scene_epoch of its spheres
+        uint32_t slot_models = 0;   // the sphere count d_tsph is laid out for
+        int64_t slot_epoch[2] = {-1, -1};   // the scene_epoch of the spheres in each slot of d_tsph (-1: none)
+        std::vector<uint32_t> h_rmap;       // the resident -> caller map on the device (empty: none)
+    } temporal;
     std::string last_error;
 };
 

@@ -40,10 +40,18 @@ size_t denoise_scratch_bytes(uint32_t width, uint32_t height);
 inline float4* denoise_result_plane(const DenoiseScratch& ds, const DenoiseSettings& st) { return ds.cv[st.iterations & 1u]; }
 DenoiseScratch denoise_scratch(char* base, uint32_t width, uint32_t height);
 
-// the guide buffer of fp's frame (fp: level 3, one part) on the resident scene
-hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& fp, const DenoiseScratch& ds, hipStream_t stream);
+// the guide buffer of fp's frame (fp: level 3, one part) on the resident scene.  sid != nullptr (a temporal frame): also the caller's
+// index of the sphere every pixel hit (0xFFFFFFFF: sky), the resident index mapped through rmap (nullptr: the identity)
+hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& fp, const DenoiseScratch& ds, hipStream_t stream,
+                                 const uint32_t* rmap = nullptr, uint32_t* sid = nullptr);
 // guides must be in ds; d_in: RGBA32F width x height (may be ds.frame); d_out: out_format (BRT_FLAG_OUT_*), may equal d_in
 hipError_t launch_denoise(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, const float* d_in, void* d_out,
                           uint32_t out_format, hipStream_t stream);
+// launch_denoise in two halves, with the temporal accumulation (brt_temporal.h) between them.  The demodulation: ds.dm, ds.aux, and
+// with keep_input a copy of d_in in ds.cv[0].  The filter: from ds.dm into d_out; temporal_moments != nullptr: ds.dm holds {h.rgb, n}
+// and the moments plane {m1, m2, ..} of a temporal frame, whose noise estimate and strength are then per pixel
+hipError_t launch_denoise_demod(const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, bool keep_input, hipStream_t stream);
+hipError_t launch_denoise_filter(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, void* d_out,
+                                 uint32_t out_format, hipStream_t stream, const float4* temporal_moments = nullptr);
 
 }  // namespace brt

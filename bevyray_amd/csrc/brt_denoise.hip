@@ -13,6 +13,7 @@
 
 #include "brt_denoise.h"
 #include "brt_store.h"
+#include "brt_temporal.h"
 
 namespace brt {
 
@@ -34,6 +35,10 @@ struct PassArgs {
     const float2* aux;
     const float4* dm;       // the demodulated input {c', var0}: what the last pass blends towards (strength < 1)
     float strength;         // the last pass returns c'_0 + strength (c'_out - c'_0)
+    // a temporal frame: dm holds {h.rgb, n}, and the strength k = min(1, sqrt(kStrengthSpp / (spp n))) is per pixel; sigma_l (unscaled
+    // here) is scaled by k below kTemporalConverged, where the variance also comes from the 7x7 neighbourhood, else from the moments
+    const float4* moments;  // {m1, m2, ..}; nullptr: not a temporal frame
+    float spp;
     const float4* cv_in;
     float4* cv_out;
 };
@@ -52,7 +57,8 @@ BRT_DEV float edge_log2(f3 np, float tp, float zscale, float4 gq, float dist, fl
 
 template <bool D16>
 __global__ __launch_bounds__(256) void k_denoise_guides(DeviceSceneView sv, FrameParams fp, float4* __restrict__ g0,
-                                                        float4* __restrict__ g1) {
+                                                        float4* __restrict__ g1, const uint32_t* __restrict__ rmap,
+                                                        uint32_t* __restrict__ sid) {
     const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
     if (px >= fp.width || py >= fp.height) return;
     ScenePtrs sc;                      // the scene in global memory, as k_trace_simple walks it
@@ -83,8 +89,10 @@ __global__ __launch_bounds__(256) void k_denoise_guides(DeviceSceneView sv, Fram
     if (t == kInf) {
         g0[p] = make_float4(0.0f, 0.0f, 0.0f, kSky);
         g1[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(kPassThrough));
+        if (sid) sid[p] = kPassThrough;
         return;
     }
+    if (sid) sid[p] = rmap ? rmap[idx] : idx;      // (the resident order is the caller's unless the hot order renumbered it)
     const float4 s = sc.spheres[idx];
     const f3 pos = mk3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z);           // ray_at (raytrace.wgsl:130-132)
     const f3 n = normalize3(mk3(pos.x - s.x, pos.y - s.y, pos.z - s.z));      // the shading normal (:356)
@@ -100,11 +108,13 @@ __global__ __launch_bounds__(256) void k_denoise_guides(DeviceSceneView sv, Fram
 
 // cv = {c / a, 0} for a hit pixel with a finite colour; {c.rgb, -1} (passes through, never a tap) for sky and non-finite pixels
 __global__ __launch_bounds__(256) void k_denoise_demod(FrameParams fp, const float4* __restrict__ in, const float4* __restrict__ g0,
-                                                       const float4* __restrict__ g1, float4* __restrict__ cv, float2* __restrict__ aux) {
+                                                       const float4* __restrict__ g1, float4* __restrict__ cv, float2* __restrict__ aux,
+                                                       float4* __restrict__ keep) {
     const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
     if (px >= fp.width || py >= fp.height) return;
     const uint32_t p = py * fp.width + px;
     const float4 c = in[p], g = g0[p], a = g1[p];
+    if (keep) keep[p] = c;
     const float4 cd = make_float4(c.x / a.x, c.y / a.y, c.z / a.z, 0.0f);
     const bool through = !(g.w < kSky) || !finite3(c) || !finite3(cd);
     // depth scale of the pixel: t * theta_px / max(|n . dir|, 0.1), theta_px = 2 tan(fov / 2) / height
@@ -127,6 +137,11 @@ __global__ __launch_bounds__(256) void k_denoise_variance(PassArgs pa) {
     const uint32_t p = py * pa.width + px;
     const float4 cp = pa.cv_in[p];
     if (cp.w < 0.0f) { pa.cv_out[p] = cp; return; }
+    if (pa.moments && cp.w >= kTemporalConverged) {             // a converged history: the noise of h is var(l) / n
+        const float4 m = pa.moments[p];
+        pa.cv_out[p] = make_float4(cp.x, cp.y, cp.z, max_f(0.0f, m.y - m.x * m.x) / cp.w);
+        return;
+    }
     const float4 gp = pa.g0[p];
     const f3 np = mk3(gp.x, gp.y, gp.z);
     const float zscale = pa.aux[p].y;
@@ -180,7 +195,13 @@ __global__ __launch_bounds__(256) void k_denoise_pass(PassArgs pa, typename OutP
             gw = gw + k;
         }
     }
-    const float inv_l = 1.0f / (pa.sigma_l * __builtin_sqrtf(max_f(0.0f, gv / gw)) + 1e-6f);
+    float sigma_l = pa.sigma_l, strength = pa.strength;
+    if (pa.moments) {
+        const float n = pa.dm[p].w;
+        strength = min_f(1.0f, __builtin_sqrtf((float)kStrengthSpp / (pa.spp * n)));
+        if (n < kTemporalConverged) sigma_l = pa.sigma_l * strength;
+    }
+    const float inv_l = 1.0f / (sigma_l * __builtin_sqrtf(max_f(0.0f, gv / gw)) + 1e-6f);
     const float4 gp = pa.g0[p];
     const f3 np = mk3(gp.x, gp.y, gp.z);
     const float zscale = pa.aux[p].y;
@@ -211,7 +232,7 @@ __global__ __launch_bounds__(256) void k_denoise_pass(PassArgs pa, typename OutP
     const float4 c = make_float4(sr / sw, sg / sw, sb / sw, sv / (sw * sw));
     if (LAST) {
         const float4 a = pa.g1[p], c0 = pa.dm[p];
-        const float r = c0.x + pa.strength * (c.x - c0.x), g = c0.y + pa.strength * (c.y - c0.y), b = c0.z + pa.strength * (c.z - c0.z);
+        const float r = c0.x + strength * (c.x - c0.x), g = c0.y + strength * (c.y - c0.y), b = c0.z + strength * (c.z - c0.z);
         out[p] = OutPixel<FMT>::make(make_float4(r * a.x, g * a.y, b * a.z, pa.aux[p].x));
     } else {
         pa.cv_out[p] = c;
@@ -240,11 +261,12 @@ DenoiseScratch denoise_scratch(char* base, uint32_t width, uint32_t height) {
 
 static dim3 tiles_of(uint32_t width, uint32_t height) { return dim3((width + kTile - 1u) / kTile, (height + kTile - 1u) / kTile); }
 
-hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& fp, const DenoiseScratch& ds, hipStream_t stream) {
+hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& fp, const DenoiseScratch& ds, hipStream_t stream,
+                                 const uint32_t* rmap, uint32_t* sid) {
     if (sv.desc16)
-        hipLaunchKernelGGL(k_denoise_guides<true>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1);
+        hipLaunchKernelGGL(k_denoise_guides<true>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1, rmap, sid);
     else
-        hipLaunchKernelGGL(k_denoise_guides<false>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1);
+        hipLaunchKernelGGL(k_denoise_guides<false>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1, rmap, sid);
     return hipGetLastError();
 }
 
@@ -256,17 +278,29 @@ static void launch_last_t(const PassArgs& pa, void* out, hipStream_t stream) {
 
 hipError_t launch_denoise(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, const float* d_in, void* d_out,
                           uint32_t out_format, hipStream_t stream) {
+    const hipError_t e = launch_denoise_demod(fp, ds, d_in, false, stream);
+    return e != hipSuccess ? e : launch_denoise_filter(fp, st, ds, d_out, out_format, stream);
+}
+
+hipError_t launch_denoise_demod(const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, bool keep_input, hipStream_t stream) {
+    hipLaunchKernelGGL(k_denoise_demod, tiles_of(fp.width, fp.height), dim3(256), 0, stream, fp, reinterpret_cast<const float4*>(d_in),
+                       ds.g0, ds.g1, ds.dm, ds.aux, keep_input ? ds.cv[0] : nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_denoise_filter(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, void* d_out,
+                                 uint32_t out_format, hipStream_t stream, const float4* temporal_moments) {
     const dim3 grid = tiles_of(fp.width, fp.height);
-    hipLaunchKernelGGL(k_denoise_demod, grid, dim3(256), 0, stream, fp, reinterpret_cast<const float4*>(d_in), ds.g0, ds.g1, ds.dm,
-                       ds.aux);
     PassArgs pa;
     pa.width = fp.width;
     pa.height = fp.height;
     pa.step = 1u;
     // the noise std of the frame falls as 1 / sqrt(spp): above kStrengthSpp samples the luminance tolerance and the strength fall with it
     const float k = fp.sample_count > kStrengthSpp ? __builtin_sqrtf((float)kStrengthSpp / (float)fp.sample_count) : 1.0f;
-    pa.sigma_l = st.sigma_l * k;
+    pa.sigma_l = temporal_moments ? st.sigma_l : st.sigma_l * k;
     pa.strength = k;
+    pa.moments = temporal_moments;
+    pa.spp = (float)fp.sample_count;
     pa.dm = ds.dm;
     pa.sigma_n = st.sigma_n;
     pa.sigma_z = st.sigma_z;

@@ -227,6 +227,15 @@ public:
     void set_denoise(uint32_t iterations = 5, float sigma_luminance = 4.0f, float sigma_normal = 128.0f, float sigma_depth = 1.0f) {
         check(brt_set_denoise(ctx_, iterations, sigma_luminance, sigma_normal, sigma_depth), ctx_);
     }
+    // the temporal history of BRT_FLAG_TEMPORAL frames (brt_set_temporal: 1..65535, empties it; brt_reset_temporal: on a camera cut)
+    void set_temporal(uint32_t max_history = 32) { check(brt_set_temporal(ctx_, max_history), ctx_); }
+    void reset_temporal() { check(brt_reset_temporal(ctx_), ctx_); }
+    // diagnostic: h.rgb, n, m1, m2, x', y' per pixel of the history after the last temporal frame (brt_debug_temporal_state)
+    std::vector<float> debug_temporal_state(uint32_t width, uint32_t height) {
+        std::vector<float> out(static_cast<size_t>(width) * height * 8);
+        check(brt_debug_temporal_state(ctx_, width, height, out.data()), ctx_);
+        return out;
+    }
     // one process per GPU: the strips dealt out to the ranks by measured cost instead of s % world (brt_plan_strips: every rank computes
     // the same table from the same probe frame; an empty vector to set_strip_table: back to s % world)
     std::vector<uint32_t> plan_strips(const std::pair<RaytraceLevelExtract, CameraExtract>& view, const WindowExtract& window, uint32_t width,

@@ -53,6 +53,7 @@ POLICY_POW_EXP2_LOG2 = 4      # ... pow(x, 5) as exp2(5 log2 x) (default: multip
 EXTMEM_OPAQUE_FD, EXTMEM_DMABUF_FD = 1, 2   # brt_import_frame_fd handle types
 FLAG_CALLER_STREAM = 4   # device entry points: `stream` is the caller's stream even when its handle is 0
 FLAG_DENOISE = 32        # brt_render / brt_render_device (level 3): the frame is denoised (RaytracePlugin.set_denoise) before it is written
+FLAG_TEMPORAL = 64       # ... and brt_denoise_device: the frame is accumulated into the context's temporal history (set_temporal)
 # format of an assembled DEVICE frame (render_device, gather_rccl, deinterleave_device): the colour target's own (pipeline.rs:311-315)
 FLAG_OUT_RGBA32F, FLAG_OUT_RGBA8_UNORM_SRGB, FLAG_OUT_RGBA16F, FLAG_OUT_RGBA8_UNORM = 0, 8, 16, 24
 OUT_PIXEL_BYTES = {FLAG_OUT_RGBA32F: 16, FLAG_OUT_RGBA8_UNORM_SRGB: 4, FLAG_OUT_RGBA16F: 8, FLAG_OUT_RGBA8_UNORM: 4}
@@ -353,6 +354,22 @@ class RaytracePlugin:
                                                       out.ctypes.data), self._ctx)
         return out
 
+    def set_temporal(self, max_history: int = 32) -> None:
+        """brt_set_temporal: the history length FLAG_TEMPORAL frames accumulate up to (1..65535; 1: no accumulation); empties the
+        history.  An invalid value raises BrtError and changes nothing."""
+        _lib.check(self._lib.brt_set_temporal(self._ctx, int(max_history)), self._ctx)
+
+    def reset_temporal(self) -> None:
+        """brt_reset_temporal: empties the temporal history (call it on a camera cut)."""
+        _lib.check(self._lib.brt_reset_temporal(self._ctx), self._ctx)
+
+    def debug_temporal_state(self, width: int, height: int) -> np.ndarray:
+        """brt_debug_temporal_state: (height, width, 8) f32 -- h.rgb, n, m1, m2, x', y' of the history after the last FLAG_TEMPORAL
+        frame (x', y': the reprojected position; NaN where the history was rejected)."""
+        out = np.empty((height, width, 8), np.float32)
+        _lib.check(self._lib.brt_debug_temporal_state(self._ctx, width, height, out.ctypes.data), self._ctx)
+        return out
+
     def alloc_frame(self, width: int, height: int) -> np.ndarray:
         """Page-locked (height, width, 4) f32 frame owned by the context (brt_host_alloc): passing it
         as `out` to RayTracingNode.run lets the library DMA straight into it."""
@@ -569,13 +586,14 @@ class RayTracingNode:
         return self.last_stats
 
     def denoise_device(self, camera, window, width: int, height: int, d_frame: int, d_out: int, stream: Optional[int] = None,
-                       out_format: int = FLAG_OUT_RGBA32F) -> dict:
+                       out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
         """brt_denoise_device: the context's denoiser on the RGBA f32 device frame d_frame (rendered with camera / window on the
-        resident scene) into d_out (out_format: FLAG_OUT_*; may be d_frame).  Stream rule as for render_part_device."""
+        resident scene) into d_out (out_format: FLAG_OUT_*; may be d_frame).  Stream rule as for render_part_device.  flags:
+        FLAG_TEMPORAL accumulates into the temporal history instead, and FLAG_TEMPORAL | FLAG_DENOISE filters the accumulation."""
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_denoise_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_frame, d_out,
-                                             stream or None, (0 if stream is None else FLAG_CALLER_STREAM) | out_format,
+                                             stream or None, (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
                                              C.byref(stats)), p._ctx)
         return stats.as_dict()
 

@@ -102,7 +102,13 @@ enum {
      * Level 3 (Pure) only: BRT_ERR_UNSUPPORTED at levels 0-2 (the raster blend of levels 1 / 2 leaves no mark of the pixels that took
      * the raster colour) and on brt_render_part_device / brt_gather_rccl / brt_deinterleave_device (a rank's strips have no
      * neighbours: denoise the assembled frame with brt_denoise_device).  The denoiser's time is part of brt_stats::total_ms only. */
-    BRT_FLAG_DENOISE = 32u
+    BRT_FLAG_DENOISE = 32u,
+    /* brt_render / brt_render_device / brt_denoise_device: the frame is traced exactly as without the flag, then accumulated into the
+     * context's temporal history (brt_set_temporal) on the first device: reprojected through the camera and sphere motion, blended with
+     * alpha = 1 / n.  Alone: the accumulated frame is written.  With BRT_FLAG_DENOISE: the denoiser filters the accumulation.  A frame
+     * with an empty history is bit-identical to the same frame without the flag.  Same restrictions as BRT_FLAG_DENOISE (level 3; not on
+     * brt_render_part_device / brt_gather_rccl / brt_deinterleave_device). */
+    BRT_FLAG_TEMPORAL = 64u
 };
 
 typedef struct brt_ctx brt_ctx;
@@ -344,12 +350,35 @@ int32_t brt_debug_eval(brt_ctx* ctx, uint32_t op, const float* in16, float* out8
  *                            BRT_FLAG_OUT_* format of `flags`; may equal d_frame_rgba).  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*
  *                            (and BRT_FLAG_DENOISE, implied); other bits BRT_ERR_INVALID_ARGUMENT.  Stream rule as for
  *                            brt_render_device; stats_or_null: total_ms only.  BRT_ERR_NO_SCENE before an upload.
+ *                            With BRT_FLAG_TEMPORAL the frame is accumulated into the temporal history, and denoised only if
+ *                            BRT_FLAG_DENOISE is set as well (the per-rank form: the root accumulates the assembled frame).
  *   brt_debug_denoise_guides diagnostic: the guide buffer of that frame, out8[(y * width + x) * 8 + k] = normal.xyz, t (+INF: no hit),
  *                            a.rgb (the demodulation factor), material id as bits (0xFFFFFFFF: no hit).  Host memory, synchronous. */
 int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance, float sigma_normal, float sigma_depth);
 int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                            const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
 int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, float* out8);
+
+/* ---- temporal accumulation ---------------------------------------------------------------------------------------------------------
+ * The context keeps, on its first device, a per-pixel history of BRT_FLAG_TEMPORAL frames: the accumulated demodulated colour, the two
+ * moments of its luminance, a history length n, and the previous frame's guides.  Every temporal frame carries each hit pixel's first
+ * hit back through its sphere's motion and into the previous camera, keeps the bilinear taps of the history there that lie on the same
+ * sphere and material with a similar normal and distance, and blends its demodulated colour in with alpha = 1 / min(n + 1, max_history).
+ * Sky and non-finite pixels pass through.  Formulas: DESIGN.md "Temporal accumulation".  Deterministic.
+ * The history is emptied by brt_reset_temporal (call it on a camera cut), by a frame of another width or height, by an upload with
+ * another sphere or material count, and by brt_set_temporal.  Frames without the flag neither read nor change it.  One temporal frame
+ * per context is in flight: the next one is ordered behind it on any stream.  Samples come from brt_window's random_seed: a caller who
+ * renders the same seed twice adds no new samples, only weight to the old ones -- change the seed every frame.
+ *   brt_set_temporal           max_history 1..65535 (default 32; 1: no accumulation), and an empty history.  Else
+ *                              BRT_ERR_INVALID_ARGUMENT, settings unchanged.
+ *   brt_reset_temporal         an empty history.
+ *   brt_debug_temporal_state   diagnostic: the history after the last temporal frame, out8[(y * width + x) * 8 + k] = h.rgb, n, m1, m2,
+ *                              x', y' (the reprojected position in the previous frame; NaN where the history was rejected, the pixel
+ *                              itself in the identity case).  An empty history: n = 0, x' = y' = NaN everywhere.  Host memory,
+ *                              synchronous.  BRT_ERR_INVALID_ARGUMENT for a size other than the history's. */
+int32_t brt_set_temporal(brt_ctx* ctx, uint32_t max_history);
+int32_t brt_reset_temporal(brt_ctx* ctx);
+int32_t brt_debug_temporal_state(brt_ctx* ctx, uint32_t width, uint32_t height, float* out8);
 
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how

@@ -15,7 +15,7 @@ for f in brt_api brt_interop brt_host; do
 done
 g++ -shared -fPIC -fsanitize=address,undefined -o "$out/libbrt_asan.so" "$out"/brt_api.o "$out"/brt_interop.o "$out"/brt_host.o \
     "$src"/build/brt_kernels.o "$src"/build/brt_trace_prod.o "$src"/build/brt_trace_tune.o "$src"/build/brt_bvh.o "$src"/build/brt_sah.o \
-    "$src"/build/brt_order.o "$src"/build/brt_denoise.o -L/opt/rocm/lib -lamdhip64 -ldl
+    "$src"/build/brt_order.o "$src"/build/brt_denoise.o "$src"/build/brt_temporal.o -L/opt/rocm/lib -lamdhip64 -ldl
 asan="$(g++ -print-file-name=libasan.so)"
 ubsan="$(g++ -print-file-name=libubsan.so)"
 cd "$root"
