@@ -1,6 +1,7 @@
 """numpy float32 restatement of the denoiser (DESIGN.md "Denoiser", bevyray_amd/csrc/brt_denoise.hip): the guide buffer from the CPU
 oracle's raycast on pixel-centre rays, and the a-trous filter with its formulas as written (pow and the two exps evaluated separately;
-the kernel folds them into one exp2, hence the tolerance of the GPU comparison)."""
+the kernel folds them into one exp2, hence the tolerance of the GPU comparison).  np.fmax / np.fmin stand for the kernel's max_f /
+min_f (fmaxf / fminf: max(0, NaN) is 0)."""
 import ctypes as C
 
 import numpy as np
@@ -56,7 +57,7 @@ def guides(oracle, buffers, cam, w, h):
             out[y, x, :4] = [r7[4], r7[5], r7[6], t]
             m = mats[mid.value]
             if F32(m["specular_transmission"]) == 0:
-                out[y, x, 4:7] = np.sqrt(np.maximum(m["base_color"].astype(F32), F32(1e-3)))
+                out[y, x, 4:7] = np.sqrt(np.fmax(m["base_color"].astype(F32), F32(1e-3)))
             else:
                 out[y, x, 4:7] = 1
             out[y, x, 7:8].view(np.uint32)[0] = mid.value
@@ -105,7 +106,7 @@ def denoise(frame, g, dirs, tan_half_fov, iterations=5, sigma_l=4.0, sigma_n=128
         fin = np.isfinite(frame[..., :3]).all(-1) & np.isfinite(cd).all(-1)
         through = ~(t < INF) | ~fin
         theta = (F32(2.0) * F32(tan_half_fov)) / F32(h)
-        zscale = np.where(through, F32(0), (t * theta) / np.maximum(np.abs(_dot(n, dirs)), F32(0.1))).astype(F32)
+        zscale = np.where(through, F32(0), (t * theta) / np.fmax(np.abs(_dot(n, dirs)), F32(0.1))).astype(F32)
         cv = np.concatenate([cd, np.zeros((h, w, 1), F32)], -1).astype(F32)
         cv[through] = np.concatenate([frame[..., :3], -np.ones((h, w, 1), F32)], -1)[through]
         c0 = cv[..., :3].copy()
@@ -113,7 +114,7 @@ def denoise(frame, g, dirs, tan_half_fov, iterations=5, sigma_l=4.0, sigma_n=128
         fill_cv = np.array([0, 0, 0, -1], F32)
 
         def edge(dx, dy, step, cq, g0q):
-            nd = np.maximum(F32(0), _dot(n, g0q[..., :3]))
+            nd = np.fmax(F32(0), _dot(n, g0q[..., :3]))
             wn = np.power(nd, sigma_n).astype(F32)
             dist = F32(step) * np.sqrt(F32(dx * dx + dy * dy))
             wz = np.exp(-np.abs(t - g0q[..., 3]) / ((sigma_z * dist) * zscale + F32(1e-6))).astype(F32)
@@ -128,13 +129,13 @@ def denoise(frame, g, dirs, tan_half_fov, iterations=5, sigma_l=4.0, sigma_n=128
             for dx in range(-3, 4):
                 cq, g0q = _taps(cv, g0, dx, dy)
                 wn, wz = edge(dx, dy, 1, cq, g0q)
-                wgt = np.where(cq[..., 3] >= 0, wn * wz, F32(0)).astype(F32)
+                wgt = np.where(~(cq[..., 3] < 0), wn * wz, F32(0)).astype(F32)
                 lq = _lum(cq)
                 sw = sw + wgt
                 sl = sl + wgt * lq
                 sl2 = sl2 + wgt * (lq * lq)
         mean = sl / sw
-        cv[..., 3] = np.where(through, F32(-1), np.maximum(F32(0), sl2 / sw - mean * mean))
+        cv[..., 3] = np.where(through, F32(-1), np.fmax(F32(0), sl2 / sw - mean * mean))
 
         for i in range(iterations):
             step = 1 << i
@@ -144,10 +145,10 @@ def denoise(frame, g, dirs, tan_half_fov, iterations=5, sigma_l=4.0, sigma_n=128
                 for dx in range(-1, 2):
                     vq = _shift(cv, dx, dy, fill_cv)[..., 3]
                     k = F32((0.5 if dx == 0 else 0.25) * (0.5 if dy == 0 else 0.25))
-                    ok = vq >= 0
+                    ok = ~(vq < 0)                  # (the kernel skips var < 0 only: a NaN variance is a tap)
                     gv = gv + np.where(ok, k * vq, F32(0))
                     gw = gw + np.where(ok, k, F32(0))
-            lscale = sigma_l * np.sqrt(np.maximum(F32(0), gv / gw)) + F32(1e-6)
+            lscale = sigma_l * np.sqrt(np.fmax(F32(0), gv / gw)) + F32(1e-6)
             lp = _lum(cv)
             sw = np.zeros((h, w), F32)
             sc = np.zeros((h, w, 3), F32)
@@ -157,7 +158,7 @@ def denoise(frame, g, dirs, tan_half_fov, iterations=5, sigma_l=4.0, sigma_n=128
                     cq, g0q = _taps(cv, g0, dx * step, dy * step)
                     wn, wz = edge(dx, dy, step, cq, g0q)
                     wl = np.exp(-np.abs(lp - _lum(cq)) / lscale).astype(F32)
-                    wgt = np.where(cq[..., 3] >= 0, (((H5[dx + 2] * H5[dy + 2]) * wn) * wz) * wl, F32(0)).astype(F32)
+                    wgt = np.where(~(cq[..., 3] < 0), (((H5[dx + 2] * H5[dy + 2]) * wn) * wz) * wl, F32(0)).astype(F32)
                     sw = sw + wgt
                     sc = sc + wgt[..., None] * cq[..., :3]
                     sv = sv + (wgt * wgt) * cq[..., 3]

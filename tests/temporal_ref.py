@@ -86,15 +86,17 @@ def sphere_ids(g, cam, models):
     idx = np.flatnonzero(hit.ravel())
     x = (cam.o[None, :] + t.ravel()[idx, None] * cam.dirs.reshape(-1, 3)[idx]).astype(np.float64)
     mid = g[..., 7].view(U32).ravel()[idx].astype(np.int64)
-    for k in range(0, len(idx), 4096):
-        xs, ms = x[k:k + 4096], mid[k:k + 4096]
-        e = np.abs(np.sqrt(((xs[:, None, :] - c[None, :, :]) ** 2).sum(-1)) - r[None, :])
-        e[mat[None, :] != ms[:, None]] = np.inf
-        order = np.argsort(e, axis=1)[:, :2]
-        best = np.take_along_axis(e, order, 1)
-        sid.ravel()[idx[k:k + 4096]] = order[:, 0]
-        if e.shape[1] > 1:
-            ties.ravel()[idx[k:k + 4096]] = best[:, 1] - best[:, 0] < TIE
+    for m in np.unique(mid):                         # (the candidates of a pixel are the spheres of its material: one group each)
+        cand = np.flatnonzero(mat == m)
+        rows = np.flatnonzero(mid == m)
+        for k in range(0, len(rows), 4096):
+            r_ = rows[k:k + 4096]
+            e = np.abs(np.sqrt(((x[r_, None, :] - c[None, cand, :]) ** 2).sum(-1)) - r[None, cand])
+            order = np.argsort(e, axis=1, kind="stable")[:, :2]
+            best = np.take_along_axis(e, order, 1)
+            sid.ravel()[idx[r_]] = cand[order[:, 0]]
+            if len(cand) > 1:
+                ties.ravel()[idx[r_]] = best[:, 1] - best[:, 0] < TIE
     return sid, ties
 
 
@@ -180,7 +182,7 @@ def accumulate(hist, frame, g, sid, cam, spheres, motion=True):
                 ok &= (cq[..., 2].view(U32) == sid) & (cq[..., 3].view(U32) == mid)
                 ok &= _dot(n_p, aq[..., :3]) >= NORMAL_MIN
                 dq = pc.ray_dirs(qxc, qyc)
-                zs = (aq[..., 3] * theta) / np.maximum(np.abs(_dot(aq[..., :3], dq)), F32(0.1))
+                zs = (aq[..., 3] * theta) / np.fmax(np.abs(_dot(aq[..., :3], dq)), F32(0.1))
                 ok &= np.abs(aq[..., 3] - dist) <= DEPTH_REL * dist + DEPTH_ZS * zs
                 ok &= bq[..., 3] > 0
                 wz = np.where(ok, w, F32(0))
@@ -192,7 +194,7 @@ def accumulate(hist, frame, g, sid, cam, spheres, motion=True):
         hp = np.concatenate([cd, np.ones((H, W, 1), F32)], -1).astype(F32)
         m1, m2 = l.astype(F32), (l * l).astype(F32)
         valid = (sw > 0) & ~through
-        n = np.minimum(sn_ / sw + F32(1.0), hist.max_history).astype(F32)
+        n = np.fmin(sn_ / sw + F32(1.0), hist.max_history).astype(F32)
         blend = valid & (n > 1)
         alpha = F32(1.0) / n
         for k, s_ in enumerate((sr, sg, sb)):
@@ -237,12 +239,12 @@ def denoise(frame, g, dirs, tan_half_fov, hp, moments, through, iterations=5, si
     h, w = frame.shape[:2]
     n = hp[..., 3]
     with np.errstate(all="ignore"):
-        k = np.minimum(F32(1.0), np.sqrt(F32(dr.STRENGTH_SPP) / (F32(spp) * n))).astype(F32)
+        k = np.fmin(F32(1.0), np.sqrt(F32(dr.STRENGTH_SPP) / (F32(spp) * n))).astype(F32)
         sl = np.where(n < CONVERGED, F32(sigma_l) * k, F32(sigma_l)).astype(F32)
         sigma_n, sigma_z = F32(sigma_n), F32(sigma_z)
         nrm, t, a = g[..., 0:3], g[..., 3], g[..., 4:7]
         theta = (F32(2.0) * F32(tan_half_fov)) / F32(h)
-        zscale = np.where(through, F32(0), (t * theta) / np.maximum(np.abs(dr._dot(nrm, dirs)), F32(0.1))).astype(F32)
+        zscale = np.where(through, F32(0), (t * theta) / np.fmax(np.abs(dr._dot(nrm, dirs)), F32(0.1))).astype(F32)
         cv = np.concatenate([hp[..., :3], np.zeros((h, w, 1), F32)], -1).astype(F32)
         cv[through] = np.concatenate([frame[..., :3], -np.ones((h, w, 1), F32)], -1)[through]
         c0 = cv[..., :3].copy()
@@ -250,7 +252,7 @@ def denoise(frame, g, dirs, tan_half_fov, hp, moments, through, iterations=5, si
         fill_cv = np.array([0, 0, 0, -1], F32)
 
         def edge(dx, dy, step, g0q):
-            nd = np.maximum(F32(0), dr._dot(nrm, g0q[..., :3]))
+            nd = np.fmax(F32(0), dr._dot(nrm, g0q[..., :3]))
             wn = np.power(nd, sigma_n).astype(F32)
             dist = F32(step) * np.sqrt(F32(dx * dx + dy * dy))
             wz = np.exp(-np.abs(t - g0q[..., 3]) / ((sigma_z * dist) * zscale + F32(1e-6))).astype(F32)
@@ -263,14 +265,14 @@ def denoise(frame, g, dirs, tan_half_fov, hp, moments, through, iterations=5, si
             for dx in range(-3, 4):
                 cq, g0q = dr._taps(cv, g0, dx, dy)
                 wn, wz = edge(dx, dy, 1, g0q)
-                wgt = np.where(cq[..., 3] >= 0, wn * wz, F32(0)).astype(F32)
+                wgt = np.where(~(cq[..., 3] < 0), wn * wz, F32(0)).astype(F32)
                 lq = dr._lum(cq)
                 sw = sw + wgt
                 s_l = s_l + wgt * lq
                 sl2 = sl2 + wgt * (lq * lq)
         mean = s_l / sw
-        var7 = np.maximum(F32(0), sl2 / sw - mean * mean)
-        var_m = np.maximum(F32(0), moments[..., 1] - moments[..., 0] * moments[..., 0]) / n
+        var7 = np.fmax(F32(0), sl2 / sw - mean * mean)
+        var_m = np.fmax(F32(0), moments[..., 1] - moments[..., 0] * moments[..., 0]) / n
         cv[..., 3] = np.where(through, F32(-1), np.where(n >= CONVERGED, var_m, var7))
 
         for i in range(iterations):
@@ -281,10 +283,10 @@ def denoise(frame, g, dirs, tan_half_fov, hp, moments, through, iterations=5, si
                 for dx in range(-1, 2):
                     vq = dr._shift(cv, dx, dy, fill_cv)[..., 3]
                     kk = F32((0.5 if dx == 0 else 0.25) * (0.5 if dy == 0 else 0.25))
-                    ok = vq >= 0
+                    ok = ~(vq < 0)                  # (the kernel skips var < 0 only: a NaN variance is a tap)
                     gv = gv + np.where(ok, kk * vq, F32(0))
                     gw = gw + np.where(ok, kk, F32(0))
-            lscale = sl * np.sqrt(np.maximum(F32(0), gv / gw)) + F32(1e-6)
+            lscale = sl * np.sqrt(np.fmax(F32(0), gv / gw)) + F32(1e-6)
             lp = dr._lum(cv)
             sw = np.zeros((h, w), F32)
             sc = np.zeros((h, w, 3), F32)
@@ -294,7 +296,7 @@ def denoise(frame, g, dirs, tan_half_fov, hp, moments, through, iterations=5, si
                     cq, g0q = dr._taps(cv, g0, dx * step, dy * step)
                     wn, wz = edge(dx, dy, step, g0q)
                     wl = np.exp(-np.abs(lp - dr._lum(cq)) / lscale).astype(F32)
-                    wgt = np.where(cq[..., 3] >= 0, (((dr.H5[dx + 2] * dr.H5[dy + 2]) * wn) * wz) * wl, F32(0)).astype(F32)
+                    wgt = np.where(~(cq[..., 3] < 0), (((dr.H5[dx + 2] * dr.H5[dy + 2]) * wn) * wz) * wl, F32(0)).astype(F32)
                     sw = sw + wgt
                     sc = sc + wgt[..., None] * cq[..., :3]
                     sv = sv + (wgt * wgt) * cq[..., 3]
