@@ -788,7 +788,7 @@ void free_device(DeviceCtx& dc) {
     if (dc.d_tile) (void)hipFree(dc.d_tile);
     if (dc.d_gather) (void)hipFree(dc.d_gather);
     if (dc.d_pack) (void)hipFree(dc.d_pack);
-    for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack})
+    for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack, dc.ev_strip, dc.ev_strip_read})
         if (e) (void)hipEventDestroy(e);
     if (dc.d_raster_rgba) (void)hipFree(dc.d_raster_rgba);
     if (dc.d_raster_depth) (void)hipFree(dc.d_raster_depth);
@@ -939,11 +939,15 @@ int32_t brt_create(const int32_t* device_ids, int32_t n_devices, brt_ctx** out_c
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_in, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_pack, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_dn, hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_strip, hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_strip_read, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreate(&dc.ev_g0));
             HIP_TRY(ctx, hipEventCreate(&dc.ev_g1));
             HIP_TRY(ctx, hipEventRecord(dc.ev_asm, dc.stream));
             HIP_TRY(ctx, hipEventRecord(dc.ev_last, dc.stream));
             HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
+            HIP_TRY(ctx, hipEventRecord(dc.ev_strip, dc.stream));
+            HIP_TRY(ctx, hipEventRecord(dc.ev_strip_read, dc.stream));
             HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dc.d_ctrl), 512));
             return BRT_OK;
         };
@@ -1227,28 +1231,44 @@ bool strip_table_valid(const uint32_t* t, uint32_t n_strips, uint32_t n_parts) {
     }
     return true;
 }
-// the device copies for `part` on device dc (made once per table and part): *part_of_strip for the assembly, fp->strip_of for the kernel
+// The device copy of the table on dc, made once per table for every part, so that a call for another part rewrites nothing.  A new
+// table is written on `stream` behind every call that may still read the old one -- kernels (ev_last) and assemblies (ev_strip_read)
+// on any stream -- and every reader on another stream starts behind the write (ev_strip): a call uses the table in force when it is
+// called.  No host synchronisation while the table is unchanged.
 int32_t strip_table_attach(brt_ctx* ctx, DeviceCtx& dc, FrameParams* fp, const uint32_t** part_of_strip, hipStream_t stream) {
     if (part_of_strip) *part_of_strip = nullptr;
-    const uint32_t strips = fp ? (fp->height + BRT_STRIP_ROWS - 1u) / BRT_STRIP_ROWS : (uint32_t)ctx->strip_part.size();
-    const uint32_t n_parts = fp ? fp->n_parts : ctx->strip_n_parts;
+    const uint32_t strips = (fp->height + BRT_STRIP_ROWS - 1u) / BRT_STRIP_ROWS, n_parts = fp->n_parts;
     if (ctx->strip_part.empty() || ctx->strip_n_parts != n_parts || ctx->strip_part.size() != strips || n_parts < 2u) return BRT_OK;
-    const uint32_t part = fp ? fp->part : 0u, local = (strips + n_parts - 1u) / n_parts;
-    if (dc.strip_epoch != ctx->strip_epoch || dc.strip_part != part || !dc.d_strip_table) {
-        std::vector<uint32_t> h(ctx->strip_part);
-        h.resize((size_t)strips + local, 0xffffffu);                           // strip_of: a group without a strip of this part: padding
-        for (uint32_t s = 0; s < strips; s++)
-            if (ctx->strip_part[s] == part) h[(size_t)strips + s / n_parts] = s;
-        int32_t rc = ensure(ctx, &dc.d_strip_table, &dc.strip_table_cap, h.size() * 4u);
+    const uint32_t local = (strips + n_parts - 1u) / n_parts;
+    if (dc.strip_epoch != ctx->strip_epoch || !dc.d_strip_table) {
+        const size_t words = (size_t)strips + (size_t)n_parts * local;
+        HIP_TRY(ctx, hipEventSynchronize(dc.ev_strip));                      // the previous upload has read h_strip_table (a new table only)
+        if (dc.strip_table_cap < words * 4u)                                 // a larger buffer: the old one goes once nothing reads it
+            for (hipEvent_t e : {dc.ev_last, dc.ev_strip_read}) HIP_TRY(ctx, hipEventSynchronize(e));
+        int32_t rc = ensure(ctx, &dc.d_strip_table, &dc.strip_table_cap, words * 4u);
         if (rc != BRT_OK) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_strip_table, h.data(), h.size() * 4u, hipMemcpyHostToDevice, stream));
-        HIP_TRY(ctx, hipStreamSynchronize(stream));                            // (h is a local; once per table)
+        std::vector<uint32_t>& h = dc.h_strip_table;
+        h.assign(words, 0xffffffu);                                          // strip_of: a group without a strip of the part: padding
+        std::copy(ctx->strip_part.begin(), ctx->strip_part.end(), h.begin());
+        for (uint32_t s = 0; s < strips; s++) h[(size_t)strips + (size_t)ctx->strip_part[s] * local + s / n_parts] = s;
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_last, 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_strip_read, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_strip_table, h.data(), words * 4u, hipMemcpyHostToDevice, stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_strip, stream));
         dc.strip_epoch = ctx->strip_epoch;
-        dc.strip_part = part;
+    } else {
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_strip, 0));           // (written on another stream, perhaps not yet)
     }
     const uint32_t* d = reinterpret_cast<const uint32_t*>(dc.d_strip_table);
     if (part_of_strip) *part_of_strip = d;
-    if (fp) fp->strip_of = d + strips;
+    fp->strip_of = d + strips + (size_t)fp->part * local;
+    return BRT_OK;
+}
+// behind an assembly on `stream` that read the table: ev_strip_read then marks the end of it and of every assembly before it
+int32_t strip_table_read(brt_ctx* ctx, DeviceCtx& dc, const uint32_t* part_of_strip, hipStream_t stream) {
+    if (!part_of_strip) return BRT_OK;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_strip_read, 0));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_strip_read, stream));
     return BRT_OK;
 }
 uint64_t part_pixels_table(const brt_ctx* ctx, const FrameParams& fp) {
@@ -1882,11 +1902,12 @@ int32_t brt_render_device(brt_ctx* ctx, const void* camera80, const void* window
 int32_t brt_set_strip_table(brt_ctx* ctx, uint32_t n_parts, uint32_t n_strips, const uint32_t* part_of_strip) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    ctx->strip_epoch++;
-    if (!part_of_strip) { ctx->strip_part.clear(); ctx->strip_n_parts = 0u; return BRT_OK; }
+    if (!part_of_strip) { ctx->strip_epoch++; ctx->strip_part.clear(); ctx->strip_n_parts = 0u; return BRT_OK; }
+    // (a refused table changes nothing: the table in force stays)
     if (n_parts < 1u || n_strips < 1u || n_strips > 4096u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_parts / n_strips out of range");
     if (!strip_table_valid(part_of_strip, n_strips, n_parts))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "strip table: every group of n_parts consecutive strips must hold each part at most once");
+    ctx->strip_epoch++;
     ctx->strip_part.assign(part_of_strip, part_of_strip + n_strips);
     ctx->strip_n_parts = n_parts;
     return BRT_OK;
@@ -1947,10 +1968,12 @@ int32_t brt_deinterleave_device(brt_ctx* ctx, const float* d_tiles, uint32_t n_p
     {
         FrameParams key{};                                        // (which frame and split: the table must be one for them)
         key.height = height; key.n_parts = n_parts; key.part = 0u;
-        int32_t rc = strip_table_attach(ctx, ctx->devs[0], &key, &part_of_strip, stream);
+        int32_t rc = strip_table_attach(ctx, dc, &key, &part_of_strip, stream);
         if (rc != BRT_OK) return rc;
     }
     HIP_TRY(ctx, launch_deinterleave(d_tiles, d_frame, width, height, n_parts, brt_tile_rows(height, n_parts), flags & BRT_FLAG_OUT_MASK, stream, part_of_strip));
+    int32_t rc = strip_table_read(ctx, dc, part_of_strip, stream);
+    if (rc != BRT_OK) return rc;
     if (own_stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
     return BRT_OK;
     });

@@ -60,10 +60,14 @@ struct DeviceCtx {
     uint32_t order_crit = 0;                             // d_tile_order[0 .. crit) are the CRITICAL tiles
     size_t tile_order_cap = 0;
     uint32_t* d_order_meta = nullptr;                    // order built on the GPU: [0] critical tiles, [1] longest pixel
-    // strip table on this device (brt_set_strip_table): part_of_strip[n_strips], then strip_of[local_strips] of `strip_part`
+    // strip table on this device (brt_set_strip_table), made once per table: part_of_strip[n_strips], then strip_of[local_strips] of
+    // every part in turn -- a call for another part reads its own slice and rewrites nothing
     char* d_strip_table = nullptr;
     size_t strip_table_cap = 0;
-    uint32_t strip_epoch = 0, strip_part = 0xffffffffu;  // the ctx->strip_epoch / part the device copy was made for
+    uint32_t strip_epoch = 0;                            // the ctx->strip_epoch the device copy was made for
+    std::vector<uint32_t> h_strip_table;                 // the source of its upload (read by the copy after the call has returned)
+    hipEvent_t ev_strip = nullptr;                       // the device copy is written (a reader on another stream starts behind it)
+    hipEvent_t ev_strip_read = nullptr;                  // end of the last assembly that read it and of every one before (any stream)
     char* d_order_scratch = nullptr;
     size_t order_scratch_cap = 0;
     bool order_on_device = false;                        // d_tile_order / d_order_meta were written by brt_order.hip
@@ -222,9 +226,11 @@ void release_external_frames(brt_ctx* ctx);   // brt_interop.cpp; called by brt_
 }  // namespace brt
 
 namespace brt {
-// strip table (brt_api.cpp): the device copies for fp->part on dc; *part_of_strip (frame strip -> part) for the assembly, fp->strip_of
-// (this part's k-th local strip -> frame strip) for the kernel.  Nothing is attached when the context holds no table for fp's frame and split.
+// strip table (brt_api.cpp): the device copy on dc, for work on `stream`; *part_of_strip (frame strip -> part) for the assembly,
+// fp->strip_of (fp->part's k-th local strip -> frame strip) for the kernel.  Nothing is attached when the context holds no table for
+// fp's frame and split.  An assembly that got a table calls strip_table_read behind its launch.
 bool strip_table_valid(const uint32_t* part_of_strip, uint32_t n_strips, uint32_t n_parts);
 int32_t strip_table_attach(brt_ctx* ctx, DeviceCtx& dc, FrameParams* fp, const uint32_t** part_of_strip, hipStream_t stream);
+int32_t strip_table_read(brt_ctx* ctx, DeviceCtx& dc, const uint32_t* part_of_strip, hipStream_t stream);
 uint64_t part_pixels_table(const brt_ctx* ctx, const FrameParams& fp);
 }  // namespace brt

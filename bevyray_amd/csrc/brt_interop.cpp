@@ -205,6 +205,8 @@ int32_t brt_gather_rccl(brt_ctx* ctx, void* nccl_comm, int32_t rank, int32_t wor
         const int32_t rt = strip_table_attach(ctx, dc, &key, &part_of_strip, stream);
         if (rt != BRT_OK) return rt;
         HIP_TRY(ctx, launch_deinterleave(d_tiles_on_root, d_frame_on_root, width, height, (uint32_t)world, tile_rows, flags & BRT_FLAG_OUT_MASK, stream, part_of_strip));
+        const int32_t rr = strip_table_read(ctx, dc, part_of_strip, stream);
+        if (rr != BRT_OK) return rr;
     }
     if (own_stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
     return BRT_OK;

@@ -270,8 +270,13 @@ int32_t brt_deinterleave_device(brt_ctx* ctx, const float* d_tiles, uint32_t n_p
  * pixel's seed depends on its frame coordinates only (raytrace.wgsl:95).
  *   brt_set_strip_table   installs the table for frames of n_strips = ceil(height / 8) strips split n_parts ways (NULL: back to s % n_parts);
  *                         brt_render_part_device, brt_deinterleave_device and brt_gather_rccl of such frames use it; EVERY rank must set
- *                         the same table.  BRT_ERR_INVALID_ARGUMENT if a group holds a part twice.  (brt_render / brt_render_device -- one
- *                         context over N devices -- keep s % n_parts.)
+ *                         the same table.  BRT_ERR_INVALID_ARGUMENT (and brt_last_error) if a group holds a part twice or a part >= n_parts,
+ *                         if n_parts > 64 or n_strips > 4096: a refused table changes nothing, the table in force stays.  A frame whose
+ *                         height or split does not fit the table in force renders and assembles by s % n_parts, in render and assembly
+ *                         alike.  (brt_render / brt_render_device -- one context over N devices -- keep s % n_parts.)
+ *                         A call uses the table in force WHEN IT IS CALLED: calls still in flight on any stream keep the table they were
+ *                         called under, and a new table (or NULL) affects only the calls after it.  Changing the part from call to call
+ *                         rewrites nothing; with an unchanged table no call waits on the host for a caller's stream.
  *   brt_plan_strips       makes a table from measured costs and installs it: the frame of this camera is rendered once at `probe_spp`
  *                         samples per pixel on the context's first device with the per-tile ray counts switched on; per group the dearest
  *                         strip goes to the part with the least so far.  Deterministic: every rank of a job computes the same table from
