@@ -92,6 +92,7 @@ _PROTOTYPES = {
     "brt_debug_eval": (_I32, [_VP, _U32, _VP, _VP, _U32]),
     "brt_set_denoise": (_I32, [_VP, _U32, _F, _F, _F]),
     "brt_denoise_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_blend_post_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_debug_denoise_guides": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP]),
     "brt_set_temporal": (_I32, [_VP, _U32]),
     "brt_reset_temporal": (_I32, [_VP]),

@@ -1394,12 +1394,13 @@ int32_t temporal_begin(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, hipSt
 
 // guides of fp's frame on the resident scene, then the passes (BRT_FLAG_DENOISE) and / or the temporal accumulation
 // (BRT_FLAG_TEMPORAL) from d_in (RGBA32F) into d_out (out_format), on `stream` (which denoise_scratch_of has ordered behind the
-// previous denoise of the context)
+// previous denoise of the context).  bp.on: d_in is a coverage frame (BRT_FLAG_BLEND_POST / brt_blend_post_device)
 int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, void* d_out,
-                    uint32_t out_format, hipStream_t stream, uint32_t flags = BRT_FLAG_DENOISE) {
+                    uint32_t out_format, hipStream_t stream, uint32_t flags = BRT_FLAG_DENOISE, const BlendPost& bp = BlendPost()) {
+    const float* d_cov = bp.on ? d_in : nullptr;
     if (!(flags & BRT_FLAG_TEMPORAL)) {
-        HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream));
-        HIP_TRY(ctx, launch_denoise(fp, ctx->denoise, ds, d_in, d_out, out_format, stream));
+        HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream, nullptr, nullptr, d_cov));
+        HIP_TRY(ctx, launch_denoise(fp, ctx->denoise, ds, d_in, d_out, out_format, stream, bp));
         HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
         return BRT_OK;
     }
@@ -1409,10 +1410,10 @@ int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const De
     int32_t rc = temporal_begin(ctx, dc, fp, stream, &th, &ta, &rmap);
     if (rc != BRT_OK) return rc;
     const bool filter = (flags & BRT_FLAG_DENOISE) != 0u;
-    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream, rmap, th.sid));
+    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, stream, rmap, th.sid, d_cov));
     HIP_TRY(ctx, launch_denoise_demod(fp, ds, d_in, !filter, stream));
-    HIP_TRY(ctx, launch_temporal(fp, ctx->temporal.prev, ta, ds, th, filter ? nullptr : d_out, out_format, stream));
-    if (filter) HIP_TRY(ctx, launch_denoise_filter(fp, ctx->denoise, ds, d_out, out_format, stream, th.c[ta.prev ^ 1u]));
+    HIP_TRY(ctx, launch_temporal(fp, ctx->temporal.prev, ta, ds, th, filter ? nullptr : d_out, out_format, stream, bp));
+    if (filter) HIP_TRY(ctx, launch_denoise_filter(fp, ctx->denoise, ds, d_out, out_format, stream, th.c[ta.prev ^ 1u], bp));
     HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
     auto& tp = ctx->temporal;
     tp.valid = true;
@@ -1422,6 +1423,23 @@ int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const De
     tp.prev = fp;
     tp.prev_models = dc.view.n_models;
     tp.prev_epoch = ctx->scene_epoch;
+    return BRT_OK;
+}
+
+// BRT_FLAG_BLEND_POST takes effect at the levels that blend (1 / 2); level 3 ignores it (post_flags_check has refused the rest)
+bool blend_post_on(uint32_t level, uint32_t flags) {
+    return (flags & BRT_FLAG_BLEND_POST) != 0u && (level == BRT_LEVEL_FALLBACK_RASTER || level == BRT_LEVEL_FALLBACK_RAYTRACED);
+}
+
+// the post-pass flags of brt_render / brt_render_device against the level
+int32_t post_flags_check(brt_ctx* ctx, uint32_t level, uint32_t flags) {
+    const bool post = (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) != 0u;
+    if ((flags & BRT_FLAG_BLEND_POST) && !post)
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "BRT_FLAG_BLEND_POST needs BRT_FLAG_DENOISE and / or BRT_FLAG_TEMPORAL");
+    if (post && level != BRT_LEVEL_PURE && !blend_post_on(level, flags))
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, (flags & BRT_FLAG_BLEND_POST)
+                            ? "BRT_FLAG_BLEND_POST needs level 1, 2 or 3: level 0 traces nothing"
+                            : "BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL need level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
     return BRT_OK;
 }
 
@@ -1508,6 +1526,10 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
     const bool direct = is_pinned(ctx, out_rgba, frame_px * 16);
     const bool denoise = (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) != 0u;
     const uint32_t post = flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL);
+    // BRT_FLAG_BLEND_POST: the trace gets the depth and no raster colour (a coverage frame); the colour goes to the first device alone,
+    // whole, where the post-passes composite it
+    BlendPost bp;
+    bp.on = blend_post_on(level, flags);
 
     // launch every device, then collect: the devices trace their strips concurrently
     for (uint32_t p = 0; p < n_parts; p++) {
@@ -1541,10 +1563,16 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
                                             (size_t)(height - full * BRT_STRIP_ROWS) * width * px_bytes, hipMemcpyHostToDevice, dc.stream));
             return BRT_OK;
         };
-        if (raster_rgba) {
+        if (raster_rgba && !bp.on) {
             rc = send(raster_rgba, &dc.d_raster_rgba, &dc.raster_rgba_cap, 4u);
             if (rc != BRT_OK) return rc;
             d_rgba = dc.d_raster_rgba;
+        }
+        if (raster_rgba && bp.on && p == 0) {
+            rc = ensure(ctx, &dc.d_raster_rgba, &dc.raster_rgba_cap, frame_px * 16);
+            if (rc != BRT_OK) return rc;
+            HIP_TRY(ctx, hipMemcpyAsync(dc.d_raster_rgba, raster_rgba, frame_px * 16, hipMemcpyHostToDevice, dc.stream));
+            bp.d_raster_rgba = dc.d_raster_rgba;
         }
         if (raster_depth) {
             rc = send(raster_depth, &dc.d_raster_depth, &dc.raster_depth_cap, 1u);
@@ -1572,7 +1600,7 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
             FrameParams gp;
             rc = denoise_params(ctx, camera80, window16, width, height, &gp);
             if (rc == BRT_OK) rc = denoise_scratch_of(ctx, dc, width, height, dc.stream, &ds);
-            if (rc == BRT_OK) rc = run_denoise(ctx, dc, gp, ds, dc.d_tile, dc.d_tile, BRT_FLAG_OUT_RGBA32F, dc.stream, post);
+            if (rc == BRT_OK) rc = run_denoise(ctx, dc, gp, ds, dc.d_tile, dc.d_tile, BRT_FLAG_OUT_RGBA32F, dc.stream, post, bp);
             if (rc != BRT_OK) return rc;
         }
         if (direct) {
@@ -1631,7 +1659,7 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
         if (rc != BRT_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(ds.frame, out_rgba, frame_px * 16, hipMemcpyHostToDevice, d0.stream));
         float4* result = denoise_result_plane(ds, ctx->denoise);      // (a plane the last pass does not read)
-        rc = run_denoise(ctx, d0, gp, ds, reinterpret_cast<float*>(ds.frame), result, BRT_FLAG_OUT_RGBA32F, d0.stream, post);
+        rc = run_denoise(ctx, d0, gp, ds, reinterpret_cast<float*>(ds.frame), result, BRT_FLAG_OUT_RGBA32F, d0.stream, post, bp);
         if (rc != BRT_OK) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(out_rgba, result, frame_px * 16, hipMemcpyDeviceToHost, d0.stream));
         HIP_TRY(ctx, hipStreamSynchronize(d0.stream));
@@ -1663,6 +1691,14 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
                             brt_stats* stats) {
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t n_parts = (uint32_t)ctx->devs.size();
+    // BRT_FLAG_BLEND_POST: no device traces with the raster colour (a coverage frame), so it is not forwarded -- the post-passes read it
+    // on the first device, where the caller holds it
+    BlendPost bp;
+    bp.on = blend_post_on(level, flags);
+    if (bp.on) {
+        bp.d_raster_rgba = d_raster_rgba;
+        d_raster_rgba = nullptr;
+    }
     std::vector<FrameParams> fps(n_parts);
     for (uint32_t p = 0; p < n_parts; p++) {
         int32_t rc = make_frame_params(ctx, camera80, window16, level, width, height, p, n_parts, &fps[p]);
@@ -1783,7 +1819,7 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
             assembled = reinterpret_cast<const float*>(ds.frame);
         }
         HIP_TRY(ctx, hipEventRecord(d0.ev_g1, stream0));
-        rc = run_denoise(ctx, d0, gp, ds, assembled, d_frame, flags & BRT_FLAG_OUT_MASK, stream0, flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL));
+        rc = run_denoise(ctx, d0, gp, ds, assembled, d_frame, flags & BRT_FLAG_OUT_MASK, stream0, flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL), bp);
         if (rc != BRT_OK) return rc;
     } else {
         HIP_TRY(ctx, launch_deinterleave(d0.d_gather, d_frame, width, height, n_parts, tile_rows, flags & BRT_FLAG_OUT_MASK, stream0));
@@ -1844,8 +1880,7 @@ int32_t brt_render(brt_ctx* ctx, const void* camera80, const void* window16, uin
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!out_rgba) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_rgba is null");
-    if ((flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) && level != BRT_LEVEL_PURE)
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL need level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
+    if (const int32_t bad = post_flags_check(ctx, level, flags)) return bad;
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_OUT_MASK) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "brt_render writes RGBA f32 (BRT_FLAG_OUT_* apply to the device frame of brt_render_device / brt_gather_rccl / brt_deinterleave_device)");
     uint32_t rebuilt = 0u;
@@ -1863,8 +1898,8 @@ int32_t brt_render_part_device(brt_ctx* ctx, const void* camera80, const void* w
                                brt_stats* stats) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's strips have no neighbours: denoise / accumulate the assembled frame (brt_denoise_device)");
+    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL | BRT_FLAG_BLEND_POST))
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's strips have no neighbours: denoise / accumulate the assembled frame (brt_denoise_device, brt_blend_post_device)");
     if (!d_out_tile) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out_tile is null");
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_OUT_MASK) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's tile is RGBA f32 (the format is applied where the frame is assembled: brt_gather_rccl / brt_deinterleave_device)");
@@ -1885,8 +1920,7 @@ int32_t brt_render_device(brt_ctx* ctx, const void* camera80, const void* window
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
-    if ((flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL)) && level != BRT_LEVEL_PURE)
-        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL need level 3 (Pure): the raster blend of levels 1 / 2 is not known to the guides");
+    if (const int32_t bad = post_flags_check(ctx, level, flags)) return bad;
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (flags & BRT_FLAG_KERNEL_SIMPLE) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "brt_render_device runs the persistent kernel only");
     uint32_t rebuilt = 0u;
@@ -1957,7 +1991,7 @@ int32_t brt_deinterleave_device(brt_ctx* ctx, const float* d_tiles, uint32_t n_p
                                 void* d_frame, void* hip_stream, uint32_t flags) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
+    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL | BRT_FLAG_BLEND_POST))
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the de-interleave does not denoise or accumulate: brt_denoise_device on the assembled frame");
     if (!d_tiles || !d_frame || n_parts == 0) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null buffer / n_parts == 0");
     DeviceCtx& dc = ctx->devs[0];
@@ -2088,12 +2122,16 @@ int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance
     });
 }
 
-int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
-                           const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+}  // extern "C"
+
+namespace {
+
+// brt_denoise_device, and brt_blend_post_device (bp.on: d_frame_rgba is a coverage frame)
+int32_t denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const float* d_frame_rgba,
+                       void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats, const BlendPost& bp) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (!d_frame_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame_rgba / d_out is null");
+    if (!d_frame_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, bp.on ? "d_coverage_rgba / d_out is null" : "d_frame_rgba / d_out is null");
     if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only");
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
@@ -2110,7 +2148,7 @@ int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* windo
     rc = denoise_scratch_of(ctx, dc, width, height, stream, &ds);
     // without BRT_FLAG_TEMPORAL the call denoises (BRT_FLAG_DENOISE implied); with it, it accumulates, and filters if BRT_FLAG_DENOISE is set too
     const uint32_t post = (flags & BRT_FLAG_TEMPORAL) ? flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL) : (uint32_t)BRT_FLAG_DENOISE;
-    if (rc == BRT_OK) rc = run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, stream, post);
+    if (rc == BRT_OK) rc = run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, stream, post, bp);
     if (rc == BRT_OK && own_stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
     if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
     if (stats) {
@@ -2119,6 +2157,27 @@ int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* windo
         tree_stats(ctx, rebuilt, stats);
     }
     return BRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                           const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    return denoise_device(ctx, camera80, window16, width, height, d_frame_rgba, d_out, hip_stream, flags, stats, BlendPost());
+    });
+}
+
+int32_t brt_blend_post_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                              const float* d_coverage_rgba, const float* d_raster_rgba, void* d_out, void* hip_stream, uint32_t flags,
+                              brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    BlendPost bp;
+    bp.on = true;
+    bp.d_raster_rgba = d_raster_rgba;
+    return denoise_device(ctx, camera80, window16, width, height, d_coverage_rgba, d_out, hip_stream, flags, stats, bp);
     });
 }
 

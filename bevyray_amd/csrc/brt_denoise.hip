@@ -8,6 +8,9 @@
 // k_denoise_pass      one a-trous iteration of step s = 2^i: 5x5 taps, weights h(dx) h(dy) w_n w_z w_l; the last one blends with the
 //                     demodulated input by the strength of the sample count, remodulates and stores in the requested BRT_FLAG_OUT_*
 //                     format (OutPixel, brt_store.h).
+// Post-passes on a blended (level 1 / 2) frame: the input is a coverage frame, alpha exactly +0.0 where the raster
+// colour wins.  k_denoise_guides_cov gives those pixels the miss guide without casting their ray (everything downstream then treats
+// them as pass-through), and k_denoise_pass<true, FMT, const float4*>, the last pass with the raster colour bound, stores their raster texel instead of the input's zeros.
 // Every kernel: 256 threads = one 16x16 pixel tile (a wave is 4 rows of 16), one thread per pixel, no atomics (bitwise deterministic).
 #include <hip/hip_runtime.h>
 
@@ -56,11 +59,8 @@ BRT_DEV float edge_log2(f3 np, float tp, float zscale, float4 gq, float dist, fl
 // ---- guide buffer ------------------------------------------------------------------------------------------------------------------
 
 template <bool D16>
-__global__ __launch_bounds__(256) void k_denoise_guides(DeviceSceneView sv, FrameParams fp, float4* __restrict__ g0,
-                                                        float4* __restrict__ g1, const uint32_t* __restrict__ rmap,
-                                                        uint32_t* __restrict__ sid) {
-    const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
-    if (px >= fp.width || py >= fp.height) return;
+BRT_DEV void denoise_guides_pixel(const DeviceSceneView& sv, const FrameParams& fp, float4* __restrict__ g0, float4* __restrict__ g1,
+                                  const uint32_t* __restrict__ rmap, uint32_t* __restrict__ sid, uint32_t px, uint32_t py) {
     ScenePtrs sc;                      // the scene in global memory, as k_trace_simple walks it
     sc.pairs = reinterpret_cast<const char*>(sv.pairs);
     sc.pairs_far = sc.pairs;
@@ -102,6 +102,33 @@ __global__ __launch_bounds__(256) void k_denoise_guides(DeviceSceneView sv, Fram
     g0[p] = make_float4(n.x, n.y, n.z, t);
     g1[p] = make_float4(plain ? __builtin_sqrtf(max_f(m0.x, 1e-3f)) : 1.0f, plain ? __builtin_sqrtf(max_f(m0.y, 1e-3f)) : 1.0f,
                         plain ? __builtin_sqrtf(max_f(m0.z, 1e-3f)) : 1.0f, __uint_as_float(sv.sphere_material[idx]));
+}
+
+template <bool D16>
+__global__ __launch_bounds__(256) void k_denoise_guides(DeviceSceneView sv, FrameParams fp, float4* __restrict__ g0,
+                                                        float4* __restrict__ g1, const uint32_t* __restrict__ rmap,
+                                                        uint32_t* __restrict__ sid) {
+    const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
+    if (px >= fp.width || py >= fp.height) return;
+    denoise_guides_pixel<D16>(sv, fp, g0, g1, rmap, sid, px, py);
+}
+
+// The guides of a coverage frame `cov` (RGBA32F): a covered pixel (alpha +0.0) reads as a miss and casts no ray -- a wave (4 rows of a
+// tile) whose pixels are all covered skips the walk, a fully covered tile does none
+template <bool D16>
+__global__ __launch_bounds__(256) void k_denoise_guides_cov(DeviceSceneView sv, FrameParams fp, float4* __restrict__ g0,
+                                                            float4* __restrict__ g1, const uint32_t* __restrict__ rmap,
+                                                            uint32_t* __restrict__ sid, const float4* __restrict__ cov) {
+    const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
+    if (px >= fp.width || py >= fp.height) return;
+    const uint32_t p = py * fp.width + px;
+    if (covered(cov[p].w)) {
+        g0[p] = make_float4(0.0f, 0.0f, 0.0f, kSky);
+        g1[p] = make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(kPassThrough));
+        if (sid) sid[p] = kPassThrough;
+        return;
+    }
+    denoise_guides_pixel<D16>(sv, fp, g0, g1, rmap, sid, px, py);
 }
 
 // ---- demodulation, variance --------------------------------------------------------------------------------------------------------
@@ -169,13 +196,21 @@ __global__ __launch_bounds__(256) void k_denoise_variance(PassArgs pa) {
 
 // ---- a-trous passes ----------------------------------------------------------------------------------------------------------------
 
-template <bool LAST, uint32_t FMT>
-__global__ __launch_bounds__(256) void k_denoise_pass(PassArgs pa, typename OutPixel<FMT>::type* __restrict__ out) {
+// Raster: empty, or one `const float4*` -- the last pass of a coverage frame, in which a covered pixel stores its raster texel (nullptr:
+// zeros), never the input's zeros.  The empty pack is the kernel as it always was, name and arguments included.
+template <bool LAST, uint32_t FMT, typename... Raster>
+__global__ __launch_bounds__(256) void k_denoise_pass(PassArgs pa, typename OutPixel<FMT>::type* __restrict__ out, Raster... raster) {
     const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
     if (px >= pa.width || py >= pa.height) return;
     const uint32_t p = py * pa.width + px;
     const float4 cp = pa.cv_in[p];
     if (cp.w < 0.0f) {                                              // sky / non-finite: unchanged
+        if constexpr (LAST && sizeof...(Raster) != 0) {
+            if (covered(pa.aux[p].x)) {
+                out[p] = OutPixel<FMT>::make(raster_texel(p, raster...));
+                return;
+            }
+        }
         if (LAST) out[p] = OutPixel<FMT>::make(make_float4(cp.x, cp.y, cp.z, pa.aux[p].x));
         else pa.cv_out[p] = cp;
         return;
@@ -262,8 +297,13 @@ DenoiseScratch denoise_scratch(char* base, uint32_t width, uint32_t height) {
 static dim3 tiles_of(uint32_t width, uint32_t height) { return dim3((width + kTile - 1u) / kTile, (height + kTile - 1u) / kTile); }
 
 hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& fp, const DenoiseScratch& ds, hipStream_t stream,
-                                 const uint32_t* rmap, uint32_t* sid) {
-    if (sv.desc16)
+                                 const uint32_t* rmap, uint32_t* sid, const float* d_coverage) {
+    const float4* cov = reinterpret_cast<const float4*>(d_coverage);
+    if (cov && sv.desc16)
+        hipLaunchKernelGGL(k_denoise_guides_cov<true>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1, rmap, sid, cov);
+    else if (cov)
+        hipLaunchKernelGGL(k_denoise_guides_cov<false>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1, rmap, sid, cov);
+    else if (sv.desc16)
         hipLaunchKernelGGL(k_denoise_guides<true>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1, rmap, sid);
     else
         hipLaunchKernelGGL(k_denoise_guides<false>, tiles_of(fp.width, fp.height), dim3(256), 0, stream, sv, fp, ds.g0, ds.g1, rmap, sid);
@@ -271,15 +311,19 @@ hipError_t launch_denoise_guides(const DeviceSceneView& sv, const FrameParams& f
 }
 
 template <uint32_t FMT>
-static void launch_last_t(const PassArgs& pa, void* out, hipStream_t stream) {
-    hipLaunchKernelGGL((k_denoise_pass<true, FMT>), tiles_of(pa.width, pa.height), dim3(256), 0, stream, pa,
-                       reinterpret_cast<typename OutPixel<FMT>::type*>(out));
+static void launch_last_t(const PassArgs& pa, void* out, hipStream_t stream, const BlendPost& bp) {
+    if (bp.on)
+        hipLaunchKernelGGL((k_denoise_pass<true, FMT, const float4*>), tiles_of(pa.width, pa.height), dim3(256), 0, stream, pa,
+                           reinterpret_cast<typename OutPixel<FMT>::type*>(out), reinterpret_cast<const float4*>(bp.d_raster_rgba));
+    else
+        hipLaunchKernelGGL((k_denoise_pass<true, FMT>), tiles_of(pa.width, pa.height), dim3(256), 0, stream, pa,
+                           reinterpret_cast<typename OutPixel<FMT>::type*>(out));
 }
 
 hipError_t launch_denoise(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, const float* d_in, void* d_out,
-                          uint32_t out_format, hipStream_t stream) {
+                          uint32_t out_format, hipStream_t stream, const BlendPost& bp) {
     const hipError_t e = launch_denoise_demod(fp, ds, d_in, false, stream);
-    return e != hipSuccess ? e : launch_denoise_filter(fp, st, ds, d_out, out_format, stream);
+    return e != hipSuccess ? e : launch_denoise_filter(fp, st, ds, d_out, out_format, stream, nullptr, bp);
 }
 
 hipError_t launch_denoise_demod(const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, bool keep_input, hipStream_t stream) {
@@ -289,7 +333,7 @@ hipError_t launch_denoise_demod(const FrameParams& fp, const DenoiseScratch& ds,
 }
 
 hipError_t launch_denoise_filter(const FrameParams& fp, const DenoiseSettings& st, const DenoiseScratch& ds, void* d_out,
-                                 uint32_t out_format, hipStream_t stream, const float4* temporal_moments) {
+                                 uint32_t out_format, hipStream_t stream, const float4* temporal_moments, const BlendPost& bp) {
     const dim3 grid = tiles_of(fp.width, fp.height);
     PassArgs pa;
     pa.width = fp.width;
@@ -319,10 +363,10 @@ hipError_t launch_denoise_filter(const FrameParams& fp, const DenoiseSettings& s
             continue;
         }
         switch (out_format) {
-            case BRT_FLAG_OUT_RGBA32F: launch_last_t<BRT_FLAG_OUT_RGBA32F>(pa, d_out, stream); break;
-            case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: launch_last_t<BRT_FLAG_OUT_RGBA8_UNORM_SRGB>(pa, d_out, stream); break;
-            case BRT_FLAG_OUT_RGBA16F: launch_last_t<BRT_FLAG_OUT_RGBA16F>(pa, d_out, stream); break;
-            case BRT_FLAG_OUT_RGBA8_UNORM: launch_last_t<BRT_FLAG_OUT_RGBA8_UNORM>(pa, d_out, stream); break;
+            case BRT_FLAG_OUT_RGBA32F: launch_last_t<BRT_FLAG_OUT_RGBA32F>(pa, d_out, stream, bp); break;
+            case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: launch_last_t<BRT_FLAG_OUT_RGBA8_UNORM_SRGB>(pa, d_out, stream, bp); break;
+            case BRT_FLAG_OUT_RGBA16F: launch_last_t<BRT_FLAG_OUT_RGBA16F>(pa, d_out, stream, bp); break;
+            case BRT_FLAG_OUT_RGBA8_UNORM: launch_last_t<BRT_FLAG_OUT_RGBA8_UNORM>(pa, d_out, stream, bp); break;
             default: return hipErrorInvalidValue;
         }
     }

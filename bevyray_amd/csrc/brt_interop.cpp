@@ -182,7 +182,7 @@ int32_t brt_gather_rccl(brt_ctx* ctx, void* nccl_comm, int32_t rank, int32_t wor
                         uint32_t width, uint32_t height, void* d_frame_on_root, void* hip_stream, uint32_t flags) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
+    if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL | BRT_FLAG_BLEND_POST))
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the gather does not denoise or accumulate: brt_denoise_device on the root's assembled frame");
     if (!nccl_comm || !d_tile) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null communicator / tile");
     if (world < 1 || rank < 0 || rank >= world) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "rank / world out of range");

@@ -52,8 +52,10 @@ struct TemporalArgs {
 // After the guides (with hist.sid) and the demodulation: reprojects, validates and accumulates every pixel into set args.prev ^ 1.
 // d_out == nullptr: ds.dm becomes {h.rgb, n} for the filter (BRT_FLAG_TEMPORAL | BRT_FLAG_DENOISE); else the accumulated frame h a
 // (the input itself where n = 1 or the pixel passes through: the demodulation's copy in ds.cv[0]) is stored into d_out in out_format
-// (d_out may be the input frame, or ds.cv[0] itself).
+// (d_out may be the input frame, or ds.cv[0] itself).  bp.on (the guides came from the coverage frame): a covered pixel's store is its
+// raster texel.
 hipError_t launch_temporal(const FrameParams& fp, const FrameParams& prev, const TemporalArgs& args, const DenoiseScratch& ds,
-                           const TemporalHistory& hist, void* d_out, uint32_t out_format, hipStream_t stream);
+                           const TemporalHistory& hist, void* d_out, uint32_t out_format, hipStream_t stream,
+                           const BlendPost& bp = BlendPost());
 
 }  // namespace brt

@@ -6,6 +6,7 @@
 //             around that position are validated (same sphere and material, normals, distance), and the surviving ones give the
 //             history the demodulated colour c' is blended into with alpha = 1 / n.  Writes the next history set, and either {h, n}
 //             into the filter's input plane or the remodulated frame h a in the requested BRT_FLAG_OUT_* format.
+// k_temporal<true, FMT, const float4*>  the same with the raster colour bound, on a coverage frame: covered pixels store their texel.
 // 256 threads = one 16x16 pixel tile, as the denoise kernels; no atomics, a fixed tap order (bitwise deterministic).
 #include <hip/hip_runtime.h>
 
@@ -41,8 +42,11 @@ struct Kernel {
 
 }  // namespace
 
-template <bool STORE, uint32_t FMT>
-__global__ __launch_bounds__(256) void k_temporal(Kernel k, typename OutPixel<FMT>::type* __restrict__ out) {
+// Raster: empty, or one `const float4*` -- a coverage frame, in which a covered pixel (alpha +0.0 in the input, a
+// miss in the guides, so it passes through) stores its raster texel (nullptr: zeros) instead of the input's zeros.  The empty pack is the
+// kernel as it always was, name and arguments included.
+template <bool STORE, uint32_t FMT, typename... Raster>
+__global__ __launch_bounds__(256) void k_temporal(Kernel k, typename OutPixel<FMT>::type* __restrict__ out, Raster... raster) {
     const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
     const uint32_t W = k.fp.width, H = k.fp.height;
     if (px >= W || py >= H) return;
@@ -55,6 +59,12 @@ __global__ __launch_bounds__(256) void k_temporal(Kernel k, typename OutPixel<FM
         k.b_out[p] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         k.c_out[p] = make_float4(0.0f, 0.0f, __uint_as_float(sp), __uint_as_float(mp));
         k.xy[p] = make_float2(nan, nan);
+        if constexpr (STORE && sizeof...(Raster) != 0) {
+            if (covered(k.in[p].w)) {
+                out[p] = OutPixel<FMT>::make(raster_texel(p, raster...));
+                return;
+            }
+        }
         if (STORE) out[p] = OutPixel<FMT>::make(k.in[p]);
         return;
     }
@@ -206,13 +216,17 @@ TemporalCamera temporal_camera(const FrameParams& pp) {
 static dim3 tiles_of(uint32_t width, uint32_t height) { return dim3((width + kTile - 1u) / kTile, (height + kTile - 1u) / kTile); }
 
 template <bool STORE, uint32_t FMT>
-static void launch_t(const Kernel& k, void* out, hipStream_t stream) {
-    hipLaunchKernelGGL((k_temporal<STORE, FMT>), tiles_of(k.fp.width, k.fp.height), dim3(256), 0, stream, k,
-                       reinterpret_cast<typename OutPixel<FMT>::type*>(out));
+static void launch_t(const Kernel& k, void* out, hipStream_t stream, const BlendPost& bp) {
+    if (STORE && bp.on)       // (without a store nothing of a covered pixel leaves the kernel: the filter's last pass composites)
+        hipLaunchKernelGGL((k_temporal<true, FMT, const float4*>), tiles_of(k.fp.width, k.fp.height), dim3(256), 0, stream, k,
+                           reinterpret_cast<typename OutPixel<FMT>::type*>(out), reinterpret_cast<const float4*>(bp.d_raster_rgba));
+    else
+        hipLaunchKernelGGL((k_temporal<STORE, FMT>), tiles_of(k.fp.width, k.fp.height), dim3(256), 0, stream, k,
+                           reinterpret_cast<typename OutPixel<FMT>::type*>(out));
 }
 
 hipError_t launch_temporal(const FrameParams& fp, const FrameParams& prev, const TemporalArgs& args, const DenoiseScratch& ds,
-                           const TemporalHistory& hist, void* d_out, uint32_t out_format, hipStream_t stream) {
+                           const TemporalHistory& hist, void* d_out, uint32_t out_format, hipStream_t stream, const BlendPost& bp) {
     Kernel k;
     k.fp = fp;
     k.pp = prev;
@@ -233,14 +247,14 @@ hipError_t launch_temporal(const FrameParams& fp, const FrameParams& prev, const
     k.c_out = hist.c[s ^ 1u];
     k.xy = hist.xy;
     if (!d_out) {
-        launch_t<false, BRT_FLAG_OUT_RGBA32F>(k, nullptr, stream);
+        launch_t<false, BRT_FLAG_OUT_RGBA32F>(k, nullptr, stream, bp);
         return hipGetLastError();
     }
     switch (out_format) {
-        case BRT_FLAG_OUT_RGBA32F: launch_t<true, BRT_FLAG_OUT_RGBA32F>(k, d_out, stream); break;
-        case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: launch_t<true, BRT_FLAG_OUT_RGBA8_UNORM_SRGB>(k, d_out, stream); break;
-        case BRT_FLAG_OUT_RGBA16F: launch_t<true, BRT_FLAG_OUT_RGBA16F>(k, d_out, stream); break;
-        case BRT_FLAG_OUT_RGBA8_UNORM: launch_t<true, BRT_FLAG_OUT_RGBA8_UNORM>(k, d_out, stream); break;
+        case BRT_FLAG_OUT_RGBA32F: launch_t<true, BRT_FLAG_OUT_RGBA32F>(k, d_out, stream, bp); break;
+        case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: launch_t<true, BRT_FLAG_OUT_RGBA8_UNORM_SRGB>(k, d_out, stream, bp); break;
+        case BRT_FLAG_OUT_RGBA16F: launch_t<true, BRT_FLAG_OUT_RGBA16F>(k, d_out, stream, bp); break;
+        case BRT_FLAG_OUT_RGBA8_UNORM: launch_t<true, BRT_FLAG_OUT_RGBA8_UNORM>(k, d_out, stream, bp); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

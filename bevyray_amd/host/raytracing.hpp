@@ -176,6 +176,14 @@ public:
                         void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
         check(brt_denoise_device(ctx_, &camera, &window, width, height, d_frame, d_out, hip_stream, flags, stats), ctx_);
     }
+    // denoise_device for a level-1 / level-2 frame (brt_blend_post_device): d_coverage is that level's RGBA f32 device frame rendered with
+    // the raster depth and no raster colour (alpha exactly 0: covered), d_raster_rgba the raster colour on the first device (nullptr:
+    // zeros).  Covered pixels of d_out are the raster texels; the rest is denoised / accumulated.  run / run_device do the same with
+    // BRT_FLAG_BLEND_POST | BRT_FLAG_DENOISE (| BRT_FLAG_TEMPORAL) in `flags`.
+    void blend_post_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, const float* d_coverage,
+                           const float* d_raster_rgba, void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_blend_post_device(ctx_, &camera, &window, width, height, d_coverage, d_raster_rgba, d_out, hip_stream, flags, stats), ctx_);
+    }
     // The same pass on an N-device context with the frame assembled ON THE FIRST DEVICE (brt_render_device: tiles by peer
     // copy over xGMI, one de-interleave kernel): `d_destination` is a device pointer, e.g. the mapped colour target
     // (pipeline.rs:191-203).  d_raster_* are optional device buffers on the first device.

@@ -54,6 +54,8 @@ EXTMEM_OPAQUE_FD, EXTMEM_DMABUF_FD = 1, 2   # brt_import_frame_fd handle types
 FLAG_CALLER_STREAM = 4   # device entry points: `stream` is the caller's stream even when its handle is 0
 FLAG_DENOISE = 32        # brt_render / brt_render_device (level 3): the frame is denoised (RaytracePlugin.set_denoise) before it is written
 FLAG_TEMPORAL = 64       # ... and brt_denoise_device: the frame is accumulated into the context's temporal history (set_temporal)
+FLAG_BLEND_POST = 128    # brt_render / brt_render_device at levels 1 / 2, with FLAG_DENOISE and / or FLAG_TEMPORAL: the post-passes run on the
+                         # ray-traced pixels, the raster-covered ones are written as their raster texels (level 3 ignores the flag)
 # format of an assembled DEVICE frame (render_device, gather_rccl, deinterleave_device): the colour target's own (pipeline.rs:311-315)
 FLAG_OUT_RGBA32F, FLAG_OUT_RGBA8_UNORM_SRGB, FLAG_OUT_RGBA16F, FLAG_OUT_RGBA8_UNORM = 0, 8, 16, 24
 OUT_PIXEL_BYTES = {FLAG_OUT_RGBA32F: 16, FLAG_OUT_RGBA8_UNORM_SRGB: 4, FLAG_OUT_RGBA16F: 8, FLAG_OUT_RGBA8_UNORM: 4}
@@ -595,6 +597,19 @@ class RayTracingNode:
         _lib.check(p._lib.brt_denoise_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_frame, d_out,
                                              stream or None, (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
                                              C.byref(stats)), p._ctx)
+        return stats.as_dict()
+
+    def blend_post_device(self, camera, window, width: int, height: int, d_coverage: int, d_out: int, d_raster_rgba: int = 0,
+                          stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_blend_post_device: denoise_device for a level-1 / level-2 frame.  d_coverage: the RGBA f32 device frame of that level
+        rendered with the raster depth and no raster colour (alpha exactly 0: covered); d_raster_rgba: the raster colour on the first
+        device (0: zeros).  Covered pixels of d_out (out_format; may be d_coverage) are the raster texels, the others are denoised,
+        or with FLAG_TEMPORAL (| FLAG_DENOISE) accumulated (and filtered).  Stream rule as for render_part_device."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_blend_post_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_coverage,
+                                                d_raster_rgba or None, d_out, stream or None,
+                                                (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags, C.byref(stats)), p._ctx)
         return stats.as_dict()
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,

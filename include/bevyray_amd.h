@@ -101,14 +101,29 @@ enum {
      * (brt_set_denoise) runs on the assembled frame on the first device and its result is what is written, in the requested format.
      * Level 3 (Pure) only: BRT_ERR_UNSUPPORTED at levels 0-2 (the raster blend of levels 1 / 2 leaves no mark of the pixels that took
      * the raster colour) and on brt_render_part_device / brt_gather_rccl / brt_deinterleave_device (a rank's strips have no
-     * neighbours: denoise the assembled frame with brt_denoise_device).  The denoiser's time is part of brt_stats::total_ms only. */
+     * neighbours: denoise the assembled frame with brt_denoise_device).  The denoiser's time is part of brt_stats::total_ms only.
+     * Levels 1 / 2 take the flag together with BRT_FLAG_BLEND_POST (below). */
     BRT_FLAG_DENOISE = 32u,
     /* brt_render / brt_render_device / brt_denoise_device: the frame is traced exactly as without the flag, then accumulated into the
      * context's temporal history (brt_set_temporal) on the first device: reprojected through the camera and sphere motion, blended with
      * alpha = 1 / n.  Alone: the accumulated frame is written.  With BRT_FLAG_DENOISE: the denoiser filters the accumulation.  A frame
      * with an empty history is bit-identical to the same frame without the flag.  Same restrictions as BRT_FLAG_DENOISE (level 3; not on
-     * brt_render_part_device / brt_gather_rccl / brt_deinterleave_device). */
-    BRT_FLAG_TEMPORAL = 64u
+     * brt_render_part_device / brt_gather_rccl / brt_deinterleave_device), and levels 1 / 2 with BRT_FLAG_BLEND_POST likewise. */
+    BRT_FLAG_TEMPORAL = 64u,
+    /* brt_render / brt_render_device, together with BRT_FLAG_DENOISE and / or BRT_FLAG_TEMPORAL: the post-passes on a level-1 / level-2
+     * frame.  The frame is traced with the caller's raster depth and WITHOUT the raster colour, which makes it a coverage frame: alpha
+     * 1 and the ray-traced colour where the pixel is ray-traced, all four channels +0.0 where the raster wins.  The post-passes run on
+     * the ray-traced pixels; a covered pixel passes through them like a sky pixel (never a tap of another pixel, no temporal history:
+     * n = 0, x' = y' = NaN) and is written as the raster_rgba texel of its own index, all four channels (NULL: zeros), in the requested
+     * BRT_FLAG_OUT_* format.  With an empty history BRT_FLAG_BLEND_POST | BRT_FLAG_TEMPORAL is the level's plain frame bit for bit.
+     * The raster colour is read on the first device only: an N-device context no longer forwards it, and brt_stats::forwarded_bytes
+     * counts the depth alone.  Pure-level and blended temporal frames of one size share one history.  brt_render_device: the kernel that
+     * stores d_frame reads d_raster_rgba, so with the flag the two must not overlap (without it the trace has consumed the colour
+     * before anything is stored).
+     * Without BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL: BRT_ERR_INVALID_ARGUMENT.  Level 0: BRT_ERR_UNSUPPORTED (nothing is ray-traced).
+     * Level 3: ignored (Pure has no blend).  brt_render_part_device / brt_gather_rccl / brt_deinterleave_device:
+     * BRT_ERR_UNSUPPORTED, as BRT_FLAG_DENOISE (the per-rank form is brt_blend_post_device). */
+    BRT_FLAG_BLEND_POST = 128u
 };
 
 typedef struct brt_ctx brt_ctx;
@@ -138,7 +153,8 @@ typedef struct brt_stats {
     uint32_t tree_rebuilt;     /* 1: the callee-built tree was rebuilt for this call's camera before the launch (see brt_upload_scene) */
     float    tree_reach;       /* the `reach` the resident callee-built SAH tree was built with (what brt_build_bvh_sah takes: 0 = the
                                   scene's own extent); 0 for a caller's tree */
-    uint64_t forwarded_bytes;  /* brt_render_device: bytes of the raster inputs forwarded to the other devices of the context */
+    uint64_t forwarded_bytes;  /* brt_render_device: bytes of the raster inputs forwarded to the other devices of the context
+                                  (BRT_FLAG_BLEND_POST: the depth alone) */
     uint32_t hot_records;      /* a scene walked from an LDS tile + L2 (scene_in_lds == 2): the tree's records are numbered by how often this
                                   view visits them (measured by the pre-pass of a first frame), so that the tile holds the ones the walk
                                   uses; this many of them were visited at all.  0: breadth-first numbering (no pre-pass yet / another mode) */
@@ -363,6 +379,19 @@ int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance
 int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                            const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
 int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, float* out8);
+
+/* ---- post-passes on blended frames ---------------------------------------------------------------------------------------------------
+ * brt_blend_post_device is brt_denoise_device for a level-1 / level-2 frame the caller holds (the per-rank form of BRT_FLAG_BLEND_POST).
+ * d_coverage_rgba: the assembled RGBA f32 width x height DEVICE frame of that level rendered with d_raster_rgba = NULL and the raster
+ * depth (any entry point, brt_render_part_device + brt_gather_rccl included) -- a pixel counts as covered iff its alpha is exactly +0.0.
+ * d_raster_rgba_or_null: the raster colour, RGBA f32 width x height on the first device (NULL: zeros); it must not overlap d_out.
+ * The covered pixels of d_out are their raster texels, the others are denoised / accumulated as brt_denoise_device does with a Pure
+ * frame; d_out (the BRT_FLAG_OUT_* format of `flags`) may equal d_coverage_rgba.  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*,
+ * BRT_FLAG_DENOISE, BRT_FLAG_TEMPORAL (BRT_FLAG_DENOISE is implied without BRT_FLAG_TEMPORAL); other bits BRT_ERR_INVALID_ARGUMENT.
+ * Stream rule and stats as for brt_denoise_device.  Formulas: DESIGN.md "Post-passes on blended frames". */
+int32_t brt_blend_post_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                              const float* d_coverage_rgba, const float* d_raster_rgba_or_null, void* d_out, void* hip_stream,
+                              uint32_t flags, brt_stats* stats_or_null);
 
 /* ---- temporal accumulation ---------------------------------------------------------------------------------------------------------
  * The context keeps, on its first device, a per-pixel history of BRT_FLAG_TEMPORAL frames: the accumulated demodulated colour, the two
