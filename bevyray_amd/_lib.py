@@ -16,7 +16,7 @@ _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BRT_LIB_PATH") or os.path.join(_HERE, "libbevyray_amd.so")   # BRT_LIB_PATH: A/B of builds
 _SOURCES = ["brt_api.cpp", "brt_interop.cpp", "brt_ctx.h", "brt_host.cpp", "brt_kernels.hip", "brt_trace_prod.hip", "brt_trace_tune.hip", "brt_trace.h",
             "brt_host.h", "brt_kernels.h", "brt_layout.h", "brt_device.h", "brt_ploc.h", "brt_sah.h", "brt_srgb_table.h", "brt_bvh.hip", "brt_sah.hip", "brt_order.hip", "brt_denoise.hip",
-            "brt_denoise.h", "brt_store.h", "brt_temporal.hip", "brt_temporal.h", "Makefile"]
+            "brt_denoise.h", "brt_store.h", "brt_temporal.hip", "brt_temporal.h", "brt_query.hip", "brt_query.h", "Makefile"]
 
 _lock = threading.Lock()
 _lib = None
@@ -97,6 +97,10 @@ _PROTOTYPES = {
     "brt_set_temporal": (_I32, [_VP, _U32]),
     "brt_reset_temporal": (_I32, [_VP]),
     "brt_debug_temporal_state": (_I32, [_VP, _U32, _U32, _VP]),
+    "brt_query_rays_device": (_I32, [_VP, _VP, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
+    "brt_query_rays": (_I32, [_VP, _VP, _U32, _U32, _F, _VP, C.POINTER(C.c_uint64)]),
+    "brt_query_origin_bound": (_I32, [_VP, C.POINTER(_F)]),
+    "brt_host_pixel_ray": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP]),
     "brt_debug_profile": (_I32, [_VP, C.POINTER(C.c_uint64)]),
     "brt_debug_tile_order": (_I32, [_VP, _VP, _VP, _U32, _U32, C.c_uint64, _U32, _U32, _U32, _VP, _VP]),
     "brt_build_bvh": (_I32, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),

@@ -645,6 +645,8 @@ int32_t apply_hot_order(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream) {
     std::vector<uint32_t> mat;
     uint32_t new_root = 0;
     permute_scene(cur, dc.h_spheres_cur, dc.h_sphmat_cur, dc.h_sphmats_cur, cur_root, rank, srank, &dc.h_pairs_hot, &sph, &mat, &mats, &new_root);
+    HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));        // (a ray query on another stream may still be walking the old numbering)
+    dc.hot_serial++;
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(dc.view.pairs), dc.h_pairs_hot.data(), dc.h_pairs_hot.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(dc.view.spheres), sph.data(), sph.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint32_t*>(dc.view.sphere_material), mat.data(), mat.size() * 4, hipMemcpyHostToDevice, stream));
@@ -804,6 +806,11 @@ void free_device(DeviceCtx& dc) {
     if (dc.d_denoise) (void)hipFree(dc.d_denoise);
     if (dc.d_temporal) (void)hipFree(dc.d_temporal);
     if (dc.d_tsph) (void)hipFree(dc.d_tsph);
+    if (dc.d_qctl) (void)hipFree(dc.d_qctl);
+    if (dc.d_qmap) (void)hipFree(dc.d_qmap);
+    if (dc.d_qrays) (void)hipFree(dc.d_qrays);
+    if (dc.d_qhits) (void)hipFree(dc.d_qhits);
+    if (dc.ev_q) (void)hipEventDestroy(dc.ev_q);
     if (dc.ev_dn) (void)hipEventDestroy(dc.ev_dn);
     if (dc.ev0) (void)hipEventDestroy(dc.ev0);
     if (dc.ev1) (void)hipEventDestroy(dc.ev1);
@@ -872,6 +879,7 @@ int32_t ensure_tree_reach(brt_ctx* ctx, const void* camera80, uint32_t* rebuilt)
     Camera cam;
     std::memcpy(&cam, camera80, sizeof cam);
     uint32_t need = tree_level_for(ctx->tree_scene.scale, ctx->tree_scene.big, cam.position);
+    if (need < ctx->query_level) need = ctx->query_level;      // (a ray query asked for more since the upload: brt_query_rays*, origin_bound)
     if (tree_pads_equal(ctx->tree_scene, 0.0f, tree_reach_of(ctx->tree_scene.scale, need))) need = 0u;   // the tree of the scene's own extent is that tree
     if (need <= ctx->tree_level && need + 2u > ctx->tree_level) return BRT_OK;
     // (the cover camera at its usual place already "needs" level 5 -- with every pad still at the 0.01 floor: same bytes, level 0)
@@ -940,6 +948,7 @@ int32_t brt_create(const int32_t* device_ids, int32_t n_devices, brt_ctx** out_c
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_pack, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_dn, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_strip, hipEventDisableTiming));
+            HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_q, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreateWithFlags(&dc.ev_strip_read, hipEventDisableTiming));
             HIP_TRY(ctx, hipEventCreate(&dc.ev_g0));
             HIP_TRY(ctx, hipEventCreate(&dc.ev_g1));
@@ -947,8 +956,10 @@ int32_t brt_create(const int32_t* device_ids, int32_t n_devices, brt_ctx** out_c
             HIP_TRY(ctx, hipEventRecord(dc.ev_last, dc.stream));
             HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
             HIP_TRY(ctx, hipEventRecord(dc.ev_strip, dc.stream));
+            HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));
             HIP_TRY(ctx, hipEventRecord(dc.ev_strip_read, dc.stream));
             HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dc.d_ctrl), 512));
+            HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&dc.d_qctl), 32));
             return BRT_OK;
         };
         rc = body();
@@ -981,6 +992,7 @@ int32_t brt_set_tuning(brt_ctx* ctx, const char* name, uint32_t value) {
     for (int k = 0; k < K_COUNT; k++)
         if (std::strcmp(name, kKnobs[k].name) == 0) {
             ctx->knobs.v[k] = value;
+            if (k == K_QUERY_FORM || k == K_QUERY_STREAM_MIN) return BRT_OK;   // (ray queries only: no frame depends on them)
             // a knob may change how the dispatch order is built or used: forget the history of every view (the next frame of
             // a view is a "first frame" again: pre-pass, measuring frame)
             for (auto& dc : ctx->devs) { dc.order_valid = false; dc.view_rays = 0; }
@@ -1074,7 +1086,7 @@ int32_t upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const 
     // scene buffers are rewritten only once every device of the context has drained
     for (auto& dc : ctx->devs) {
         HIP_TRY(ctx, hipSetDevice(dc.device));
-        for (hipEvent_t e : {dc.ev_last, dc.ev_copy, dc.ev_asm}) HIP_TRY(ctx, hipEventSynchronize(e));
+        for (hipEvent_t e : {dc.ev_last, dc.ev_copy, dc.ev_asm, dc.ev_q}) HIP_TRY(ctx, hipEventSynchronize(e));
     }
     ctx->has_scene = false;
     // the scale of the scene and its big spheres, for the reach a camera needs (brt_sah.h; ensure_tree_reach)
@@ -1084,6 +1096,7 @@ int32_t upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const 
         ctx->tree_callee_sah = false;
         ctx->tree_level = 0;
         ctx->tree_reach = 0.0f;
+        ctx->query_level = 0;
     } else {
         reach = tree_reach_of(ctx->tree_scene.scale, level);
     }
@@ -2279,6 +2292,275 @@ int32_t brt_debug_eval(brt_ctx* ctx, uint32_t op, const float* in16, float* out8
     (void)hipFree(d_in);
     (void)hipFree(d_out);
     return rc;
+    });
+}
+
+}  // extern "C"
+
+// ---- ray queries (brt_query.hip; DESIGN.md "Ray queries") on the first device ------------------------------------------------------------
+
+namespace {
+
+// The reach level an origin of 1-norm l1 needs of the callee-built tree: tree_level_for's rule for a camera there.  A query gives no
+// position, so the tangent to every big sphere is taken from as far as a point of that norm can be from it (|p|_2 <= |p|_1: the
+// distance to the centre is at most l1 + |c|_2) -- never less than the camera rule gives at any such position OUTSIDE the sphere, and
+// monotone in l1.  Only a big sphere that holds the coordinate origin (a dome) is charged its chord, as the camera rule charges a camera
+// inside it; an origin inside any other big sphere (under the ground) gets less here than a camera there would.
+uint32_t query_level_for(const TreeScene& ts, double l1) {
+    const double S = ts.scale;
+    if (!(S > 0.0) || !std::isfinite(S)) return 0u;
+    double L = 0.0;
+    for (size_t i = 0; i + 3 < ts.big.size(); i += 4) {
+        const double cx = ts.big[i], cy = ts.big[i + 1], cz = ts.big[i + 2], r = ts.big[i + 3];
+        const double c = std::sqrt(cx * cx + cy * cy + cz * cz), h = l1 + c - r;
+        double t = h > 0.0 ? std::sqrt(h * (2.0 * r + h)) : 0.0;
+        if (c < r && t < 2.0 * r) t = 2.0 * r;
+        if (t > L) L = t;
+    }
+    const double need = l1 + S + L;
+    if (!std::isfinite(need)) return kTreeLevelMax;
+    if (need <= 2.0 * S) return 0u;
+    const double k = std::ceil(4.0 * std::log2(need / (2.0 * S)));
+    return k < 1.0 ? 1u : (k > (double)kTreeLevelMax ? kTreeLevelMax : (uint32_t)k);
+}
+
+// the resident callee-built tree serves an origin that needs `level`: it was built for that level or a higher one, or for the same pads
+bool tree_covers(const brt_ctx* ctx, uint32_t level) {
+    return level <= ctx->tree_level || tree_pads_equal(ctx->tree_scene, ctx->tree_reach, tree_reach_of(ctx->tree_scene.scale, level));
+}
+
+// the largest origin 1-norm the resident tree covers (+INF: any; < 0: none)
+float query_bound_of(const brt_ctx* ctx) {
+    const float inf = std::numeric_limits<float>::infinity();
+    if (!ctx->tree_callee_sah) return inf;                      // a caller's tree (and the callee's PLOC tree) is honoured as it comes
+    const TreeScene& ts = ctx->tree_scene;
+    if (!(ts.scale > 0.0f) || !std::isfinite(ts.scale)) return inf;
+    if (tree_covers(ctx, kTreeLevelMax)) return inf;
+    if (!tree_covers(ctx, query_level_for(ts, 0.0))) return -1.0f;
+    double lo = 0.0, hi = 1.0;
+    while (hi < 1.0e39 && tree_covers(ctx, query_level_for(ts, hi))) { lo = hi; hi *= 2.0; }
+    if (hi >= 1.0e39) return inf;
+    for (int i = 0; i < 100 && hi - lo > 0.0; i++) {
+        const double mid = 0.5 * (lo + hi);
+        if (mid <= lo || mid >= hi) break;
+        if (tree_covers(ctx, query_level_for(ts, mid))) lo = mid; else hi = mid;
+    }
+    float b = (float)lo;
+    if ((double)b > lo) b = std::nextafter(b, 0.0f);            // (rounded down: every f32 norm <= b is covered)
+    return b;
+}
+
+// origin_bound > 0: the tree's reach raised, if needed, to what origins of that 1-norm need
+int32_t ensure_query_reach(brt_ctx* ctx, float origin_bound, uint32_t* rebuilt) {
+    *rebuilt = 0u;
+    if (!(origin_bound > 0.0f) || !ctx->tree_callee_sah) return BRT_OK;
+    const uint32_t need = query_level_for(ctx->tree_scene, (double)origin_bound);
+    if (!tree_covers(ctx, need)) {
+        const int32_t rc = upload_scene(ctx, ctx->last_models.data(), (uint32_t)(ctx->last_models.size() / sizeof(Model)), ctx->last_materials.data(),
+                                        (uint32_t)(ctx->last_materials.size() / sizeof(Material)), nullptr, 0u, need, true);
+        if (rc != BRT_OK) return rc;
+        *rebuilt = 1u;
+    }
+    if (need > ctx->query_level) ctx->query_level = need;       // (cameras keep it from now on: ensure_tree_reach)
+    return BRT_OK;
+}
+
+// Which form a batch takes and the streaming form's launch shape.  BRT_QUERY_FORM 1 / 2 force the plain / the streaming form; else a
+// batch of at least BRT_QUERY_STREAM_MIN rays streams (0: none does).  The streaming form stages what k_trace_persistent would
+// (plan_launch): the whole scene where it fits a workgroup's LDS beside the stacks, else the top of the tree, else nothing (scenes of
+// 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE); BRT_FORCE_LDS_TOP=<records> as there.
+void plan_query(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, QueryLaunch* ql) {
+    const Knobs& kn = ctx->knobs;
+    ql->scene = dc.view;
+    ql->scene.lds_pairs = 0u;
+    ql->form = QUERY_PLAIN;
+    ql->scene_mode = SCENE_GLOBAL;
+    ql->grid = ql->block = 0u;
+    ql->lds_bytes = 0;
+    const uint32_t form = kn[K_QUERY_FORM], stream_min = kn[K_QUERY_STREAM_MIN];
+    if (form == 1u || (form != 2u && (stream_min == 0u || n_rays < stream_min))) return;
+    ql->form = QUERY_STREAM;
+    const bool force_global = kn[K_FORCE_GLOBAL_SCENE] != 0u;
+    const uint32_t force_top = kn[K_FORCE_LDS_TOP];
+    uint32_t per_cu = 1u;
+    if (!force_global && !force_top && dc.view.desc16) {
+        for (uint32_t block : {1024u, 512u, 256u}) {
+            const size_t need = trace_lds_bytes(dc.view, SCENE_LDS, block, 0u);
+            if (need <= dc.max_lds) { ql->scene_mode = SCENE_LDS; ql->block = block; ql->lds_bytes = need; break; }
+        }
+    }
+    if (ql->scene_mode != SCENE_LDS && !force_global && dc.view.desc16) {
+        const size_t fixed = trace_lds_bytes(ql->scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);       // (lds_pairs = 0: stacks only)
+        if (fixed + 64 * PAIR_BYTES <= dc.max_lds) {
+            uint32_t k = (uint32_t)((dc.max_lds - fixed) / PAIR_BYTES);
+            if (k > dc.view.n_pairs) k = dc.view.n_pairs;
+            if (force_top && force_top < k) k = force_top;
+            ql->scene.lds_pairs = k;
+            ql->scene_mode = SCENE_LDS_TOP;
+            ql->block = BRT_BLOCK;
+            ql->lds_bytes = trace_lds_bytes(ql->scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);
+        }
+    }
+    if (ql->scene_mode == SCENE_GLOBAL) {
+        ql->block = 256u;
+        ql->lds_bytes = trace_lds_bytes(dc.view, SCENE_GLOBAL, 256u, 0u);
+        per_cu = (uint32_t)(dc.max_lds / (ql->lds_bytes ? ql->lds_bytes : 1));
+        // waves per SIMD: the simple-tree instantiation of 16-bit descriptors holds the hand-written loop's 114 VGPRs (4), the others 60-64 (8)
+        const uint32_t by_regs = (dc.view.desc16 && dc.view.simple_tree) ? 4u : 8u;
+        if (per_cu > by_regs) per_cu = by_regs;
+        if (per_cu < 1u) per_cu = 1u;
+    }
+    ql->grid = (uint32_t)dc.num_cus * per_cu;
+    const uint32_t useful = (n_rays + ql->block - 1u) / ql->block;
+    if (ql->grid > useful) ql->grid = useful;
+    if (ql->grid < 1u) ql->grid = 1u;
+}
+
+// the resident -> caller sphere map of the first device for work on `stream` (nullptr: the resident order is the upload order)
+int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32_t** rmap) {
+    *rmap = nullptr;
+    const uint32_t m = dc.view.n_models;
+    if (dc.hot_tree != ctx->tree_epoch || dc.h_total_srank.size() != m || m == 0u) return BRT_OK;
+    if (dc.qmap_tree != ctx->tree_epoch || dc.qmap_serial != dc.hot_serial || !dc.d_qmap) {
+        int32_t rc = ensure(ctx, &dc.d_qmap, &dc.qmap_cap, (size_t)m * 4u);
+        if (rc != BRT_OK) return rc;
+        std::vector<uint32_t> map(m);
+        for (uint32_t i = 0; i < m; i++) map[dc.h_total_srank[i]] = i;      // h_total_srank[caller index] = resident index
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_qmap, map.data(), (size_t)m * 4u, hipMemcpyHostToDevice, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));                          // (a pageable source; after a renumbering only)
+        dc.qmap_tree = ctx->tree_epoch;
+        dc.qmap_serial = dc.hot_serial;
+    }
+    *rmap = dc.d_qmap;
+    return BRT_OK;
+}
+
+// one batch on `stream`, behind the previous query of the context; counted: the counts are gathered (the caller synchronises and reads d_qctl)
+int32_t query_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits,
+                      bool counted, QueryLaunch* ql) {
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    plan_query(ctx, dc, n_rays, ql);
+    const uint32_t* rmap = nullptr;
+    int32_t rc = query_rmap(ctx, dc, stream, &rmap);
+    if (rc != BRT_OK) return rc;
+    QueryArgs& qa = ql->args;
+    qa.rays = static_cast<const float4*>(d_rays);
+    qa.hits = static_cast<float4*>(d_hits);
+    qa.n_rays = n_rays;
+    qa.mode = mode;
+    qa.bound = query_bound_of(ctx);
+    qa.rmap = rmap;
+    qa.stat = counted ? dc.d_qctl : nullptr;
+    qa.counter = dc.d_qctl + 4;
+    ql->stream = stream;
+    if (counted || ql->form == QUERY_STREAM) HIP_TRY(ctx, hipMemsetAsync(dc.d_qctl, 0, 32, stream));
+    HIP_TRY(ctx, launch_query(*ql));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+    return BRT_OK;
+}
+
+int32_t query_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mode, float origin_bound, const void* hits) {
+    if (mode != BRT_QUERY_CLOSEST && mode != BRT_QUERY_ANY) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "mode must be BRT_QUERY_CLOSEST or BRT_QUERY_ANY");
+    if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    if (n_rays > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_rays too large");
+    if (n_rays != 0u && (!rays || !hits)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "rays / hits is null");
+    if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
+    return BRT_OK;
+}
+
+void query_stats(const brt_ctx* ctx, const QueryLaunch& ql, uint32_t rebuilt, const uint32_t* counts3, uint64_t* out8) {
+    if (!out8) return;
+    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
+    uint32_t reach_bits;
+    std::memcpy(&reach_bits, &reach, 4);
+    out8[0] = counts3 ? counts3[0] : 0u;
+    out8[1] = counts3 ? counts3[1] : 0u;
+    out8[2] = counts3 ? counts3[2] : 0u;
+    out8[3] = rebuilt;
+    out8[4] = reach_bits;
+    out8[5] = (uint64_t)ql.form;
+    out8[6] = ql.form == QUERY_STREAM ? ql.grid : (ql.args.n_rays + 255u) / 256u;
+    out8[7] = 0u;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t brt_query_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* d_hits,
+                              void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
+    int32_t rc = query_check(ctx, d_rays, n_rays, mode, origin_bound, d_hits);
+    if (rc != BRT_OK) return rc;
+    QueryLaunch ql{};
+    uint32_t rebuilt = 0u;
+    if (n_rays == 0u) { query_stats(ctx, ql, 0u, nullptr, out_stats8); return BRT_OK; }
+    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    const bool own_stream = (hip_stream == nullptr) && !(flags & BRT_FLAG_CALLER_STREAM);
+    hipStream_t stream = own_stream ? dc.stream : static_cast<hipStream_t>(hip_stream);
+    uint32_t counts[3] = {0u, 0u, 0u};
+    auto body = [&]() -> int32_t {
+        int32_t r = query_enqueue(ctx, dc, stream, d_rays, n_rays, mode, d_hits, own_stream, &ql);
+        if (r != BRT_OK || !own_stream) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        return BRT_OK;
+    };
+    rc = body();
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    query_stats(ctx, ql, rebuilt, own_stream ? counts : nullptr, out_stats8);
+    return BRT_OK;
+    });
+}
+
+int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* hits, uint64_t* out_stats8) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc = query_check(ctx, rays, n_rays, mode, origin_bound, hits);
+    if (rc != BRT_OK) return rc;
+    QueryLaunch ql{};
+    uint32_t rebuilt = 0u;
+    if (n_rays == 0u) { query_stats(ctx, ql, 0u, nullptr, out_stats8); return BRT_OK; }
+    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    uint32_t counts[3] = {0u, 0u, 0u};
+    auto body = [&]() -> int32_t {
+        const size_t bytes = (size_t)n_rays * 32u;
+        if (dc.qrays_cap < bytes || dc.qhits_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));   // (the staging buffers grow only when no query uses them)
+        int32_t r = ensure(ctx, &dc.d_qrays, &dc.qrays_cap, bytes);
+        if (r == BRT_OK) r = ensure(ctx, &dc.d_qhits, &dc.qhits_cap, bytes);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_qrays, rays, bytes, hipMemcpyHostToDevice, dc.stream));
+        r = query_enqueue(ctx, dc, dc.stream, dc.d_qrays, n_rays, mode, dc.d_qhits, true, &ql);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(hits, dc.d_qhits, bytes, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
+        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
+        return BRT_OK;
+    };
+    rc = body();
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    query_stats(ctx, ql, rebuilt, counts, out_stats8);
+    return BRT_OK;
+    });
+}
+
+int32_t brt_query_origin_bound(brt_ctx* ctx, float* out_bound) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (!out_bound) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_bound is null");
+    if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
+    *out_bound = query_bound_of(ctx);
+    return BRT_OK;
     });
 }
 

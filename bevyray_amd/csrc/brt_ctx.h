@@ -12,6 +12,7 @@
 #include "brt_temporal.h"
 #include "brt_host.h"
 #include "brt_kernels.h"
+#include "brt_query.h"
 
 namespace brt {
 
@@ -107,6 +108,18 @@ struct DeviceCtx {
     size_t temporal_cap = 0;
     char* d_tsph = nullptr;         // two slots of float4[n_models] {centre, r^2} in the caller's order, then u32[n_models] resident -> caller
     size_t tsph_cap = 0;
+    // ray queries (brt_query.h), first device only.  Queries of the context run one behind the other (every one waits for ev_q and
+    // records it), so the batch counter, the resident -> caller map and the staging buffers of brt_query_rays have one user at a time
+    hipEvent_t ev_q = nullptr;      // end of the last query (any stream): uploads, rebuilds and the hot-order renumbering wait for it
+    uint32_t* d_qctl = nullptr;     // [0..2] rays walked, hits, refused; [4] the streaming form's batch counter
+    uint32_t* d_qmap = nullptr;     // resident sphere index -> the caller's, when the hot order has renumbered the spheres
+    size_t qmap_cap = 0;
+    uint32_t qmap_tree = 0, qmap_serial = 0;   // the tree_epoch / hot_serial d_qmap was made for (0: none)
+    uint32_t hot_serial = 0;        // bumped by every renumbering of the resident spheres (apply_hot_order)
+    char* d_qrays = nullptr;        // brt_query_rays: the host batch on the device, and its results
+    size_t qrays_cap = 0;
+    char* d_qhits = nullptr;
+    size_t qhits_cap = 0;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;
@@ -123,7 +136,7 @@ struct DeviceCtx {
 enum Knob : int {
     K_BOTTOM_UP, K_REFILL_MIN, K_WALK_EXIT, K_LEAF_VOTE, K_DRAIN_DONATE, K_POOL_ADOPT, K_WGQ_BATCH, K_LPT_LANE_PERMILLE, K_TUNABLE,
     K_FORCE_GLOBAL_SCENE, K_FORCE_LDS_TOP, K_BLOCK_THREADS, K_WG_PER_CU, K_POOL_CAP, K_LPT, K_LPT_SORT, K_LPT_SKY_SLACK, K_CRIT,
-    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_BALL_SERVERS, K_COUNT
+    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_BALL_SERVERS, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_COUNT
 };
 struct KnobDef { const char* name; uint32_t dflt; };
 constexpr KnobDef kKnobs[K_COUNT] = {
@@ -132,7 +145,9 @@ constexpr KnobDef kKnobs[K_COUNT] = {
     {"BRT_TUNABLE", 0}, {"BRT_FORCE_GLOBAL_SCENE", 0}, {"BRT_FORCE_LDS_TOP", 0}, {"BRT_BLOCK_THREADS", 0}, {"BRT_WG_PER_CU", 0},
     {"BRT_POOL_CAP", 384}, {"BRT_LPT", 1}, {"BRT_LPT_SORT", 1}, {"BRT_LPT_SKY_SLACK", 20}, {"BRT_CRIT", 1}, {"BRT_ORDER_ON_HOST", 0},
     {"BRT_NO_LEAN", 0}, {"BRT_PREPASS_SPP", 4}, {"BRT_NO_DIRTY_TRACKING", 0}, {"BRT_CPU_BVH", 0},
-    {"BRT_PLOC_ONE_BLOCK_MAX", kPlocOneBlockMax}, {"BRT_BVH_QUALITY", 1}, {"BRT_POOL_FORCE", 0}, {"BRT_LPT_REFRESH_EVERY", 0}, {"BRT_LEAN_MEASURE", 1}, {"BRT_LPT_DILATE", 3}, {"BRT_SPLIT_TAIL", 16}, {"BRT_SPLIT_FORCE", 0}, {"BRT_HOT_RECORDS", 1}, {"BRT_TEST_THROW", 0}, {"BRT_BALL_SERVERS", 0}};
+    {"BRT_PLOC_ONE_BLOCK_MAX", kPlocOneBlockMax}, {"BRT_BVH_QUALITY", 1}, {"BRT_POOL_FORCE", 0}, {"BRT_LPT_REFRESH_EVERY", 0}, {"BRT_LEAN_MEASURE", 1}, {"BRT_LPT_DILATE", 3}, {"BRT_SPLIT_TAIL", 16}, {"BRT_SPLIT_FORCE", 0}, {"BRT_HOT_RECORDS", 1}, {"BRT_TEST_THROW", 0}, {"BRT_BALL_SERVERS", 0},
+    // ray queries: the form of a call (0: by batch size, 1 plain, 2 streaming) and the batch size from which the default rule streams (0: never)
+    {"BRT_QUERY_FORM", 0}, {"BRT_QUERY_STREAM_MIN", 0}};
 struct Knobs {
     uint32_t v[K_COUNT];
     Knobs() { for (int i = 0; i < K_COUNT; i++) v[i] = kKnobs[i].dflt; }
@@ -176,6 +191,7 @@ struct brt_ctx {
     uint32_t tree_level = 0;             // reach of the resident tree = 2 S * 2^(level / 4); level 0: the scene's own extent
     float tree_reach = 0.0f;             // ... as passed to the builder (0 at level 0)
     uint32_t tree_rebuilds = 0;          // rebuilds since brt_create (diagnostic)
+    uint32_t query_level = 0;            // the highest level a ray query has asked for since the last upload: cameras do not lower the tree below it
     brt::Knobs knobs;           // tuning knobs (brt_set_tuning; environment once at brt_create under BRT_ENABLE_TUNING=1)
     uint32_t policy_flags = 0;  // brt_set_policy
     brt::DenoiseSettings denoise;   // brt_set_denoise

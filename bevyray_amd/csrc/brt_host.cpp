@@ -853,6 +853,44 @@ int32_t brt_host_material(const float* base_color_srgb3, float metallic, float p
     });
 }
 
+// The pixel-centre ray of the guide buffer and of picking, on the host: make_frame_params' camera terms (brt_api.cpp) and
+// camera_ray_dir_center (brt_device.h) operation for operation in f32 (this file is built with -ffp-contract=off; the device's
+// divide and sqrt are correctly rounded, as these are).
+int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py,
+                           void* out_ray32) {
+    return guard(nullptr, [&]() -> int32_t {
+    if (!camera80 || !window16 || !out_ray32) return fail(BRT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (width == 0 || height == 0 || width > 32768u || height > 32768u) return fail(BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    if (px >= width || py >= height) return fail(BRT_ERR_INVALID_ARGUMENT, "pixel outside the frame");
+    Camera cam;
+    Window win;
+    std::memcpy(&cam, camera80, sizeof cam);
+    std::memcpy(&win, window16, sizeof win);
+    const float heightf = (float)win.height;
+    const float widthf = (float)win.height * cam.aspect;
+    const float inv_width = 1.0f / widthf, inv_height = 1.0f / heightf;
+    const float tan_half = tan_half_fov(cam.fov);
+    const float* a = cam.direction;
+    const float* b = cam.up;
+    const float right[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+    const float uvx = ((float)px + 0.5f) / (float)width;
+    const float uvy = ((float)py + 0.5f) / (float)height;
+    const float ndc_x = (uvx * 2.0f - 1.0f) + inv_width * 0.0f;
+    const float ndc_y = (1.0f - uvy * 2.0f) + inv_height * 0.0f;
+    const float sx = (ndc_x * cam.aspect) * tan_half;
+    const float sy = ndc_y * tan_half;
+    float v[3];
+    for (int k = 0; k < 3; k++) v[k] = (a[k] + sx * right[k]) + sy * b[k];
+    const float len = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    float ray[8] = {cam.position[0], cam.position[1], cam.position[2], std::numeric_limits<float>::infinity(),
+                    v[0] / len, v[1] / len, v[2] / len, 0.0f};
+    const uint32_t user = py * width + px;
+    std::memcpy(&ray[7], &user, 4);
+    std::memcpy(out_ray32, ray, sizeof ray);
+    return BRT_OK;
+    });
+}
+
 int32_t brt_host_tile_order(const uint32_t* ray_sum, const uint32_t* longest_pixel, uint32_t n_tiles, uint32_t sample_count,
                             uint64_t grid_lanes, uint32_t sorted, uint32_t lane_permille, uint32_t tiles_x, uint32_t dilate,
                             uint32_t split_tail, uint32_t* out_order, uint32_t* out_info5) {

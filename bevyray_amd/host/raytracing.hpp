@@ -184,6 +184,24 @@ public:
                            const float* d_raster_rgba, void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
         check(brt_blend_post_device(ctx_, &camera, &window, width, height, d_coverage, d_raster_rgba, d_out, hip_stream, flags, stats), ctx_);
     }
+    // Ray queries against the resident scene (brt_query_rays*, include/bevyray_amd.h "ray queries"): 32-byte rays in, 32-byte hits out.
+    // mode: BRT_QUERY_CLOSEST / BRT_QUERY_ANY; origin_bound > 0 first raises the callee-built tree's reach for origins of that 1-norm.
+    struct Ray { float origin[3]; float t_max; float direction[3]; uint32_t user; };
+    struct Hit { float t; float normal[3]; uint32_t sphere, material, status, user; };
+    void query_rays(const Ray* rays, uint32_t n_rays, Hit* hits, uint32_t mode = BRT_QUERY_CLOSEST, float origin_bound = 0.0f,
+                    uint64_t* stats8 = nullptr) {
+        check(brt_query_rays(ctx_, rays, n_rays, mode, origin_bound, hits, stats8), ctx_);
+    }
+    void query_rays_device(const void* d_rays, uint32_t n_rays, void* d_hits, uint32_t mode = BRT_QUERY_CLOSEST, float origin_bound = 0.0f,
+                           void* hip_stream = nullptr, uint32_t flags = 0, uint64_t* stats8 = nullptr) {
+        check(brt_query_rays_device(ctx_, d_rays, n_rays, mode, origin_bound, d_hits, hip_stream, flags, stats8), ctx_);
+    }
+    // the pixel-centre ray of pixel (px, py): what the guide buffer casts there (picking)
+    static Ray pixel_ray(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, uint32_t px, uint32_t py) {
+        Ray r{};
+        check(brt_host_pixel_ray(&camera, &window, width, height, px, py, &r), nullptr);
+        return r;
+    }
     // The same pass on an N-device context with the frame assembled ON THE FIRST DEVICE (brt_render_device: tiles by peer
     // copy over xGMI, one de-interleave kernel): `d_destination` is a device pointer, e.g. the mapped colour target
     // (pipeline.rs:191-203).  d_raster_* are optional device buffers on the first device.

@@ -281,6 +281,25 @@ def tile_rows(height: int, n_parts: int) -> int:
     return int(_lib.load().brt_tile_rows(height, n_parts))
 
 
+# ray queries: brt_query_rays* (include/bevyray_amd.h)
+QUERY_CLOSEST, QUERY_ANY = 0, 1
+QUERY_STATUS_MISS, QUERY_STATUS_HIT, QUERY_STATUS_FRONT_FACE, QUERY_STATUS_INVALID, QUERY_STATUS_OUT_OF_REACH = 0, 1, 2, 4, 8
+QUERY_NONE = 0xFFFFFFFF
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("user", np.uint32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("normal", np.float32, 3), ("sphere", np.uint32), ("material", np.uint32),
+                      ("status", np.uint32), ("user", np.uint32)])
+assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+
+
+def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.ndarray:
+    """brt_host_pixel_ray: the pixel-centre ray of pixel (px, py) as one RAY_DTYPE record (t_max = inf, user = py * width + px): the
+    ray the guide buffer casts for that pixel.  Host arithmetic; for picking through RayTracingNode.query_rays."""
+    ray = np.zeros(1, RAY_DTYPE)
+    _lib.check(_lib.load().brt_host_pixel_ray(camera.ctypes.data, window.ctypes.data, int(width), int(height), int(px), int(py),
+                                              ray.ctypes.data))
+    return ray
+
+
 class RaytracePlugin:
     """mod.rs:24-84.  build()/finish() create the GPU context (the reference queues the
     render pipeline in RaytracingPipeline::from_world, pipeline.rs:233-331)."""
@@ -514,6 +533,7 @@ class RayTracingNode:
     def __init__(self, plugin: RaytracePlugin):
         self._p = plugin
         self.last_stats: Optional[dict] = None
+        self.last_query_stats: Optional[dict] = None
 
     def write_buffers(self, buffers: Buffers) -> None:
         """pipeline.rs:136-138"""
@@ -611,6 +631,45 @@ class RayTracingNode:
                                                 d_raster_rgba or None, d_out, stream or None,
                                                 (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags, C.byref(stats)), p._ctx)
         return stats.as_dict()
+
+    # -- ray queries (include/bevyray_amd.h "ray queries") ------------------------------------------
+
+    @staticmethod
+    def _query_stats(words) -> dict:
+        return {"rays_walked": int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
+                "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
+                "form": int(words[5]), "n_workgroups": int(words[6])}
+
+    def query_rays(self, rays: np.ndarray, mode: int = QUERY_CLOSEST, origin_bound: float = 0.0) -> np.ndarray:
+        """brt_query_rays: a batch of RAY_DTYPE records (host memory) against the resident scene -> HIT_DTYPE records.  mode:
+        QUERY_CLOSEST / QUERY_ANY; origin_bound > 0 first raises the tree's reach for origins of that 1-norm.  last_query_stats holds
+        the call's counts."""
+        p = self._p
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.empty(rays.shape, HIT_DTYPE)
+        words = (C.c_uint64 * 8)()
+        _lib.check(p._lib.brt_query_rays(p._ctx, rays.ctypes.data if rays.size else None, rays.size, int(mode), float(origin_bound),
+                                         hits.ctypes.data if rays.size else None, words), p._ctx)
+        self.last_query_stats = self._query_stats(words)
+        return hits
+
+    def query_rays_device(self, d_rays: int, n_rays: int, d_hits: int, mode: int = QUERY_CLOSEST, origin_bound: float = 0.0,
+                          stream: Optional[int] = None) -> dict:
+        """brt_query_rays_device: n_rays 32-byte rays at d_rays -> 32-byte hits at d_hits (device pointers on the first device).
+        Stream rule as for render_part_device; on a caller's stream the three counts of the returned stats are 0."""
+        p = self._p
+        words = (C.c_uint64 * 8)()
+        _lib.check(p._lib.brt_query_rays_device(p._ctx, d_rays or None, int(n_rays), int(mode), float(origin_bound), d_hits or None,
+                                                stream or None, 0 if stream is None else FLAG_CALLER_STREAM, words), p._ctx)
+        self.last_query_stats = self._query_stats(words)
+        return self.last_query_stats
+
+    def query_origin_bound(self) -> float:
+        """brt_query_origin_bound: the largest origin 1-norm the resident tree covers (inf: any)."""
+        p = self._p
+        b = C.c_float(0.0)
+        _lib.check(p._lib.brt_query_origin_bound(p._ctx, C.byref(b)), p._ctx)
+        return float(b.value)
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

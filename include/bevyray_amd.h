@@ -414,6 +414,59 @@ int32_t brt_set_temporal(brt_ctx* ctx, uint32_t max_history);
 int32_t brt_reset_temporal(brt_ctx* ctx);
 int32_t brt_debug_temporal_state(brt_ctx* ctx, uint32_t width, uint32_t height, float* out8);
 
+/* ---- ray queries ---------------------------------------------------------------------------------------------------------------------
+ * Batches of rays against the resident scene and tree (picking, line of sight, probes): the reference's `raycast`
+ * (raytrace.wgsl:313-362: push and pop order, strict `<` ties, root box untested, the 32-entry overflow rule) for every ray, on the
+ * context's first device.  Rules, kernels and costs: DESIGN.md "Ray queries".  Deterministic.
+ *   ray, 32 bytes    { origin.xyz, t_max, direction.xyz, user }: f32 x 7 and a u32 that is carried into the result untouched.  The
+ *                    direction is used as given (not normalised): t is in units of |direction|.  t_max = +INF: unbounded.
+ *   hit, 32 bytes    { t, normal.xyz, sphere, material, status, user }: f32 x 4 and u32 x 4.  sphere: the index into the `models` of
+ *                    the last brt_upload_scene (whatever numbering is resident); normal = normalize(ray_at(t) - centre)
+ *                    (raytrace.wgsl:356, not flipped); status: BRT_QUERY_STATUS_*.  A miss: t = +INF, normal 0, sphere = material =
+ *                    BRT_QUERY_NONE.  The reference's lower bound stays: a hit has t > 0.001.
+ *   mode             BRT_QUERY_CLOSEST: the reference's closest hit; with a finite t_max it is reported iff its t < t_max, else a
+ *                    miss.  BRT_QUERY_ANY: status only (BRT_QUERY_STATUS_HIT iff CLOSEST would report a hit under the same t_max;
+ *                    the other fields read as a miss's); the walk may stop at the first accepted sphere.
+ *   refusals         a ray with a non-finite component, or t_max NaN or <= 0: BRT_QUERY_STATUS_INVALID.  A ray whose
+ *                    (|o.x| + |o.y|) + |o.z| (f32) exceeds what the resident tree covers (brt_query_origin_bound):
+ *                    BRT_QUERY_STATUS_OUT_OF_REACH.  Neither is walked; both read as a miss otherwise.
+ *   origin_bound     0: the tree is used as it stands.  > 0 (finite): a callee-built tree whose bound is below it is first rebuilt
+ *                    for a reach that covers origins of that 1-norm (the rule of a camera there, judged without its position); a
+ *                    query never lowers the reach, and later frames are traced on that tree too until the next upload (a side effect on
+ *                    the frames: same walk rule, longer leaf pads).  NaN or < 0:
+ *                    BRT_ERR_INVALID_ARGUMENT.  A caller's tree is honoured as it comes: its bound is +INF.
+ *   brt_query_rays_device   d_rays / d_hits: DEVICE buffers of n_rays records on the first device (they must not overlap).  flags:
+ *                    BRT_FLAG_CALLER_STREAM only.  Stream rule as for brt_denoise_device: on the context's own stream the call
+ *                    returns when the results are there; on a caller's stream it only enqueues.  Queries of one context run one
+ *                    behind the other on whatever streams they come; uploads and tree rebuilds wait for them.  A query changes no
+ *                    frame and no frame changes a query.
+ *   brt_query_rays   the same for HOST buffers, synchronous.
+ *   out_stats8_or_null   [0] rays walked, [1] hits, [2] rays refused (these three are counted only by calls that synchronise: the own
+ *                    stream and brt_query_rays; 0 on a caller's stream), [3] the tree was rebuilt, [4] its reach (f32 bits in the low
+ *                    word; brt_stats::tree_reach), [5] the kernel form taken (0 plain, 1 streaming), [6] workgroups (both diagnostic: what the launch decision was), [7] reserved.
+ *   brt_query_origin_bound  *out_bound = the largest origin 1-norm the resident tree covers (+INF: any).
+ *   brt_host_pixel_ray      host arithmetic, no context: the pixel-centre ray of pixel (px, py) of a width x height frame of that camera
+ *                    and window, as the guide buffer casts it (f32, the kernel's order of operations), t_max = +INF, user =
+ *                    py * width + px.  BRT_ERR_INVALID_ARGUMENT for a pixel outside the frame.
+ * n_rays = 0 is BRT_OK and launches nothing.  BRT_ERR_NO_SCENE before an upload; null pointers and unknown modes
+ * BRT_ERR_INVALID_ARGUMENT.  Which kernel form a call takes is a launch decision (tuning knob BRT_QUERY_FORM: 0 the default rule, 1 plain,
+ * 2 streaming); the results do not depend on it. */
+#define BRT_QUERY_CLOSEST 0u
+#define BRT_QUERY_ANY 1u
+#define BRT_QUERY_STATUS_MISS 0u
+#define BRT_QUERY_STATUS_HIT 1u
+#define BRT_QUERY_STATUS_FRONT_FACE 2u     /* set beside HIT (CLOSEST only): dot(direction, normal) < 0 (raytrace.wgsl:358) */
+#define BRT_QUERY_STATUS_INVALID 4u
+#define BRT_QUERY_STATUS_OUT_OF_REACH 8u
+#define BRT_QUERY_NONE 4294967295u
+int32_t brt_query_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* d_hits,
+                              void* hip_stream, uint32_t flags, uint64_t* out_stats8_or_null);
+int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* hits,
+                       uint64_t* out_stats8_or_null);
+int32_t brt_query_origin_bound(brt_ctx* ctx, float* out_bound);
+int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py,
+                           void* out_ray32);
+
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how
  * often the waves executed code section k and the sum of active lanes over those executions

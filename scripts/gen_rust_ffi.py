@@ -28,6 +28,10 @@ DOCS = {
     "brt_debug_denoise_guides": "diagnostic: the denoiser's guide buffer (normal, t, demodulation factor, material id per pixel) in host memory",
     "brt_set_temporal": "the temporal history's max_history (1..65535, default 32; 1: no accumulation); empties the history",
     "brt_reset_temporal": "empties the temporal history (a camera cut)",
+    "brt_query_rays_device": "batched ray queries (closest hit / occlusion) against the resident scene: 32-byte rays in, 32-byte hits out, DEVICE buffers; the reference offers none (a host would rebuild a CPU BVH per frame, extract.rs:315-332)",
+    "brt_query_rays": "the same for host buffers, synchronous",
+    "brt_query_origin_bound": "the largest origin 1-norm the resident tree covers (+INF: any)",
+    "brt_host_pixel_ray": "host arithmetic: the pixel-centre ray of a pixel (raytrace.wgsl:139-156 without the jitter), for picking",
     "brt_debug_temporal_state": "diagnostic: the temporal history per pixel (h.rgb, n, m1, m2, reprojected x', y') in host memory",
 }
 
@@ -78,7 +82,7 @@ pub const BRT_OK: i32 = 0;
         rs += f"pub const {k}: i32 = {v};\n"
     for title, prefix in (("Raytracing level, reference src/raytracing/mod.rs:94-101 (#[repr(u32)])", "BRT_LEVEL_"), ("brt_render* flags", "BRT_FLAG_"),
                           ("brt_set_policy: the WGSL-spec (short-circuit) reading of `||` in raytrace.wgsl:269; default 0 = both operands evaluated", "BRT_POLICY_"),
-                          ("brt_import_frame_fd handle types", "BRT_EXTMEM_"), ("brt_scene_generate kinds", "BRT_SCENE_"), ("brt_debug_eval op codes", "BRT_DBG_")):
+                          ("brt_import_frame_fd handle types", "BRT_EXTMEM_"), ("brt_scene_generate kinds", "BRT_SCENE_"), ("brt_query_rays*: modes, status bits, the \"no sphere\" index", "BRT_QUERY_"), ("brt_debug_eval op codes", "BRT_DBG_")):
         rs += f"\n/// {title}\n"
         for k, v in grp(prefix):
             rs += f"pub const {k}: u32 = {v};\n"

@@ -1,0 +1,389 @@
+"""Batched ray queries against the resident scene (brt_query_rays*, DESIGN.md "Ray queries").  CPU: the exports, brt_host_pixel_ray
+against a numpy f32 restatement, argument rejections.  GPU: every result bitwise against oracle_raycast on the tree the GPU walked
+(tests/query_ref.py), both kernel forms, both entry points."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bevyray_amd as brt
+import query_ref as qr
+from bevyray_amd import _lib
+from helpers import chain_bvh, make_buffers, median_split_bvh, single_leaf_bvh, uniforms
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXPORTS = ("brt_query_rays_device", "brt_query_rays", "brt_query_origin_bound", "brt_host_pixel_ray")
+F32 = np.float32
+PLAIN, STREAM = 1, 2          # values of the knob BRT_QUERY_FORM
+
+
+# ---- CPU --------------------------------------------------------------------------------------------------------------------------
+
+def test_exports_in_header_ctypes_rust_and_library():
+    header = open(os.path.join(ROOT, "include", "bevyray_amd.h")).read()
+    rust = open(os.path.join(ROOT, "integration", "bevyray_amd_sys", "src", "lib.rs")).read()
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.build()], capture_output=True, text=True, check=True).stdout
+    defined = {ln.split()[-1] for ln in out.splitlines() if " T " in ln}
+    for name in EXPORTS:
+        assert f"int32_t {name}(" in header, name
+        assert name in _lib.EXPORTS, name
+        assert f"pub fn {name}(" in rust, name
+        assert name in defined, name
+    assert _lib.load().brt_abi_version() == 6
+
+
+@pytest.mark.parametrize("w,h", [(1, 1), (17, 9), (1920, 1080)])
+def test_pixel_ray_equals_the_numpy_restatement(oracle, w, h):
+    cams = [brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, 0.5),
+            uniforms(w, h, 2, 4, (-3.5, 7.25, 11.0), (0.3, -0.2, 0.1), 1.1, 0.25, up=(0.1, 1.0, 0.2), window_height=2 * h + 1)]
+    pixels = {(0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1), (w // 2, h // 2), (w // 3, (2 * h) // 3)}
+    for _, cam, win in cams:
+        for px, py in sorted(pixels):
+            got = brt.pixel_ray(cam, win, w, h, px, py)[0]
+            o, d = qr.pixel_ray_np(oracle, cam, win, w, h, px, py)
+            assert np.array_equal(got["origin"].view(np.uint32), o.view(np.uint32)), (px, py)
+            assert np.array_equal(got["direction"].view(np.uint32), d.view(np.uint32)), (px, py, got["direction"], d)
+            assert got["t_max"] == np.inf and got["user"] == py * w + px
+
+
+def test_rejections_that_need_no_device():
+    lib = _lib.load()
+    _, cam, win = brt.cover_camera(16, 9, 1, 1)
+    ray = np.zeros(1, brt.RAY_DTYPE)
+    INVALID = -1
+    assert lib.brt_host_pixel_ray(None, win.ctypes.data, 16, 9, 0, 0, ray.ctypes.data) == INVALID
+    assert lib.brt_host_pixel_ray(cam.ctypes.data, None, 16, 9, 0, 0, ray.ctypes.data) == INVALID
+    assert lib.brt_host_pixel_ray(cam.ctypes.data, win.ctypes.data, 16, 9, 0, 0, None) == INVALID
+    assert lib.brt_host_pixel_ray(cam.ctypes.data, win.ctypes.data, 16, 9, 16, 0, ray.ctypes.data) == INVALID
+    assert lib.brt_host_pixel_ray(cam.ctypes.data, win.ctypes.data, 16, 9, 0, 9, ray.ctypes.data) == INVALID
+    assert lib.brt_host_pixel_ray(cam.ctypes.data, win.ctypes.data, 0, 9, 0, 0, ray.ctypes.data) == INVALID
+    hits = np.zeros(1, brt.HIT_DTYPE)
+    assert lib.brt_query_rays(None, ray.ctypes.data, 1, 0, 0.0, hits.ctypes.data, None) == INVALID
+    assert lib.brt_query_rays_device(None, ray.ctypes.data, 1, 0, 0.0, hits.ctypes.data, None, 0, None) == INVALID
+    b = C.c_float(0)
+    assert lib.brt_query_origin_bound(None, C.byref(b)) == INVALID
+    assert b"null" in lib.brt_last_error(None)
+
+
+# ---- GPU --------------------------------------------------------------------------------------------------------------------------
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8)).cuda()
+
+
+def _query(plugin, rays, form, mode=brt.QUERY_CLOSEST, device=False, stream=None, origin_bound=0.0):
+    """The batch through the host-buffer or the device-buffer entry point, the kernel form forced by the knob."""
+    import torch
+    with plugin.tuning(BRT_QUERY_FORM=form):
+        if not device:
+            hits = plugin.node.query_rays(rays, mode, origin_bound)
+        else:
+            d_rays = _dev(rays)
+            d_hits = torch.full((max(1, rays.size) * 32,), 0xAB, dtype=torch.uint8, device="cuda")
+            plugin.node.query_rays_device(d_rays.data_ptr() if rays.size else 0, rays.size, d_hits.data_ptr() if rays.size else 0, mode,
+                                          origin_bound, stream=stream)
+            torch.cuda.synchronize()
+            hits = d_hits.cpu().numpy()[: rays.size * 32].view(brt.HIT_DTYPE)
+        assert plugin.node.last_query_stats["form"] == form - 1 or rays.size == 0
+    return hits
+
+
+def _same_bytes(a, b, what):
+    assert a.tobytes() == b.tobytes(), what
+
+
+def _scene(plugin, case):
+    """-> (buffers with the tree the GPU walks, camera, (w, h)); the scene is resident when it returns."""
+    w, h = 96, 54
+    if case in ("cover_caller", "cover_callee"):
+        b = brt.generate_scene(brt.SCENE_COVER, 1)
+        lvl, cam, win = brt.cover_camera(w, h, 2, 4)
+    elif case == "rtiow":
+        b = brt.generate_scene(brt.SCENE_RTIOW_FINAL, 1)
+        lvl, cam, win = brt.rtiow_camera(w, h, 2, 4)
+    elif case == "stress":
+        b = brt.generate_scene(brt.SCENE_STRESS_GRID, 1)
+        lvl, cam, win = brt.cover_camera(w, h, 64, 4)
+    elif case.startswith("topology"):
+        c = brt.generate_scene(brt.SCENE_COVER, 1)
+        tree = {"topology_single_leaf": single_leaf_bvh(c.models), "topology_median3": median_split_bvh(c.models, 3),
+                "topology_median1": median_split_bvh(c.models, 1)}[case]
+        b = brt.Buffers(c.models, c.materials, tree)
+        lvl, cam, win = brt.cover_camera(w, h, 2, 4)
+    else:                      # raytrace.wgsl:320: a 40-deep caterpillar overflows the 32-entry stack and drops subtrees
+        data = [((0.0, 0.0, -5.0 - i), 0.5, brt.StandardMaterial(base_color=(0.8, 0.3, 0.3))) for i in range(40)]
+        b = make_buffers(data, chain_bvh)
+        lvl, cam, win = uniforms(w, h, spp=2, bounces=3, pos=(0, 0, 0), target=(0, 0, -1), fov=0.3, seed=0.5)
+    if case in ("cover_callee", "stress"):
+        # the callee's SAH tree, its reach raised to the camera's 1-norm by a first query (the position-free rule asks for more than the
+        # camera's own); then frames, so that the stress grid's spheres are in the hot order when the queries come
+        plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
+        plugin.node.query_rays(brt.pixel_ray(cam, win, w, h, 0, 0), origin_bound=_l1(cam[0]["position"]))
+        for seed in (0.5, 0.25, 0.75):
+            win = brt.WindowExtract.extract_component(h, seed)
+            plugin.node.run(lvl, cam, win, w, h, buffers=brt.Buffers(b.models, b.materials, None))
+        st = plugin.node.last_stats
+        if case == "stress":
+            assert st["scene_in_lds"] == 2 and st["hot_records"] > 0        # top of the tree in LDS, spheres renumbered
+        b = brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models, st["tree_reach"]))   # the CPU twin of the resident tree
+    else:
+        plugin.node.run(lvl, cam, win, w, h, buffers=b)
+    return b, cam, win, (w, h)
+
+
+CASES = ["cover_caller", "cover_callee", "rtiow", "stress", "topology_single_leaf", "topology_median3", "topology_median1", "overflow"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES)
+def test_queries_match_the_oracle_raycast(plugin, oracle, case):
+    b, cam, win, (w, h) = _scene(plugin, case)
+    rng = np.random.default_rng(7)
+    sets = qr.ray_sets(oracle, b.models, b.bvh, cam, w, h, rng, n=600 if case.startswith("topology") or case == "overflow" else 2000)
+    bound = plugin.node.query_origin_bound()
+    n_hits = 0
+    for name, rays in sets.items():
+        l1 = np.abs(rays["origin"]).astype(F32)
+        rays = rays[((l1[:, 0] + l1[:, 1]) + l1[:, 2]) <= bound]              # (a callee's tree: the rays inside its reach)
+        assert len(rays) >= 16, name
+        want, t_unb = qr.expected(oracle, b.models, b.bvh, rays)
+        got = _query(plugin, rays, PLAIN)
+        qr.assert_hits_equal(got, want, f"{case}/{name} plain")
+        qr.check_spheres(oracle, b.models, rays, got)
+        st = plugin.node.last_query_stats
+        is_hit = (want["status"] & brt.QUERY_STATUS_HIT) != 0
+        assert (st["rays_walked"], st["hits"], st["refused"]) == (len(rays), int(is_hit.sum()), 0)
+        n_hits += int(is_hit.sum())
+        _same_bytes(_query(plugin, rays, STREAM), got, f"{case}/{name} streaming form")
+        _same_bytes(_query(plugin, rays, PLAIN, device=True), got, f"{case}/{name} device buffers, plain")
+        _same_bytes(_query(plugin, rays, STREAM, device=True), got, f"{case}/{name} device buffers, streaming")
+        # t_max just below, at and just above the unbounded t: miss, miss, hit; ANY agrees with CLOSEST on every ray
+        t = np.where(np.isfinite(t_unb), t_unb, F32(1.0)).astype(F32)
+        for t_max in (np.nextafter(t, F32(0)), t, np.nextafter(t, F32(np.inf)), np.full(len(rays), np.inf, F32)):
+            bounded_rays = rays.copy()
+            bounded_rays["t_max"] = t_max
+            for mode in (brt.QUERY_CLOSEST, brt.QUERY_ANY):
+                want_b = qr.bounded(want, t_max, mode)
+                got_p = _query(plugin, bounded_rays, PLAIN, mode)
+                qr.assert_hits_equal(got_p, want_b, f"{case}/{name} t_max mode {mode}")
+                if mode == brt.QUERY_CLOSEST:
+                    qr.check_spheres(oracle, b.models, bounded_rays, got_p)
+                else:
+                    assert (got_p["sphere"] == brt.QUERY_NONE).all()
+                _same_bytes(_query(plugin, bounded_rays, STREAM, mode), got_p, f"{case}/{name} t_max mode {mode} streaming")
+        below = _query(plugin, _with_tmax(rays, np.nextafter(t, F32(0))), PLAIN)
+        above = _query(plugin, _with_tmax(rays, np.nextafter(t, F32(np.inf))), PLAIN)
+        assert not (below["status"] & brt.QUERY_STATUS_HIT).any()
+        assert np.array_equal((above["status"] & brt.QUERY_STATUS_HIT) != 0, is_hit)
+    assert n_hits > 0
+    # batch sizes around a wave, and one that is no multiple of a workgroup's rays
+    rays = sets["shuffled"]
+    full = _query(plugin, rays, PLAIN)
+    for n in (1, 63, 64, 65, min(len(rays), 517)):
+        for form in (PLAIN, STREAM):
+            for device in (False, True):
+                _same_bytes(_query(plugin, rays[:n], form, device=device), full[:n], f"{case} batch of {n}, form {form}, device {device}")
+
+
+def _l1(v):
+    v = np.abs(np.asarray(v, F32))
+    return float((v[0] + v[1]) + v[2])
+
+
+def _with_tmax(rays, t_max):
+    r = rays.copy()
+    r["t_max"] = t_max
+    return r
+
+
+@pytest.mark.gpu
+def test_streaming_form_in_every_scene_mode(plugin, oracle):
+    """The cover scene walked by the streaming form from LDS, from a forced top-of-tree tile and from global memory: the same bytes."""
+    b, cam, win, (w, h) = _scene(plugin, "cover_caller")
+    rays = qr.pixel_rays(oracle, cam, w, h)
+    want = _query(plugin, rays, PLAIN)
+    qr.assert_hits_equal(want, qr.expected(oracle, b.models, b.bvh, rays)[0], "plain")
+    for knobs in ({}, {"BRT_FORCE_LDS_TOP": 70}, {"BRT_FORCE_GLOBAL_SCENE": 1}):
+        with plugin.tuning(**knobs):
+            for mode in (brt.QUERY_CLOSEST, brt.QUERY_ANY):
+                _same_bytes(_query(plugin, rays, STREAM, mode), _query(plugin, rays, PLAIN, mode), f"{knobs} mode {mode}")
+    # the default rule: a batch below BRT_QUERY_STREAM_MIN takes the plain form, one at or above it streams
+    with plugin.tuning(BRT_QUERY_STREAM_MIN=1000):
+        plugin.node.query_rays(rays[:999])
+        assert plugin.node.last_query_stats["form"] == 0
+        got = plugin.node.query_rays(rays[:1000])
+        assert plugin.node.last_query_stats["form"] == 1
+        _same_bytes(got, want[:1000], "default rule")
+
+
+@pytest.mark.gpu
+def test_refused_rays_and_reach(plugin, oracle):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h = 96, 54
+    lvl, cam, win = brt.cover_camera(w, h, 2, 4)
+    plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
+    rays = qr.pixel_rays(oracle, cam, w, h)[:256].copy()
+    plugin.node.query_rays(rays[:1], origin_bound=_l1(cam[0]["position"]))      # (the camera's own rays are in reach from here on)
+    plugin.node.run(lvl, cam, win, w, h)
+    tree = brt.build_bvh_sah(b.models, plugin.node.last_stats["tree_reach"])
+    bound = plugin.node.query_origin_bound()
+    assert _l1(cam[0]["position"]) <= bound < np.inf
+    rays["user"] = np.arange(256, dtype=np.uint32) ^ np.uint32(0xDEADBEEF)
+    want, _ = qr.expected(oracle, b.models, tree, rays)
+    bad = {3: ("origin", (np.nan, 0, 0)), 64: ("origin", (0, np.inf, 0)), 65: ("direction", (0, 0, -np.inf)), 100: ("direction", (np.nan,) * 3),
+           127: ("t_max", np.nan), 128: ("t_max", 0.0), 129: ("t_max", -1.0), 130: ("t_max", -np.inf)}
+    far = {10: (np.nextafter(F32(bound), F32(np.inf)), 0, 0), 200: (0, -F32(bound) * 2, 0), 255: (3.0e38, 3.0e38, 3.0e38)}
+    edge = {20: (F32(bound), 0, 0)}                                    # exactly at the bound: walked
+    for i, (field, v) in bad.items():
+        rays[field][i] = v
+    for i, v in {**far, **edge}.items():
+        rays["origin"][i] = v
+    want_edge, _ = qr.expected(oracle, b.models, tree, rays[list(edge)])
+    for form in (PLAIN, STREAM):
+        for device in (False, True):
+            got = _query(plugin, rays, form, device=device)
+            assert np.array_equal(got["user"], rays["user"])
+            status = np.zeros(256, np.uint32)
+            status[list(bad)] = brt.QUERY_STATUS_INVALID
+            status[list(far)] = brt.QUERY_STATUS_OUT_OF_REACH
+            refused = status != 0
+            assert np.array_equal(got["status"][refused], status[refused])
+            assert np.isposinf(got["t"][refused]).all() and (got["normal"][refused] == 0).all()
+            assert (got["sphere"][refused] == brt.QUERY_NONE).all() and (got["material"][refused] == brt.QUERY_NONE).all()
+            ok = ~refused
+            ok[list(edge)] = False
+            qr.assert_hits_equal(got[ok], want[ok], f"neighbours of refused rays, form {form}")
+            qr.assert_hits_equal(got[list(edge)], want_edge, "at the bound")
+            if not device:
+                assert plugin.node.last_query_stats["refused"] == int(refused.sum())
+                assert plugin.node.last_query_stats["rays_walked"] == 256 - int(refused.sum())
+    # a far origin with origin_bound given is answered on a tree of a longer reach
+    k = 60.0
+    far_o = np.array([13.0 * k, 2.0 * k, 3.0 * k], F32)
+    target = b.models["position"][:200].astype(F32)
+    far_rays = qr.make_rays(np.broadcast_to(far_o, target.shape), target - far_o)
+    refused = _query(plugin, far_rays, PLAIN)
+    assert (refused["status"] == brt.QUERY_STATUS_OUT_OF_REACH).all()
+    l1 = float((abs(far_o[0]) + abs(far_o[1])) + abs(far_o[2]))
+    got = _query(plugin, far_rays, PLAIN, origin_bound=l1)
+    st = plugin.node.last_query_stats
+    assert st["tree_rebuilt"] == 1 and st["tree_reach"] > 0 and plugin.node.query_origin_bound() >= l1
+    twin = brt.build_bvh_sah(b.models, st["tree_reach"])
+    want_far, _ = qr.expected(oracle, b.models, twin, far_rays)
+    qr.assert_hits_equal(got, want_far, "far origin")
+    assert ((got["status"] & brt.QUERY_STATUS_HIT) != 0).any()
+    _same_bytes(_query(plugin, far_rays, STREAM, origin_bound=l1), got, "far origin, streaming")
+    assert plugin.node.last_query_stats["tree_rebuilt"] == 0              # (a query never lowers the reach, and does not rebuild twice)
+    # the next render of the cover frame still equals the oracle's frame on the tree the context reports
+    frame = plugin.node.run(lvl, cam, win, w, h)
+    twin = brt.build_bvh_sah(b.models, plugin.node.last_stats["tree_reach"])
+    ref, _ = oracle.render(brt.Buffers(b.models, b.materials, twin), lvl, cam, win, w, h)
+    assert np.array_equal(frame.view(np.uint32), ref.view(np.uint32))
+    # a caller's tree is honoured as it comes
+    plugin.node.write_buffers(b)
+    assert plugin.node.query_origin_bound() == np.inf
+
+
+@pytest.mark.gpu
+def test_picking_equals_the_guide_buffer(plugin):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h = 320, 180
+    lvl, cam, win = brt.cover_camera(w, h, 2, 4)
+    plugin.node.run(lvl, cam, win, w, h, buffers=brt.Buffers(b.models, b.materials, None))
+    rays = np.concatenate([brt.pixel_ray(cam, win, w, h, x, y) for y in range(h) for x in range(w)])
+    bound = _l1(cam[0]["position"])
+    plugin.node.query_rays(rays[:1], origin_bound=bound)               # (may raise the reach: the guides below walk the same tree)
+    g = plugin.debug_denoise_guides(cam, win, w, h)
+    for form in (PLAIN, STREAM):
+        hits = _query(plugin, rays, form, origin_bound=bound).reshape(h, w)
+        assert plugin.node.last_query_stats["tree_rebuilt"] == 0
+        assert np.array_equal(hits["user"], np.arange(w * h, dtype=np.uint32).reshape(h, w))
+        assert np.array_equal(hits["t"].view(np.uint32), g[..., 3].view(np.uint32))
+        assert np.array_equal(hits["normal"].view(np.uint32), g[..., :3].view(np.uint32))
+        assert np.array_equal(hits["material"], g[..., 7].view(np.uint32))
+        assert ((hits["status"] & brt.QUERY_STATUS_HIT) != 0).any() and (hits["status"] == brt.QUERY_STATUS_MISS).any()
+    # a pick: one ray, the default form
+    one = plugin.node.query_rays(brt.pixel_ray(cam, win, w, h, w // 2, h // 2))
+    _same_bytes(one, hits[h // 2, w // 2 : w // 2 + 1], "one pick")
+
+
+@pytest.mark.gpu
+def test_render_and_query_on_two_caller_streams_and_across_an_upload(plugin, oracle):
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h = 160, 90
+    lvl, cam, win = brt.cover_camera(w, h, 4, 4)
+    plugin.node.run(lvl, cam, win, w, h, buffers=b)
+    rays = qr.pixel_rays(oracle, cam, w, h)
+    serial_frame = plugin.node.run(lvl, cam, win, w, h).copy()
+    serial = {form: _query(plugin, rays, form) for form in (PLAIN, STREAM)}
+    _same_bytes(serial[PLAIN], serial[STREAM], "forms")
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    d_frame = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+    d_rays = _dev(rays)
+    d_hits = [torch.zeros(rays.size * 32, dtype=torch.uint8, device="cuda") for _ in range(4)]
+    torch.cuda.synchronize()
+    for i, form in enumerate((PLAIN, STREAM, PLAIN, STREAM)):
+        with plugin.tuning(BRT_QUERY_FORM=form):
+            if i == 1:
+                plugin.node.render_device(lvl, cam, win, w, h, d_frame.data_ptr(), stream=s1.cuda_stream)
+            plugin.node.query_rays_device(d_rays.data_ptr(), rays.size, d_hits[i].data_ptr(), stream=(s2 if i % 2 else s1).cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_frame.cpu().numpy().view(np.uint32), serial_frame.view(np.uint32))
+    for i in range(4):
+        _same_bytes(d_hits[i].cpu().numpy().view(brt.HIT_DTYPE), serial[PLAIN], f"query {i} in flight")
+    # a query enqueued before a re-upload that moves a sphere sees the old scene, one after it the new one
+    moved = b.models.copy()
+    target = int(serial[PLAIN]["sphere"][(serial[PLAIN]["status"] & brt.QUERY_STATUS_HIT) != 0][0])
+    moved["position"][target] += np.array([0.0, 0.35, 0.0], F32)
+    b2 = brt.Buffers(moved, b.materials, brt.build_bvh(moved))
+    plugin.node.query_rays_device(d_rays.data_ptr(), rays.size, d_hits[0].data_ptr(), stream=s1.cuda_stream)
+    plugin.node.write_buffers(b2)
+    plugin.node.query_rays_device(d_rays.data_ptr(), rays.size, d_hits[1].data_ptr(), stream=s2.cuda_stream)
+    torch.cuda.synchronize()
+    _same_bytes(d_hits[0].cpu().numpy().view(brt.HIT_DTYPE), serial[PLAIN], "before the upload")
+    after = d_hits[1].cpu().numpy().view(brt.HIT_DTYPE)
+    want, _ = qr.expected(oracle, b2.models, b2.bvh, rays)
+    qr.assert_hits_equal(after, want, "after the upload")
+    assert after.tobytes() != serial[PLAIN].tobytes()
+
+
+@pytest.mark.gpu
+def test_frames_do_not_move_and_host_rules(plugin, oracle):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h = 320, 180
+    lvl, cam, win = brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, 0.5)
+    before = plugin.node.run(lvl, cam, win, w, h, buffers=b, flags=brt.FLAG_COUNTERS).copy()
+    stats_before = dict(plugin.node.last_stats)
+    rays = qr.pixel_rays(oracle, cam, w, h)[:5000]
+    for form in (PLAIN, STREAM):
+        for mode in (brt.QUERY_CLOSEST, brt.QUERY_ANY):
+            _query(plugin, rays, form, mode)
+            _query(plugin, rays, form, mode, device=True)
+    after = plugin.node.run(lvl, cam, win, w, h, flags=brt.FLAG_COUNTERS)
+    assert np.array_equal(before.view(np.uint32), after.view(np.uint32))
+    for k in ("rays", "node_pops", "interior_visits", "sphere_tests", "hits", "kernel_variant", "n_workgroups", "scene_in_lds"):
+        assert plugin.node.last_stats[k] == stats_before[k], k
+    # n_rays = 0 is OK and launches nothing; null buffers, unknown modes, bad bounds and flags are refused
+    assert plugin.node.query_rays(np.zeros(0, brt.RAY_DTYPE)).shape == (0,)
+    assert plugin.node.last_query_stats["n_workgroups"] == 0
+    lib, ctx = plugin._lib, plugin._ctx
+    hits = np.zeros(4, brt.HIT_DTYPE)
+    r4 = np.ascontiguousarray(rays[:4])
+    assert lib.brt_query_rays(ctx, None, 4, 0, 0.0, hits.ctypes.data, None) == -1
+    assert lib.brt_query_rays(ctx, r4.ctypes.data, 4, 0, 0.0, None, None) == -1
+    assert lib.brt_query_rays(ctx, r4.ctypes.data, 4, 2, 0.0, hits.ctypes.data, None) == -1
+    assert lib.brt_query_rays(ctx, r4.ctypes.data, 4, 0, float("nan"), hits.ctypes.data, None) == -1
+    assert lib.brt_query_rays(ctx, r4.ctypes.data, 4, 0, -1.0, hits.ctypes.data, None) == -1
+    assert lib.brt_query_rays_device(ctx, r4.ctypes.data, 4, 0, 0.0, hits.ctypes.data, None, brt.FLAG_DENOISE, None) == -1
+    assert lib.brt_query_origin_bound(ctx, None) == -1
+    with brt.RaytracePlugin([0]) as empty:
+        with pytest.raises(brt.BrtError) as e:
+            empty.node.query_rays(r4)
+        assert e.value.code == -7                                        # BRT_ERR_NO_SCENE
+        with pytest.raises(brt.BrtError) as e:
+            empty.node.query_origin_bound()
+        assert e.value.code == -7
