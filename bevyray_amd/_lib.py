@@ -14,9 +14,6 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("BRT_LIB_PATH") or os.path.join(_HERE, "libbevyray_amd.so")   # BRT_LIB_PATH: A/B of builds
-_SOURCES = ["brt_api.cpp", "brt_interop.cpp", "brt_ctx.h", "brt_host.cpp", "brt_kernels.hip", "brt_trace_prod.hip", "brt_trace_tune.hip", "brt_trace.h",
-            "brt_host.h", "brt_kernels.h", "brt_layout.h", "brt_device.h", "brt_ploc.h", "brt_sah.h", "brt_srgb_table.h", "brt_bvh.hip", "brt_sah.hip", "brt_order.hip", "brt_denoise.hip",
-            "brt_denoise.h", "brt_store.h", "brt_temporal.hip", "brt_temporal.h", "brt_query.hip", "brt_query.h", "Makefile"]
 
 _lock = threading.Lock()
 _lib = None
@@ -42,7 +39,8 @@ def _stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    paths = [os.path.join(_CSRC, s) for s in _SOURCES] + [os.path.join(_HERE, "..", "include", "bevyray_amd.h")]
+    paths = [os.path.join(_CSRC, s) for s in os.listdir(_CSRC) if s.endswith((".cpp", ".hip", ".h")) or s == "Makefile"]
+    paths.append(os.path.join(_HERE, "..", "include", "bevyray_amd.h"))
     return any(os.path.exists(p) and os.path.getmtime(p) > t for p in paths)
 
 

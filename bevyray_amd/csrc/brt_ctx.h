@@ -1,5 +1,6 @@
 // brt_ctx.h -- the opaque context of the C ABI (include/bevyray_amd.h) and the helpers its translation units share:
-// brt_api.cpp (upload, render, builds) and brt_interop.cpp (RCCL gather, external-memory frames).  Internal.
+// brt_api*.cpp (upload, launch, order, render, post-passes, queries; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
+// gather, external-memory frames).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -85,7 +86,7 @@ struct DeviceCtx {
     uint32_t order_key[6] = {0, 0, 0, 0, 0, 0};   // width, height, part, n_parts, scene epoch, n_tiles
     std::vector<uint32_t> h_cost;
     std::vector<uint32_t> h_order;
-    // pair records re-numbered by how often the view visits them (brt_api.cpp apply_hot_order)
+    // pair records re-numbered by how often the view visits them (brt_api_order.cpp apply_hot_order)
     uint32_t* d_record_hits = nullptr;                   // FrameParams::record_hits of a pre-pass
     size_t record_hits_cap = 0;
     uint32_t hot_tree = 0;                               // brt_ctx::tree_epoch of the tree whose records are in hot order on this device (0: none)
@@ -242,7 +243,7 @@ void release_external_frames(brt_ctx* ctx);   // brt_interop.cpp; called by brt_
 }  // namespace brt
 
 namespace brt {
-// strip table (brt_api.cpp): the device copy on dc, for work on `stream`; *part_of_strip (frame strip -> part) for the assembly,
+// strip table (brt_api_order.cpp): the device copy on dc, for work on `stream`; *part_of_strip (frame strip -> part) for the assembly,
 // fp->strip_of (fp->part's k-th local strip -> frame strip) for the kernel.  Nothing is attached when the context holds no table for
 // fp's frame and split.  An assembly that got a table calls strip_table_read behind its launch.
 bool strip_table_valid(const uint32_t* part_of_strip, uint32_t n_strips, uint32_t n_parts);

@@ -1,0 +1,106 @@
+// brt_frame.h -- what the host units of the C ABI (brt_api*.cpp) share beyond the context of brt_ctx.h.  Internal and host only:
+// no .hip, and no header a .hip includes, may include it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "brt_ctx.h"
+
+namespace brt {
+
+constexpr uint32_t kPolicyMask = BRT_POLICY_OR_SHORT_CIRCUIT | BRT_POLICY_MINMAX_SELECT | BRT_POLICY_POW_EXP2_LOG2;
+constexpr uint32_t kLptAfterUpload = 4;      // frames after a scene upload within which the tile costs are measured again (brt_api_order.cpp)
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The stream of an asynchronous entry point: the context's own (the call then synchronises, measures and reads the counters) unless the
+// caller passes one or sets BRT_FLAG_CALLER_STREAM (a null stream is then the caller's null stream).
+struct StreamChoice { bool own; hipStream_t stream; };
+inline StreamChoice stream_of(const DeviceCtx& dc, void* hip_stream, uint32_t flags) {
+    const bool own = (hip_stream == nullptr) && !(flags & BRT_FLAG_CALLER_STREAM);
+    return {own, own ? dc.stream : static_cast<hipStream_t>(hip_stream)};
+}
+
+// The strips of part `part` when the strips of a frame go to n_parts parts in turn: its k-th strip is frame strip part + k * n_parts
+// and lies at row k * BRT_STRIP_ROWS of its tile.  All of them are whole but the frame's last one, if that is partial and this part's.
+struct PartStrips {
+    uint32_t part, n_parts;
+    uint32_t n_full;         // whole strips: k = 0 .. n_full - 1
+    uint32_t tail_rows;      // rows of the partial strip k = n_full (0: none)
+    PartStrips(uint32_t height, uint32_t part_, uint32_t n_parts_) : part(part_), n_parts(n_parts_) {
+        const uint32_t full = height / BRT_STRIP_ROWS;
+        n_full = full > part ? (full - part + n_parts - 1u) / n_parts : 0u;
+        tail_rows = full % n_parts == part ? height - full * BRT_STRIP_ROWS : 0u;
+    }
+    uint32_t count() const { return n_full + (tail_rows ? 1u : 0u); }
+    uint32_t frame_row(uint32_t k) const { return (part + k * n_parts) * BRT_STRIP_ROWS; }
+    uint32_t rows(uint32_t k) const { return k < n_full ? BRT_STRIP_ROWS : tail_rows; }
+    uint64_t total_rows() const { return (uint64_t)n_full * BRT_STRIP_ROWS + tail_rows; }
+};
+
+// ---- brt_api.cpp ----
+// brt_upload_scene; with `rebuild`, the resident scene's bytes again in a callee-built SAH tree of reach level `level`
+int32_t upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
+                     const void* bvh_nodes, uint32_t n_nodes, uint32_t level, bool rebuild);
+int32_t ensure_tree_reach(brt_ctx* ctx, const void* camera80, uint32_t* rebuilt);
+void tree_stats(const brt_ctx* ctx, uint32_t rebuilt, brt_stats* stats);
+
+// ---- brt_api_launch.cpp ----
+struct LaunchPlan {
+    int scene_mode;              // SceneMode (brt_layout.h)
+    uint32_t lds_pairs;          // SCENE_LDS_TOP: pair records staged in LDS
+    uint32_t block, grid, wg_per_cu;
+    uint32_t pool_cap;           // records of the drain pool per workgroup (0: none)
+    uint32_t rows;               // 1: with the scratch of the row-mode walk (SCENE_LDS)
+    size_t lds_bytes;
+    uint32_t variant;            // brt_stats::kernel_variant of the launch
+    uint32_t measured;           // the launch measured the tile costs
+};
+int32_t make_frame_params(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t width,
+                          uint32_t height, uint32_t part, uint32_t n_parts, FrameParams* out);
+LaunchPlan plan_launch(const Knobs& kn, const DeviceCtx& dc, const FrameParams& fp);
+int32_t launch_part(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const float* d_raster_rgba,
+                    const float* d_raster_depth, float* d_out_tile, hipStream_t stream, uint32_t flags, bool timed,
+                    LaunchPlan* plan_out);
+uint64_t part_pixels(const FrameParams& fp);
+// the launch fields of brt_stats: the plan of the (last) launch, and the hot records of dc
+void launch_stats(const brt_ctx* ctx, const DeviceCtx& dc, const LaunchPlan& lp, brt_stats* stats);
+// behind the frame of fp enqueued on dc's `stream`: the order of the next frames, then -- synchronising -- the counters added to *st and
+// the kernel and pre-pass times as running maxima in st->kernel_ms / st->prepass_ms
+int32_t collect_part(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, hipStream_t stream, bool prepass_ran, brt_stats* st);
+
+// ---- brt_api_order.cpp ----
+void view_key_of(const brt_ctx* ctx, const FrameParams& fp, uint32_t key[8]);
+int32_t attach_tile_order(brt_ctx* ctx, DeviceCtx& dc, FrameParams& fp, hipStream_t stream, bool may_measure, uint32_t flags);
+int32_t update_tile_order(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, hipStream_t stream);
+int32_t prepass_order(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const float* d_raster_rgba,
+                      const float* d_raster_depth, float* d_out_tile, hipStream_t stream, uint32_t flags, bool* ran);
+uint64_t tree_shape_hash(const EncodedScene& e);
+void permute_scene(const std::vector<float>& pairs, const std::vector<float>& spheres, const std::vector<uint32_t>& sphmat,
+                   const std::vector<float>& sphmats, uint32_t root, const std::vector<uint32_t>& rank, const std::vector<uint32_t>& srank,
+                   std::vector<float>* out_pairs, std::vector<float>* out_spheres, std::vector<uint32_t>* out_sphmat,
+                   std::vector<float>* out_sphmats, uint32_t* out_root);
+
+// ---- brt_api_render.cpp ----
+void drain_all_streams(brt_ctx* ctx);
+
+// ---- brt_api_post.cpp ----
+// the guides' frame parameters (one part, level 3) and the denoiser's scratch of a width x height frame for work on `stream`
+int32_t denoise_begin(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                      hipStream_t stream, FrameParams* fp, DenoiseScratch* ds);
+int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const DenoiseScratch& ds, const float* d_in, void* d_out,
+                    uint32_t out_format, hipStream_t stream, uint32_t flags, const BlendPost& bp);
+bool blend_post_on(uint32_t level, uint32_t flags);
+int32_t post_flags_check(brt_ctx* ctx, uint32_t level, uint32_t flags);
+
+}  // namespace brt

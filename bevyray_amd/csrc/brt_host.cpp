@@ -553,7 +553,7 @@ int32_t scene_generate(uint32_t kind, uint64_t seed, std::vector<Model>* models,
 float tan_half_fov(float fov) { return (float)std::tan((double)(fov * 0.5f)); }
 
 // ---------------------------------------------------------------------------------------
-// Dispatch order of the 8x8 tiles (used by brt_api.cpp for k_trace_persistent's queues).
+// Dispatch order of the 8x8 tiles (used by brt_api_order.cpp for k_trace_persistent's queues).
 //
 // A pixel is one sequential chain of samples (the reference threads one RNG state through them), so a frame
 // ends when its slowest pixels end: a tile with a long pixel must not be handed out late.  From the rays each
@@ -853,7 +853,7 @@ int32_t brt_host_material(const float* base_color_srgb3, float metallic, float p
     });
 }
 
-// The pixel-centre ray of the guide buffer and of picking, on the host: make_frame_params' camera terms (brt_api.cpp) and
+// The pixel-centre ray of the guide buffer and of picking, on the host: make_frame_params' camera terms (brt_api_launch.cpp) and
 // camera_ray_dir_center (brt_device.h) operation for operation in f32 (this file is built with -ffp-contract=off; the device's
 // divide and sqrt are correctly rounded, as these are).
 int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py,

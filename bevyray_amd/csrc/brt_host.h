@@ -32,7 +32,7 @@ inline int32_t guard(std::string* ctx_error, F&& body) noexcept {
         return guard_fail(ctx_error, BRT_ERR_INTERNAL, "unknown error");
     }
 }
-// test hook: throws what `kind` names (1 std::bad_alloc, 2 std::logic_error, 3 a non-standard type); brt_api.cpp calls it from
+// test hook: throws what `kind` names (1 std::bad_alloc, 2 std::logic_error, 3 a non-standard type); upload_scene and make_frame_params call it from
 // brt_upload_scene / brt_render* when the tuning knob BRT_TEST_THROW is set (and clears the knob), so that the GPU suite can
 // force an exception through the barrier of exports that own a context
 [[noreturn]] void throw_for_test(uint32_t kind);

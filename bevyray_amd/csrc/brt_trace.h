@@ -664,7 +664,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_persistent(DeviceSceneView 
         }
         return;
     }
-    // slots a workgroup takes from the global queue at a time (chosen by the host, brt_api.cpp launch_part)
+    // slots a workgroup takes from the global queue at a time (chosen by the host, brt_api_launch.cpp launch_part)
     const uint32_t wgq_batch = fp.wgq_batch >= 64u ? fp.wgq_batch : 64u;
     // tuning knobs: live in the TUNABLE instantiation, constants (brt_layout.h) in the production one
     const uint32_t queue_lane = TUNABLE ? fp.queue_lane : 0u;

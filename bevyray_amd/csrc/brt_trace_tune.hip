@@ -1,5 +1,5 @@
 // brt_trace_tune.hip -- k_trace_persistent with the tuning knobs live (TUNABLE = true): chosen by
-// brt_api.cpp when any BRT_* tuning variable differs from its default (experiments, knob tests).
+// brt_api_launch.cpp when any BRT_* tuning variable differs from its default (experiments, knob tests).
 #include "brt_trace.h"
 
 namespace brt {

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The library's HOST side (brt_api.cpp, brt_interop.cpp, brt_host.cpp: validation, encoders, both CPU BVH builders, tree reach rule,
+# The library's HOST side (every .cpp of csrc -- brt_api*.cpp, brt_interop.cpp, brt_host.cpp: validation, encoders, both CPU BVH builders, tree reach rule,
 # store-format tables, RCCL loader) compiled by g++ with AddressSanitizer + UndefinedBehaviorSanitizer, linked with the hipcc-built
 # kernel objects, and the CPU test suite run against it (BRT_LIB_PATH).  CPU only: the GPU boxes run no sanitizers.
 #   bash scripts/asan_host.sh            -> all passed (the address-space-cap test skips itself), 0 sanitizer reports expected
@@ -9,13 +9,18 @@ src="$root/bevyray_amd/csrc"
 out="${TMPDIR:-/tmp}/brt_asan"
 mkdir -p "$out"
 make -s -C "$src" -j8
-for f in brt_api brt_interop brt_host; do
+host=()
+for f in "$src"/*.cpp; do                      # the host units: every .cpp
+    o="$out/$(basename "$f" .cpp).o"
     g++ -std=c++17 -O1 -g -fPIC -ffp-contract=off -fno-fast-math -fsanitize=address,undefined -fno-omit-frame-pointer \
-        -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wextra -Wno-unused-parameter -c -o "$out/$f.o" "$src/$f.cpp"
+        -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Wall -Wextra -Wno-unused-parameter -c -o "$o" "$f"
+    host+=("$o")
 done
-g++ -shared -fPIC -fsanitize=address,undefined -o "$out/libbrt_asan.so" "$out"/brt_api.o "$out"/brt_interop.o "$out"/brt_host.o \
-    "$src"/build/brt_kernels.o "$src"/build/brt_trace_prod.o "$src"/build/brt_trace_tune.o "$src"/build/brt_bvh.o "$src"/build/brt_sah.o \
-    "$src"/build/brt_order.o "$src"/build/brt_denoise.o "$src"/build/brt_temporal.o -L/opt/rocm/lib -lamdhip64 -ldl
+kernels=()
+for o in "$src"/build/*.o; do                  # the kernel objects: every object that did not come from a .cpp
+    [ -e "$src/$(basename "$o" .o).cpp" ] || kernels+=("$o")
+done
+g++ -shared -fPIC -fsanitize=address,undefined -o "$out/libbrt_asan.so" "${host[@]}" "${kernels[@]}" -L/opt/rocm/lib -lamdhip64 -ldl
 asan="$(g++ -print-file-name=libasan.so)"
 ubsan="$(g++ -print-file-name=libubsan.so)"
 cd "$root"

@@ -93,7 +93,7 @@ def random_case(rng):
     if rng.random() < 0.1:
         h = int(rng.integers(60, 200))    # enough 8-row strips for every part of an 8-way split
     # (32+ samples: the first frame of a view runs a pre-pass, which for a scene walked from an LDS tile + L2 also re-numbers the tree's
-    #  records by their use -- brt_api.cpp apply_hot_order)
+    #  records by their use -- brt_api_order.cpp apply_hot_order)
     spp = int(rng.choice([0, 1, 2, 3, 5, 9, 33, 64], p=[0.03, 0.29, 0.24, 0.19, 0.11, 0.06, 0.05, 0.03]))
     bounces = int(rng.choice([0, 1, 3, 8, 20, 70], p=[0.1, 0.15, 0.3, 0.3, 0.1, 0.05]))
     per_ray = n if topo in (1, 3, 4) else 40          # sphere/box tests per ray, roughly

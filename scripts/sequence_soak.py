@@ -4,7 +4,7 @@ through one context, every frame against the CPU oracle, bit for bit.
 
     python scripts/sequence_soak.py --sequences 200 --seed 3 [--log gpurun_out/sequence_soak.txt]
 
-scripts/fuzz_parity.py draws independent frames; the state this round added lives ACROSS frames (brt_api.cpp):
+scripts/fuzz_parity.py draws independent frames; the state this round added lives ACROSS frames (brt_api.cpp, brt_api_order.cpp):
   * the pair records and spheres re-numbered by a view's visit counts (apply_hot_order), counted again after a camera jump -- the
     permutations compose --, kept over the upload of a tree of the same shape (an animated scene), dropped when the shape changes;
   * the callee's tree rebuilt when the camera leaves its reach and again when it comes back (ensure_tree_reach);

@@ -849,7 +849,7 @@ def test_records_numbered_by_visits_same_pixels_and_counters(oracle):
     """a scene whose tree does not fit the LDS is walked from a tile of the first K pair records in LDS and the rest
     from L2.  The pre-pass of a first frame counts the interior visits per record and the records are re-numbered by them (most
     visited first), so that the tile holds what THIS view walks instead of the breadth-first top of the tree
-    (brt_api.cpp apply_hot_order).  Only the numbering changes: pixels, ray count and all five counters equal the oracle's, with
+    (brt_api_order.cpp apply_hot_order).  Only the numbering changes: pixels, ray count and all five counters equal the oracle's, with
     the order on and off, after a camera jump (counted again, permutations compose), with a tile of a handful of records, over three
     sub-contexts, and in the counting and the production instantiations."""
     b = brt.generate_scene(brt.SCENE_STRESS_GRID, 1)
@@ -1184,7 +1184,7 @@ def test_async_render_on_a_caller_stream(plugin, oracle):
 
 
 def test_expensive_first_dispatch_never_changes_pixels(plugin, oracle):
-    # the tile order of a frame comes from the previous frame's per-tile ray counts (brt_api.cpp
+    # the tile order of a frame comes from the previous frame's per-tile ray counts (brt_api_order.cpp
     # attach_tile_order): first frame raster order, later frames expensive tiles first
     b = brt.generate_scene(brt.SCENE_COVER, 4)
     w, h = 200, 120
