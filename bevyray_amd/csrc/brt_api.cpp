@@ -1,5 +1,5 @@
 // brt_api.cpp -- the extern "C" boundary (include/bevyray_amd.h): context lifecycle, knobs, scene upload, tree builds.  Its other
-// units: brt_api_launch.cpp, brt_api_order.cpp, brt_api_render.cpp, brt_api_post.cpp, brt_api_query.cpp; brt_frame.h is what they share.
+// units: brt_api_launch.cpp, brt_api_order.cpp, brt_api_render.cpp, brt_api_post.cpp, brt_api_upscale.cpp, brt_api_query.cpp; brt_frame.h is what they share.
 //
 // What each export replaces in the reference is cited in the header.  This file holds no ray
 // arithmetic: rays are traced only by the HIP kernels (brt_kernels.hip).  Without a usable
@@ -21,7 +21,7 @@ void free_device(DeviceCtx& dc) {
     if (hipSetDevice(dc.device) != hipSuccess) return;
     for (void* p : std::initializer_list<void*>{dc.d_scene, dc.d_ctrl, dc.d_strip_table, dc.d_tile, dc.d_gather, dc.d_pack, dc.d_raster_rgba,
              dc.d_raster_depth, dc.d_bvh_scratch, dc.d_tile_cost, dc.d_tile_order, dc.d_order_meta, dc.d_order_scratch, dc.d_slice_state,
-             dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits})
+             dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_uplow, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits})
         if (p) (void)hipFree(p);
     if (dc.h_stage) (void)hipHostFree(dc.h_stage);
     for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack, dc.ev_strip, dc.ev_strip_read, dc.ev_q, dc.ev_dn,

@@ -211,6 +211,9 @@ int32_t render_frame(brt_ctx* ctx, const void* camera80, const void* window16, u
     return BRT_OK;
 }
 
+}  // namespace
+
+namespace brt {
 
 // The frame of an N-device context assembled on its FIRST device: every device traces its strips, the tiles of the
 // others travel to the first device's gather buffer by peer copy (xGMI between the GPUs of a node; a plain device copy
@@ -377,21 +380,15 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
     return BRT_OK;
 }
 
-// What the three render exports share around their own argument checks.  scene_ready: a level that traces needs a scene.  with_tree_reach:
-// the resident tree serves this camera (ensure_tree_reach) before `render` runs; a failed call leaves nothing in flight on the context's
-// own streams (a caller's stream is the caller's to drain), a successful one reports the tree in its stats.
+}  // namespace brt
+
+namespace {
+
+// What the three render exports share around their own argument checks.  scene_ready: a level that traces needs a scene.  with_tree_reach
+// (brt_frame.h) runs each of them on a tree that serves the camera.
 int32_t scene_ready(brt_ctx* ctx, uint32_t level) {
     if (!ctx->has_scene && level != 0u) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     return BRT_OK;
-}
-template <class Render>
-int32_t with_tree_reach(brt_ctx* ctx, const void* camera80, uint32_t level, brt_stats* stats, Render&& render) {
-    uint32_t rebuilt = 0u;
-    int32_t rc = level != 0u ? ensure_tree_reach(ctx, camera80, &rebuilt) : BRT_OK;
-    if (rc == BRT_OK) rc = render();
-    if (rc != BRT_OK) drain_all_streams(ctx);
-    else tree_stats(ctx, rebuilt, stats);
-    return rc;
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // brt_ctx.h -- the opaque context of the C ABI (include/bevyray_amd.h) and the helpers its translation units share:
-// brt_api*.cpp (upload, launch, order, render, post-passes, queries; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
+// brt_api*.cpp (upload, launch, order, render, post-passes, upsampling, queries; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
 // gather, external-memory frames).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "brt_host.h"
 #include "brt_kernels.h"
 #include "brt_query.h"
+#include "brt_upscale.h"
 
 namespace brt {
 
@@ -109,6 +110,9 @@ struct DeviceCtx {
     size_t temporal_cap = 0;
     char* d_tsph = nullptr;         // two slots of float4[n_models] {centre, r^2} in the caller's order, then u32[n_models] resident -> caller
     size_t tsph_cap = 0;
+    // the low frame of brt_render_upscaled_device (RGBA32F), first device only; ordered by ev_dn like the denoiser's scratch
+    float* d_uplow = nullptr;
+    size_t uplow_cap = 0;
     // ray queries (brt_query.h), first device only.  Queries of the context run one behind the other (every one waits for ev_q and
     // records it), so the batch counter, the resident -> caller map and the staging buffers of brt_query_rays have one user at a time
     hipEvent_t ev_q = nullptr;      // end of the last query (any stream): uploads, rebuilds and the hot-order renumbering wait for it

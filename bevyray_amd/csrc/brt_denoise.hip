@@ -58,6 +58,7 @@ BRT_DEV float edge_log2(f3 np, float tp, float zscale, float4 gq, float dist, fl
 
 // ---- guide buffer ------------------------------------------------------------------------------------------------------------------
 
+// (k_upscale, brt_upscale.hip, casts the same guide into registers: the ray, normal, a and material id below and there must move together)
 template <bool D16>
 BRT_DEV void denoise_guides_pixel(const DeviceSceneView& sv, const FrameParams& fp, float4* __restrict__ g0, float4* __restrict__ g1,
                                   const uint32_t* __restrict__ rmap, uint32_t* __restrict__ sid, uint32_t px, uint32_t py) {

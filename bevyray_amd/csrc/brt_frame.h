@@ -93,6 +93,22 @@ void permute_scene(const std::vector<float>& pairs, const std::vector<float>& sp
 
 // ---- brt_api_render.cpp ----
 void drain_all_streams(brt_ctx* ctx);
+// What the entry points that trace or cast rays share: the resident tree serves this camera (ensure_tree_reach; level 0 traces nothing)
+// before `body` runs; a failed call leaves nothing in flight on the context's own streams (a caller's stream is the caller's to drain), a
+// successful one reports the tree in its stats.
+template <class Body>
+int32_t with_tree_reach(brt_ctx* ctx, const void* camera80, uint32_t level, brt_stats* stats, Body&& body) {
+    uint32_t rebuilt = 0u;
+    int32_t rc = level != 0u ? ensure_tree_reach(ctx, camera80, &rebuilt) : BRT_OK;
+    if (rc == BRT_OK) rc = body();
+    if (rc != BRT_OK) drain_all_streams(ctx);
+    else tree_stats(ctx, rebuilt, stats);
+    return rc;
+}
+// brt_render_device behind its argument checks: the frame of every device of the context, assembled on the first one
+int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t width, uint32_t height,
+                            const float* d_raster_rgba, const float* d_raster_depth, void* d_frame, void* hip_stream, uint32_t flags,
+                            brt_stats* stats);
 
 // ---- brt_api_post.cpp ----
 // the guides' frame parameters (one part, level 3) and the denoiser's scratch of a width x height frame for work on `stream`

@@ -1,0 +1,26 @@
+// brt_upscale.h -- host-callable launcher of the guide-buffer upsampling (brt_upscale.hip).  The rule: DESIGN.md "Guide-buffer upsampling".
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "brt_denoise.h"
+#include "brt_layout.h"
+
+namespace brt {
+
+// The three constants that only keep a stage's weight sum above zero: the floor of the bilinear weight, the floor of
+// the edge-stopping weight, and the 1 of stage B's 1 / (1 + d^2).  The bilinear floor is 2^-26 so that a tap of bilinear weight 0 moves
+// the result by less than an ulp when another one is eligible: at ratio 1 the upsampling is the identity to rounding.  The edge floor is
+// 1 / 4: on spheres a few low pixels wide w_n = cos^128 alone leaves one tap, and the frame keeps the noise bilinear averaging removes
+constexpr float kUpscaleBilinearFloor = 0x1p-26f;
+constexpr float kUpscaleEdgeFloor = 0.25f;
+
+// full: the frame parameters of the width x height output (its pixel-centre rays are cast by the kernel itself); low: those of the traced
+// frame; ds_low: the scratch whose g0 / g1 hold the guides of the low frame (launch_denoise_guides with `low`); d_low: the low frame,
+// RGBA32F low.width x low.height; d_out: full.width x full.height in out_format (BRT_FLAG_OUT_*), not overlapping d_low.  The sigmas of
+// the edge-stopping weights are st's (brt_set_denoise).
+hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, const FrameParams& low, const DenoiseSettings& st,
+                          const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream);
+
+}  // namespace brt

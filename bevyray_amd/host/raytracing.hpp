@@ -184,6 +184,25 @@ public:
                            const float* d_raster_rgba, void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
         check(brt_blend_post_device(ctx_, &camera, &window, width, height, d_coverage, d_raster_rgba, d_out, hip_stream, flags, stats), ctx_);
     }
+    // Guide-buffer upsampling (include/bevyray_amd.h "guide-buffer upsampling"; Pure frames only).  upscale_device: the RGBA f32
+    // low_width x low_height device frame d_low -- rendered with `camera` and upscale_window(window, height, low_height) -- into d_out
+    // (width x height, the BRT_FLAG_OUT_* format of `flags`; not overlapping d_low).  render_upscaled_device: trace at the low size,
+    // post-passes on the low frame with BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL in `flags`, upsampling into d_destination.
+    void upscale_device(const CameraExtract& camera, const WindowExtract& window, uint32_t low_width, uint32_t low_height, const float* d_low,
+                        uint32_t width, uint32_t height, void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_upscale_device(ctx_, &camera, &window, low_width, low_height, d_low, width, height, d_out, hip_stream, flags, stats), ctx_);
+    }
+    void render_upscaled_device(const CameraExtract& camera, const WindowExtract& window, uint32_t low_width, uint32_t low_height,
+                                uint32_t width, uint32_t height, void* d_destination, void* hip_stream = nullptr, uint32_t flags = 0,
+                                brt_stats* stats = nullptr) {
+        check(brt_render_upscaled_device(ctx_, &camera, &window, low_width, low_height, width, height, d_destination, hip_stream, flags, stats), ctx_);
+    }
+    // the window a low_height frame is traced with when it is presented at `height` rows
+    static WindowExtract upscale_window(const WindowExtract& window, uint32_t height, uint32_t low_height) {
+        WindowExtract w{};
+        check(brt_host_upscale_window(&window, height, low_height, &w), nullptr);
+        return w;
+    }
     // Ray queries against the resident scene (brt_query_rays*, include/bevyray_amd.h "ray queries"): 32-byte rays in, 32-byte hits out.
     // mode: BRT_QUERY_CLOSEST / BRT_QUERY_ANY; origin_bound > 0 first raises the callee-built tree's reach for origins of that 1-norm.
     struct Ray { float origin[3]; float t_max; float direction[3]; uint32_t user; };

@@ -277,6 +277,14 @@ def rtiow_camera(width: int, height: int, sample_count: int, bounces: int,
     return lvl, cex, WindowExtract.extract_component(height, seed)
 
 
+def upscale_window(window, height: int, low_height: int) -> np.ndarray:
+    """brt_host_upscale_window: the window a low_height frame is traced with when it is to be upsampled to `height` rows -- the seed of
+    `window`, its height scaled to max(1, window.height * low_height // height).  Host arithmetic."""
+    out = np.zeros(1, WINDOW_DTYPE)
+    _lib.check(_lib.load().brt_host_upscale_window(window.ctypes.data, int(height), int(low_height), out.ctypes.data))
+    return out
+
+
 def tile_rows(height: int, n_parts: int) -> int:
     return int(_lib.load().brt_tile_rows(height, n_parts))
 
@@ -631,6 +639,35 @@ class RayTracingNode:
                                                 d_raster_rgba or None, d_out, stream or None,
                                                 (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags, C.byref(stats)), p._ctx)
         return stats.as_dict()
+
+    # -- guide-buffer upsampling (include/bevyray_amd.h "guide-buffer upsampling") ------------------
+
+    def upscale_device(self, camera, window, low_width: int, low_height: int, d_low: int, width: int, height: int, d_out: int,
+                       stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F) -> dict:
+        """brt_upscale_device: the RGBA f32 low_width x low_height Pure device frame d_low (rendered with camera and
+        upscale_window(window, height, low_height) on the resident scene; denoised / accumulated or not) upsampled into d_out
+        (width x height, out_format: FLAG_OUT_*; must not overlap d_low).  Stream rule as for render_part_device."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_upscale_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, d_low or None, width,
+                                             height, d_out or None, stream or None,
+                                             (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+        return stats.as_dict()
+
+    def render_upscaled_device(self, camera, window, low_width: int, low_height: int, width: int, height: int, d_frame: int,
+                               stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_upscaled_device: a Pure frame traced at low_width x low_height (render_device with upscale_window(window, height,
+        low_height)), with flags FLAG_DENOISE and / or FLAG_TEMPORAL post-processed at that size, and upsampled into d_frame
+        (width x height, out_format).  Pure only: there is no level.  Stream rule as for render_part_device; last_stats: the low
+        frame's, total_ms of the whole call."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_upscaled_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, width, height,
+                                                     d_frame or None, stream or None,
+                                                     (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                                     C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
 
     # -- ray queries (include/bevyray_amd.h "ray queries") ------------------------------------------
 

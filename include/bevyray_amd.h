@@ -467,6 +467,42 @@ int32_t brt_query_origin_bound(brt_ctx* ctx, float* out_bound);
 int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py,
                            void* out_ray32);
 
+/* ---- guide-buffer upsampling ----------------------------------------------------------------------------------------------------------
+ * A frame traced at low_width x low_height is presented at width x height: every OUTPUT pixel casts its own pixel-centre ray (the guide
+ * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
+ * of the low frame's taps that lie on the same material, weighted bilinearly and by the denoiser's normal and depth terms (sigma_normal,
+ * sigma_depth of brt_set_denoise).  Rule, kernel and costs: DESIGN.md "Guide-buffer upsampling".  Deterministic.  Pure (level 3) frames
+ * only: neither call takes a level -- a coverage frame's upsampling would need the raster blend at full size.
+ * Sizes, per axis: 1 <= low <= full <= 32768 and full <= 4 x low; else BRT_ERR_INVALID_ARGUMENT.  camera80: the frame's camera, the same
+ * for both sizes.  BRT_ERR_NO_SCENE before an upload.
+ *   brt_upscale_device          upsamples an RGBA f32 low_width x low_height DEVICE frame the caller holds -- a Pure frame of any entry
+ *                               point (the root's frame after brt_gather_rccl), denoised / accumulated or not, rendered with camera80 on
+ *                               the resident scene and the window of brt_host_upscale_window -- into d_out (DEVICE, width x height in the
+ *                               BRT_FLAG_OUT_* format of `flags`; it must not overlap d_low_rgba).  window16: the full-size or the low
+ *                               window (only pixel-centre rays are cast: its height is not read).  flags: BRT_FLAG_CALLER_STREAM,
+ *                               BRT_FLAG_OUT_*; other bits BRT_ERR_INVALID_ARGUMENT.  Stream rule and stats (total_ms only) as for
+ *                               brt_denoise_device; the call shares the denoiser's scratch and runs one behind another with the context's
+ *                               denoise / temporal calls on whatever streams they come.
+ *   brt_render_upscaled_device  trace, post-passes and upsampling in one call.  The low frame is exactly the low_width x low_height Pure
+ *                               frame of brt_render_device (every device of the context) with the same camera and the window of
+ *                               brt_host_upscale_window(window16, height, low_height); it stays in the context.  With BRT_FLAG_DENOISE
+ *                               and / or BRT_FLAG_TEMPORAL the post-passes run on the LOW frame (the temporal history is that of the low
+ *                               size) and the upsampling comes last.  d_frame: DEVICE, width x height in the BRT_FLAG_OUT_* format of
+ *                               `flags`.  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE, BRT_FLAG_TEMPORAL; other bits
+ *                               BRT_ERR_INVALID_ARGUMENT.  Stream rule as for brt_render_device; stats_or_null as brt_render_device
+ *                               fills them for the low frame, total_ms for the whole call.
+ *   brt_host_upscale_window     host arithmetic, no context: out_window16 = window16 with height = max(1, window.height * low_height /
+ *                               height) in integer arithmetic -- the window a low frame is traced with (the reference sizes the jitter
+ *                               of a sample by window.height, raytrace.wgsl:139-147).  1 <= low_height <= height, else
+ *                               BRT_ERR_INVALID_ARGUMENT. */
+int32_t brt_upscale_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
+                           const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, void* hip_stream, uint32_t flags,
+                           brt_stats* stats_or_null);
+int32_t brt_render_upscaled_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
+                                   uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags,
+                                   brt_stats* stats_or_null);
+int32_t brt_host_upscale_window(const void* window16, uint32_t height, uint32_t low_height, void* out_window16);
+
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how
  * often the waves executed code section k and the sum of active lanes over those executions

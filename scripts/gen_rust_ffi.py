@@ -31,6 +31,9 @@ DOCS = {
     "brt_query_rays_device": "batched ray queries (closest hit / occlusion) against the resident scene: 32-byte rays in, 32-byte hits out, DEVICE buffers; the reference offers none (a host would rebuild a CPU BVH per frame, extract.rs:315-332)",
     "brt_query_rays": "the same for host buffers, synchronous",
     "brt_query_origin_bound": "the largest origin 1-norm the resident tree covers (+INF: any)",
+    "brt_upscale_device": "guide-buffer upsampling of a low-resolution Pure DEVICE frame the caller holds to the colour target's size: every output pixel casts its own centre ray, so silhouettes, base colour and sky are at full sharpness",
+    "brt_render_upscaled_device": "trace at low_width x low_height (brt_render_device's frame, every device of the context), post-passes on the low frame, upsampling into the full-size target: the pass on post_process.destination (pipeline.rs:191-217) at a fraction of the rays",
+    "brt_host_upscale_window": "host arithmetic: the WindowExtract a low frame is traced with (height scaled in integer arithmetic, at least 1)",
     "brt_host_pixel_ray": "host arithmetic: the pixel-centre ray of a pixel (raytrace.wgsl:139-156 without the jitter), for picking",
     "brt_debug_temporal_state": "diagnostic: the temporal history per pixel (h.rgb, n, m1, m2, reprojected x', y') in host memory",
 }

@@ -1,0 +1,504 @@
+"""Guide-buffer upsampling (brt_upscale_device, brt_render_upscaled_device, brt_host_upscale_window; DESIGN.md "Guide-buffer
+upsampling").  CPU: the exports, the argument checks, the window rule, properties of the numpy restatement (tests/upscale_ref.py) with
+guides from the oracle's raycast at both sizes, and its quality bar against plain bilinear upsampling.  GPU: the low frame bitwise against
+the oracle, the kernel against the restatement, the store formats, the one-call form against the two-step form, no change to plain
+frames or to the history of another size, streams, rejections, quality."""
+import functools
+import struct
+
+import numpy as np
+import pytest
+
+import bevyray_amd as brt
+from bevyray_amd import _lib
+import denoise_ref as dr
+import upscale_ref as ur
+from helpers import make_buffers, uniforms
+
+F32 = np.float32
+ERR_INVALID, ERR_NO_SCENE = -1, -7
+# Quality: MSE over the full-size hit pixels of the upsampled frame / of the plain bilinear upsampling of the same low frame, both
+# against a 1024-spp full-size frame of another seed; cover scene, 8 bounces, ratio 2.  {spp: bar}, bar = measured x 1.1 and below 1.
+# CPU restatement, 96x54 from 48x27: measured 0.963 at 4 spp, 0.802 at 64 spp.  GPU, 480x270 from 240x135, reference traced on the GPU:
+# measured 0.921 at 4 spp, 0.649 at 64 spp (profiles/upscale/upscale_time.json).  1.1 x 0.963 and 1.1 x 0.921 are above 1: held at 0.999.
+CPU_BARS = {4: 0.999, 64: 0.882}
+GPU_BARS = {4: 0.999, 64: 0.714}
+
+
+def bilinear(low, w, h):
+    """Plain bilinear upsampling of the colour of `low` to w x h (pixel centres aligned, edges clamped): the baseline of the quality
+    measurement.  Independent of the code under test but for the position rule."""
+    lh, lw = low.shape[:2]
+    out = np.zeros((h, w, 3), np.float64)
+    xs = np.clip((np.arange(w) + 0.5) * lw / w - 0.5, 0, lw - 1)
+    ys = np.clip((np.arange(h) + 0.5) * lh / h - 0.5, 0, lh - 1)
+    x0, y0 = np.floor(xs).astype(int), np.floor(ys).astype(int)
+    x1, y1 = np.minimum(x0 + 1, lw - 1), np.minimum(y0 + 1, lh - 1)
+    fx, fy = (xs - x0)[None, :, None], (ys - y0)[:, None, None]
+    c = low[..., :3].astype(np.float64)
+    out = (c[y0][:, x0] * (1 - fx) + c[y0][:, x1] * fx) * (1 - fy) + (c[y1][:, x0] * (1 - fx) + c[y1][:, x1] * fx) * fy
+    return out.astype(F32)
+
+
+# ---- CPU --------------------------------------------------------------------------------------------------------------------------
+
+def test_upscale_exports_exist():
+    lib = _lib.load()
+    for name in ("brt_upscale_device", "brt_render_upscaled_device", "brt_host_upscale_window"):
+        assert name in _lib.EXPORTS and getattr(lib, name) is not None
+    assert lib.brt_abi_version() == 6
+    assert callable(brt.RayTracingNode.upscale_device) and callable(brt.RayTracingNode.render_upscaled_device) and callable(brt.upscale_window)
+
+
+def test_upscale_argument_checks_without_a_context():
+    lib = _lib.load()
+    cam, win, out = np.zeros(80, np.uint8), np.zeros(16, np.uint8), np.zeros(16, np.uint8)
+    assert lib.brt_upscale_device(None, cam.ctypes.data, win.ctypes.data, 4, 4, 16, 8, 8, 4096, None, 0, None) == ERR_INVALID
+    assert lib.brt_render_upscaled_device(None, cam.ctypes.data, win.ctypes.data, 4, 4, 8, 8, 4096, None, 0, None) == ERR_INVALID
+    assert lib.brt_host_upscale_window(None, 8, 4, out.ctypes.data) == ERR_INVALID
+    assert lib.brt_host_upscale_window(win.ctypes.data, 8, 4, None) == ERR_INVALID
+    for height, low in ((0, 0), (8, 0), (4, 8), (0, 4)):
+        assert lib.brt_host_upscale_window(win.ctypes.data, height, low, out.ctypes.data) == ERR_INVALID
+
+
+def test_upscale_window_is_the_integer_rule():
+    rng = np.random.default_rng(5)
+    cases = [(54, 54, 27), (1080, 1080, 540), (1080, 1080, 720), (1, 4, 1), (3, 1080, 270), (0, 8, 4), (7, 9, 9), (2000, 1080, 1080),
+             (4294967295, 32768, 32768), (4294967295, 32768, 8192), (1081, 1081, 271)]
+    cases += [tuple(int(v) for v in (rng.integers(0, 5000), h, rng.integers(1, h + 1))) for h in rng.integers(1, 3000, 40)]
+    for wh, height, low in cases:
+        win = brt.WindowExtract.extract_component(wh, 0.375)
+        got = brt.upscale_window(win, height, low)
+        want = struct.pack("<fIff", 0.375, max(1, wh * low // height), 0.0, 0.0)      # (seed kept, padding zero)
+        assert got.view(np.uint8).tobytes() == want, (wh, height, low)
+        if low == height and wh != 0:
+            assert got.view(np.uint8).tobytes() == win.view(np.uint8).tobytes()
+
+
+RED = brt.StandardMaterial(base_color=(0.8, 0.3, 0.3))
+BLUE = brt.StandardMaterial(base_color=(0.2, 0.4, 0.9))
+
+
+def _view(w, h, spp=1):
+    return uniforms(w, h, spp, 2, (0.0, 0.0, 6.0), (0.0, 0.0, 0.0), 0.5, 0.5)
+
+
+def _guides_pair(oracle, b, w, h, lw, lh):
+    _, cam, _ = _view(w, h)
+    return cam, dr.guides(oracle, b, cam, lw, lh), dr.guides(oracle, b, cam, w, h)
+
+
+def _random_low(g_low, seed, lo=0.25, hi=1.0):
+    lh, lw = g_low.shape[:2]
+    low = np.ones((lh, lw, 4), F32)
+    low[..., :3] = np.random.default_rng(seed).uniform(lo, hi, (lh, lw, 3)).astype(F32)
+    return low
+
+
+def test_restatement_is_the_identity_at_ratio_one_and_the_sky_is_analytic(oracle):
+    """Low = full: every hit pixel takes stage A with its own tap at bilinear weight 1 and the three others at 2^-26, so the result is
+    c / a * a: five roundings of at most half an ulp of values below 2 (a >= 0.5 here), plus 3 x 2^-26 of a neighbour's c': 1e-6."""
+    b = make_buffers([((0.0, 0.0, 0.0), 1.0, RED)])
+    w, h = 24, 18
+    cam, g_low, g_full = _guides_pair(oracle, b, w, h, w, h)
+    assert np.array_equal(g_low.view(np.uint32), g_full.view(np.uint32))
+    low = _random_low(g_low, 3)
+    out, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    hit = g_full[..., 3] < np.inf
+    assert 40 < hit.sum() < w * h - 40
+    assert (stage[hit] == ur.STAGE_A).all() and (stage[~hit] == ur.SKY).all()
+    assert np.abs(out[hit][:, :3] - low[hit][:, :3]).max() <= 1e-6
+    assert (out[..., 3] == 1).all()
+    # the sky: sqrt(background_gradient(d)) of the pixel's own centre ray, restated per pixel in scalar f32
+    _, dirs, _ = dr.pixel_center_rays(oracle, cam, w, h)
+    for y, x in np.argwhere(~hit):
+        d = dirs[y, x]
+        u = d / np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], dtype=F32)
+        a = F32(0.5) * (u[1] + F32(1.0))
+        col = np.sqrt((F32(1.0) - a) * np.ones(3, F32) + a * np.array([0.5, 0.7, 1.0], F32), dtype=F32)
+        assert np.array_equal(out[y, x, :3].view(np.uint32), col.view(np.uint32)), (y, x)
+
+
+def test_restatement_keeps_a_constant_sphere_constant(oracle):
+    b = make_buffers([((0.0, 0.0, 0.0), 1.0, RED)])
+    for (w, h, lw, lh) in ((32, 24, 16, 12), (32, 24, 21, 16), (33, 25, 9, 7)):
+        cam, g_low, g_full = _guides_pair(oracle, b, w, h, lw, lh)
+        low = _random_low(g_low, 4)                      # (whatever the sky taps hold)
+        k = np.array([0.3, 0.2, 0.1], F32)
+        low[g_low[..., 3] < np.inf, :3] = k
+        out, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+        hit = g_full[..., 3] < np.inf
+        assert np.isin(stage[hit], (ur.STAGE_A, ur.STAGE_B)).all()
+        assert np.abs(out[hit][:, :3] - k).max() <= 1e-6, (w, h, lw, lh)
+
+
+def test_restatement_carries_nothing_across_a_material_boundary(oracle):
+    """Two touching spheres of two colours: every output pixel has the colour of its own sphere, so the output's partition into
+    spheres and sky is the full-size guides'."""
+    b = make_buffers([((-1.0, 0.0, 0.0), 1.0, RED), ((1.0, 0.0, 0.0), 1.0, BLUE)])
+    for (w, h, lw, lh) in ((40, 24, 20, 12), (40, 24, 27, 16), (41, 25, 11, 7)):
+        cam, g_low, g_full = _guides_pair(oracle, b, w, h, lw, lh)
+        ks = np.array([[0.9, 0.1, 0.1], [0.1, 0.2, 0.8]], F32)
+        low = np.ones((lh, lw, 4), F32)
+        low[..., :3] = (0.0, 1.0, 0.0)                  # (a sky colour no output may show)
+        mat_low, mat_full = g_low[..., 7].view(np.uint32), g_full[..., 7].view(np.uint32)
+        for m in (0, 1):
+            low[mat_low == m, :3] = ks[m]
+        out, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+        hit = g_full[..., 3] < np.inf
+        assert np.isin(stage[hit], (ur.STAGE_A, ur.STAGE_B)).all()
+        for m in (0, 1):
+            assert (mat_full == m).sum() > 20
+            assert np.abs(out[mat_full == m][:, :3] - ks[m]).max() <= 1e-6, (w, h, lw, lh, m)
+        sky = ur.sky_colour(dr.pixel_center_rays(oracle, cam, w, h)[1])
+        assert np.array_equal(out[~hit][:, :3].view(np.uint32), sky[~hit].view(np.uint32))
+
+
+def test_restatement_takes_stage_c_for_a_sphere_thinner_than_a_low_pixel(oracle):
+    w, h, lw, lh = 32, 24, 8, 6
+    _, cam, _ = _view(w, h)
+    o, dirs, _ = dr.pixel_center_rays(oracle, cam, w, h)
+    py, px = 8, 12                                      # 1.5 full pixels from the nearest low pixel centre on both axes
+    centre = (o + F32(6.0) * dirs[py, px]).astype(np.float64)
+    b = make_buffers([(tuple(centre), 0.08, RED)])     # 0.08 < 1.5 full pixels (0.19 at that distance)
+    g_low, g_full = dr.guides(oracle, b, cam, lw, lh), dr.guides(oracle, b, cam, w, h)
+    assert g_full[py, px, 3] < np.inf and not (g_low[..., 3] < np.inf).any()
+    low = _random_low(g_low, 6)
+    out, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    hit = g_full[..., 3] < np.inf
+    assert (stage[hit] == ur.STAGE_C).all()
+    assert np.abs(out[hit][:, :3] - bilinear(low, w, h)[hit]).max() <= 1e-6     # no demodulation
+    low[...] = np.nan                                   # no finite tap: zero
+    out, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    assert (stage[hit] == ur.STAGE_NONE).all() and (out[hit][:, :3] == 0).all() and (out[..., 3] == 1).all()
+
+
+def test_restatement_never_taps_a_non_finite_pixel(oracle):
+    b = make_buffers([((0.0, 0.0, 0.0), 1.0, RED)])
+    w, h, lw, lh = 32, 24, 16, 12
+    cam, g_low, g_full = _guides_pair(oracle, b, w, h, lw, lh)
+    hit_low = np.argwhere(g_low[..., 3] < np.inf)
+    bad = hit_low[[3, len(hit_low) // 2, len(hit_low) // 2 + 1, -4]]
+    a = _random_low(g_low, 7)
+    c = a.copy()
+    for k, (y, x) in enumerate(bad):
+        a[y, x, k % 3] = (np.nan, np.inf, -np.inf, np.nan)[k]
+        c[y, x, :3] = (np.inf, np.nan, 3.0e38, -np.inf)[k]        # (3e38 is finite, 3e38 / a is not: a < 1)
+    out_a, _ = ur.upscale_frame(oracle, a, g_low, g_full, cam)
+    out_c, _ = ur.upscale_frame(oracle, c, g_low, g_full, cam)
+    assert np.isfinite(out_a).all() and np.isfinite(out_c).all()
+    assert np.array_equal(out_a.view(np.uint32), out_c.view(np.uint32))         # whatever those pixels hold
+
+
+@functools.lru_cache(maxsize=None)
+def _cpu_reference(oracle):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h = 96, 54
+    lvl, cam_r, win_r = brt.cover_camera(w, h, 1024, 8, brt.Raytracing.Pure, 0.25)
+    ref, _ = oracle.render(b, lvl, cam_r, win_r, w, h)
+    return b, ref, dr.guides(oracle, b, cam_r, w, h), dr.guides(oracle, b, cam_r, 48, 27)
+
+
+@pytest.mark.parametrize("spp", [4, 64])
+def test_restatement_quality_bar(oracle, spp):
+    """Cover scene, 96x54 from 48x27: the upsampled low oracle frame has at most CPU_BARS[spp] x the MSE of its plain bilinear
+    upsampling, over the full-size hit pixels, against 1024 spp of another seed."""
+    b, ref, g_full, g_low = _cpu_reference(oracle)
+    w, h, lw, lh = 96, 54, 48, 27
+    lvl, cam, win = brt.cover_camera(w, h, spp, 8, brt.Raytracing.Pure, 0.5)
+    low, _ = oracle.render(b, lvl, cam, brt.upscale_window(win, h, lh), lw, lh)
+    out, _ = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    ratio = dr.hit_mse(out, ref, g_full) / dr.hit_mse(bilinear(low, w, h), ref, g_full)
+    print(f"upsampling quality at {spp} spp: {ratio:.4f}")
+    assert ratio <= CPU_BARS[spp] and ratio < 1.0, ratio
+
+
+# ---- GPU --------------------------------------------------------------------------------------------------------------------------
+
+def _device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _out_tensor(w, h, out_format=brt.FLAG_OUT_RGBA32F):
+    import torch
+    return torch.zeros((h, w * brt.OUT_PIXEL_BYTES[out_format] // 4), dtype=torch.int32, device="cuda")
+
+
+def _host(t, h, w):
+    import torch
+    torch.cuda.synchronize()
+    return t.cpu().numpy().view(np.uint8).reshape(h, w, -1)
+
+
+def _upscale_dev(plugin, cam, win, lw, lh, low, w, h, out_format=brt.FLAG_OUT_RGBA32F, stream=None):
+    d_low, out = _device(low), _out_tensor(w, h, out_format)
+    plugin.node.upscale_device(cam, win, lw, lh, d_low.data_ptr(), w, h, out.data_ptr(), stream=stream, out_format=out_format)
+    return _host(out, h, w)
+
+
+def _render_upscaled(plugin, cam, win, lw, lh, w, h, flags=0, out_format=brt.FLAG_OUT_RGBA32F, stream=None):
+    out = _out_tensor(w, h, out_format)
+    plugin.node.render_upscaled_device(cam, win, lw, lh, w, h, out.data_ptr(), stream=stream, out_format=out_format, flags=flags)
+    return _host(out, h, w)
+
+
+def _render_low(plugin, lvl, cam, win, lw, lh, h, flags=0):
+    import torch
+    low = torch.empty((lh, lw, 4), dtype=torch.float32, device="cuda")
+    plugin.node.render_device(lvl, cam, brt.upscale_window(win, h, lh), lw, lh, low.data_ptr(), flags=flags)
+    return low
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+@pytest.mark.gpu
+def test_low_frame_is_the_oracles(plugin, oracle):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 96, 54, 48, 27
+    lvl, cam, win = brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, 0.5)
+    lwin = brt.upscale_window(win, h, lh)
+    assert int(lwin["height"][0]) == 27
+    want, _ = oracle.render(b, lvl, cam, lwin, lw, lh)
+    plugin.node.write_buffers(b)
+    low = _render_low(plugin, lvl, cam, win, lw, lh, h)
+    assert _same_bits(low.cpu().numpy(), want)
+    one_call = _render_upscaled(plugin, cam, win, lw, lh, w, h)
+    assert _same_bits(one_call, _upscale_dev(plugin, cam, win, lw, lh, want, w, h))
+    assert plugin.node.last_stats["paths"] == lw * lh * 4 and plugin.node.last_stats["total_ms"] > 0
+
+
+SIZES = [(640, 360, 320, 180), (640, 360, 427, 240), (641, 361, 161, 91), (1, 1, 1, 1)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d_from_%dx%d" % s)
+@pytest.mark.parametrize("case", ["cover_callee", "cover_caller", "rtiow", "stress"])
+def test_kernel_matches_the_restatement(plugin, oracle, case, size):
+    w, h, lw, lh = size
+    kind = {"rtiow": brt.SCENE_RTIOW_FINAL, "stress": brt.SCENE_STRESS_GRID}.get(case, brt.SCENE_COVER)
+    b = brt.generate_scene(kind, 1)
+    lvl, cam, win = (brt.rtiow_camera if case == "rtiow" else brt.cover_camera)(w, h, 2, 4)
+    lwin = brt.upscale_window(win, h, lh)
+    buffers = brt.Buffers(b.models, b.materials, None) if case == "cover_callee" else b
+    low = plugin.node.run(lvl, cam, lwin, lw, lh, buffers=buffers).copy()
+    if case == "stress" and w > 1:
+        assert plugin.node.last_stats["scene_in_lds"] == 2             # top of the tree in LDS, the rest from L2
+    g_low, g_full = plugin.debug_denoise_guides(cam, lwin, lw, lh), plugin.debug_denoise_guides(cam, win, w, h)
+    got = _upscale_dev(plugin, cam, win, lw, lh, low, w, h).view(F32)
+    want, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    err = np.abs(got.astype(np.float64) - want) / np.maximum(1.0, np.abs(want))
+    print(f"{case} {size}: max err {err.max():.3g}, stages {np.bincount(stage.ravel(), minlength=5).tolist()}")
+    assert err.max() <= 1e-4, float(err.max())
+    sky = stage == ur.SKY
+    assert _same_bits(got[sky], want[sky])
+    if w > 1:
+        assert sky.any() and (stage == ur.STAGE_A).any()
+
+
+@pytest.mark.gpu
+def test_output_formats_are_the_store_of_the_f32_result(plugin, oracle):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 200, 120, 100, 60
+    lvl, cam, win = brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, 0.5)
+    low = plugin.node.run(lvl, cam, brt.upscale_window(win, h, lh), lw, lh, buffers=b).copy()
+    f32 = _upscale_dev(plugin, cam, win, lw, lh, low, w, h).view(F32)
+    for fmt, name in ((brt.FLAG_OUT_RGBA8_UNORM_SRGB, "srgb8"), (brt.FLAG_OUT_RGBA8_UNORM, "unorm8"), (brt.FLAG_OUT_RGBA16F, "f16")):
+        want = oracle.encode_frame(f32, name)
+        got = _upscale_dev(plugin, cam, win, lw, lh, low, w, h, out_format=fmt)
+        assert np.array_equal(got.view(want.dtype).reshape(want.shape), want), name
+        got = _render_upscaled(plugin, cam, win, lw, lh, w, h, out_format=fmt)
+        assert np.array_equal(got.view(want.dtype).reshape(want.shape), want), name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("flags", [0, brt.FLAG_DENOISE, brt.FLAG_DENOISE | brt.FLAG_TEMPORAL, brt.FLAG_TEMPORAL],
+                         ids=["plain", "denoise", "denoise_temporal", "temporal"])
+def test_one_call_equals_the_two_step_form(plugin, flags):
+    """render_upscaled_device = render_device at the low size (+ denoise_device with the same flags) + upscale_device, bit for bit, over
+    a 4-frame sequence (the temporal history is keyed by the low size in both forms)."""
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 320, 180, 160, 90
+    plugin.node.write_buffers(b)
+    seeds = (0.5, 0.25, 0.75, 0.125)
+
+    def sequence(one_call):
+        plugin.reset_temporal()
+        frames = []
+        for seed in seeds:
+            lvl, cam, win = brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, seed)
+            if one_call:
+                frames.append(_render_upscaled(plugin, cam, win, lw, lh, w, h, flags=flags))
+                continue
+            low = _render_low(plugin, lvl, cam, win, lw, lh, h)
+            if flags:
+                post = torch.empty_like(low)
+                plugin.node.denoise_device(cam, brt.upscale_window(win, h, lh), lw, lh, low.data_ptr(), post.data_ptr(), flags=flags)
+                low = post
+            out = _out_tensor(w, h)
+            plugin.node.upscale_device(cam, win, lw, lh, low.data_ptr(), w, h, out.data_ptr())
+            frames.append(_host(out, h, w))
+        return frames
+
+    one, two = sequence(True), sequence(False)
+    for k in range(len(seeds)):
+        assert _same_bits(one[k], two[k]), k
+    assert not _same_bits(one[0], one[1])
+    plugin.reset_temporal()
+
+
+@pytest.mark.gpu
+def test_plain_frames_and_the_history_of_another_size_are_untouched(plugin, oracle):
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 200, 120, 100, 60
+    lvl, cam, win = brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, 0.5)
+    lvl2, cam2, win2 = brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, 0.25)
+    want, _ = oracle.render(b, lvl, cam, win, w, h)
+    frame = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+
+    def plain():
+        plugin.node.render_device(lvl, cam, win, w, h, frame.data_ptr())
+        return frame.cpu().numpy()
+
+    def temporal_pair(between):
+        plugin.reset_temporal()
+        plugin.node.render_device(lvl, cam, win, w, h, frame.data_ptr(), flags=brt.FLAG_TEMPORAL)
+        between()
+        plugin.node.render_device(lvl2, cam2, win2, w, h, frame.data_ptr(), flags=brt.FLAG_TEMPORAL)
+        return frame.cpu().numpy(), plugin.debug_temporal_state(w, h)
+
+    def upscaled_calls():
+        _render_upscaled(plugin, cam, win, lw, lh, w, h)
+        _render_upscaled(plugin, cam2, win2, lw, lh, w, h, flags=brt.FLAG_DENOISE)
+        _upscale_dev(plugin, cam, win, lw, lh, np.ones((lh, lw, 4), F32), w, h)
+
+    plugin.node.write_buffers(b)
+    assert _same_bits(plain(), want)
+    upscaled_calls()
+    assert _same_bits(plain(), want)
+    assert _same_bits(plugin.node.run(lvl, cam, win, w, h), want)
+    f_a, s_a = temporal_pair(lambda: None)
+    f_b, s_b = temporal_pair(upscaled_calls)
+    assert _same_bits(f_a, f_b) and _same_bits(s_a, s_b)
+    assert (s_b[..., 3] == 2).any()                                  # (the second frame did find the first one's history)
+    # an upscaled TEMPORAL frame is a temporal frame of the low size: "another size empties the history"
+    plugin.node.render_device(lvl, cam, win, w, h, frame.data_ptr(), flags=brt.FLAG_TEMPORAL)
+    _render_upscaled(plugin, cam2, win2, lw, lh, w, h, flags=brt.FLAG_TEMPORAL)
+    assert (plugin.debug_temporal_state(lw, lh)[..., 3] <= 1).all()
+    plugin.node.render_device(lvl, cam, win, w, h, frame.data_ptr(), flags=brt.FLAG_TEMPORAL)
+    s_c = plugin.debug_temporal_state(w, h)
+    assert (s_c[..., 3] <= 1).all() and (s_c[..., 3] == 1).any()      # the full-size history was emptied: this frame starts at n = 1
+    plugin.reset_temporal()
+
+
+@pytest.mark.gpu
+def test_streams(plugin):
+    """A caller's stream, the default stream under BRT_FLAG_CALLER_STREAM, and two calls in flight on two streams (the pattern of
+    tests/test_caller_streams.py): every result is the synchronous call's."""
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 320, 180, 160, 90
+    plugin.node.write_buffers(b)
+    views = [brt.cover_camera(w, h, 4, 8, brt.Raytracing.Pure, s) for s in (0.5, 0.25)]
+    lows = [_render_low(plugin, lvl, cam, win, lw, lh, h) for lvl, cam, win in views]
+    want_up = [_upscale_dev(plugin, cam, win, lw, lh, low.cpu().numpy(), w, h) for (_, cam, win), low in zip(views, lows)]
+    want_one = [_render_upscaled(plugin, cam, win, lw, lh, w, h, flags=brt.FLAG_DENOISE) for _, cam, win in views]
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    # one stream, both forms one behind the other
+    outs = [_out_tensor(w, h) for _ in range(4)]
+    with torch.cuda.stream(s1):
+        for k, (_, cam, win) in enumerate(views):
+            plugin.node.upscale_device(cam, win, lw, lh, lows[k].data_ptr(), w, h, outs[k].data_ptr(), stream=s1.cuda_stream)
+            plugin.node.render_upscaled_device(cam, win, lw, lh, w, h, outs[2 + k].data_ptr(), stream=s1.cuda_stream, flags=brt.FLAG_DENOISE)
+    s1.synchronize()
+    for k in range(2):
+        assert _same_bits(_host(outs[k], h, w), want_up[k]) and _same_bits(_host(outs[2 + k], h, w), want_one[k])
+    # the default stream, named by the flag
+    outs = [_out_tensor(w, h) for _ in range(2)]
+    _, cam, win = views[0]
+    plugin.node.upscale_device(cam, win, lw, lh, lows[0].data_ptr(), w, h, outs[0].data_ptr(), stream=0)
+    plugin.node.render_upscaled_device(cam, win, lw, lh, w, h, outs[1].data_ptr(), stream=0, flags=brt.FLAG_DENOISE)
+    torch.cuda.synchronize()
+    assert _same_bits(_host(outs[0], h, w), want_up[0]) and _same_bits(_host(outs[1], h, w), want_one[0])
+    # two streams, calls of both forms in flight on each at once
+    outs = [_out_tensor(w, h) for _ in range(8)]
+    for r in range(2):
+        for k, s in enumerate((s1, s2)):
+            _, cam, win = views[k]
+            plugin.node.render_upscaled_device(cam, win, lw, lh, w, h, outs[4 * r + k].data_ptr(), stream=s.cuda_stream, flags=brt.FLAG_DENOISE)
+            plugin.node.upscale_device(cam, win, lw, lh, lows[k].data_ptr(), w, h, outs[4 * r + 2 + k].data_ptr(), stream=s.cuda_stream)
+    s1.synchronize()
+    s2.synchronize()
+    for r in range(2):
+        for k in range(2):
+            assert _same_bits(_host(outs[4 * r + k], h, w), want_one[k]), (r, k)
+            assert _same_bits(_host(outs[4 * r + 2 + k], h, w), want_up[k]), (r, k)
+
+
+@pytest.mark.gpu
+def test_rejections(plugin):
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 64, 40, 32, 20
+    lvl, cam, win = brt.cover_camera(w, h, 2, 4)
+    plugin.node.write_buffers(b)
+    low = _render_low(plugin, lvl, cam, win, lw, lh, h)
+    buf = torch.zeros((h + lh, w, 4), dtype=torch.float32, device="cuda")
+    out = buf[:h]
+    before = _upscale_dev(plugin, cam, win, lw, lh, low.cpu().numpy(), w, h)
+    lib, ctx, c, wn = plugin._lib, plugin._ctx, cam.ctypes.data, win.ctypes.data
+
+    def up(lw_=lw, lh_=lh, w_=w, h_=h, d_low=low.data_ptr(), d_out=out.data_ptr(), flags=0, cam_=c, win_=wn):
+        return lib.brt_upscale_device(ctx, cam_, win_, lw_, lh_, d_low, w_, h_, d_out, None, flags, None)
+
+    def one(lw_=lw, lh_=lh, w_=w, h_=h, d_out=out.data_ptr(), flags=0, cam_=c, win_=wn):
+        return lib.brt_render_upscaled_device(ctx, cam_, win_, lw_, lh_, w_, h_, d_out, None, flags, None)
+
+    assert up() == 0 and one() == 0
+    for call in (up, one):
+        for sizes in (dict(lw_=0), dict(lh_=0), dict(lw_=w + 1), dict(lh_=h + 1), dict(w_=4 * lw + 1), dict(h_=4 * lh + 1),
+                      dict(lw_=16384, lh_=lh, w_=32769, h_=h), dict(lw_=lw, lh_=16384, w_=w, h_=32769)):
+            assert call(**sizes) == ERR_INVALID, (call.__name__, sizes)
+        for flags in (brt.FLAG_COUNTERS, brt.FLAG_KERNEL_SIMPLE, brt.FLAG_BLEND_POST, 256, 1 << 31):
+            assert call(flags=flags) == ERR_INVALID, (call.__name__, flags)
+        assert call(d_out=None) == ERR_INVALID and call(cam_=None) == ERR_INVALID and call(win_=None) == ERR_INVALID
+    for flags in (brt.FLAG_DENOISE, brt.FLAG_TEMPORAL):                # the post-passes belong to the one-call form
+        assert up(flags=flags) == ERR_INVALID
+    assert up(d_low=None) == ERR_INVALID
+    # d_out must not overlap d_low_rgba
+    whole = buf.data_ptr()
+    assert up(d_low=whole, d_out=whole) == ERR_INVALID
+    assert up(d_low=whole + (w * h - 1) * 16, d_out=whole) == ERR_INVALID
+    assert up(d_low=whole, d_out=whole + (lw * lh - 1) * 16) == ERR_INVALID
+    assert lib.brt_upscale_device(ctx, c, wn, lw, lh, whole + w * h * 16, w, h, whole, None, 0, None) == 0       # adjacent: fine
+    # before any upload
+    with brt.RaytracePlugin([0]) as fresh:
+        f = lambda fn, *a: fn(fresh._ctx, c, wn, lw, lh, *a)
+        assert f(fresh._lib.brt_upscale_device, low.data_ptr(), w, h, out.data_ptr(), None, 0, None) == ERR_NO_SCENE
+        assert f(fresh._lib.brt_render_upscaled_device, w, h, out.data_ptr(), None, 0, None) == ERR_NO_SCENE
+    # the context is as usable as before
+    assert _same_bits(_upscale_dev(plugin, cam, win, lw, lh, low.cpu().numpy(), w, h), before)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("spp", [4, 64])
+def test_quality_on_the_gpu(plugin, spp):
+    """480x270 from 240x135 on the cover scene: the upsampled frame against the plain bilinear upsampling of the same low frame, both
+    against a 1024-spp full-size frame of another seed traced on the GPU.  The bar is 1.1 x the GPU's first measurement (GPU_BARS) and
+    below 1."""
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 480, 270, 240, 135
+    _, cam_r, win_r = brt.cover_camera(w, h, 1024, 8, brt.Raytracing.Pure, 0.25)
+    lvl, cam, win = brt.cover_camera(w, h, spp, 8, brt.Raytracing.Pure, 0.5)
+    ref = plugin.node.run(lvl, cam_r, win_r, w, h, buffers=b).copy()
+    low = _render_low(plugin, lvl, cam, win, lw, lh, h).cpu().numpy()
+    up = _render_upscaled(plugin, cam, win, lw, lh, w, h).view(F32)
+    g = plugin.debug_denoise_guides(cam, win, w, h)
+    ratio = dr.hit_mse(up, ref, g) / dr.hit_mse(bilinear(low, w, h), ref, g)
+    print(f"upsampling quality at {spp} spp: {ratio:.4f}")
+    assert ratio <= GPU_BARS[spp] and ratio < 1.0, ratio
