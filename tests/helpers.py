@@ -1,5 +1,6 @@
-"""Shared test helpers: hand-made BVHs (single leaf, median split, caterpillar chain), uniform
-builders and a numpy-f32 restatement of the camera/sky arithmetic for analytic checks."""
+"""Shared test helpers: hand-made BVHs (single leaf, median split, caterpillar chain, a composer that grafts one onto another),
+a seeded scene large enough for 32-bit tree descriptors with its camera, the upload of a scene whose tree the callee builds,
+uniform builders and a numpy-f32 restatement of the camera/sky arithmetic for analytic checks."""
 import os
 
 import numpy as np
@@ -77,6 +78,92 @@ def chain_bvh(models, far_first=False):
     nodes[cur]["bounds_min"], nodes[cur]["bounds_max"] = lo[m], hi[m]
     nodes[cur]["index"], nodes[cur]["model_count"] = m, 1
     return nodes
+
+
+def graft_bvh(top, leaf_slot, sub, model_offset):
+    """`top` with its leaf `leaf_slot` turned into an interior node over {that leaf, the root of `sub`}: a composer of node arrays.
+    `sub` is a tree over models[model_offset:] numbered from 0; its leaves are moved by model_offset, its interior indices by where
+    its nodes land (appended behind `top`, the two children of every interior node still adjacent).  Every interior box of the
+    result is refitted bottom-up (children lie behind their parent in every array this module makes), so the boxes above the
+    graft enclose the grafted spheres."""
+    assert top[leaf_slot]["model_count"] > 0
+    base = len(top) + 1                                      # where sub's node 0 lands
+    out = np.zeros(len(top) + 1 + len(sub), brt.BVH_NODE_DTYPE)
+    out[:len(top)] = top
+    out[len(top)] = top[leaf_slot]
+    moved = sub.copy()
+    leaf = moved["model_count"] > 0
+    moved["index"][leaf] += model_offset
+    moved["index"][~leaf] += base
+    out[base:] = moved
+    out[leaf_slot]["index"], out[leaf_slot]["model_count"] = len(top), 0
+    for i in range(len(out) - 1, -1, -1):
+        if out[i]["model_count"] == 0:
+            a, b = out[out[i]["index"]], out[out[i]["index"] + 1]
+            out[i]["bounds_min"] = np.minimum(a["bounds_min"], b["bounds_min"])
+            out[i]["bounds_max"] = np.maximum(a["bounds_max"], b["bounds_max"])
+    return out
+
+
+def big_scene(n, seed, n_materials=48):
+    """-> Buffers(models, materials, None): `n` small spheres with uniform random centres in a slab in front of BIG_VIEW's camera,
+    seeded numpy only.  From 16 383 spheres on the uploaded tree needs the 32-bit descriptor form (brt_layout.h DESC16_MAX_INDEX).
+    The slab is wider than the view at its far end and thin enough (optical depth about 1) that a 96x54 frame shows sky, near
+    spheres and far spheres.  Every sphere is an independent draw (centre, radius and material come from one row of one array), so
+    big_scene(n, s).models[:k] is big_scene(k, s).models: a cropped scene is a strict subset.  Ids carry no spatial order.
+    Materials: every third one metal, three refracting (specular_transmission = 1: the guides' `a` is 1), one diffuse with a
+    base-colour channel below 1e-3 (the guides clamp it), the rest diffuse."""
+    rng = np.random.default_rng(seed)
+    mats = np.zeros(n_materials, brt.MATERIAL_DTYPE)
+    for m in range(n_materials):
+        colour = tuple(float(x) for x in rng.uniform(0.15, 0.95, 3))
+        if m % 3 == 0:
+            sm = brt.StandardMaterial(base_color=colour, metallic=1.0, perceptual_roughness=float(rng.uniform(0.0, 0.8)))
+        elif m in (1, 13, 25):
+            sm = brt.StandardMaterial(specular_transmission=1.0, ior=float(rng.uniform(1.2, 1.7)))
+        elif m == 2:
+            sm = brt.StandardMaterial(base_color=(0.6, 0.0, 0.35))
+        else:
+            sm = brt.StandardMaterial(base_color=colour, perceptual_roughness=float(rng.uniform(0.0, 1.0)))
+        mats[m] = brt.RaytraceMaterial.prepare_asset(sm)[0]
+    draw = np.random.default_rng([seed, 1]).random((n, 5))                # one row per sphere: x, y, z, radius, material
+    models = np.zeros(n, brt.MODEL_DTYPE)
+    lo, hi = np.array(BIG_SLAB[0]), np.array(BIG_SLAB[1])
+    models["position"] = (lo + draw[:, :3] * (hi - lo)).astype(F32)
+    models["radius"] = (0.07 + 0.11 * draw[:, 3]).astype(F32)
+    models["material_id"] = np.minimum((draw[:, 4] * n_materials).astype(np.uint32), n_materials - 1)
+    return brt.Buffers(models, mats, None)
+
+
+BIG_SLAB = ((-17.0, -10.0, -44.0), (17.0, 10.0, -14.0))
+BIG_VIEW = dict(pos=(0.75, 0.5, 0.0), target=(0.0, 0.0, -29.0), fov=0.5)
+
+
+def big_view(w, h, spp=2, bounces=4, seed=0.5, level=brt.Raytracing.Pure, **kw):
+    """The fixed camera of big_scene (the raster wall and disc of blend_post_ref.raster_inputs, at distances 9 and 6, lie in front
+    of the slab)."""
+    return uniforms(w, h, spp, bounces, seed=seed, level=level, **{**BIG_VIEW, **kw})
+
+
+def l1_norm(v):
+    v = np.abs(np.asarray(v, F32))
+    return float((v[0] + v[1]) + v[2])
+
+
+def resident_callee_tree(plugin, b, lvl, cam, win, w, h, seeds=()):
+    """Uploads `b` without a tree, so the callee builds its SAH tree; a first query raises that tree's reach to the camera's 1-norm
+    (the position-free rule asks for more than the camera's own); then one frame per seed.  -> (Buffers with the CPU twin of the
+    resident tree, the last window, last_stats)."""
+    none = brt.Buffers(b.models, b.materials, None)
+    plugin.node.write_buffers(none)
+    plugin.node.query_rays(brt.pixel_ray(cam, win, w, h, 0, 0), origin_bound=l1_norm(cam[0]["position"]))
+    for seed in seeds:
+        win = brt.WindowExtract.extract_component(h, seed)
+        plugin.node.run(lvl, cam, win, w, h, buffers=none)
+    if not seeds:
+        plugin.node.run(lvl, cam, win, w, h)
+    st = dict(plugin.node.last_stats)
+    return brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models, st["tree_reach"])), win, st
 
 
 def make_buffers(data, bvh_fn=None):

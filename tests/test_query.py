@@ -11,7 +11,7 @@ import pytest
 import bevyray_amd as brt
 import query_ref as qr
 from bevyray_amd import _lib
-from helpers import chain_bvh, make_buffers, median_split_bvh, single_leaf_bvh, uniforms
+from helpers import chain_bvh, l1_norm as _l1, make_buffers, median_split_bvh, resident_callee_tree, single_leaf_bvh, uniforms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("brt_query_rays_device", "brt_query_rays", "brt_query_origin_bound", "brt_host_pixel_ray")
@@ -118,17 +118,11 @@ def _scene(plugin, case):
         b = make_buffers(data, chain_bvh)
         lvl, cam, win = uniforms(w, h, spp=2, bounces=3, pos=(0, 0, 0), target=(0, 0, -1), fov=0.3, seed=0.5)
     if case in ("cover_callee", "stress"):
-        # the callee's SAH tree, its reach raised to the camera's 1-norm by a first query (the position-free rule asks for more than the
-        # camera's own); then frames, so that the stress grid's spheres are in the hot order when the queries come
-        plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
-        plugin.node.query_rays(brt.pixel_ray(cam, win, w, h, 0, 0), origin_bound=_l1(cam[0]["position"]))
-        for seed in (0.5, 0.25, 0.75):
-            win = brt.WindowExtract.extract_component(h, seed)
-            plugin.node.run(lvl, cam, win, w, h, buffers=brt.Buffers(b.models, b.materials, None))
-        st = plugin.node.last_stats
+        # the callee's SAH tree, its reach raised to the camera's 1-norm by a first query; then frames, so that the stress grid's
+        # spheres are in the hot order when the queries come; `b` gets the CPU twin of the resident tree
+        b, win, st = resident_callee_tree(plugin, b, lvl, cam, win, w, h, seeds=(0.5, 0.25, 0.75))
         if case == "stress":
             assert st["scene_in_lds"] == 2 and st["hot_records"] > 0        # top of the tree in LDS, spheres renumbered
-        b = brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models, st["tree_reach"]))   # the CPU twin of the resident tree
     else:
         plugin.node.run(lvl, cam, win, w, h, buffers=b)
     return b, cam, win, (w, h)
@@ -186,11 +180,6 @@ def test_queries_match_the_oracle_raycast(plugin, oracle, case):
         for form in (PLAIN, STREAM):
             for device in (False, True):
                 _same_bytes(_query(plugin, rays[:n], form, device=device), full[:n], f"{case} batch of {n}, form {form}, device {device}")
-
-
-def _l1(v):
-    v = np.abs(np.asarray(v, F32))
-    return float((v[0] + v[1]) + v[2])
 
 
 def _with_tmax(rays, t_max):
