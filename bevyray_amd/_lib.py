@@ -102,6 +102,11 @@ _PROTOTYPES = {
     "brt_upscale_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_host_upscale_window": (_I32, [_VP, _U32, _U32, _VP]),
+    "brt_upscale_blend_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _U32,
+                                        C.POINTER(BrtStats)]),
+    "brt_render_upscaled_blend_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _U32,
+                                                C.POINTER(BrtStats)]),
+    "brt_host_blend_covered": (_I32, [_VP, _U32, _F, _F, C.POINTER(_U32)]),
     "brt_debug_profile": (_I32, [_VP, C.POINTER(C.c_uint64)]),
     "brt_debug_tile_order": (_I32, [_VP, _VP, _VP, _U32, _U32, C.c_uint64, _U32, _U32, _U32, _VP, _VP]),
     "brt_build_bvh": (_I32, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),

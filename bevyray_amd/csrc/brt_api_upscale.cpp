@@ -1,5 +1,6 @@
 // brt_api_upscale.cpp -- guide-buffer upsampling on the first device (brt_upscale.hip): of a low frame the caller holds, and of one the
-// call traces (and post-processes) itself.  DESIGN.md "Guide-buffer upsampling".
+// call traces (and post-processes) itself.  DESIGN.md "Guide-buffer upsampling"; with a level and the full-size raster inputs
+// (brt_upscale_blend_device, brt_render_upscaled_blend_device): "Upsampling blended frames".
 #include "brt_frame.h"
 
 using namespace brt;
@@ -27,45 +28,81 @@ int32_t sizes_check(brt_ctx* ctx, uint32_t low_width, uint32_t low_height, uint3
     return BRT_OK;
 }
 
+// The frame an upsampling presents: level 3 (what the calls without a level pass), or a level that blends with its full-size raster
+// inputs on the first device (either may be null: zeros) -- the low frame is a Pure frame in both
+struct Blend {
+    uint32_t level = BRT_LEVEL_PURE;
+    const float* d_raster_rgba = nullptr;
+    const float* d_raster_depth = nullptr;
+    bool on() const { return level != BRT_LEVEL_PURE; }
+};
+
+// the level of a blended call: 3 is the call without a level (the raster inputs are not read), 0 traces nothing
+int32_t level_check(brt_ctx* ctx, Blend* bl) {
+    if (bl->level == BRT_LEVEL_SKIP) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "level 0 traces nothing: there is no frame to upsample");
+    if (bl->level != BRT_LEVEL_FALLBACK_RASTER && bl->level != BRT_LEVEL_FALLBACK_RAYTRACED && bl->level != BRT_LEVEL_PURE)
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "level must be 1, 2 or 3");
+    if (!bl->on()) bl->d_raster_rgba = bl->d_raster_depth = nullptr;
+    return BRT_OK;
+}
+
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char* pa = static_cast<const char*>(a);
+    const char* pb = static_cast<const char*>(b);
+    return a && b && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt) {
+    return (size_t)width * height * (fmt == BRT_FLAG_OUT_RGBA32F ? 16u : fmt == BRT_FLAG_OUT_RGBA16F ? 8u : 4u);
+}
+
+// the output of a blended frame is written while other pixels' raster texels and depths are still to be read
+int32_t raster_overlap_check(brt_ctx* ctx, const Blend& bl, const void* d_out, uint32_t width, uint32_t height, uint32_t fmt) {
+    const size_t n = (size_t)width * height, ob = out_bytes(width, height, fmt);
+    if (overlaps(d_out, ob, bl.d_raster_rgba, n * 16u)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "the output overlaps d_raster_rgba");
+    if (overlaps(d_out, ob, bl.d_raster_depth, n * 4u)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "the output overlaps d_raster_depth");
+    return BRT_OK;
+}
+
 // behind the low frame at d_low on `stream`: its guides unless a post-pass has just left them in the scratch, then the upsampling into
 // d_out; the scratch is the denoiser's and the event its ordering event, so the call queues up with the context's other post-passes
 int32_t upscale_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* low_window16, uint32_t low_width, uint32_t low_height,
                         const float* d_low, const void* window16, uint32_t width, uint32_t height, void* d_out, uint32_t out_format,
-                        hipStream_t stream, bool guides_resident) {
+                        hipStream_t stream, bool guides_resident, const Blend& bl) {
     FrameParams low, full;
     DenoiseScratch ds;
-    int32_t rc = make_frame_params(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, 0u, 1u, &full);
+    int32_t rc = make_frame_params(ctx, camera80, window16, bl.level, width, height, 0u, 1u, &full);      // (near, far, fallback_far)
     if (rc == BRT_OK) rc = denoise_begin(ctx, dc, camera80, low_window16, low_width, low_height, stream, &low, &ds);
     if (rc != BRT_OK) return rc;
     if (!guides_resident) HIP_TRY(ctx, launch_denoise_guides(dc.view, low, ds, stream));
-    HIP_TRY(ctx, launch_upscale(dc.view, full, low, ctx->denoise, ds, d_low, d_out, out_format, stream));
+    const UpscaleBlend ub = {reinterpret_cast<const float4*>(bl.d_raster_rgba), bl.d_raster_depth};
+    HIP_TRY(ctx, launch_upscale(dc.view, full, low, ctx->denoise, ds, d_low, d_out, out_format, stream, bl.on() ? &ub : nullptr));
     HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
     return BRT_OK;
 }
 
 int32_t upscale_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                        const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, void* hip_stream, uint32_t flags,
-                       brt_stats* stats) {
+                       brt_stats* stats, Blend bl) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
     if (!d_low_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_low_rgba / d_out is null");
     if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only");
+    if (const int32_t bad = level_check(ctx, &bl)) return bad;
     if (const int32_t bad = sizes_check(ctx, low_width, low_height, width, height)) return bad;
     const uint32_t fmt = flags & BRT_FLAG_OUT_MASK;
-    const size_t out_px = fmt == BRT_FLAG_OUT_RGBA32F ? 16u : fmt == BRT_FLAG_OUT_RGBA16F ? 8u : 4u;
-    const char* lo = reinterpret_cast<const char*>(d_low_rgba);
-    const char* out = static_cast<const char*>(d_out);
-    if (lo < out + (size_t)width * height * out_px && out < lo + (size_t)low_width * low_height * 16u)
+    if (overlaps(d_out, out_bytes(width, height, fmt), d_low_rgba, (size_t)low_width * low_height * 16u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out overlaps d_low_rgba");
+    if (const int32_t bad = raster_overlap_check(ctx, bl, d_out, width, height, fmt)) return bad;
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     DeviceCtx& dc = ctx->devs[0];
     const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {     // (the guides walk the tree of the frame)
         HIP_TRY(ctx, hipSetDevice(dc.device));
         const StreamChoice sc = stream_of(dc, hip_stream, flags);
         const int32_t r = upscale_enqueue(ctx, dc, camera80, window16, low_width, low_height, d_low_rgba, window16, width, height, d_out, fmt,
-                                          sc.stream, false);
+                                          sc.stream, false, bl);
         if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
         if (r == BRT_OK && stats) std::memset(stats, 0, sizeof *stats);      // (total_ms only, and the tree)
         return r;
@@ -75,14 +112,17 @@ int32_t upscale_device(brt_ctx* ctx, const void* camera80, const void* window16,
 }
 
 int32_t render_upscaled_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
-                               uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats) {
+                               uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats,
+                               Blend bl) {
     const auto t0 = std::chrono::steady_clock::now();
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
     if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only");
+    if (const int32_t bad = level_check(ctx, &bl)) return bad;
     if (const int32_t bad = sizes_check(ctx, low_width, low_height, width, height)) return bad;
+    if (const int32_t bad = raster_overlap_check(ctx, bl, d_frame, width, height, flags & BRT_FLAG_OUT_MASK)) return bad;
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     char low_win[16];
     low_window(window16, height, low_height, low_win);
@@ -98,13 +138,14 @@ int32_t render_upscaled_device(brt_ctx* ctx, const void* camera80, const void* w
         int32_t r = ensure(ctx, &dc.d_uplow, &dc.uplow_cap, bytes);
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_dn, 0));
-        // exactly brt_render_device's low_width x low_height Pure frame (every device of the context), post-passes on the low frame
+        // exactly brt_render_device's low_width x low_height Pure frame (every device of the context), post-passes on the low frame;
+        // whatever the level of the presented frame: its raster blend is decided per output pixel by the upsampling
         r = render_frame_device(ctx, camera80, low_win, BRT_LEVEL_PURE, low_width, low_height, nullptr, nullptr, dc.d_uplow, hip_stream,
                                 (flags & BRT_FLAG_CALLER_STREAM) | post, stats);
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipSetDevice(dc.device));
         r = upscale_enqueue(ctx, dc, camera80, low_win, low_width, low_height, dc.d_uplow, window16, width, height, d_frame,
-                            flags & BRT_FLAG_OUT_MASK, sc.stream, post != 0u);  // (the post-passes cast the low guides: not cast twice)
+                            flags & BRT_FLAG_OUT_MASK, sc.stream, post != 0u, bl);  // (the post-passes cast the low guides: not cast twice)
         if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
         return r;
     });
@@ -120,14 +161,60 @@ int32_t brt_upscale_device(brt_ctx* ctx, const void* camera80, const void* windo
                            const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, void* hip_stream, uint32_t flags,
                            brt_stats* stats) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    return upscale_device(ctx, camera80, window16, low_width, low_height, d_low_rgba, width, height, d_out, hip_stream, flags, stats);
+    return upscale_device(ctx, camera80, window16, low_width, low_height, d_low_rgba, width, height, d_out, hip_stream, flags, stats, Blend());
+    });
+}
+
+int32_t brt_upscale_blend_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t low_width,
+                                 uint32_t low_height, const float* d_low_rgba, uint32_t width, uint32_t height,
+                                 const float* d_raster_rgba_or_null, const float* d_raster_depth_or_null, void* d_out, void* hip_stream,
+                                 uint32_t flags, brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    Blend bl;
+    bl.level = level;
+    bl.d_raster_rgba = d_raster_rgba_or_null;
+    bl.d_raster_depth = d_raster_depth_or_null;
+    return upscale_device(ctx, camera80, window16, low_width, low_height, d_low_rgba, width, height, d_out, hip_stream, flags, stats, bl);
     });
 }
 
 int32_t brt_render_upscaled_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                                    uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    return render_upscaled_device(ctx, camera80, window16, low_width, low_height, width, height, d_frame, hip_stream, flags, stats);
+    return render_upscaled_device(ctx, camera80, window16, low_width, low_height, width, height, d_frame, hip_stream, flags, stats, Blend());
+    });
+}
+
+int32_t brt_render_upscaled_blend_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t low_width,
+                                         uint32_t low_height, uint32_t width, uint32_t height, const float* d_raster_rgba_or_null,
+                                         const float* d_raster_depth_or_null, void* d_frame, void* hip_stream, uint32_t flags,
+                                         brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    Blend bl;
+    bl.level = level;
+    bl.d_raster_rgba = d_raster_rgba_or_null;
+    bl.d_raster_depth = d_raster_depth_or_null;
+    return render_upscaled_device(ctx, camera80, window16, low_width, low_height, width, height, d_frame, hip_stream, flags, stats, bl);
+    });
+}
+
+// resolve_pixel's compare (brt_device.h) for ONE sample of depth t, every operation a separately rounded f32 one: the rule of k_upscale's
+// blended form (brt_upscale.hip blend_covered) on the host
+int32_t brt_host_blend_covered(const void* camera80, uint32_t level, float t, float raster_depth, uint32_t* out_covered) {
+    return guard(nullptr, [&]() -> int32_t {
+    if (!camera80 || !out_covered) return fail(BRT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (level == BRT_LEVEL_SKIP) return fail(BRT_ERR_UNSUPPORTED, "level 0 traces nothing");
+    if (level != BRT_LEVEL_FALLBACK_RASTER && level != BRT_LEVEL_FALLBACK_RAYTRACED && level != BRT_LEVEL_PURE)
+        return fail(BRT_ERR_INVALID_ARGUMENT, "level must be 1, 2 or 3");
+    Camera cam;
+    std::memcpy(&cam, camera80, sizeof cam);
+    *out_covered = 0u;
+    if (level == BRT_LEVEL_PURE) return BRT_OK;                                   // (no blend)
+    const float fallback_far = level == BRT_LEVEL_FALLBACK_RASTER ? cam.far_ + 10.0f : cam.far_ - 1.0f;
+    const float depth = t == std::numeric_limits<float>::infinity() ? fallback_far : t;
+    const float rd = depth > cam.far_ ? -1.0f : cam.near_ / depth;
+    *out_covered = raster_depth > rd ? 1u : 0u;
+    return BRT_OK;
     });
 }
 

@@ -16,11 +16,20 @@ namespace brt {
 constexpr float kUpscaleBilinearFloor = 0x1p-26f;
 constexpr float kUpscaleEdgeFloor = 0.25f;
 
+// The raster inputs of a frame of a level that blends (1 / 2; DESIGN.md "Upsampling blended frames"): RGBA32F colour and reverse-Z f32
+// depth, both full.width x full.height on the device of the launch, either may be nullptr (zeros).
+struct UpscaleBlend {
+    const float4* raster_rgba;
+    const float* raster_depth;
+};
+
 // full: the frame parameters of the width x height output (its pixel-centre rays are cast by the kernel itself); low: those of the traced
 // frame; ds_low: the scratch whose g0 / g1 hold the guides of the low frame (launch_denoise_guides with `low`); d_low: the low frame,
 // RGBA32F low.width x low.height; d_out: full.width x full.height in out_format (BRT_FLAG_OUT_*), not overlapping d_low.  The sigmas of
-// the edge-stopping weights are st's (brt_set_denoise).
+// the edge-stopping weights are st's (brt_set_denoise).  blend != nullptr: `full` is made for level 1 or 2 (its near_, far_ and
+// fallback_far decide the blend) and a covered output pixel is its raster texel; d_out overlaps neither raster buffer.
 hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, const FrameParams& low, const DenoiseSettings& st,
-                          const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream);
+                          const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream,
+                          const UpscaleBlend* blend = nullptr);
 
 }  // namespace brt

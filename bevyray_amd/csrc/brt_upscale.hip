@@ -8,6 +8,8 @@
 //             and its guide planes: the 2x2 bilinear footprint (stage A), the 4x4 around it when none of those taps lies on p's material
 //             (stage B), the plain bilinear colour when none of those does either (stage C).  A pixel whose ray misses gets the sky of its
 //             own ray.  The result is stored in the requested BRT_FLAG_OUT_* format (OutPixel, brt_store.h).
+//             With the trailing UpscaleBlend argument (levels 1 / 2, DESIGN.md "Upsampling blended frames") the raster blend is decided
+//             per output pixel between the walk and the gather: a covered pixel stores its raster texel and reads no tap.
 #include <hip/hip_runtime.h>
 
 #include "brt_store.h"
@@ -53,9 +55,22 @@ BRT_DEV bool tap(const UpscaleArgs& ua, const Pixel& pp, uint32_t q, f3& cd, flo
     return true;
 }
 
-template <bool D16, uint32_t FMT>
+// resolve_pixel's compare (brt_device.h, raytrace.wgsl:104-120) fed with ONE sample whose depth is t: a miss has the depth fallback_far
+// of fp's level, and a NaN raster depth never covers
+BRT_DEV bool blend_covered(const FrameParams& fp, float t, uint32_t p, const UpscaleBlend& b) {
+    const float depth_p = b.raster_depth ? b.raster_depth[p] : 0.0f;
+    const float depth = t == kInf ? fp.fallback_far : t;
+    const float rd = depth > fp.far_ ? -1.0f : fp.near_ / depth;
+    return depth_p > rd;
+}
+BRT_DEV float4 blend_texel(uint32_t p, const UpscaleBlend& b) { return raster_texel(p, b.raster_rgba); }
+
+// Blend: empty, or one UpscaleBlend -- the frame of a level that blends, fp.level 1 or 2: a covered pixel stores the raster texel of its
+// own index (no raster colour: zeros) and returns before the gather, so a wave whose lanes are all covered branches over it; the others
+// are the kernel of the empty pack bit for bit.  The empty pack is the kernel as it always was, name and arguments included.
+template <bool D16, uint32_t FMT, typename... Blend>
 __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams fp, UpscaleArgs ua,
-                                                 typename OutPixel<FMT>::type* __restrict__ out) {
+                                                 typename OutPixel<FMT>::type* __restrict__ out, Blend... blend) {
     const uint32_t px = blockIdx.x * kTile + (threadIdx.x & (kTile - 1u)), py = blockIdx.y * kTile + threadIdx.x / kTile;
     if (px >= fp.width || py >= fp.height) return;
     const uint32_t p = py * fp.width + px;
@@ -86,6 +101,12 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
     float t;
     uint32_t idx;
     raycast<1, false, D16, false>(sc, sv.root_desc, stack, o, d, t, idx, hc);
+    if constexpr (sizeof...(Blend) != 0) {
+        if (blend_covered(fp, t, p, blend...)) {
+            out[p] = OutPixel<FMT>::make(blend_texel(p, blend...));
+            return;
+        }
+    }
     if (t == kInf) {      // sky: what one sample of the ray loop stores for a ray that misses everything, on the centre ray
         const f3 bg = background_gradient(d);
         out[p] = OutPixel<FMT>::make(make_float4(__builtin_sqrtf(bg.x), __builtin_sqrtf(bg.y), __builtin_sqrtf(bg.z), 1.0f));
@@ -170,18 +191,32 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
     out[p] = OutPixel<FMT>::make(sw != 0.0f ? make_float4(sr / sw, sg / sw, sb / sw, 1.0f) : make_float4(0.0f, 0.0f, 0.0f, 1.0f));
 }
 
-template <uint32_t FMT>
-void launch_t(const DeviceSceneView& sv, const FrameParams& fp, const UpscaleArgs& ua, void* out, hipStream_t stream) {
+template <uint32_t FMT, typename... Blend>
+void launch_t(const DeviceSceneView& sv, const FrameParams& fp, const UpscaleArgs& ua, void* out, hipStream_t stream, Blend... blend) {
     const dim3 grid((fp.width + kTile - 1u) / kTile, (fp.height + kTile - 1u) / kTile);
     auto* o = reinterpret_cast<typename OutPixel<FMT>::type*>(out);
-    if (sv.desc16) hipLaunchKernelGGL((k_upscale<true, FMT>), grid, dim3(256), 0, stream, sv, fp, ua, o);
-    else hipLaunchKernelGGL((k_upscale<false, FMT>), grid, dim3(256), 0, stream, sv, fp, ua, o);
+    if (sv.desc16) hipLaunchKernelGGL((k_upscale<true, FMT, Blend...>), grid, dim3(256), 0, stream, sv, fp, ua, o, blend...);
+    else hipLaunchKernelGGL((k_upscale<false, FMT, Blend...>), grid, dim3(256), 0, stream, sv, fp, ua, o, blend...);
+}
+
+template <typename... Blend>
+hipError_t launch_f(uint32_t out_format, const DeviceSceneView& sv, const FrameParams& fp, const UpscaleArgs& ua, void* out,
+                    hipStream_t stream, Blend... blend) {
+    switch (out_format) {
+        case BRT_FLAG_OUT_RGBA32F: launch_t<BRT_FLAG_OUT_RGBA32F>(sv, fp, ua, out, stream, blend...); break;
+        case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: launch_t<BRT_FLAG_OUT_RGBA8_UNORM_SRGB>(sv, fp, ua, out, stream, blend...); break;
+        case BRT_FLAG_OUT_RGBA16F: launch_t<BRT_FLAG_OUT_RGBA16F>(sv, fp, ua, out, stream, blend...); break;
+        case BRT_FLAG_OUT_RGBA8_UNORM: launch_t<BRT_FLAG_OUT_RGBA8_UNORM>(sv, fp, ua, out, stream, blend...); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 }  // namespace
 
 hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, const FrameParams& low, const DenoiseSettings& st,
-                          const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream) {
+                          const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream,
+                          const UpscaleBlend* blend) {
     UpscaleArgs ua;
     ua.low_width = low.width;
     ua.low_height = low.height;
@@ -191,14 +226,8 @@ hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, co
     ua.low = reinterpret_cast<const float4*>(d_low);
     ua.g0 = ds_low.g0;
     ua.g1 = ds_low.g1;
-    switch (out_format) {
-        case BRT_FLAG_OUT_RGBA32F: launch_t<BRT_FLAG_OUT_RGBA32F>(sv, full, ua, d_out, stream); break;
-        case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: launch_t<BRT_FLAG_OUT_RGBA8_UNORM_SRGB>(sv, full, ua, d_out, stream); break;
-        case BRT_FLAG_OUT_RGBA16F: launch_t<BRT_FLAG_OUT_RGBA16F>(sv, full, ua, d_out, stream); break;
-        case BRT_FLAG_OUT_RGBA8_UNORM: launch_t<BRT_FLAG_OUT_RGBA8_UNORM>(sv, full, ua, d_out, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (blend) return launch_f(out_format, sv, full, ua, d_out, stream, *blend);
+    return launch_f(out_format, sv, full, ua, d_out, stream);
 }
 
 }  // namespace brt

@@ -197,6 +197,28 @@ public:
                                 brt_stats* stats = nullptr) {
         check(brt_render_upscaled_device(ctx_, &camera, &window, low_width, low_height, width, height, d_destination, hip_stream, flags, stats), ctx_);
     }
+    // The same two for a frame of level 1 / 2 (include/bevyray_amd.h "upsampling blended frames"): the low frame is a Pure frame, and every
+    // output pixel the full-size raster depth wins is its texel of d_raster_rgba (either raster pointer may be null: zeros; both on the
+    // first device, not overlapping the output).  level 3: the calls above.
+    void upscale_blend_device(const CameraExtract& camera, const WindowExtract& window, uint32_t level, uint32_t low_width, uint32_t low_height,
+                              const float* d_low, uint32_t width, uint32_t height, const float* d_raster_rgba, const float* d_raster_depth,
+                              void* d_out, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_upscale_blend_device(ctx_, &camera, &window, level, low_width, low_height, d_low, width, height, d_raster_rgba, d_raster_depth,
+                                       d_out, hip_stream, flags, stats), ctx_);
+    }
+    void render_upscaled_blend_device(const CameraExtract& camera, const WindowExtract& window, uint32_t level, uint32_t low_width,
+                                      uint32_t low_height, uint32_t width, uint32_t height, const float* d_raster_rgba,
+                                      const float* d_raster_depth, void* d_destination, void* hip_stream = nullptr, uint32_t flags = 0,
+                                      brt_stats* stats = nullptr) {
+        check(brt_render_upscaled_blend_device(ctx_, &camera, &window, level, low_width, low_height, width, height, d_raster_rgba,
+                                               d_raster_depth, d_destination, hip_stream, flags, stats), ctx_);
+    }
+    // whether the raster wins a pixel whose centre ray hits at distance t (+INF: a miss) against raster_depth, at `level`
+    static bool blend_covered(const CameraExtract& camera, uint32_t level, float t, float raster_depth) {
+        uint32_t c = 0;
+        check(brt_host_blend_covered(&camera, level, t, raster_depth, &c), nullptr);
+        return c != 0;
+    }
     // the window a low_height frame is traced with when it is presented at `height` rows
     static WindowExtract upscale_window(const WindowExtract& window, uint32_t height, uint32_t low_height) {
         WindowExtract w{};

@@ -277,6 +277,20 @@ def rtiow_camera(width: int, height: int, sample_count: int, bounces: int,
     return lvl, cex, WindowExtract.extract_component(height, seed)
 
 
+def blend_covered(camera, level, t, raster_depth) -> np.ndarray:
+    """brt_host_blend_covered per element of the broadcast of t (distance of a pixel's centre ray, inf: a miss) and raster_depth: whether
+    the raster wins the pixel in a frame of `level` (LEVEL_DTYPE or int) upsampled by upscale_blend_device."""
+    lib = _lib.load()
+    lvl = int(level["level"][0]) if isinstance(level, np.ndarray) else int(level)
+    t, d = np.broadcast_arrays(np.asarray(t, np.float32), np.asarray(raster_depth, np.float32))
+    out = np.zeros(t.shape, bool)
+    c = C.c_uint32(0)
+    for i in np.ndindex(t.shape):
+        _lib.check(lib.brt_host_blend_covered(camera.ctypes.data, lvl, float(t[i]), float(d[i]), C.byref(c)))
+        out[i] = c.value != 0
+    return out
+
+
 def upscale_window(window, height: int, low_height: int) -> np.ndarray:
     """brt_host_upscale_window: the window a low_height frame is traced with when it is to be upsampled to `height` rows -- the seed of
     `window`, its height scaled to max(1, window.height * low_height // height).  Host arithmetic."""
@@ -666,6 +680,38 @@ class RayTracingNode:
                                                      d_frame or None, stream or None,
                                                      (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
                                                      C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    # -- upsampling blended frames (include/bevyray_amd.h "upsampling blended frames") -------------
+
+    def upscale_blend_device(self, level, camera, window, low_width: int, low_height: int, d_low: int, width: int, height: int,
+                             d_out: int, d_raster_rgba: int = 0, d_raster_depth: int = 0, stream: Optional[int] = None,
+                             out_format: int = FLAG_OUT_RGBA32F) -> dict:
+        """brt_upscale_blend_device: upscale_device for a frame of `level` (LEVEL_DTYPE; 1 / 2 blend, 3 is upscale_device).  d_low is a
+        Pure low frame; d_raster_rgba / d_raster_depth: the full-size raster colour (RGBA f32) and reverse-Z depth on the first device
+        (0: zeros), neither overlapping d_out.  An output pixel the raster depth wins (blend_covered) is its raster texel."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_upscale_blend_device(p._ctx, camera.ctypes.data, window.ctypes.data, int(level["level"][0]), low_width,
+                                                   low_height, d_low or None, width, height, d_raster_rgba or None, d_raster_depth or None,
+                                                   d_out or None, stream or None,
+                                                   (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+        return stats.as_dict()
+
+    def render_upscaled_blend_device(self, level, camera, window, low_width: int, low_height: int, width: int, height: int, d_frame: int,
+                                     d_raster_rgba: int = 0, d_raster_depth: int = 0, stream: Optional[int] = None,
+                                     out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_upscaled_blend_device: render_upscaled_device for a frame of `level`: the low frame is traced at level 3 (post-passes
+        of `flags` on it), the raster blend is decided per output pixel against the full-size raster inputs.  last_stats: the low
+        frame's, total_ms of the whole call."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_upscaled_blend_device(p._ctx, camera.ctypes.data, window.ctypes.data, int(level["level"][0]), low_width,
+                                                           low_height, width, height, d_raster_rgba or None, d_raster_depth or None,
+                                                           d_frame or None, stream or None,
+                                                           (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                                           C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
 

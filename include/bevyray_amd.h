@@ -472,7 +472,7 @@ int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t 
  * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
  * of the low frame's taps that lie on the same material, weighted bilinearly and by the denoiser's normal and depth terms (sigma_normal,
  * sigma_depth of brt_set_denoise).  Rule, kernel and costs: DESIGN.md "Guide-buffer upsampling".  Deterministic.  Pure (level 3) frames
- * only: neither call takes a level -- a coverage frame's upsampling would need the raster blend at full size.
+ * only: neither call takes a level -- levels 1 / 2 go through the two calls of "upsampling blended frames" below.
  * Sizes, per axis: 1 <= low <= full <= 32768 and full <= 4 x low; else BRT_ERR_INVALID_ARGUMENT.  camera80: the frame's camera, the same
  * for both sizes.  BRT_ERR_NO_SCENE before an upload.
  *   brt_upscale_device          upsamples an RGBA f32 low_width x low_height DEVICE frame the caller holds -- a Pure frame of any entry
@@ -502,6 +502,34 @@ int32_t brt_render_upscaled_device(brt_ctx* ctx, const void* camera80, const voi
                                    uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags,
                                    brt_stats* stats_or_null);
 int32_t brt_host_upscale_window(const void* window16, uint32_t height, uint32_t low_height, void* out_window16);
+
+/* ---- upsampling blended frames (levels 1 / 2) -----------------------------------------------------------------------------------------
+ * The two upsampling calls with a level and the FULL-SIZE raster inputs: the host traces low and presents a frame of the shipping level.
+ * The low frame stays a Pure frame (the colour of a ray-traced pixel does not depend on the level); the raster blend of the reference
+ * (raytrace.wgsl:104-120) is decided per OUTPUT pixel p by the upsampling kernel, which holds the distance t_p of p's centre ray:
+ *   depth = t_p, or on a miss far + 10 at level 1 and far - 1 at level 2;  rd = depth > far ? -1 : near / depth;
+ *   p is covered iff d_raster_depth[p] > rd   (f32, each operation rounded; a null depth reads as 0, a NaN depth never covers).
+ * A covered pixel is the raster texel of its own index, all four channels (a null colour reads as zeros), in the BRT_FLAG_OUT_* format; any
+ * other pixel is bit for bit what the call without a level stores.  Rule, kernel, costs: DESIGN.md "Upsampling blended frames".
+ * level: 3 is exactly the call without a level (the raster inputs are not read); 0 BRT_ERR_UNSUPPORTED; others BRT_ERR_INVALID_ARGUMENT.
+ * d_raster_rgba_or_null (RGBA f32) / d_raster_depth_or_null (reverse-Z f32): DEVICE, width x height, on the context's first device; the
+ * output must overlap neither (BRT_ERR_INVALID_ARGUMENT).  Sizes, flags, stream rule, stats, scratch and ordering: those of the call
+ * without a level.
+ *   brt_upscale_blend_device          brt_upscale_device; d_low_rgba is a PURE low frame of any entry point.
+ *   brt_render_upscaled_blend_device  brt_render_upscaled_device: the low frame is traced at level 3 on every device of the context -- no
+ *                                     raster input is forwarded to another device -- and BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL run on it
+ *                                     with the low size's history.
+ *   brt_host_blend_covered            host arithmetic, no context: the rule above for one (t, raster_depth) pair, t = +INF meaning a miss,
+ *                                     into *out_covered (0 / 1; always 0 at level 3).  Lets a host predict the seam. */
+int32_t brt_upscale_blend_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t low_width,
+                                 uint32_t low_height, const float* d_low_rgba, uint32_t width, uint32_t height,
+                                 const float* d_raster_rgba_or_null, const float* d_raster_depth_or_null, void* d_out, void* hip_stream,
+                                 uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_render_upscaled_blend_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t low_width,
+                                         uint32_t low_height, uint32_t width, uint32_t height, const float* d_raster_rgba_or_null,
+                                         const float* d_raster_depth_or_null, void* d_frame, void* hip_stream, uint32_t flags,
+                                         brt_stats* stats_or_null);
+int32_t brt_host_blend_covered(const void* camera80, uint32_t level, float t, float raster_depth, uint32_t* out_covered);
 
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how

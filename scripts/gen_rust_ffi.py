@@ -34,6 +34,9 @@ DOCS = {
     "brt_upscale_device": "guide-buffer upsampling of a low-resolution Pure DEVICE frame the caller holds to the colour target's size: every output pixel casts its own centre ray, so silhouettes, base colour and sky are at full sharpness",
     "brt_render_upscaled_device": "trace at low_width x low_height (brt_render_device's frame, every device of the context), post-passes on the low frame, upsampling into the full-size target: the pass on post_process.destination (pipeline.rs:191-217) at a fraction of the rays",
     "brt_host_upscale_window": "host arithmetic: the WindowExtract a low frame is traced with (height scaled in integer arithmetic, at least 1)",
+    "brt_upscale_blend_device": "brt_upscale_device for a frame of level 1 / 2: the low frame is a Pure frame, the raster blend (raytrace.wgsl:104-120) is decided per output pixel against the full-size raster depth and colour",
+    "brt_render_upscaled_blend_device": "brt_render_upscaled_device for a frame of level 1 / 2: trace low at level 3, present full with the raster blend -- the pass of the shipping level (FallbackRaytraced) at a fraction of the rays",
+    "brt_host_blend_covered": "host arithmetic: whether the raster wins a pixel whose centre ray hits at distance t (+INF: a miss) against a raster depth, the blend rule of the two calls above",
     "brt_host_pixel_ray": "host arithmetic: the pixel-centre ray of a pixel (raytrace.wgsl:139-156 without the jitter), for picking",
     "brt_debug_temporal_state": "diagnostic: the temporal history per pixel (h.rgb, n, m1, m2, reprojected x', y') in host memory",
 }
