@@ -364,18 +364,16 @@ def test_error_behaviour(plugin):
         plugin.node.run(lvl, cam, win, 0, 18)
 
 
-def test_sampler_stage_of_the_workgroup_renders_the_same_pixels(oracle):
-    """The rejection sampler as a STAGE of the workgroup (knob BRT_BALL_SERVERS; brt_trace.h SRV, brt_device.h ball_server_asm): fourteen
-    waves trace, two serve the other waves' samplers through mailboxes in LDS.  A lane's draws are the same hash chain whichever wave
-    runs them: whole frames and ray counts equal the oracle's, in the steady-state instantiation (kernel_variant 2 + 32) the stage exists
-    for; no pick-up runs into its bound."""
+def test_steady_state_instantiation_at_low_sample_counts_renders_the_same_pixels(oracle):
+    """A view that keeps still settles, within six frames, in the steady-state instantiation of the trace kernel (LEAN = 2: Pure level,
+    no critical tile possible; kernel_variant 2 and no other bit).  At 4 and 8 samples per pixel -- below the 16 from which tiles are
+    split into half-sample jobs -- every one of the six frames and its ray count equal the oracle's, on the callee's tree."""
     b = brt.generate_scene(brt.SCENE_COVER, 1)
     bb = brt.Buffers(b.models, b.materials, None)
     for (w, h, spp, bounces) in ((1920, 1080, 4, 2), (1920, 1080, 8, 8)):
         lvl, cam, win = brt.cover_camera(w, h, spp, bounces)
         want, cnt = oracle.render(b, lvl, cam, win, w, h)
         with brt.RaytracePlugin([0]) as p:
-            p.set_tuning("BRT_BALL_SERVERS", 1)
             seen = set()
             for i in range(6):
                 f = p.node.run(lvl, cam, win, w, h, buffers=bb if i == 0 else None)
@@ -383,10 +381,7 @@ def test_sampler_stage_of_the_workgroup_renders_the_same_pixels(oracle):
                 seen.add(st["kernel_variant"])
                 assert st["rays"] == cnt["rays"], (i, st["kernel_variant"])
                 assert_frames_equal(f, want)
-            assert st["kernel_variant"] == 2 + 32, seen                    # the last frames ran in the instantiation with the stage
-            p.debug_profile()
-            stage = p.last_sampler_stage
-            assert stage["gave_up"] == 0 and stage["iterations"] > 0 and stage["lanes"] > stage["iterations"], stage
+            assert st["kernel_variant"] == 2, seen                         # the last frame ran in the steady-state instantiation
 
 
 def test_exception_barrier_on_exports_that_own_a_context(plugin, oracle):
