@@ -107,6 +107,12 @@ _PROTOTYPES = {
     "brt_render_upscaled_blend_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _U32,
                                                 C.POINTER(BrtStats)]),
     "brt_host_blend_covered": (_I32, [_VP, _U32, _F, _F, C.POINTER(_U32)]),
+    "brt_render_pixels_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_pixels": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_upscale_refine_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_upscaled_refined_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _U32,
+                                                  C.POINTER(BrtStats)]),
+    "brt_upscale_refine_mask_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _U32]),
     "brt_debug_profile": (_I32, [_VP, C.POINTER(C.c_uint64)]),
     "brt_debug_tile_order": (_I32, [_VP, _VP, _VP, _U32, _U32, C.c_uint64, _U32, _U32, _U32, _VP, _VP]),
     "brt_build_bvh": (_I32, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),

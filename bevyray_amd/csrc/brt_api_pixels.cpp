@@ -1,0 +1,171 @@
+// brt_api_pixels.cpp -- the sparse pixel tracer (brt_pixels.hip; DESIGN.md "Refined upsampling") on the first device: a list of pixels
+// of a Pure frame, each traced alone to the value the whole frame holds there.
+#include "brt_frame.h"
+
+using namespace brt;
+
+namespace brt {
+
+// Which form a list takes: BRT_FLAG_KERNEL_SIMPLE or BRT_PIXELS_FORM 1 the plain form (what brt_api_query.cpp hands to k_query_plain
+// goes to it here: every representation and tree), else the streaming form in the launch shape of plan_stream.
+int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                       const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
+                       hipStream_t stream, bool force_plain, PixelsLaunch* pl) {
+    int32_t rc = make_frame_params(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, 0u, 1u, &pl->frame);
+    if (rc != BRT_OK) return rc;
+    if (pl->frame.policy_flags != 0u)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the pixel tracer implements the default policy only (brt_set_policy)");
+    const uint32_t form = ctx->knobs[K_PIXELS_FORM];
+    pl->scene = dc.view;
+    pl->scene.lds_pairs = 0u;
+    pl->form = (form == 1u || (force_plain && form != 2u)) ? PIXELS_PLAIN : PIXELS_STREAM;
+    pl->scene_mode = SCENE_GLOBAL;
+    pl->grid = pl->block = 0u;
+    pl->lds_bytes = 0;
+    if (pl->form == PIXELS_STREAM) {
+        // waves per SIMD where nothing is staged: 114 VGPRs with the hand-written loop (4), 86 without (5)
+        const StreamPlan sp = plan_stream(ctx, dc, n_pixels, 4u, 5u);
+        pl->scene = sp.scene;
+        pl->scene_mode = sp.scene_mode;
+        pl->grid = sp.grid;
+        pl->block = sp.block;
+        pl->lds_bytes = sp.lds_bytes;
+    }
+    PixelsArgs& pa = pl->args;
+    pa.pixels = d_pixels;
+    pa.n_pixels = n_pixels;
+    pa.count = d_count;
+    pa.out = target.d_out;
+    pa.scatter = target.scatter ? 1u : 0u;
+    pa.out_format = target.out_format;
+    pa.stat = reinterpret_cast<unsigned long long*>(d_ctl);
+    pa.counter = d_ctl + 4;
+    pl->stream = stream;
+    HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 20, stream));
+    HIP_TRY(ctx, launch_trace_pixels(*pl));
+    return BRT_OK;
+}
+
+}  // namespace brt
+
+namespace {
+
+int32_t pixels_check(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const void* pixels,
+                     uint32_t n_pixels, const void* out, uint32_t flags, uint32_t allowed) {
+    if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
+    if (flags & ~allowed) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM (device form) and BRT_FLAG_KERNEL_SIMPLE only");
+    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    if (n_pixels > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_pixels too large");
+    if (n_pixels != 0u && (!pixels || !out)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "pixels / out is null");
+    if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
+    Camera cam;
+    std::memcpy(&cam, camera80, sizeof cam);
+    if (cam.projection_type != 0) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "only perspective projection (0) is supported (extract.rs:148)");
+    if (ctx->policy_flags & kPolicyMask)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the pixel tracer implements the default policy only (brt_set_policy)");
+    return BRT_OK;
+}
+
+// the control words of the first device (DeviceCtx::d_pxbuf), for work behind ev_q
+int32_t pixels_ctl(brt_ctx* ctx, DeviceCtx& dc) {
+    if (dc.d_pxbuf) return BRT_OK;
+    return ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, 32u);
+}
+
+void pixels_stats(const PixelsLaunch& pl, const unsigned long long* counts2, brt_stats* stats) {
+    // (the tree fields are with_tree_reach's)
+    stats->rays = counts2 ? counts2[0] : 0u;
+    stats->reserved = counts2 ? (uint32_t)std::min<unsigned long long>(counts2[1], 0xffffffffull) : 0u;      // entries refused
+    stats->n_workgroups = pl.form == PIXELS_STREAM ? pl.grid : (pl.args.n_pixels + 255u) / 256u;
+    stats->threads_per_workgroup = pl.form == PIXELS_STREAM ? pl.block : 256u;
+    stats->lds_bytes = (uint32_t)pl.lds_bytes;
+    stats->scene_in_lds = pl.form != PIXELS_STREAM ? 0u : pl.scene_mode == SCENE_LDS ? 1u : (pl.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
+    stats->kernel_variant = pl.form == PIXELS_STREAM ? 32u : 33u;      // (the persistent kernel's variants are below 32)
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t brt_render_pixels_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                 const uint32_t* d_pixels, uint32_t n_pixels, float* d_out_rgba32f, void* hip_stream, uint32_t flags,
+                                 brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (const int32_t bad = pixels_check(ctx, camera80, window16, width, height, d_pixels, n_pixels, d_out_rgba32f, flags,
+                                         BRT_FLAG_CALLER_STREAM | BRT_FLAG_KERNEL_SIMPLE))
+        return bad;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_pixels == 0u) return BRT_OK;
+    DeviceCtx& dc = ctx->devs[0];
+    PixelsLaunch pl{};
+    unsigned long long counts[2] = {0u, 0u};
+    bool own = false;
+    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
+        HIP_TRY(ctx, hipSetDevice(dc.device));
+        const StreamChoice sc = stream_of(dc, hip_stream, flags);
+        own = sc.own;
+        int32_t r = pixels_ctl(ctx, dc);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_q, 0));
+        r = pixels_enqueue(ctx, dc, camera80, window16, width, height, d_pixels, n_pixels, nullptr, {d_out_rgba32f, false, 0u}, dc.d_pxbuf,
+                           sc.stream, (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u, &pl);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));
+        if (!sc.own) return BRT_OK;
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_pxbuf, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+        return BRT_OK;
+    });
+    if (rc == BRT_OK && stats) {
+        pixels_stats(pl, own ? counts : nullptr, stats);
+        stats->paths = own ? ((uint64_t)n_pixels - counts[1]) * pl.frame.sample_count : 0u;
+        stats->total_ms = ms_since(t0);
+    }
+    return rc;
+    });
+}
+
+int32_t brt_render_pixels(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const uint32_t* pixels,
+                          uint32_t n_pixels, float* out_rgba32f, uint32_t flags, brt_stats* stats) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (const int32_t bad = pixels_check(ctx, camera80, window16, width, height, pixels, n_pixels, out_rgba32f, flags, BRT_FLAG_KERNEL_SIMPLE))
+        return bad;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_pixels == 0u) return BRT_OK;
+    DeviceCtx& dc = ctx->devs[0];
+    PixelsLaunch pl{};
+    unsigned long long counts[2] = {0u, 0u};
+    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
+        HIP_TRY(ctx, hipSetDevice(dc.device));
+        const size_t list_bytes = (size_t)n_pixels * 4u, out_bytes = (size_t)n_pixels * 16u;
+        if (dc.pxlist_cap < list_bytes || dc.pxout_cap < out_bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));   // (the staging buffers grow only when no list uses them)
+        int32_t r = pixels_ctl(ctx, dc);
+        if (r == BRT_OK) r = ensure(ctx, &dc.d_pxlist, &dc.pxlist_cap, list_bytes);
+        if (r == BRT_OK) r = ensure(ctx, &dc.d_pxout, &dc.pxout_cap, out_bytes);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_pxlist, pixels, list_bytes, hipMemcpyHostToDevice, dc.stream));
+        r = pixels_enqueue(ctx, dc, camera80, window16, width, height, reinterpret_cast<const uint32_t*>(dc.d_pxlist), n_pixels, nullptr,
+                           {dc.d_pxout, false, 0u}, dc.d_pxbuf, dc.stream, (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u, &pl);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(out_rgba32f, dc.d_pxout, out_bytes, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_pxbuf, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
+        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
+        return BRT_OK;
+    });
+    if (rc == BRT_OK && stats) {
+        pixels_stats(pl, counts, stats);
+        stats->paths = ((uint64_t)n_pixels - counts[1]) * pl.frame.sample_count;
+        stats->total_ms = ms_since(t0);
+    }
+    return rc;
+    });
+}
+
+}  // extern "C"

@@ -69,10 +69,8 @@ int32_t ensure_query_reach(brt_ctx* ctx, float origin_bound, uint32_t* rebuilt) 
     return BRT_OK;
 }
 
-// Which form a batch takes and the streaming form's launch shape.  BRT_QUERY_FORM 1 / 2 force the plain / the streaming form; else a
-// batch of at least BRT_QUERY_STREAM_MIN rays streams (0: none does).  The streaming form stages what k_trace_persistent would
-// (plan_launch): the whole scene where it fits a workgroup's LDS beside the stacks, else the top of the tree, else nothing (scenes of
-// 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE); BRT_FORCE_LDS_TOP=<records> as there.
+// Which form a batch takes and the streaming form's launch shape (plan_stream).  BRT_QUERY_FORM 1 / 2 force the plain / the streaming
+// form; else a batch of at least BRT_QUERY_STREAM_MIN rays streams (0: none does).
 void plan_query(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, QueryLaunch* ql) {
     const Knobs& kn = ctx->knobs;
     ql->scene = dc.view;
@@ -84,41 +82,67 @@ void plan_query(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, QueryL
     const uint32_t form = kn[K_QUERY_FORM], stream_min = kn[K_QUERY_STREAM_MIN];
     if (form == 1u || (form != 2u && (stream_min == 0u || n_rays < stream_min))) return;
     ql->form = QUERY_STREAM;
+    // waves per SIMD: the simple-tree instantiation of 16-bit descriptors holds the hand-written loop's 114 VGPRs (4), the others 60-64 (8)
+    const StreamPlan sp = plan_stream(ctx, dc, n_rays, 4u, 8u);
+    ql->scene = sp.scene;
+    ql->scene_mode = sp.scene_mode;
+    ql->grid = sp.grid;
+    ql->block = sp.block;
+    ql->lds_bytes = sp.lds_bytes;
+}
+
+}  // namespace
+
+namespace brt {
+
+// The streaming forms stage what k_trace_persistent would (plan_launch): the whole scene where it fits a workgroup's LDS beside the
+// stacks, else the top of the tree, else nothing (scenes of 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE); BRT_FORCE_LDS_TOP=<records> as
+// there.
+StreamPlan plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, uint32_t waves_by_hand, uint32_t waves_other) {
+    const Knobs& kn = ctx->knobs;
+    StreamPlan sp{};
+    sp.scene = dc.view;
+    sp.scene.lds_pairs = 0u;
+    sp.scene_mode = SCENE_GLOBAL;
     const bool force_global = kn[K_FORCE_GLOBAL_SCENE] != 0u;
     const uint32_t force_top = kn[K_FORCE_LDS_TOP];
     uint32_t per_cu = 1u;
     if (!force_global && !force_top && dc.view.desc16) {
         for (uint32_t block : {1024u, 512u, 256u}) {
             const size_t need = trace_lds_bytes(dc.view, SCENE_LDS, block, 0u);
-            if (need <= dc.max_lds) { ql->scene_mode = SCENE_LDS; ql->block = block; ql->lds_bytes = need; break; }
+            if (need <= dc.max_lds) { sp.scene_mode = SCENE_LDS; sp.block = block; sp.lds_bytes = need; break; }
         }
     }
-    if (ql->scene_mode != SCENE_LDS && !force_global && dc.view.desc16) {
-        const size_t fixed = trace_lds_bytes(ql->scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);       // (lds_pairs = 0: stacks only)
+    if (sp.scene_mode != SCENE_LDS && !force_global && dc.view.desc16) {
+        const size_t fixed = trace_lds_bytes(sp.scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);       // (lds_pairs = 0: stacks only)
         if (fixed + 64 * PAIR_BYTES <= dc.max_lds) {
             uint32_t k = (uint32_t)((dc.max_lds - fixed) / PAIR_BYTES);
             if (k > dc.view.n_pairs) k = dc.view.n_pairs;
             if (force_top && force_top < k) k = force_top;
-            ql->scene.lds_pairs = k;
-            ql->scene_mode = SCENE_LDS_TOP;
-            ql->block = BRT_BLOCK;
-            ql->lds_bytes = trace_lds_bytes(ql->scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);
+            sp.scene.lds_pairs = k;
+            sp.scene_mode = SCENE_LDS_TOP;
+            sp.block = BRT_BLOCK;
+            sp.lds_bytes = trace_lds_bytes(sp.scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);
         }
     }
-    if (ql->scene_mode == SCENE_GLOBAL) {
-        ql->block = 256u;
-        ql->lds_bytes = trace_lds_bytes(dc.view, SCENE_GLOBAL, 256u, 0u);
-        per_cu = (uint32_t)(dc.max_lds / (ql->lds_bytes ? ql->lds_bytes : 1));
-        // waves per SIMD: the simple-tree instantiation of 16-bit descriptors holds the hand-written loop's 114 VGPRs (4), the others 60-64 (8)
-        const uint32_t by_regs = (dc.view.desc16 && dc.view.simple_tree) ? 4u : 8u;
+    if (sp.scene_mode == SCENE_GLOBAL) {
+        sp.block = 256u;
+        sp.lds_bytes = trace_lds_bytes(dc.view, SCENE_GLOBAL, 256u, 0u);
+        per_cu = (uint32_t)(dc.max_lds / (sp.lds_bytes ? sp.lds_bytes : 1));
+        const uint32_t by_regs = (dc.view.desc16 && dc.view.simple_tree) ? waves_by_hand : waves_other;
         if (per_cu > by_regs) per_cu = by_regs;
         if (per_cu < 1u) per_cu = 1u;
     }
-    ql->grid = (uint32_t)dc.num_cus * per_cu;
-    const uint32_t useful = (n_rays + ql->block - 1u) / ql->block;
-    if (ql->grid > useful) ql->grid = useful;
-    if (ql->grid < 1u) ql->grid = 1u;
+    sp.grid = (uint32_t)dc.num_cus * per_cu;
+    const uint32_t useful = (n_items + sp.block - 1u) / sp.block;
+    if (sp.grid > useful) sp.grid = useful;
+    if (sp.grid < 1u) sp.grid = 1u;
+    return sp;
 }
+
+}  // namespace brt
+
+namespace {
 
 // the resident -> caller sphere map of the first device for work on `stream` (nullptr: the resident order is the upload order)
 int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32_t** rmap) {

@@ -13,6 +13,7 @@
 #include "brt_temporal.h"
 #include "brt_host.h"
 #include "brt_kernels.h"
+#include "brt_pixels.h"
 #include "brt_query.h"
 #include "brt_upscale.h"
 
@@ -125,6 +126,15 @@ struct DeviceCtx {
     size_t qrays_cap = 0;
     char* d_qhits = nullptr;
     size_t qhits_cap = 0;
+    // sparse pixel tracer and refined upsampling (brt_pixels.h), first device only: 8 control words {u64 rays, u64 refused entries, the
+    // streaming form's batch counter, the entries of the list, -, -}, then the list of brt_upscale_refine* (one word per output pixel).
+    // Its users run one behind the other, ordered by ev_q like the queries (so uploads and renumberings wait for them too)
+    uint32_t* d_pxbuf = nullptr;
+    size_t pxbuf_cap = 0;
+    char* d_pxlist = nullptr;       // brt_render_pixels: the host list on the device, and its results
+    size_t pxlist_cap = 0;
+    char* d_pxout = nullptr;
+    size_t pxout_cap = 0;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;
@@ -141,7 +151,7 @@ struct DeviceCtx {
 enum Knob : int {
     K_BOTTOM_UP, K_REFILL_MIN, K_WALK_EXIT, K_LEAF_VOTE, K_DRAIN_DONATE, K_POOL_ADOPT, K_WGQ_BATCH, K_LPT_LANE_PERMILLE, K_TUNABLE,
     K_FORCE_GLOBAL_SCENE, K_FORCE_LDS_TOP, K_BLOCK_THREADS, K_WG_PER_CU, K_POOL_CAP, K_LPT, K_LPT_SORT, K_LPT_SKY_SLACK, K_CRIT,
-    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_COUNT
+    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_PIXELS_FORM, K_COUNT
 };
 struct KnobDef { const char* name; uint32_t dflt; };
 constexpr KnobDef kKnobs[K_COUNT] = {
@@ -152,7 +162,9 @@ constexpr KnobDef kKnobs[K_COUNT] = {
     {"BRT_NO_LEAN", 0}, {"BRT_PREPASS_SPP", 4}, {"BRT_NO_DIRTY_TRACKING", 0}, {"BRT_CPU_BVH", 0},
     {"BRT_PLOC_ONE_BLOCK_MAX", kPlocOneBlockMax}, {"BRT_BVH_QUALITY", 1}, {"BRT_POOL_FORCE", 0}, {"BRT_LPT_REFRESH_EVERY", 0}, {"BRT_LEAN_MEASURE", 1}, {"BRT_LPT_DILATE", 3}, {"BRT_SPLIT_TAIL", 16}, {"BRT_SPLIT_FORCE", 0}, {"BRT_HOT_RECORDS", 1}, {"BRT_TEST_THROW", 0},
     // ray queries: the form of a call (0: by batch size, 1 plain, 2 streaming) and the batch size from which the default rule streams (0: never)
-    {"BRT_QUERY_FORM", 0}, {"BRT_QUERY_STREAM_MIN", 0}};
+    {"BRT_QUERY_FORM", 0}, {"BRT_QUERY_STREAM_MIN", 0},
+    // sparse pixel tracer: the form of a call (0: streaming unless BRT_FLAG_KERNEL_SIMPLE, 1 plain, 2 streaming)
+    {"BRT_PIXELS_FORM", 0}};
 struct Knobs {
     uint32_t v[K_COUNT];
     Knobs() { for (int i = 0; i < K_COUNT; i++) v[i] = kKnobs[i].dflt; }

@@ -110,6 +110,32 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
                             const float* d_raster_rgba, const float* d_raster_depth, void* d_frame, void* hip_stream, uint32_t flags,
                             brt_stats* stats);
 
+// ---- brt_api_query.cpp ----
+// The launch shape of a streaming kernel (k_query_stream, k_trace_pixels_stream) over n_items: what it stages in LDS, its block and its
+// fixed grid.  waves_by_hand / waves_other: the waves per SIMD its registers admit where nothing is staged -- of the instantiation that
+// holds the hand-written walk loop (16-bit descriptors, simple tree) and of the others.
+struct StreamPlan {
+    DeviceSceneView scene;       // (lds_pairs set for SCENE_LDS_TOP)
+    int scene_mode;              // SceneMode
+    uint32_t grid, block;
+    size_t lds_bytes;            // trace_lds_bytes(scene, scene_mode, block, 0)
+};
+StreamPlan plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, uint32_t waves_by_hand, uint32_t waves_other);
+
+// ---- brt_api_pixels.cpp ----
+// What a list of pixels is traced into (brt_pixels.h PixelsArgs): packed RGBA32F, or scattered into a frame in a BRT_FLAG_OUT_* format
+struct PixelsTarget {
+    void* d_out;
+    bool scatter;
+    uint32_t out_format;
+};
+// Behind whatever wrote the list on `stream`: the list traced as pixels of the width x height Pure frame of camera80 / window16 on the
+// first device.  d_count: a device word holding the number of entries (nullptr: n_pixels, which is else the list's capacity).  ctl: 8
+// words of the caller's {u64 rays, u64 refused, u32 batch counter, ...}, zeroed here.  Refuses a non-default policy.
+int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                       const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
+                       hipStream_t stream, bool force_plain, PixelsLaunch* pl);
+
 // ---- brt_api_post.cpp ----
 // the guides' frame parameters (one part, level 3) and the denoiser's scratch of a width x height frame for work on `stream`
 int32_t denoise_begin(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,

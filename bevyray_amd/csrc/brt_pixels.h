@@ -1,0 +1,40 @@
+// brt_pixels.h -- host-callable launcher of the sparse pixel tracer (brt_pixels.hip).  The rules: DESIGN.md "Refined upsampling".
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "brt_layout.h"
+
+namespace brt {
+
+// One list of pixels of the width x height Pure frame of `frame`.  Entry i names pixel p = py * width + px; its value is what the frame
+// holds there ({rgb, 1}).  Packed: entry i is stored at out[i] as RGBA32F; scatter: at out[p] of a width x height frame in out_format.
+// An entry >= width * height is never traced: packed it stores four zeros, scattered it stores nothing; both count it as refused.
+struct PixelsArgs {
+    const uint32_t* pixels;
+    uint32_t n_pixels;          // entries of the list (its capacity when count is set)
+    const uint32_t* count;      // a device word that holds the number of entries, read by the kernel (nullptr: n_pixels)
+    void* out;
+    uint32_t scatter;           // 0: packed RGBA32F; 1: out[p] in out_format
+    uint32_t out_format;        // BRT_FLAG_OUT_* (scatter only)
+    unsigned long long* stat;   // [0] rays, [1] refused entries, zeroed by the caller (nullptr: not counted)
+    uint32_t* counter;          // streaming form: the batch counter, zeroed by the caller
+};
+
+enum PixelsForm : int { PIXELS_PLAIN = 0, PIXELS_STREAM = 1 };
+
+struct PixelsLaunch {
+    DeviceSceneView scene;      // (lds_pairs set for SCENE_LDS_TOP)
+    FrameParams frame;          // one part, level 3, the default policy
+    PixelsArgs args;
+    int form;                   // PixelsForm
+    int scene_mode;             // streaming form: SceneMode
+    uint32_t grid, block;       // streaming form
+    size_t lds_bytes;           // streaming form: trace_lds_bytes(scene, scene_mode, block, 0)
+    hipStream_t stream;
+};
+hipError_t launch_trace_pixels(const PixelsLaunch& pl);
+
+}  // namespace brt

@@ -1,0 +1,300 @@
+// brt_pixels.hip -- the sparse pixel tracer (brt_render_pixels*, and the refinement of brt_upscale_refine*; DESIGN.md "Refined
+// upsampling").  A list entry names a pixel of the width x height Pure frame; its value is that frame's: the seed of a pixel depends on
+// its frame coordinates alone (pixel_seed), and per pixel the draws and operations are k_trace_simple's (pixel_begin / camera_ray_dir /
+// walk / shade_segment), whichever form runs it.
+//
+// k_trace_pixels_plain<D16>                one thread per entry: k_trace_simple's loop over a list, the scene in global memory, a private
+//                                          stack.  Every scene representation and tree.
+// k_trace_pixels_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in
+//                                          LDS as k_query_stream stages it, the stacks in LDS, so the hand-written walk loops serve it.
+//                                          A lane carries one path.  A round: the wave takes entries from the batch counter (one
+//                                          fetch-add) for the lanes whose pixel has ended, walk_run for all lanes, and the lanes whose
+//                                          walk has ended shade their segment and begin the next one, end the sample or end the pixel.
+// Both forms write the same bytes: an entry's result depends on its pixel alone.  No atomic touches a result.
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "brt_pixels.h"
+#include "brt_store.h"
+#include "brt_trace.h"
+
+namespace brt {
+
+namespace {
+
+// the wave's counts into pa.stat (all lanes of the wave call it)
+BRT_DEV void pixels_count(const PixelsArgs& pa, uint32_t rays, uint32_t refused) {
+    if (!pa.stat) return;
+    rays = wave_sum(rays);
+    refused = wave_sum(refused);
+    if (lane_id() == 0u) {
+        if (rays) atomicAdd(pa.stat + 0, (unsigned long long)rays);
+        if (refused) atomicAdd(pa.stat + 1, (unsigned long long)refused);
+    }
+}
+
+BRT_DEV uint32_t pixels_n(const PixelsArgs& pa) {
+    if (!pa.count) return pa.n_pixels;
+    const uint32_t n = *pa.count;
+    return n < pa.n_pixels ? n : pa.n_pixels;
+}
+
+// entry i, pixel p: its value where the call wants it
+BRT_DEV void pixels_store(const PixelsArgs& pa, uint32_t i, uint32_t p, float4 v) {
+    if (!pa.scatter) {
+        reinterpret_cast<float4*>(pa.out)[i] = v;
+        return;
+    }
+    switch (pa.out_format) {
+        case BRT_FLAG_OUT_RGBA8_UNORM_SRGB: reinterpret_cast<uint32_t*>(pa.out)[p] = OutPixel<BRT_FLAG_OUT_RGBA8_UNORM_SRGB>::make(v); break;
+        case BRT_FLAG_OUT_RGBA16F: reinterpret_cast<uint2*>(pa.out)[p] = OutPixel<BRT_FLAG_OUT_RGBA16F>::make(v); break;
+        case BRT_FLAG_OUT_RGBA8_UNORM: reinterpret_cast<uint32_t*>(pa.out)[p] = OutPixel<BRT_FLAG_OUT_RGBA8_UNORM>::make(v); break;
+        default: reinterpret_cast<float4*>(pa.out)[p] = OutPixel<BRT_FLAG_OUT_RGBA32F>::make(v); break;
+    }
+}
+
+// entry i names no pixel of the frame
+BRT_DEV void pixels_refuse(const PixelsArgs& pa, uint32_t i) {
+    if (!pa.scatter) reinterpret_cast<float4*>(pa.out)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+BRT_DEV void pixels_begin(const FrameParams& fp, uint32_t p, PixelState& ps) {
+    PixelCoord c;
+    c.py = p / fp.width;
+    c.px = p - c.py * fp.width;
+    c.local_row = c.py;
+    c.tile = 0u;
+    c.t = 0u;
+    c.inside = true;
+    pixel_begin(fp, c, ps);
+}
+
+// the Pure frame's value of a pixel whose samples have ended (pixel_finish<true>, raytrace.wgsl:169, :122)
+BRT_DEV float4 pixels_value(const FrameParams& fp, const PixelState& ps) {
+    return make_float4(ps.sum.x / fp.spp_f, ps.sum.y / fp.spp_f, ps.sum.z / fp.spp_f, 1.0f);
+}
+
+BRT_DEV ScenePtrs pixels_scene_global(const DeviceSceneView& sv) {      // the scene in global memory, as k_trace_simple walks it
+    ScenePtrs sc = {};
+    sc.pairs = reinterpret_cast<const char*>(sv.pairs);
+    sc.pairs_far = sc.pairs;
+    sc.boxes_ordered = sv.boxes_ordered != 0u;
+    sc.spheres = reinterpret_cast<const float4*>(sv.spheres);
+    sc.sphere_material = sv.sphere_material;
+    sc.materials = reinterpret_cast<const float4*>(sv.materials);
+    sc.sphere_mats = reinterpret_cast<const float4*>(sv.sphere_mats);
+    sc.leaf_table = reinterpret_cast<const uint2*>(sv.leaf_table);
+    return sc;
+}
+
+}  // namespace
+
+// ---- plain form ----------------------------------------------------------------------------------------------------------------------
+
+template <bool D16>
+__global__ __launch_bounds__(256) void k_trace_pixels_plain(DeviceSceneView sv, FrameParams fp, PixelsArgs pa) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t n_rays = 0u, refused = 0u;
+    if (i < pixels_n(pa)) {
+        const uint32_t p = pa.pixels[i];
+        if (p >= fp.width * fp.height) {
+            pixels_refuse(pa, i);
+            refused = 1u;
+        } else {
+            const ScenePtrs sc = pixels_scene_global(sv);
+            HitCounters hc = {};
+            PixelState ps;
+            pixels_begin(fp, p, ps);
+            uint32_t stack[34];   // DONE sentinel + 32 entries + one spare
+            for (uint32_t s = 0; s < fp.sample_count; s++) {          // raytrace.wgsl:161
+                f3 d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);
+                f3 o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
+                f3 tput = mk3(1.0f, 1.0f, 1.0f);
+                float first_depth = kInf;
+                uint32_t bounce = 0;
+                f3 color;
+                for (;;) {
+                    float t;
+                    uint32_t idx;
+                    raycast<1, false, D16, false>(sc, sv.root_desc, stack, o, d, t, idx, hc);
+                    n_rays++;
+                    if (shade_segment<false>(sc, fp, o, d, tput, bounce, first_depth, t, idx, ps.rng, color, hc)) break;
+                }
+                ps.sum = ps.sum + color;
+            }
+            pixels_store(pa, i, p, pixels_value(fp, ps));
+        }
+    }
+    pixels_count(pa, n_rays, refused);
+}
+
+// ---- streaming form ------------------------------------------------------------------------------------------------------------------
+
+template <int MODE, bool D16, bool SIMPLE>
+__global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneView sv, FrameParams fp, PixelsArgs pa) {
+    static_assert(MODE == SCENE_GLOBAL || D16, "a scene staged in LDS always uses 16-bit descriptors");
+    using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
+    using DS = Desc<D16>;
+    // one dynamic array, carved as k_trace_persistent and k_query_stream carve it: the hand-written loops address the pair records from
+    // LDS address 0, so they come first (every carve offset is a multiple of 16), then spheres, leaf table and the stacks
+    extern __shared__ uint4 smem[];
+    ScenePtrs sc = pixels_scene_global(sv);
+    StackT* stacks;
+    if (MODE == SCENE_LDS) {
+        const uint32_t pair_granules = (uint32_t)(pair_array_bytes(sv.n_pairs) / 16);
+        float4* p = reinterpret_cast<float4*>(smem);
+        float4* l_pairs = p; p += pair_granules;
+        float4* l_sp = p; p += sv.n_models;
+        uint2* l_lt = reinterpret_cast<uint2*>(p);
+        stacks = reinterpret_cast<StackT*>(l_lt + sv.n_leaf_table);
+        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
+        const float4* g_sp = reinterpret_cast<const float4*>(sv.spheres);
+        const uint2* g_lt = reinterpret_cast<const uint2*>(sv.leaf_table);
+        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
+        for (uint32_t i = threadIdx.x; i < sv.n_models; i += blockDim.x) l_sp[i] = g_sp[i];
+        for (uint32_t i = threadIdx.x; i < sv.n_leaf_table; i += blockDim.x) l_lt[i] = g_lt[i];
+        sc.pairs = reinterpret_cast<const char*>(l_pairs);
+        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
+        sc.sph_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_sp);
+        sc.spheres = l_sp;
+        sc.leaf_table = l_lt;
+    } else if (MODE == SCENE_LDS_TOP) {
+        const uint32_t pair_granules = sv.lds_pairs * PAIR_UNITS;
+        float4* l_pairs = reinterpret_cast<float4*>(smem);
+        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
+        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
+        sc.pairs = reinterpret_cast<const char*>(l_pairs);
+        sc.near_bytes = sv.lds_pairs * PAIR_BYTES;
+        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
+        stacks = reinterpret_cast<StackT*>(l_pairs + pair_granules);
+    } else {
+        stacks = reinterpret_cast<StackT*>(smem);
+    }
+    __syncthreads();
+    const uint32_t lane = lane_id();
+    const uint32_t wave = threadIdx.x >> 6;
+    // this lane's column of the wave's [entry][64] stack array (16-bit entries: lanes l and l + 32 share a dword, brt_trace.h)
+    const uint32_t stack_col = D16 ? ((lane & 31u) * 2u + (lane >> 5)) : lane;
+    StackT* stk = stacks + wave * ((sv.stack_entries + 2u) * 64u) + stack_col;
+    const uint32_t n = pixels_n(pa), frame_px = fp.width * fp.height;
+
+    WalkState<StackT> walk;
+    walk.a = 0.0f; walk.inv = mk3(0.0f, 0.0f, 0.0f); walk.closest = kInf; walk.closest_idx = 0xffffffffu;
+    walk.cur = DS::DONE; walk.sp = stk; walk.n = 0;
+    walk.ox = walk.oy = walk.oz = 0u;
+    PixelState ps = {};
+    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f), tput = mk3(1.0f, 1.0f, 1.0f);
+    uint32_t bounce = 0u;
+    float first_depth = kInf;
+    uint32_t entry = 0u, pixel = 0u;
+    bool in_flight = false;          // this lane holds a pixel whose samples have not ended
+    bool exhausted = false;          // wave-uniform: the batch counter has passed the last entry
+    uint32_t n_rays = 0u, refused = 0u;
+    HitCounters hc = {};
+    for (;;) {
+        if (!exhausted) {
+            // entries for the idle lanes: one fetch-add of the wave
+            const uint64_t idle = __ballot(!in_flight);
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            uint32_t base = 0u;
+            if (lane == 0u) base = atomicAdd(pa.counter, cnt);
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            exhausted = base >= n || n - base <= cnt;
+            const uint32_t mine = base + mbcnt64(idle);
+            if (!in_flight && base < n && mine < n) {
+                const uint32_t p = pa.pixels[mine];
+                if (p >= frame_px) {
+                    pixels_refuse(pa, mine);
+                    refused++;
+                } else {
+                    entry = mine;
+                    pixel = p;
+                    pixels_begin(fp, p, ps);
+                    if (fp.sample_count == 0u) {                       // (no sample: the average of nothing)
+                        pixels_store(pa, entry, pixel, pixels_value(fp, ps));
+                    } else {
+                        d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);          // raytrace.wgsl:162, :175-186
+                        o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
+                        tput = mk3(1.0f, 1.0f, 1.0f);
+                        first_depth = kInf;
+                        bounce = 0u;
+                        walk_begin<D16>(walk, sc, sv.root_desc, stk, d);
+                        in_flight = true;
+                    }
+                }
+            }
+        }
+        walk_run<64, false, D16, SIMPLE, MODE, StackT>(sc, walk, stk, o, d, kWalkExitLanes, kLeafVote, hc);
+        if (in_flight && !walk_pending<D16, SIMPLE>(walk)) {
+            n_rays++;
+            f3 color;
+            if (shade_segment<false>(sc, fp, o, d, tput, bounce, first_depth, walk.closest, walk.closest_idx, ps.rng, color, hc)) {
+                ps.sum = ps.sum + color;                                // :165
+                ps.sample++;
+                if (ps.sample < fp.sample_count) {
+                    d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);
+                    o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
+                    tput = mk3(1.0f, 1.0f, 1.0f);
+                    first_depth = kInf;
+                    bounce = 0u;
+                } else {
+                    pixels_store(pa, entry, pixel, pixels_value(fp, ps));
+                    in_flight = false;
+                }
+            }
+            if (in_flight) walk_begin<D16>(walk, sc, sv.root_desc, stk, d);
+            else walk.cur = DS::DONE;
+        }
+        if (exhausted && __ballot(in_flight) == 0ull) break;
+    }
+    pixels_count(pa, n_rays, refused);
+}
+
+// ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
+
+template <int MODE, bool D, bool S>
+static hipError_t launch_stream_t(const PixelsLaunch& pl) {
+    auto kern = k_trace_pixels_stream<MODE, D, S>;
+    if (MODE == SCENE_LDS || MODE == SCENE_LDS_TOP) {
+        // the hand-written walk loops address the pair records from LDS address 0: the dynamic LDS must start there
+        static const size_t static_lds = [&] {
+            hipFuncAttributes at{};
+            return hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kern)) == hipSuccess ? at.sharedSizeBytes : (size_t)1;
+        }();
+        if (static_lds != 0) return hipErrorInvalidConfiguration;
+    }
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.block), pl.lds_bytes, pl.stream, pl.scene, pl.frame, pl.args);
+    return hipGetLastError();
+}
+
+template <int MODE, bool D>
+static hipError_t launch_stream_md(const PixelsLaunch& pl) {
+    return pl.scene.simple_tree ? launch_stream_t<MODE, D, true>(pl) : launch_stream_t<MODE, D, false>(pl);
+}
+
+hipError_t launch_trace_pixels(const PixelsLaunch& pl) {
+    if (pl.args.n_pixels == 0u) return hipSuccess;
+    if (!pl.args.pixels || !pl.args.out || pl.frame.policy_flags != 0u) return hipErrorInvalidValue;
+    if (pl.form == PIXELS_PLAIN) {
+        const dim3 grid((pl.args.n_pixels + 255u) / 256u);
+        if (pl.scene.desc16) hipLaunchKernelGGL(k_trace_pixels_plain<true>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
+        else hipLaunchKernelGGL(k_trace_pixels_plain<false>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
+        return hipGetLastError();
+    }
+    if (pl.grid == 0u || pl.block == 0u || (pl.block & 63u) != 0u || pl.block > BRT_BLOCK || !pl.args.counter) return hipErrorInvalidValue;
+    switch (pl.scene_mode) {
+        case SCENE_LDS:
+            if (!pl.scene.desc16) return hipErrorInvalidValue;
+            return launch_stream_md<SCENE_LDS, true>(pl);
+        case SCENE_LDS_TOP:
+            if (!pl.scene.desc16) return hipErrorInvalidValue;
+            return launch_stream_md<SCENE_LDS_TOP, true>(pl);
+        default:
+            return pl.scene.desc16 ? launch_stream_md<SCENE_GLOBAL, true>(pl) : launch_stream_md<SCENE_GLOBAL, false>(pl);
+    }
+}
+
+}  // namespace brt

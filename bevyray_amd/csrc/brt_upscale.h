@@ -23,13 +23,27 @@ struct UpscaleBlend {
     const float* raster_depth;
 };
 
+// Refined upsampling (DESIGN.md "Refined upsampling"): the classes of an output pixel whose guide is a hit -- BRT_REFINE_EDGES: no tap of
+// its 2x2 footprint is eligible (stage A's weight sum is zero: the pixel would go to stage B or C); BRT_REFINE_SPECULAR: its sphere's
+// material has metallic > 0 or specular_transmission > 0.  mask == nullptr: a pixel in one of `classes` is SELECTED -- its index is
+// appended to list (count: its count word, zeroed by the caller; the order is that of the waves' arrival) and nothing is stored for
+// it; any other pixel is the plain kernel's.  mask != nullptr: the class bits of every output pixel (0 for the sky) go to mask, nothing
+// else is written.
+struct UpscaleSelect {
+    uint32_t classes;
+    uint32_t* count;            // the list's count word
+    uint32_t* list;             // full.width * full.height words
+    uint8_t* mask;
+};
+
 // full: the frame parameters of the width x height output (its pixel-centre rays are cast by the kernel itself); low: those of the traced
 // frame; ds_low: the scratch whose g0 / g1 hold the guides of the low frame (launch_denoise_guides with `low`); d_low: the low frame,
 // RGBA32F low.width x low.height; d_out: full.width x full.height in out_format (BRT_FLAG_OUT_*), not overlapping d_low.  The sigmas of
 // the edge-stopping weights are st's (brt_set_denoise).  blend != nullptr: `full` is made for level 1 or 2 (its near_, far_ and
-// fallback_far decide the blend) and a covered output pixel is its raster texel; d_out overlaps neither raster buffer.
+// fallback_far decide the blend) and a covered output pixel is its raster texel; d_out overlaps neither raster buffer.  select != nullptr
+// (level 3 only, blend == nullptr): see UpscaleSelect; with a mask d_out is not written and may be nullptr.
 hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, const FrameParams& low, const DenoiseSettings& st,
                           const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream,
-                          const UpscaleBlend* blend = nullptr);
+                          const UpscaleBlend* blend = nullptr, const UpscaleSelect* select = nullptr);
 
 }  // namespace brt

@@ -10,7 +10,12 @@
 //             own ray.  The result is stored in the requested BRT_FLAG_OUT_* format (OutPixel, brt_store.h).
 //             With the trailing UpscaleBlend argument (levels 1 / 2, DESIGN.md "Upsampling blended frames") the raster blend is decided
 //             per output pixel between the walk and the gather: a covered pixel stores its raster texel and reads no tap.
+//             With a trailing UpscaleSelect instead (DESIGN.md "Refined upsampling") a pixel of the call's classes is appended to the
+//             call's list -- one ballot and one atomicAdd per wave -- and leaves before stages B and C; or, with a mask, only the class
+//             bits of every pixel are written.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "brt_store.h"
 #include "brt_upscale.h"
@@ -64,10 +69,29 @@ BRT_DEV bool blend_covered(const FrameParams& fp, float t, uint32_t p, const Ups
     return depth_p > rd;
 }
 BRT_DEV float4 blend_texel(uint32_t p, const UpscaleBlend& b) { return raster_texel(p, b.raster_rgba); }
+BRT_DEV uint8_t* select_mask(const UpscaleSelect& us) { return us.mask; }
+BRT_DEV uint32_t select_classes(const UpscaleSelect& us) { return us.classes; }
+
+// the lanes of the wave that are here and have `sel` set append p to the list: one ballot, one atomicAdd of the wave on the count word,
+// plain vector stores
+BRT_DEV void select_append(const UpscaleSelect& us, bool sel, uint32_t p) {
+    const uint64_t m = __ballot(sel);
+    if (m == 0ull) return;
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const uint32_t leader = (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
+    uint32_t base = 0u;
+    if (lane == leader) base = atomicAdd(us.count, (uint32_t)__popcll(m));
+    base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)leader);
+    if (sel) us.list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = p;
+}
+
+// whether the kernel's optional pack holds a T
+template <typename T, typename... Opt> constexpr bool opt_is() { return (std::is_same<T, Opt>::value || ...); }
 
 // Blend: empty, or one UpscaleBlend -- the frame of a level that blends, fp.level 1 or 2: a covered pixel stores the raster texel of its
 // own index (no raster colour: zeros) and returns before the gather, so a wave whose lanes are all covered branches over it; the others
-// are the kernel of the empty pack bit for bit.  The empty pack is the kernel as it always was, name and arguments included.
+// are the kernel of the empty pack bit for bit.  Or one UpscaleSelect (level 3): see select_append and brt_upscale.h; a pixel that is not
+// selected is the kernel of the empty pack bit for bit.  The empty pack is the kernel as it always was, name and arguments included.
 template <bool D16, uint32_t FMT, typename... Blend>
 __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams fp, UpscaleArgs ua,
                                                  typename OutPixel<FMT>::type* __restrict__ out, Blend... blend) {
@@ -101,9 +125,15 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
     float t;
     uint32_t idx;
     raycast<1, false, D16, false>(sc, sv.root_desc, stack, o, d, t, idx, hc);
-    if constexpr (sizeof...(Blend) != 0) {
+    if constexpr (opt_is<UpscaleBlend, Blend...>()) {
         if (blend_covered(fp, t, p, blend...)) {
             out[p] = OutPixel<FMT>::make(blend_texel(p, blend...));
+            return;
+        }
+    }
+    if constexpr (opt_is<UpscaleSelect, Blend...>()) {
+        if (t == kInf && select_mask(blend...)) {      // (the sky is in no class)
+            select_mask(blend...)[p] = 0u;
             return;
         }
     }
@@ -149,6 +179,17 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
             sg = sg + w * cd.y;
             sb = sb + w * cd.z;
         }
+    }
+    if constexpr (opt_is<UpscaleSelect, Blend...>()) {
+        // p's classes: both tests are exact (a material word, and the weight sum of stage A, whose every term is positive)
+        const uint32_t cls = (sw == 0.0f ? BRT_REFINE_EDGES : 0u) | ((m0.w > 0.0f || m1.w > 0.0f) ? BRT_REFINE_SPECULAR : 0u);
+        if (select_mask(blend...)) {
+            select_mask(blend...)[p] = (uint8_t)cls;
+            return;
+        }
+        const bool sel = (cls & select_classes(blend...)) != 0u;
+        select_append(blend..., sel, p);
+        if (sel) return;
     }
     // ---- stage B: no tap of the footprint lies on p's material -- the 4x4 around it, by inverse square distance
     if (sw == 0.0f) {
@@ -216,7 +257,7 @@ hipError_t launch_f(uint32_t out_format, const DeviceSceneView& sv, const FrameP
 
 hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, const FrameParams& low, const DenoiseSettings& st,
                           const DenoiseScratch& ds_low, const float* d_low, void* d_out, uint32_t out_format, hipStream_t stream,
-                          const UpscaleBlend* blend) {
+                          const UpscaleBlend* blend, const UpscaleSelect* select) {
     UpscaleArgs ua;
     ua.low_width = low.width;
     ua.low_height = low.height;
@@ -226,6 +267,8 @@ hipError_t launch_upscale(const DeviceSceneView& sv, const FrameParams& full, co
     ua.low = reinterpret_cast<const float4*>(d_low);
     ua.g0 = ds_low.g0;
     ua.g1 = ds_low.g1;
+    if (blend && select) return hipErrorInvalidValue;
+    if (select) return launch_f(select->mask ? (uint32_t)BRT_FLAG_OUT_RGBA32F : out_format, sv, full, ua, d_out, stream, *select);
     if (blend) return launch_f(out_format, sv, full, ua, d_out, stream, *blend);
     return launch_f(out_format, sv, full, ua, d_out, stream);
 }

@@ -219,6 +219,38 @@ public:
         check(brt_host_blend_covered(&camera, level, t, raster_depth, &c), nullptr);
         return c != 0;
     }
+    // The sparse pixel tracer (include/bevyray_amd.h "sparse pixel tracer"): entry i of the list (p = py * width + px) -> out[i] = the Pure
+    // frame's value at pixel p, bit for bit what run_device stores there.  flags: BRT_FLAG_KERNEL_SIMPLE, BRT_FLAG_CALLER_STREAM (device).
+    void render_pixels(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, const uint32_t* pixels,
+                       uint32_t n_pixels, float* out_rgba, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_pixels(ctx_, &camera, &window, width, height, pixels, n_pixels, out_rgba, flags, stats), ctx_);
+    }
+    void render_pixels_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height,
+                              const uint32_t* d_pixels, uint32_t n_pixels, float* d_out_rgba, void* hip_stream = nullptr, uint32_t flags = 0,
+                              brt_stats* stats = nullptr) {
+        check(brt_render_pixels_device(ctx_, &camera, &window, width, height, d_pixels, n_pixels, d_out_rgba, hip_stream, flags, stats), ctx_);
+    }
+    // Refined upsampling (include/bevyray_amd.h "refined upsampling"): upscale_device / render_upscaled_device with the output pixels of
+    // `classes` (BRT_REFINE_EDGES | BRT_REFINE_SPECULAR) traced at full size.  `window` is the FULL-SIZE window.  d_refined_count: a device
+    // word that receives the number of refined pixels (or nullptr).  upscale_refine_mask_device: the class bits per pixel, nothing traced.
+    void upscale_refine_device(const CameraExtract& camera, const WindowExtract& window, uint32_t low_width, uint32_t low_height,
+                               const float* d_low, uint32_t width, uint32_t height, void* d_out, uint32_t classes,
+                               uint32_t* d_refined_count = nullptr, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_upscale_refine_device(ctx_, &camera, &window, low_width, low_height, d_low, width, height, d_out, classes, d_refined_count,
+                                        hip_stream, flags, stats), ctx_);
+    }
+    void render_upscaled_refined_device(const CameraExtract& camera, const WindowExtract& window, uint32_t low_width, uint32_t low_height,
+                                        uint32_t width, uint32_t height, void* d_destination, uint32_t classes,
+                                        uint32_t* d_refined_count = nullptr, void* hip_stream = nullptr, uint32_t flags = 0,
+                                        brt_stats* stats = nullptr) {
+        check(brt_render_upscaled_refined_device(ctx_, &camera, &window, low_width, low_height, width, height, d_destination, classes,
+                                                 d_refined_count, hip_stream, flags, stats), ctx_);
+    }
+    void upscale_refine_mask_device(const CameraExtract& camera, const WindowExtract& window, uint32_t low_width, uint32_t low_height,
+                                    const float* d_low, uint32_t width, uint32_t height, void* d_mask_u8, void* hip_stream = nullptr,
+                                    uint32_t flags = 0) {
+        check(brt_upscale_refine_mask_device(ctx_, &camera, &window, low_width, low_height, d_low, width, height, d_mask_u8, hip_stream, flags), ctx_);
+    }
     // the window a low_height frame is traced with when it is presented at `height` rows
     static WindowExtract upscale_window(const WindowExtract& window, uint32_t height, uint32_t low_height) {
         WindowExtract w{};

@@ -307,6 +307,8 @@ def tile_rows(height: int, n_parts: int) -> int:
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 QUERY_STATUS_MISS, QUERY_STATUS_HIT, QUERY_STATUS_FRONT_FACE, QUERY_STATUS_INVALID, QUERY_STATUS_OUT_OF_REACH = 0, 1, 2, 4, 8
 QUERY_NONE = 0xFFFFFFFF
+# refined upsampling: brt_upscale_refine* (include/bevyray_amd.h): the classes of output pixels that are traced at full size
+REFINE_EDGES, REFINE_SPECULAR = 1, 2
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direction", np.float32, 3), ("user", np.uint32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("normal", np.float32, 3), ("sphere", np.uint32), ("material", np.uint32),
                       ("status", np.uint32), ("user", np.uint32)])
@@ -711,6 +713,68 @@ class RayTracingNode:
                                                            C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
+
+    # -- sparse pixel tracer and refined upsampling (include/bevyray_amd.h) -------------------------
+
+    def render_pixels(self, camera, window, width: int, height: int, pixels: np.ndarray, flags: int = 0) -> np.ndarray:
+        """brt_render_pixels: the uint32 list `pixels` (p = py * width + px, host memory) -> (n, 4) f32, entry i the value the Pure
+        width x height frame holds at pixels[i] (an entry >= width * height: zeros, counted in last_stats["reserved"]).  flags:
+        FLAG_KERNEL_SIMPLE (the one-thread-per-entry form; same bytes)."""
+        p = self._p
+        pixels = np.ascontiguousarray(pixels, np.uint32)
+        out = np.zeros((pixels.size, 4), np.float32)
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_pixels(p._ctx, camera.ctypes.data, window.ctypes.data, width, height,
+                                            pixels.ctypes.data if pixels.size else None, pixels.size,
+                                            out.ctypes.data if pixels.size else None, flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return out
+
+    def render_pixels_device(self, camera, window, width: int, height: int, d_pixels: int, n_pixels: int, d_out: int,
+                             stream: Optional[int] = None, flags: int = 0) -> dict:
+        """brt_render_pixels_device: n_pixels uint32 entries at d_pixels -> n_pixels RGBA f32 values at d_out (device pointers on the
+        first device).  Stream rule as for render_part_device; the counts of last_stats only on the own stream."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_pixels_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_pixels or None,
+                                                   int(n_pixels), d_out or None, stream or None,
+                                                   (0 if stream is None else FLAG_CALLER_STREAM) | flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def upscale_refine_device(self, camera, window, low_width: int, low_height: int, d_low: int, width: int, height: int, d_out: int,
+                              classes: int = REFINE_EDGES | REFINE_SPECULAR, d_refined_count: int = 0, stream: Optional[int] = None,
+                              out_format: int = FLAG_OUT_RGBA32F) -> dict:
+        """brt_upscale_refine_device: upscale_device with the output pixels of `classes` (REFINE_*) traced at full size.  `window` is the
+        FULL-SIZE window; d_refined_count: a device uint32 that receives the number of refined pixels (0: none)."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_upscale_refine_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, d_low or None,
+                                                    width, height, d_out or None, int(classes), d_refined_count or None, stream or None,
+                                                    (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+        return stats.as_dict()
+
+    def render_upscaled_refined_device(self, camera, window, low_width: int, low_height: int, width: int, height: int, d_frame: int,
+                                       classes: int = REFINE_EDGES | REFINE_SPECULAR, d_refined_count: int = 0,
+                                       stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_upscaled_refined_device: the low trace of render_upscaled_device, then upscale_refine_device.  No post-pass flags."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_upscaled_refined_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, width,
+                                                             height, d_frame or None, int(classes), d_refined_count or None,
+                                                             stream or None,
+                                                             (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                                             C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def upscale_refine_mask_device(self, camera, window, low_width: int, low_height: int, d_low: int, width: int, height: int,
+                                   d_mask: int, stream: Optional[int] = None) -> None:
+        """brt_upscale_refine_mask_device: the REFINE_* class bits of every output pixel into the width x height bytes at d_mask."""
+        p = self._p
+        _lib.check(p._lib.brt_upscale_refine_mask_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height,
+                                                         d_low or None, width, height, d_mask or None, stream or None,
+                                                         0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
 
     # -- ray queries (include/bevyray_amd.h "ray queries") ------------------------------------------
 

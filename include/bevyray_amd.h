@@ -158,7 +158,7 @@ typedef struct brt_stats {
     uint32_t hot_records;      /* a scene walked from an LDS tile + L2 (scene_in_lds == 2): the tree's records are numbered by how often this
                                   view visits them (measured by the pre-pass of a first frame), so that the tile holds the ones the walk
                                   uses; this many of them were visited at all.  0: breadth-first numbering (no pre-pass yet / another mode) */
-    uint32_t reserved;
+    uint32_t reserved;         /* brt_render_pixels*: list entries refused (they name no pixel of the frame); else 0 */
 } brt_stats;
 
 uint32_t brt_abi_version(void);
@@ -530,6 +530,63 @@ int32_t brt_render_upscaled_blend_device(brt_ctx* ctx, const void* camera80, con
                                          const float* d_raster_depth_or_null, void* d_frame, void* hip_stream, uint32_t flags,
                                          brt_stats* stats_or_null);
 int32_t brt_host_blend_covered(const void* camera80, uint32_t level, float t, float raster_depth, uint32_t* out_covered);
+
+/* ---- sparse pixel tracer ----------------------------------------------------------------------------------------------------------------
+ * Traces SOME pixels of a Pure (level 3) frame.  A list entry is p = py * width + px (uint32); for entry i the call computes the value
+ * {rgb, 1} that brt_render_device stores at pixel p for the same camera, window, width, height and resident scene, bit for bit: the seed
+ * of a pixel depends on its frame coordinates alone.  The output is packed: entry i goes to out[i] (RGBA f32).  A pixel may be named any
+ * number of times.  Kernel forms and costs: DESIGN.md "Refined upsampling".
+ *   brt_render_pixels_device  d_pixels / d_out_rgba32f: DEVICE buffers of n_pixels entries on the first device (the whole pass runs there,
+ *                             whatever the number of devices of the context).  flags: BRT_FLAG_CALLER_STREAM, and BRT_FLAG_KERNEL_SIMPLE
+ *                             (the one-thread-per-entry form instead of the persistent one; the bytes are the same); other bits
+ *                             BRT_ERR_INVALID_ARGUMENT.  Stream rule and tree reach as for brt_render_device.  Lists of one context run
+ *                             one behind the other, and behind its ray queries, on whatever streams they come.
+ *   brt_render_pixels         the same for HOST buffers, synchronous.  flags: BRT_FLAG_KERNEL_SIMPLE only.
+ *   stats_or_null             rays, paths (entries traced x sample_count), reserved (= entries refused), total_ms, the tree fields, and the
+ *                             launch (lds_bytes, scene_in_lds, n_workgroups, threads_per_workgroup; kernel_variant 32: the persistent
+ *                             form, 33: the plain form).  rays, paths and reserved only where the call synchronises (the own stream,
+ *                             brt_render_pixels); 0 on a caller's stream.
+ * Refusals: n_pixels = 0 is BRT_OK and writes nothing.  An entry >= width * height is never traced: it stores four zeros and is counted
+ * as refused.  A non-default policy (brt_set_policy): BRT_ERR_UNSUPPORTED, as for the bring-up kernel.  Orthographic projection
+ * BRT_ERR_UNSUPPORTED, BRT_ERR_NO_SCENE before an upload, null pointers and sizes outside [1, 32768] BRT_ERR_INVALID_ARGUMENT.  A refused
+ * call leaves the context usable. */
+int32_t brt_render_pixels_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                 const uint32_t* d_pixels, uint32_t n_pixels, float* d_out_rgba32f, void* hip_stream, uint32_t flags,
+                                 brt_stats* stats_or_null);
+int32_t brt_render_pixels(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const uint32_t* pixels,
+                          uint32_t n_pixels, float* out_rgba32f, uint32_t flags, brt_stats* stats_or_null);
+
+/* ---- refined upsampling ---------------------------------------------------------------------------------------------------------------
+ * The guide-buffer upsampling with the pixels it cannot reconstruct traced at FULL size by the sparse pixel tracer.  An output pixel p
+ * whose own guide is a hit has the classes
+ *   BRT_REFINE_EDGES     no tap of p's 2x2 footprint is eligible (p would be gathered by stage B or C: thin spheres, silhouettes);
+ *   BRT_REFINE_SPECULAR  p's material has metallic > 0 or specular_transmission > 0 (what makes its image lies behind the first hit).
+ * p is SELECTED under `classes` (a mask of these, 1 .. 3) iff it has one of them; sky pixels never are.  A selected pixel holds exactly
+ * the full-size Pure frame's value there (brt_render_device with the full-size window), any other pixel exactly what brt_upscale_device
+ * stores, both in the BRT_FLAG_OUT_* format.  Pure frames only.  Rule, kernels, costs and quality: DESIGN.md "Refined upsampling".
+ * Sizes and BRT_ERR_NO_SCENE as for brt_upscale_device; `classes` 0 or above 3 BRT_ERR_INVALID_ARGUMENT; a non-default policy
+ * (brt_set_policy) BRT_ERR_UNSUPPORTED.  Everything runs on the first device and on the call's stream, one behind another with the context's
+ * denoise / upsampling calls, pixel lists and ray queries.
+ *   brt_upscale_refine_device           brt_upscale_device for a low frame the caller holds.  window16 must be the FULL-SIZE window: its
+ *                                       height sizes the jitter of the refined pixels' samples.  d_refined_count_or_null: a DEVICE word
+ *                                       that receives the number of selected pixels.  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*.
+ *                                       stats_or_null: total_ms and the tree fields.
+ *   brt_render_upscaled_refined_device  the one-call form: the low trace of brt_render_upscaled_device, then the above.  BRT_FLAG_DENOISE /
+ *                                       BRT_FLAG_TEMPORAL are BRT_ERR_INVALID_ARGUMENT here: refined pixels are raw samples and would sit
+ *                                       unfiltered among filtered ones.  stats_or_null as brt_render_upscaled_device.
+ *   brt_upscale_refine_mask_device      the class bits of every output pixel into d_mask_u8 (DEVICE, width x height bytes; 0 for the sky);
+ *                                       traces nothing: what a refinement would cost.  flags: BRT_FLAG_CALLER_STREAM only. */
+#define BRT_REFINE_EDGES 1u
+#define BRT_REFINE_SPECULAR 2u
+int32_t brt_upscale_refine_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
+                                  const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, uint32_t classes,
+                                  uint32_t* d_refined_count_or_null, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_render_upscaled_refined_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width,
+                                           uint32_t low_height, uint32_t width, uint32_t height, void* d_frame, uint32_t classes,
+                                           uint32_t* d_refined_count_or_null, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_upscale_refine_mask_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
+                                       const float* d_low_rgba, uint32_t width, uint32_t height, void* d_mask_u8, void* hip_stream,
+                                       uint32_t flags);
 
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how

@@ -1,0 +1,346 @@
+"""Refined upsampling (brt_upscale_refine_device, brt_render_upscaled_refined_device, brt_upscale_refine_mask_device; DESIGN.md "Refined
+upsampling").  CPU: the restatement (tests/upscale_refine_ref.py) fed with guides from the oracle's raycast -- the classes on the cover
+scene, a diffuse sphere, a sphere thinner than a low pixel -- and the quality bar.  GPU: the mask against the restatement on every pixel,
+the refined frame bitwise (selected pixels: the oracle's full-size frame; the others: brt_upscale_device's), the one-call form against
+its steps, unchanged paths, edge cases, refusals."""
+import functools
+
+import numpy as np
+import pytest
+
+import bevyray_amd as brt
+import denoise_ref as dr
+import upscale_ref as ur
+import upscale_refine_ref as rr
+from helpers import big_scene, big_view, make_buffers, resident_callee_tree, uniforms
+
+F32 = np.float32
+ERR_INVALID, ERR_NO_SCENE, ERR_UNSUPPORTED = -1, -7, -8
+BOTH = brt.REFINE_EDGES | brt.REFINE_SPECULAR
+# Quality: MSE over the selected pixels (both classes) of the refined frame / of the plain upsampled frame, both against a 1024-spp
+# full-size oracle frame of another seed; cover scene, 8 bounces, 96x54 from 48x27, on the oracle.  Measured: 0.0284 at 64 spp (the bar:
+# 1.1 x that), 0.3314 at 4 spp (recorded only).  The ratio crosses 1 between 1 spp (1.039) and 2 spp (0.551).
+BAR_64 = min(1.1 * 0.0284, 0.999)
+MEASURED_4 = 0.3314
+FORMATS = {brt.FLAG_OUT_RGBA32F: None, brt.FLAG_OUT_RGBA8_UNORM_SRGB: "srgb8", brt.FLAG_OUT_RGBA16F: "f16", brt.FLAG_OUT_RGBA8_UNORM: "unorm8"}
+
+
+# ---- CPU --------------------------------------------------------------------------------------------------------------------------
+
+def _classes_cpu(oracle, b, cam, w, h, lw, lh, low=None):
+    g_full, g_low = dr.guides(oracle, b, cam, w, h), dr.guides(oracle, b, cam, lw, lh)
+    if low is None:
+        low = np.ones((lh, lw, 4), F32)
+    up, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    return rr.class_mask(stage, g_full, b.materials), stage, g_full, g_low, up
+
+
+@functools.lru_cache(maxsize=None)
+def _cover_cpu(oracle):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h = 96, 54
+    lvl, cam_r, win_r = brt.cover_camera(w, h, 1024, 8, brt.Raytracing.Pure, 0.25)
+    ref, _ = oracle.render(b, lvl, cam_r, win_r, w, h)
+    return b, ref, dr.guides(oracle, b, cam_r, w, h), dr.guides(oracle, b, cam_r, 48, 27)
+
+
+def test_restatement_classes_on_the_cover_scene(oracle):
+    b, _, g_full, g_low = _cover_cpu(oracle)
+    _, cam, _ = brt.cover_camera(96, 54, 4, 8)
+    _, stage = ur.upscale_frame(oracle, np.ones((27, 48, 4), F32), g_low, g_full, cam)
+    mask = rr.class_mask(stage, g_full, b.materials)
+    edges, spec, sky = (mask & rr.EDGES) != 0, (mask & rr.SPECULAR) != 0, stage == ur.SKY
+    assert edges.any() and spec.any() and sky.any()
+    assert not (edges & sky).any() and not (spec & sky).any() and not mask[sky].any()
+    assert np.array_equal(edges, (stage == ur.STAGE_B) | (stage == ur.STAGE_C))
+    print(f"cover 96x54 from 48x27: edges {int(edges.sum())}, specular {int(spec.sum())}, both {int((edges & spec).sum())}, sky {int(sky.sum())}")
+
+
+def test_restatement_diffuse_sphere_has_no_specular_pixel(oracle):
+    b = make_buffers([((0.0, 0.0, -3.0), 1.0, brt.StandardMaterial(base_color=(0.8, 0.3, 0.2)))])
+    _, cam, _ = uniforms(96, 54, 2, 4, (0.0, 0.0, 0.0), (0.0, 0.0, -3.0), 0.9, 0.5)
+    mask, stage, *_ = _classes_cpu(oracle, b, cam, 96, 54, 48, 27)
+    assert (stage != ur.SKY).any() and not (mask & rr.SPECULAR).any()
+
+
+def test_restatement_thin_sphere_is_all_edges(oracle):
+    # a sphere narrower than a low pixel on the centre ray of full-size pixel (48, 27): the nearest low pixel centres lie 0.7 full pixels
+    # from it (0.038 at distance 3, a full pixel being 0.054 there), its radius is 0.02 -- no low guide hits it
+    _, cam, _ = uniforms(96, 54, 2, 4, (0.0, 0.0, 0.0), (0.0, 0.0, -3.0), 0.9, 0.5)
+    o, dirs, _ = dr.pixel_center_rays(oracle, cam, 96, 54)
+    centre = tuple(float(o[k] + 3.0 * dirs[27, 48, k]) for k in range(3))
+    b = make_buffers([(centre, 0.02, brt.StandardMaterial(base_color=(0.8, 0.3, 0.2)))])
+    mask, stage, g_full, g_low, _ = _classes_cpu(oracle, b, cam, 96, 54, 48, 27)
+    hit = g_full[..., 3] < ur.INF
+    assert hit.any() and not (g_low[..., 3] < ur.INF).any()
+    assert np.array_equal((mask & rr.EDGES) != 0, hit)
+
+
+def test_restatement_quality_bar(oracle):
+    """Cover scene, 8 bounces, 96x54 from 48x27, both classes, on the oracle: over the selected pixels the refined frame has at most
+    BAR_64 x the MSE of the plain upsampled frame at 64 spp, against 1024 spp of another seed.  4 spp is printed (measured 0.3314)."""
+    b, ref, g_full, g_low = _cover_cpu(oracle)
+    w, h, lw, lh = 96, 54, 48, 27
+    ratios = {}
+    for spp in (64, 4):
+        lvl, cam, win = brt.cover_camera(w, h, spp, 8, brt.Raytracing.Pure, 0.5)
+        low, _ = oracle.render(b, lvl, cam, brt.upscale_window(win, h, lh), lw, lh)
+        full, _ = oracle.render(b, lvl, cam, win, w, h)
+        up, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+        mask = rr.class_mask(stage, g_full, b.materials)
+        sel = rr.selected(mask, BOTH)
+        ratios[spp] = rr.selected_mse(rr.refine(up, full, mask, BOTH), ref, sel) / rr.selected_mse(up, ref, sel)
+        print(f"refinement quality at {spp} spp: {ratios[spp]:.4f} over {int(sel.sum())} selected pixels")
+    assert ratios[64] <= BAR_64 and ratios[64] < 1.0, ratios
+
+
+# ---- GPU --------------------------------------------------------------------------------------------------------------------------
+
+def _device(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _out_tensor(w, h, out_format=brt.FLAG_OUT_RGBA32F):
+    import torch
+    return torch.zeros((h, w * brt.OUT_PIXEL_BYTES[out_format] // 4), dtype=torch.int32, device="cuda")
+
+
+def _host(t, h, w):
+    import torch
+    torch.cuda.synchronize()
+    return t.cpu().numpy().view(np.uint8).reshape(h, w, -1)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def _upscale(plugin, cam, win, lw, lh, low, w, h, fmt=brt.FLAG_OUT_RGBA32F):
+    d_low, out = _device(low), _out_tensor(w, h, fmt)
+    plugin.node.upscale_device(cam, win, lw, lh, d_low.data_ptr(), w, h, out.data_ptr(), out_format=fmt)
+    return _host(out, h, w)
+
+
+def _refine(plugin, cam, win, lw, lh, low, w, h, classes, fmt=brt.FLAG_OUT_RGBA32F, stream=None):
+    """(frame bytes (h, w, -1) u8, the device count word)"""
+    import torch
+    d_low, out = _device(low), _out_tensor(w, h, fmt)
+    count = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    plugin.node.upscale_refine_device(cam, win, lw, lh, d_low.data_ptr(), w, h, out.data_ptr(), classes, count.data_ptr(), stream=stream,
+                                      out_format=fmt)
+    return _host(out, h, w), int(count.cpu()[0])
+
+
+def _one_call(plugin, cam, win, lw, lh, w, h, classes, fmt=brt.FLAG_OUT_RGBA32F):
+    import torch
+    out = _out_tensor(w, h, fmt)
+    count = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    plugin.node.render_upscaled_refined_device(cam, win, lw, lh, w, h, out.data_ptr(), classes, count.data_ptr(), out_format=fmt)
+    return _host(out, h, w), int(count.cpu()[0])
+
+
+def _mask(plugin, cam, win, lw, lh, low, w, h):
+    import torch
+    d_low = _device(low)
+    m = torch.full((h, w), 0x55, dtype=torch.uint8, device="cuda")
+    plugin.node.upscale_refine_mask_device(cam, win, lw, lh, d_low.data_ptr(), w, h, m.data_ptr())
+    torch.cuda.synchronize()
+    return m.cpu().numpy()
+
+
+def _encode(oracle, frame, fmt):
+    return frame if FORMATS[fmt] is None else oracle.encode_frame(frame, FORMATS[fmt])
+
+
+SIZES = [(96, 54, 48, 27), (97, 55, 33, 19), (128, 72, 64, 36), (1, 1, 1, 1)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d_from_%dx%d" % s)
+@pytest.mark.parametrize("case", ["cover", "rtiow", "stress"])
+def test_mask_equals_the_restatement(plugin, oracle, case, size):
+    w, h, lw, lh = size
+    kind = {"rtiow": brt.SCENE_RTIOW_FINAL, "stress": brt.SCENE_STRESS_GRID}.get(case, brt.SCENE_COVER)
+    b = brt.generate_scene(kind, 1)
+    lvl, cam, win = (brt.rtiow_camera if case == "rtiow" else brt.cover_camera)(w, h, 2, 4)
+    lwin = brt.upscale_window(win, h, lh)
+    low = plugin.node.run(lvl, cam, lwin, lw, lh, buffers=b).copy()
+    g_low, g_full = plugin.debug_denoise_guides(cam, lwin, lw, lh), plugin.debug_denoise_guides(cam, win, w, h)
+    _, stage = ur.upscale_frame(oracle, low, g_low, g_full, cam)
+    want = rr.class_mask(stage, g_full, b.materials)
+    got = _mask(plugin, cam, win, lw, lh, low, w, h)
+    assert np.array_equal(got, want), (case, size, int((got != want).sum()))
+    for classes in (1, 2, 3):
+        _, count = _refine(plugin, cam, win, lw, lh, low, w, h, classes)
+        assert count == int(rr.selected(want, classes).sum()), (case, size, classes)
+    print(f"{case} {size}: edges {int(((want & 1) != 0).sum())}, specular {int(((want & 2) != 0).sum())} of {w * h}")
+
+
+@pytest.fixture(scope="module")
+def cover(plugin, oracle):
+    """Cover scene, 96x54 from 48x27 at 4 spp, 4 bounces: the oracle's full-size and low frames, shared and never written."""
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    w, h, lw, lh = 96, 54, 48, 27
+    lvl, cam, win = brt.cover_camera(w, h, 4, 4)
+    full, _ = oracle.render(b, lvl, cam, win, w, h)
+    low, _ = oracle.render(b, lvl, cam, brt.upscale_window(win, h, lh), lw, lh)
+    full.setflags(write=False)
+    low.setflags(write=False)
+    return b, lvl, cam, win, full, low
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", list(FORMATS), ids=lambda f: FORMATS[f] or "f32")
+@pytest.mark.parametrize("classes", [1, 2, 3])
+def test_refined_frame(plugin, oracle, cover, fmt, classes):
+    """Every selected pixel: the store of the oracle's FULL-SIZE frame with the full window.  Every other pixel: brt_upscale_device's."""
+    b, lvl, cam, win, full, low = cover
+    w, h, lw, lh = 96, 54, 48, 27
+    plugin.node.write_buffers(b)
+    mask = _mask(plugin, cam, win, lw, lh, low, w, h)
+    up = _upscale(plugin, cam, win, lw, lh, low, w, h, fmt)
+    got, count = _refine(plugin, cam, win, lw, lh, low, w, h, classes, fmt)
+    want_full = np.ascontiguousarray(_encode(oracle, full, fmt)).view(np.uint8).reshape(h, w, -1)
+    sel = rr.selected(mask, classes)
+    assert sel.any() and (~sel).any() and count == int(sel.sum())
+    assert _same_bits(got[sel], want_full[sel])
+    assert _same_bits(got[~sel], up[~sel])
+    assert _same_bits(got, rr.refine(up, want_full, mask, classes))
+    with plugin.tuning(BRT_PIXELS_FORM=1):                                                 # the plain form writes the same frame
+        assert _same_bits(_refine(plugin, cam, win, lw, lh, low, w, h, classes, fmt)[0], got)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fmt", [brt.FLAG_OUT_RGBA32F, brt.FLAG_OUT_RGBA8_UNORM_SRGB], ids=["f32", "srgb8"])
+def test_one_call_equals_its_steps(plugin, cover, fmt):
+    import torch
+    b, lvl, cam, win, full, low = cover
+    w, h, lw, lh = 96, 54, 48, 27
+    plugin.node.write_buffers(b)
+    d_low = torch.empty((lh, lw, 4), dtype=torch.float32, device="cuda")
+    plugin.node.render_device(lvl, cam, brt.upscale_window(win, h, lh), lw, lh, d_low.data_ptr())
+    assert _same_bits(d_low.cpu().numpy(), low)
+    steps, n_steps = _refine(plugin, cam, win, lw, lh, d_low.cpu().numpy(), w, h, BOTH, fmt)
+    one, n_one = _one_call(plugin, cam, win, lw, lh, w, h, BOTH, fmt)
+    assert _same_bits(one, steps) and n_one == n_steps > 0
+    assert plugin.node.last_stats["paths"] == lw * lh * 4 and plugin.node.last_stats["total_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_other_paths_do_not_change(plugin, oracle, cover):
+    import torch
+    b, lvl, cam, win, full, low = cover
+    w, h, lw, lh = 96, 54, 48, 27
+    lvl2, cam2, win2 = brt.cover_camera(w, h, 4, 4, brt.Raytracing.Pure, 0.25)
+    plugin.node.write_buffers(b)
+    frame = torch.empty((h, w, 4), dtype=torch.float32, device="cuda")
+
+    def refined_calls():
+        _one_call(plugin, cam, win, lw, lh, w, h, BOTH)
+        _refine(plugin, cam2, win2, lw, lh, low, w, h, brt.REFINE_EDGES, brt.FLAG_OUT_RGBA16F)
+        _mask(plugin, cam, win, lw, lh, low, w, h)
+
+    def upscaled():
+        out = _out_tensor(w, h)
+        plugin.node.render_upscaled_device(cam, win, lw, lh, w, h, out.data_ptr())
+        return _host(out, h, w), _upscale(plugin, cam, win, lw, lh, low, w, h)
+
+    def temporal_pair(between):
+        plugin.reset_temporal()
+        plugin.node.render_device(lvl, cam, win, w, h, frame.data_ptr(), flags=brt.FLAG_TEMPORAL)
+        between()
+        plugin.node.render_device(lvl2, cam2, win2, w, h, frame.data_ptr(), flags=brt.FLAG_TEMPORAL)
+        return frame.cpu().numpy(), plugin.debug_temporal_state(w, h)
+
+    before = upscaled()
+    refined_calls()
+    after = upscaled()
+    assert _same_bits(before[0], after[0]) and _same_bits(before[1], after[1])
+    f_a, s_a = temporal_pair(lambda: None)
+    f_b, s_b = temporal_pair(refined_calls)
+    assert _same_bits(f_a, f_b) and _same_bits(s_a, s_b) and (s_b[..., 3] == 2).any()
+    plugin.reset_temporal()
+    plugin.node.render_device(lvl, cam, win, w, h, frame.data_ptr())
+    assert _same_bits(frame.cpu().numpy(), full)
+
+
+@pytest.mark.gpu
+def test_edge_cases(plugin, oracle):
+    w, h, lw, lh = 96, 54, 48, 27
+    # an all-sky view: nothing is selected, the frame is the upsampled one
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, win = uniforms(w, h, 2, 4, (0.0, 50.0, 0.0), (0.0, 100.0, 0.0), 0.5, 0.5, up=(0.0, 0.0, 1.0))
+    plugin.node.write_buffers(b)
+    low = plugin.node.run(lvl, cam, brt.upscale_window(win, h, lh), lw, lh).copy()
+    assert not (plugin.debug_denoise_guides(cam, win, w, h)[..., 3] < np.inf).any()
+    got, count = _refine(plugin, cam, win, lw, lh, low, w, h, BOTH)
+    assert count == 0 and _same_bits(got, _upscale(plugin, cam, win, lw, lh, low, w, h))
+    assert not _mask(plugin, cam, win, lw, lh, low, w, h).any()
+    # a view that is entirely one glass sphere: every hit pixel (here: every pixel) is refined
+    g = make_buffers([((0.0, 0.0, -3.0), 2.0, brt.StandardMaterial(specular_transmission=1.0, ior=1.5)),
+                      ((0.0, -102.0, -3.0), 100.0, brt.StandardMaterial(base_color=(0.5, 0.5, 0.5)))])
+    lvl, cam, win = uniforms(w, h, 2, 4, (0.0, 0.0, 0.0), (0.0, 0.0, -3.0), 0.6, 0.5)
+    full, _ = oracle.render(g, lvl, cam, win, w, h)
+    low = plugin.node.run(lvl, cam, brt.upscale_window(win, h, lh), lw, lh, buffers=g).copy()
+    assert (plugin.debug_denoise_guides(cam, win, w, h)[..., 3] < np.inf).all()
+    got, count = _refine(plugin, cam, win, lw, lh, low, w, h, brt.REFINE_SPECULAR)
+    assert count == w * h and _same_bits(got.view(F32), full)
+    # a scene of 32-bit descriptors
+    lvl, cam, win = big_view(w, h)
+    b32, win, st = resident_callee_tree(plugin, big_scene(16383, 7), lvl, cam, win, w, h)
+    full, _ = oracle.render(b32, lvl, cam, win, w, h)
+    low, _ = oracle.render(b32, lvl, cam, brt.upscale_window(win, h, lh), lw, lh)
+    mask = _mask(plugin, cam, win, lw, lh, low, w, h)
+    got, count = _refine(plugin, cam, win, lw, lh, low, w, h, BOTH)
+    sel = rr.selected(mask, BOTH)
+    assert 0 < count == int(sel.sum()) < w * h
+    assert _same_bits(got, rr.refine(_upscale(plugin, cam, win, lw, lh, low, w, h), full.view(np.uint8).reshape(h, w, -1), mask, BOTH))
+
+
+@pytest.mark.gpu
+def test_refusals_leave_the_context_usable(plugin, cover):
+    import torch
+    b, lvl, cam, win, full, low = cover
+    w, h, lw, lh = 96, 54, 48, 27
+    plugin.node.write_buffers(b)
+    lib, ctx = plugin._lib, plugin._ctx
+    d_low, out = _device(low), _out_tensor(w, h)
+    mask = torch.zeros((h, w), dtype=torch.uint8, device="cuda")
+    c, wn = cam.ctypes.data, win.ctypes.data
+
+    def refine(classes=3, flags=0, o=out.data_ptr(), lo=d_low.data_ptr(), cam_p=c, sizes=(lw, lh, w, h)):
+        return lib.brt_upscale_refine_device(ctx, cam_p, wn, sizes[0], sizes[1], lo, sizes[2], sizes[3], o, classes, None, None, flags, None)
+
+    def one(classes=3, flags=0):
+        return lib.brt_render_upscaled_refined_device(ctx, c, wn, lw, lh, w, h, out.data_ptr(), classes, None, None, flags, None)
+
+    for classes in (0, 4, 7, 1 << 31):
+        assert refine(classes) == ERR_INVALID and one(classes) == ERR_INVALID, classes
+    for flags in (brt.FLAG_DENOISE, brt.FLAG_TEMPORAL, brt.FLAG_DENOISE | brt.FLAG_TEMPORAL, brt.FLAG_KERNEL_SIMPLE, brt.FLAG_BLEND_POST):
+        assert one(flags=flags) == ERR_INVALID and refine(flags=flags) == ERR_INVALID, flags
+    assert refine(o=d_low.data_ptr()) == ERR_INVALID                                         # overlapping buffers
+    assert refine(o=None) == ERR_INVALID and refine(lo=None) == ERR_INVALID and refine(cam_p=None) == ERR_INVALID
+    assert refine(sizes=(lw, lh, 4 * lw + 1, h)) == ERR_INVALID and refine(sizes=(0, lh, w, h)) == ERR_INVALID
+    assert lib.brt_upscale_refine_mask_device(ctx, c, wn, lw, lh, d_low.data_ptr(), w, h, None, None, 0) == ERR_INVALID
+    assert lib.brt_upscale_refine_mask_device(ctx, c, wn, lw, lh, d_low.data_ptr(), w, h, mask.data_ptr(), None, brt.FLAG_OUT_RGBA16F) == ERR_INVALID
+    assert lib.brt_upscale_refine_mask_device(ctx, c, wn, lw, lh, d_low.data_ptr(), w, h, d_low.data_ptr(), None, 0) == ERR_INVALID
+    ortho = cam.copy()
+    ortho["projection"] = 1
+    assert refine(cam_p=ortho.ctypes.data) == ERR_UNSUPPORTED
+    plugin.set_policy(brt.POLICY_OR_SHORT_CIRCUIT)
+    try:
+        assert refine() == ERR_UNSUPPORTED and one() == ERR_UNSUPPORTED
+        assert lib.brt_upscale_refine_mask_device(ctx, c, wn, lw, lh, d_low.data_ptr(), w, h, mask.data_ptr(), None, 0) == ERR_UNSUPPORTED
+    finally:
+        plugin.set_policy(0)
+    torch.cuda.synchronize()
+    assert not out.cpu().numpy().any()
+    fresh = brt.RaytracePlugin([0])
+    try:
+        assert fresh._lib.brt_upscale_refine_device(fresh._ctx, c, wn, lw, lh, d_low.data_ptr(), w, h, out.data_ptr(), 3, None, None, 0, None) == ERR_NO_SCENE
+    finally:
+        fresh.close()
+    got, count = _refine(plugin, cam, win, lw, lh, low, w, h, BOTH)                          # the context is usable
+    sel = rr.selected(_mask(plugin, cam, win, lw, lh, low, w, h), BOTH)
+    assert count == int(sel.sum()) and _same_bits(got.view(F32)[sel], full[sel])
