@@ -5,6 +5,32 @@
 
 using namespace brt;
 
+namespace brt {
+
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char* pa = static_cast<const char*>(a);
+    const char* pb = static_cast<const char*>(b);
+    return a && b && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt) {
+    return (size_t)width * height * (fmt == BRT_FLAG_OUT_RGBA32F ? 16u : fmt == BRT_FLAG_OUT_RGBA16F ? 8u : 4u);
+}
+
+// The control words and the list of a width x height refinement or adaptive frame (DeviceCtx::d_pxbuf) for work on `stream`: a larger
+// one is allocated only once the last user of the old one has ended; the control words are zeroed behind that user
+int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream) {
+    const size_t bytes = 32u + (size_t)width * height * 4u;
+    if (dc.pxbuf_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
+    const int32_t rc = ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, bytes);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    HIP_TRY(ctx, hipMemsetAsync(dc.d_pxbuf, 0, 32, stream));
+    return BRT_OK;
+}
+
+}  // namespace brt
+
 namespace {
 
 // full <= kMaxRatio * low per axis.  The kernel is correct at any ratio (its taps are counted in low pixels); the bound is one of quality:
@@ -44,16 +70,6 @@ int32_t level_check(brt_ctx* ctx, Blend* bl) {
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "level must be 1, 2 or 3");
     if (!bl->on()) bl->d_raster_rgba = bl->d_raster_depth = nullptr;
     return BRT_OK;
-}
-
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const char* pa = static_cast<const char*>(a);
-    const char* pb = static_cast<const char*>(b);
-    return a && b && pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
-size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt) {
-    return (size_t)width * height * (fmt == BRT_FLAG_OUT_RGBA32F ? 16u : fmt == BRT_FLAG_OUT_RGBA16F ? 8u : 4u);
 }
 
 // the output of a blended frame is written while other pixels' raster texels and depths are still to be read
@@ -164,18 +180,6 @@ int32_t refine_check(brt_ctx* ctx, const void* camera80, const void* window16, u
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     if (ctx->policy_flags & kPolicyMask)
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the pixel tracer implements the default policy only (brt_set_policy)");
-    return BRT_OK;
-}
-
-// The control words and the list of a width x height refinement (DeviceCtx::d_pxbuf) for work on `stream`: a larger one is allocated only
-// once the last user of the old one has ended; the control words are zeroed behind that user
-int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream) {
-    const size_t bytes = 32u + (size_t)width * height * 4u;
-    if (dc.pxbuf_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    const int32_t rc = ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, bytes);
-    if (rc != BRT_OK) return rc;
-    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    HIP_TRY(ctx, hipMemsetAsync(dc.d_pxbuf, 0, 32, stream));
     return BRT_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "brt_adaptive.h"
 #include "brt_denoise.h"
 #include "brt_temporal.h"
 #include "brt_host.h"
@@ -77,6 +78,10 @@ struct DeviceCtx {
     bool order_on_device = false;                        // d_tile_order / d_order_meta were written by brt_order.hip
     uint64_t view_rays = 0;                              // rays of the last completed frame of the view `view_key` (0: unknown)
     uint32_t view_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // order key + sample_count, bounce_count
+    // the same pair for the base trace of brt_render_adaptive_device: swapped in around that trace, so that the view's plain frames and
+    // its base frames (another sample_count: another key) each find the ray count of their own last frame (brt_api_adaptive.cpp)
+    uint64_t base_view_rays = 0;
+    uint32_t base_view_key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool order_valid = false;
     uint32_t remeasure_in = 0;                    // frames until the costs are measured again (0: nothing pending); set by scene uploads
     uint64_t order_cam = 0;                       // hash of the camera the costs were last measured with
@@ -111,7 +116,8 @@ struct DeviceCtx {
     size_t temporal_cap = 0;
     char* d_tsph = nullptr;         // two slots of float4[n_models] {centre, r^2} in the caller's order, then u32[n_models] resident -> caller
     size_t tsph_cap = 0;
-    // the low frame of brt_render_upscaled_device (RGBA32F), first device only; ordered by ev_dn like the denoiser's scratch
+    // the low frame of brt_render_upscaled_device / the base frame of brt_render_adaptive_device (RGBA32F), first device only; ordered
+    // by ev_dn like the denoiser's scratch
     float* d_uplow = nullptr;
     size_t uplow_cap = 0;
     // ray queries (brt_query.h), first device only.  Queries of the context run one behind the other (every one waits for ev_q and
@@ -126,8 +132,9 @@ struct DeviceCtx {
     size_t qrays_cap = 0;
     char* d_qhits = nullptr;
     size_t qhits_cap = 0;
-    // sparse pixel tracer and refined upsampling (brt_pixels.h), first device only: 8 control words {u64 rays, u64 refused entries, the
-    // streaming form's batch counter, the entries of the list, -, -}, then the list of brt_upscale_refine* (one word per output pixel).
+    // sparse pixel tracer, refined upsampling and adaptive sampling (brt_pixels.h), first device only: 8 control words {u64 rays, u64
+    // refused entries, the streaming form's batch counter, the entries of the list, -, -}, then the list of brt_upscale_refine* /
+    // brt_*adaptive* (one word per output pixel).
     // Its users run one behind the other, ordered by ev_q like the queries (so uploads and renumberings wait for them too)
     uint32_t* d_pxbuf = nullptr;
     size_t pxbuf_cap = 0;
@@ -212,6 +219,11 @@ struct brt_ctx {
     brt::Knobs knobs;           // tuning knobs (brt_set_tuning; environment once at brt_create under BRT_ENABLE_TUNING=1)
     uint32_t policy_flags = 0;  // brt_set_policy
     brt::DenoiseSettings denoise;   // brt_set_denoise
+    struct Adaptive {               // brt_set_adaptive
+        uint32_t base_spp = 8;
+        float threshold = brt::kAdaptDefaultThreshold;
+        uint32_t min_taps = 6;
+    } adaptive;
     struct Temporal {               // BRT_FLAG_TEMPORAL
         uint32_t max_history = 32;  // brt_set_temporal
         bool valid = false;         // the history holds a frame (false: n = 0 everywhere)

@@ -136,6 +136,13 @@ int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const 
                        const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
                        hipStream_t stream, bool force_plain, PixelsLaunch* pl);
 
+// ---- brt_api_upscale.cpp ----
+bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes);
+size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt);
+// The control words and the list of a width x height refinement or adaptive frame (DeviceCtx::d_pxbuf) for work on `stream`: a larger
+// one is allocated only once the last user of the old one has ended; the control words are zeroed behind that user
+int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream);
+
 // ---- brt_api_post.cpp ----
 // the guides' frame parameters (one part, level 3) and the denoiser's scratch of a width x height frame for work on `stream`
 int32_t denoise_begin(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,

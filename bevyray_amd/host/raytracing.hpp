@@ -251,6 +251,22 @@ public:
                                     uint32_t flags = 0) {
         check(brt_upscale_refine_mask_device(ctx_, &camera, &window, low_width, low_height, d_low, width, height, d_mask_u8, hip_stream, flags), ctx_);
     }
+    // Adaptive sampling (include/bevyray_amd.h "adaptive sampling"): a base frame at the context's base_spp (RaytracePlugin::set_adaptive), the
+    // pixels its noise rule selects traced again at the camera's sample_count.  d_selected_count: a device word that receives their number
+    // (or nullptr).  adaptive_refine_device: for a base frame the caller holds; adaptive_mask_device: the class byte per pixel, nothing traced.
+    void render_adaptive_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, void* d_destination,
+                                uint32_t* d_selected_count = nullptr, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_adaptive_device(ctx_, &camera, &window, width, height, d_destination, d_selected_count, hip_stream, flags, stats), ctx_);
+    }
+    void adaptive_refine_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, const float* d_base,
+                                void* d_out, uint32_t* d_selected_count = nullptr, void* hip_stream = nullptr, uint32_t flags = 0,
+                                brt_stats* stats = nullptr) {
+        check(brt_adaptive_refine_device(ctx_, &camera, &window, width, height, d_base, d_out, d_selected_count, hip_stream, flags, stats), ctx_);
+    }
+    void adaptive_mask_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, const float* d_base,
+                              void* d_mask_u8, void* hip_stream = nullptr, uint32_t flags = 0) {
+        check(brt_adaptive_mask_device(ctx_, &camera, &window, width, height, d_base, d_mask_u8, hip_stream, flags), ctx_);
+    }
     // the window a low_height frame is traced with when it is presented at `height` rows
     static WindowExtract upscale_window(const WindowExtract& window, uint32_t height, uint32_t low_height) {
         WindowExtract w{};
@@ -325,6 +341,10 @@ public:
     // the denoiser's settings (brt_set_denoise; the defaults are the library's)
     void set_denoise(uint32_t iterations = 5, float sigma_luminance = 4.0f, float sigma_normal = 128.0f, float sigma_depth = 1.0f) {
         check(brt_set_denoise(ctx_, iterations, sigma_luminance, sigma_normal, sigma_depth), ctx_);
+    }
+    // the settings of adaptive frames (brt_set_adaptive; the defaults are the library's)
+    void set_adaptive(uint32_t base_spp = 8, float threshold = 0.025f, uint32_t min_taps = 6) {
+        check(brt_set_adaptive(ctx_, base_spp, threshold, min_taps), ctx_);
     }
     // the temporal history of BRT_FLAG_TEMPORAL frames (brt_set_temporal: 1..65535, empties it; brt_reset_temporal: on a camera cut)
     void set_temporal(uint32_t max_history = 32) { check(brt_set_temporal(ctx_, max_history), ctx_); }

@@ -291,6 +291,24 @@ def blend_covered(camera, level, t, raster_depth) -> np.ndarray:
     return out
 
 
+# adaptive sampling: brt_*adaptive* (include/bevyray_amd.h): the classes of the pixels that are traced again at the camera's sample count
+ADAPT_SPARSE, ADAPT_NOISY = 1, 2
+ADAPT_DEFAULT_THRESHOLD = 0.025
+
+
+def adaptive_class(t, material_id, rgb, taps_inside, taps_id, taps_rgb, threshold: float = ADAPT_DEFAULT_THRESHOLD, min_taps: int = 6) -> int:
+    """brt_host_adaptive_class: the ADAPT_* class of one pixel (distance t of its centre ray, inf: sky; material id; base colour rgb) from
+    its 25 taps in the rule's order (dy outer, dx inner, -2 .. 2): inside the frame or not, material ids, base colours (25, 3)."""
+    inside = np.ascontiguousarray(taps_inside, np.uint32).reshape(25)
+    ids = np.ascontiguousarray(taps_id, np.uint32).reshape(25)
+    cols = np.ascontiguousarray(taps_rgb, np.float32).reshape(75)
+    own = np.ascontiguousarray(rgb, np.float32).reshape(-1)[:3].copy()
+    c = C.c_uint32(0)
+    _lib.check(_lib.load().brt_host_adaptive_class(float(t), int(material_id), own.ctypes.data, inside.ctypes.data, ids.ctypes.data,
+                                                   cols.ctypes.data, float(threshold), int(min_taps), C.byref(c)))
+    return int(c.value)
+
+
 def upscale_window(window, height: int, low_height: int) -> np.ndarray:
     """brt_host_upscale_window: the window a low_height frame is traced with when it is to be upsampled to `height` rows -- the seed of
     `window`, its height scaled to max(1, window.height * low_height // height).  Host arithmetic."""
@@ -390,6 +408,11 @@ class RaytracePlugin:
         RayTracingNode.denoise_device.  Invalid values raise BrtError and leave the settings as they were."""
         _lib.check(self._lib.brt_set_denoise(self._ctx, int(iterations), float(sigma_luminance), float(sigma_normal),
                                              float(sigma_depth)), self._ctx)
+
+    def set_adaptive(self, base_spp: int = 8, threshold: float = ADAPT_DEFAULT_THRESHOLD, min_taps: int = 6) -> None:
+        """brt_set_adaptive: the settings of RayTracingNode.render_adaptive_device & co. (base_spp 1..65535, threshold finite and > 0,
+        min_taps 1..25).  Invalid values raise BrtError and leave the settings as they were."""
+        _lib.check(self._lib.brt_set_adaptive(self._ctx, int(base_spp), float(threshold), int(min_taps)), self._ctx)
 
     def debug_denoise_guides(self, camera, window, width: int, height: int) -> np.ndarray:
         """brt_debug_denoise_guides: (height, width, 8) f32 -- normal.xyz, t (inf: sky), a.rgb, material id as bits
@@ -775,6 +798,37 @@ class RayTracingNode:
         _lib.check(p._lib.brt_upscale_refine_mask_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height,
                                                          d_low or None, width, height, d_mask or None, stream or None,
                                                          0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+
+    # -- adaptive sampling (include/bevyray_amd.h "adaptive sampling") -------------------------------
+
+    def render_adaptive_device(self, camera, window, width: int, height: int, d_frame: int, d_selected_count: int = 0,
+                               stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_adaptive_device: a base frame at the context's base_spp (RaytracePlugin.set_adaptive), the pixels its rule selects
+        traced again at the camera's sample_count.  d_selected_count: a device uint32 that receives their number (0: none).  No
+        post-pass flags.  last_stats: the base trace's, rays with the re-trace's on the own stream, total_ms of the whole call."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_adaptive_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_frame or None,
+                                                     d_selected_count or None, stream or None,
+                                                     (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def adaptive_refine_device(self, camera, window, width: int, height: int, d_base: int, d_out: int, d_selected_count: int = 0,
+                               stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F) -> dict:
+        """brt_adaptive_refine_device: render_adaptive_device for a base frame (RGBA f32, width x height) the caller holds at d_base."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_adaptive_refine_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_base or None,
+                                                     d_out or None, d_selected_count or None, stream or None,
+                                                     (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+        return stats.as_dict()
+
+    def adaptive_mask_device(self, camera, window, width: int, height: int, d_base: int, d_mask: int, stream: Optional[int] = None) -> None:
+        """brt_adaptive_mask_device: the ADAPT_* class of every pixel into the width x height bytes at d_mask; traces nothing."""
+        p = self._p
+        _lib.check(p._lib.brt_adaptive_mask_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_base or None,
+                                                   d_mask or None, stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
 
     # -- ray queries (include/bevyray_amd.h "ray queries") ------------------------------------------
 

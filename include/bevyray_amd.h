@@ -588,6 +588,52 @@ int32_t brt_upscale_refine_mask_device(brt_ctx* ctx, const void* camera80, const
                                        const float* d_low_rgba, uint32_t width, uint32_t height, void* d_mask_u8, void* hip_stream,
                                        uint32_t flags);
 
+/* ---- adaptive sampling -----------------------------------------------------------------------------------------------------------------
+ * A Pure (level 3) frame whose pixels get the camera's sample_count only where a noise estimate asks for it: a BASE frame B is traced at
+ * base_spp samples per pixel (otherwise the call's camera and window), a rule selects pixels from B and the full-size guides
+ * G0 = {n, t}, G1 = {a, id} of the denoiser, and the sparse pixel tracer traces the selected pixels again with the call's own camera.  A
+ * pixel's samples share one RNG state and the sample count enters only the final division, so a selected pixel holds exactly what
+ * brt_render_device stores there at the camera's sample_count, and any other pixel exactly the base frame's value, both in the
+ * BRT_FLAG_OUT_* format, alpha 1.  The rule, for output pixel p, every operation a separately rounded f32 one:
+ *   l(c) = (0.2126 r + 0.7152 g) + 0.0722 b.  p has no class if it is sky (t = +INF) or l(B_p) is not finite.
+ *   taps q: the 5x5 window around p, dy outer and dx inner, both -2 .. 2, p included; a tap counts iff it is inside the frame,
+ *   id_q == id_p and l(B_q) is finite.  n = the number of taps, S1 = sum l_q and S2 = sum l_q * l_q in f32 in that order.
+ *   BRT_ADAPT_SPARSE  iff n < min_taps (silhouettes, thin spheres: no estimate is possible);
+ *   BRT_ADAPT_NOISY   else iff v > thr * thr, with m = S1 / n, v = max(0, S2 / n - m * m), thr = threshold * max(m, 0.01)
+ *                     (max(a, b) = a > b ? a : b).
+ * A pixel with a class is SELECTED.  Kernel, costs and quality: DESIGN.md "Adaptive sampling".
+ *   brt_set_adaptive            base_spp in [1, 65535] (default 8), threshold finite and > 0 (default 0.025), min_taps in [1, 25] (default
+ *                               6); anything else BRT_ERR_INVALID_ARGUMENT and the settings stay as they were.
+ *   brt_render_adaptive_device  the one-call form, on the call's stream: the base trace by the persistent kernel (every device of the
+ *                               context, as brt_render_device), then on the first device the guides, the selection and the re-trace.
+ *                               d_selected_count_or_null: a DEVICE word that receives the number of selected pixels.  base_spp >=
+ *                               the camera's sample_count: the plain frame is stored, nothing is selected, the count is 0.
+ *                               stats_or_null as brt_render_device for the base trace; where the call synchronises (its own stream)
+ *                               rays is base plus re-trace.
+ *   brt_adaptive_refine_device  the same for a base frame the caller holds (RGBA f32, width x height, on the first device), which d_out
+ *                               must not overlap.  stats_or_null: rays of the re-trace (own stream), total_ms and the tree fields.
+ *   brt_adaptive_mask_device    the class byte of every pixel into d_mask_u8 (DEVICE, width x height bytes); traces nothing: what a frame
+ *                               would cost.  flags: BRT_FLAG_CALLER_STREAM only.
+ *   brt_host_adaptive_class     the rule for ONE pixel on the host, the code the kernel compiles: its t, material id and base colour,
+ *                               and its 25 taps in the rule's order (inside the frame or not, material id, base colour rgb).
+ * flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_*; any other bit is BRT_ERR_INVALID_ARGUMENT -- BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL
+ * included: pixels of two sample counts sit side by side, and the denoiser's strength is set by one.  A non-default policy
+ * (brt_set_policy) and orthographic projection: BRT_ERR_UNSUPPORTED; BRT_ERR_NO_SCENE before an upload; sizes outside [1, 32768] and null
+ * pointers BRT_ERR_INVALID_ARGUMENT.  A refused call leaves the context usable.  Calls of one context run one behind the other with its
+ * denoise / upsampling calls, pixel lists and ray queries, on whatever streams they come. */
+#define BRT_ADAPT_SPARSE 1u
+#define BRT_ADAPT_NOISY 2u
+int32_t brt_set_adaptive(brt_ctx* ctx, uint32_t base_spp, float threshold, uint32_t min_taps);
+int32_t brt_render_adaptive_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* d_frame,
+                                   uint32_t* d_selected_count_or_null, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_adaptive_refine_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                   const float* d_base_rgba, void* d_out, uint32_t* d_selected_count_or_null, void* hip_stream,
+                                   uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_adaptive_mask_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                 const float* d_base_rgba, void* d_mask_u8, void* hip_stream, uint32_t flags);
+int32_t brt_host_adaptive_class(float t, uint32_t material_id, const float* rgb, const uint32_t* taps_inside25, const uint32_t* taps_id25,
+                                const float* taps_rgb75, float threshold, uint32_t min_taps, uint32_t* out_class);
+
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how
  * often the waves executed code section k and the sum of active lanes over those executions
