@@ -17,7 +17,10 @@ namespace brt {
 //          and l(B_q) is finite.  n = their number, S1 = sum l_q, S2 = sum l_q * l_q in f32 in that order
 //   BRT_ADAPT_SPARSE (1)  iff n < min_taps
 //   BRT_ADAPT_NOISY (2)   else iff v > thr * thr with m = S1 / n, v = max(0, S2 / n - m * m), thr = threshold * max(m, 0.01)
-// max(a, b) is a > b ? a : b: a NaN on the left gives b (sums that overflowed select nothing).
+// max(a, b) is a > b ? a : b: a NaN on the left gives b.  Where S2 and m * m both overflow, S2 / n - m * m is INF - INF = NaN, v is 0 and
+// the pixel is not NOISY.  Where S2 alone overflows (luminances of about 3.7e18 to 1.8e19 over a flat 25-tap window: m * m is still
+// finite) v is +INF and the pixel is NOISY at every threshold for which thr * thr stays finite (at +INF, INF > INF is false).
+// tests/test_adaptive_synthetic.py pins all three.
 constexpr uint32_t kAdaptSparse = 1u, kAdaptNoisy = 2u;      // BRT_ADAPT_SPARSE, BRT_ADAPT_NOISY (include/bevyray_amd.h)
 constexpr int kAdaptRadius = 2;
 constexpr float kAdaptMeanFloor = 0.01f;

@@ -573,6 +573,31 @@ int oracle_render(const void* models, uint32_t n_models, const void* materials, 
                                  n_threads);
 }
 
+/* The rays every pixel of a Pure (level 3) frame casts: out_rays[py * width + px].  One thread; the frame itself is not kept. */
+int oracle_pixel_rays(const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
+                      const void* bvh_nodes, uint32_t n_nodes, const void* camera80, const void* window16,
+                      uint32_t width, uint32_t height, uint32_t* out_rays) {
+    if (!camera80 || !window16 || !out_rays) return -1;
+    if (n_nodes == 0 || !bvh_nodes) return -2;
+    Scene s;
+    s.models = (const Model*)models; s.n_models = n_models;
+    s.materials = (const Material*)materials; s.n_materials = n_materials;
+    s.bvh = (const BVHNode*)bvh_nodes; s.n_nodes = n_nodes;
+    memcpy(&s.camera, camera80, 80);
+    memcpy(&s.window, window16, 16);
+    s.level = 3;
+    s.tan_half_fov = oracle_tan_half_fov(s.camera.fov);
+    for (uint32_t py = 0; py < height; py++)
+        for (uint32_t px = 0; px < width; px++) {
+            Counters cnt;
+            float out4[4];
+            memset(&cnt, 0, sizeof cnt);
+            fragment(&s, px, py, width, height, NULL, NULL, out4, &cnt);
+            out_rays[(size_t)py * width + px] = (uint32_t)cnt.rays;
+        }
+    return 0;
+}
+
 /* Small probes so tests can pin individual functions against the numpy mirror. */
 uint32_t oracle_rng_next(uint32_t state) { rngNextInt(&state); return state; }
 float oracle_rng_float(uint32_t* state) { return rngNextFloat(state); }

@@ -26,6 +26,11 @@ int oracle_render_strided(const void* models, uint32_t n_models, const void* mat
                           uint32_t row_step, const float* raster_rgba, const float* raster_depth, float* out_rgba,
                           uint64_t* counters5, int n_threads);
 
+/* The rays every pixel of a Pure (level 3) frame casts, out_rays[py * width + px]: the per-pixel split of counters5[0]. */
+int oracle_pixel_rays(const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
+                      const void* bvh_nodes, uint32_t n_nodes, const void* camera80, const void* window16,
+                      uint32_t width, uint32_t height, uint32_t* out_rays);
+
 /* Alternative readings of three implementation-defined points of the shader (bevyray_oracle.c, "alternative
  * policies"); all 0 = the default policy, which is what the product implements.  Process-wide. */
 void oracle_set_policy(int or_short_circuit, int minmax_select, int pow_exp2_log2);

@@ -54,6 +54,8 @@ class Oracle:
         lib.oracle_render_strided.restype = C.c_int
         lib.oracle_render_strided.argtypes = [VP, U32, VP, U32, VP, U32, VP, VP, U32, U32, U32, U32, U32, U32, VP, VP, VP, VP,
                                               C.c_int]
+        lib.oracle_pixel_rays.restype = C.c_int
+        lib.oracle_pixel_rays.argtypes = [VP, U32, VP, U32, VP, U32, VP, VP, U32, U32, VP]
         lib.oracle_set_policy.restype = None
         lib.oracle_set_policy.argtypes = [C.c_int, C.c_int, C.c_int]
         lib.oracle_tan_half_fov.restype = F
@@ -106,6 +108,16 @@ class Oracle:
             raise RuntimeError(f"oracle_render failed: {rc}")
         names = ["rays", "node_pops", "interior_visits", "sphere_tests", "hits"]
         return out, dict(zip(names, [int(x) for x in cnt]))
+
+    def pixel_rays(self, buffers, camera, window, width, height):
+        """(H, W) u32: the rays every pixel of the Pure frame casts (their sum is render()'s "rays")."""
+        models, materials, bvh = (np.ascontiguousarray(a) for a in (buffers.models, buffers.materials, buffers.bvh))
+        out = np.zeros((height, width), np.uint32)
+        rc = self.lib.oracle_pixel_rays(models.ctypes.data, len(models), materials.ctypes.data, len(materials), bvh.ctypes.data, len(bvh),
+                                        camera.ctypes.data, window.ctypes.data, width, height, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"oracle_pixel_rays failed: {rc}")
+        return out
 
     def encode_frame(self, frame, fmt):
         """The colour target's store conversion of an (H, W, 4) f32 frame: fmt "srgb8" / "unorm8" -> (H, W, 4) u8, "f16" -> (H, W, 4) u16 bits."""

@@ -436,6 +436,47 @@ def test_caller_streams_and_two_calls_in_flight(adaptive, cover, oracle):
 
 
 @pytest.mark.gpu
+def test_larger_frames_behind_a_held_one_grow_the_buffers(adaptive, cover, oracle):
+    """A 32x20 frame is held on stream A of a new context; 64x40 frames follow on stream B and on the context's own stream with no host
+    synchronisation in between.  They need a larger list (d_pxbuf), base frame (d_uplow) and denoise scratch, each of which is
+    reallocated only behind the held frame's last use of it.  All three frames are the expected ones; the held one is read last."""
+    import torch
+    plugin = adaptive
+    b, lvl, cam2, cam8, win, base, full = cover
+    w, h, ws, hs = 64, 40, 32, 20
+    plugin.node.write_buffers(b)
+    mask = _mask(plugin, cam8, win, w, h, base)
+    want = ar.adaptive(base, full, mask)
+    _, cam2s, wins = brt.cover_camera(ws, hs, 2, 4)
+    _, cam8s, _ = brt.cover_camera(ws, hs, 8, 4)
+    base_s, _ = oracle.render(b, lvl, cam2s, wins, ws, hs)
+    full_s, _ = oracle.render(b, lvl, cam8s, wins, ws, hs)
+    mask_s = _mask(plugin, cam8s, wins, ws, hs, base_s)
+    want_s = ar.adaptive(base_s, full_s, mask_s)
+    assert (mask_s != 0).any() and (mask_s == 0).any()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    out_a, out_b, out_c = _out_tensor(ws, hs, fill=0x11111111), _out_tensor(w, h, fill=0x11111111), _out_tensor(w, h, fill=0x11111111)
+    n_a = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    n_b = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+    fresh = brt.RaytracePlugin([0])
+    try:
+        fresh.set_adaptive(2, brt.ADAPT_DEFAULT_THRESHOLD, 6)
+        fresh.node.write_buffers(b)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sa):
+            torch.cuda._sleep(20_000_000)                   # (a few ms: A's kernels start after the later calls have been made)
+        fresh.node.render_adaptive_device(cam8s, wins, ws, hs, out_a.data_ptr(), n_a.data_ptr(), stream=sa.cuda_stream)
+        fresh.node.render_adaptive_device(cam8, win, w, h, out_b.data_ptr(), n_b.data_ptr(), stream=sb.cuda_stream)
+        fresh.node.render_adaptive_device(cam8, win, w, h, out_c.data_ptr())
+        torch.cuda.synchronize()
+        assert _same_bits(_host(out_b, h, w).view(F32), want) and int(n_b.cpu()[0]) == int((mask != 0).sum())
+        assert _same_bits(_host(out_c, h, w).view(F32), want)
+        assert _same_bits(_host(out_a, hs, ws).view(F32), want_s) and int(n_a.cpu()[0]) == int((mask_s != 0).sum())
+    finally:
+        fresh.close()
+
+
+@pytest.mark.gpu
 def test_refusals_leave_the_context_usable(adaptive, cover):
     import torch
     plugin = adaptive

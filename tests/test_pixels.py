@@ -1,6 +1,8 @@
 """The sparse pixel tracer (brt_render_pixels*, DESIGN.md "Refined upsampling").  CPU: the exports and the argument checks.  GPU: every
 entry bitwise the pixel of the oracle's frame -- every pixel of a small frame in a shuffled order on five scenes, both kernel forms and
-both entry points with the form that ran asserted; edge lists; plain against stream; streams; refusals."""
+both entry points with the form that ran asserted; edge lists; plain against stream; streams; refusals.  Lists around the streaming
+launch's lane count, no samples, no bounces, one-row and one-column frames, a window of another height, a camera beyond the callee tree's
+reach; a host-entry list whose staging buffers grow behind a list held on a caller's stream."""
 import os
 import subprocess
 
@@ -9,7 +11,7 @@ import pytest
 
 import bevyray_amd as brt
 from bevyray_amd import _lib
-from helpers import big_scene, big_view, resident_callee_tree
+from helpers import big_scene, big_view, resident_callee_tree, uniforms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("brt_render_pixels_device", "brt_render_pixels", "brt_upscale_refine_device", "brt_render_upscaled_refined_device",
@@ -203,6 +205,168 @@ def test_streams(plugin, cover):
     torch.cuda.synchronize()
     for o, p in zip(outs, lists):
         assert _same_bits(o.cpu().numpy(), want[p])
+
+
+def _both_forms(plugin, oracle, b, lvl, cam, win, w, h, order, tag):
+    """The list `order` of a w x h frame in both forms on the device entry point: entries, rays and paths against the oracle."""
+    want, cnt = oracle.render(b, lvl, cam, win, w, h)
+    rays = oracle.pixel_rays(b, cam, win, w, h).reshape(-1)
+    assert int(rays.sum()) == cnt["rays"]
+    spp = int(cam[0]["sample_count"])
+    for flags, variant in ((0, STREAM_FORM), (brt.FLAG_KERNEL_SIMPLE, PLAIN_FORM)):
+        got = _pixels_dev(plugin, cam, win, w, h, order, flags)
+        st = plugin.node.last_stats
+        assert st["kernel_variant"] == variant and st["reserved"] == 0, (tag, st)
+        assert _same_bits(got, want.reshape(-1, 4)[order]), (tag, flags)
+        assert st["rays"] == int(rays[order].sum(dtype=np.int64)) and st["paths"] == order.size * spp, (tag, flags, st)
+    return want
+
+
+@pytest.mark.gpu
+def test_lists_around_the_launch_lane_count(plugin, oracle):
+    """k_trace_pixels_stream's exit test (`base >= n || n - base <= cnt`) at lists of L - 1, L, L + 1, 2 L and 2 L + 63 entries, L the
+    lanes of the launch, at 1 spp with the longest pixels of the frame in a run at the end, so that the last fetch happens while lanes are
+    busy.  L is read twice: from a list of 1000 entries (the launch is as wide as the list needs: one workgroup) and from one that is
+    longer than the widest launch (every CU's workgroups).  The second L is above 70 000 on an MI355X and no knob plan_stream honours
+    lowers it (BRT_FORCE_GLOBAL_SCENE and BRT_FORCE_LDS_TOP change the workgroup's size and the workgroups per CU, whose product stays
+    1024 lanes per CU), so those lists are that long; at 1 spp each is a few milliseconds."""
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, win = brt.cover_camera(W, H, 1, 4)
+    plugin.node.write_buffers(b)
+    want, cnt = oracle.render(b, lvl, cam, win, W, H)
+    want = want.reshape(-1, 4)
+    rays = oracle.pixel_rays(b, cam, win, W, H).reshape(-1).astype(np.int64)
+    assert int(rays.sum()) == cnt["rays"]
+    longest = np.argsort(rays, kind="stable")[-192:].astype(np.uint32)
+    assert rays[longest].min() > rays.mean()
+    rng = np.random.default_rng(23)
+    lanes = []
+    for probe in (1000, 1 << 20):
+        _pixels_dev(plugin, cam, win, W, H, rng.integers(0, W * H, probe).astype(np.uint32))
+        st = plugin.node.last_stats
+        assert st["kernel_variant"] == STREAM_FORM
+        lanes.append(st["n_workgroups"] * st["threads_per_workgroup"])
+    assert lanes[0] >= 1000 and lanes[1] < (1 << 20), lanes          # (the second launch was capped by the device, not by its list)
+    print(f"lanes of the launch: {lanes[0]} for 1000 entries, {lanes[1]} at most")
+    for L in lanes:
+        for n in (L - 1, L, L + 1, 2 * L, 2 * L + 63):
+            px = np.concatenate([rng.integers(0, W * H, n - longest.size).astype(np.uint32), longest])
+            for flags in (0, brt.FLAG_KERNEL_SIMPLE):
+                got = _pixels_dev(plugin, cam, win, W, H, px, flags)
+                st = plugin.node.last_stats
+                assert _same_bits(got, want[px]), (L, n, flags)
+                assert st["rays"] == int(rays[px].sum()) and st["paths"] == n and st["reserved"] == 0, (L, n, flags, st)
+
+
+@pytest.mark.gpu
+def test_sample_count_zero(plugin):
+    """No sample: every entry is the pixel of brt_render_device's 0-spp frame (0 / 0 in the colour channels, alpha 1), no ray cast; the
+    streaming form's branch of its own, the plain form and the host entry point."""
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, win = brt.cover_camera(W, H, 0, 4)
+    plugin.node.write_buffers(b)
+    frame = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
+    plugin.node.render_device(lvl, cam, win, W, H, frame.data_ptr())
+    want = frame.cpu().numpy().reshape(-1, 4)
+    assert np.isnan(want[:, :3]).all() and (want[:, 3] == 1.0).all()
+    px = np.random.default_rng(29).permutation(W * H).astype(np.uint32)[:3001]
+    for flags, variant in ((0, STREAM_FORM), (brt.FLAG_KERNEL_SIMPLE, PLAIN_FORM)):
+        for got in (_pixels_dev(plugin, cam, win, W, H, px, flags), plugin.node.render_pixels(cam, win, W, H, px, flags)):
+            st = plugin.node.last_stats
+            assert st["kernel_variant"] == variant and st["rays"] == 0 and st["paths"] == 0 and st["reserved"] == 0, st
+            assert _same_bits(got, want[px]), flags
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bounces", [0, 1])
+def test_no_bounce_and_one_bounce_at_one_sample(plugin, oracle, bounces):
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, win = brt.cover_camera(W, H, 1, bounces)
+    plugin.node.write_buffers(b)
+    order = np.random.default_rng(31).permutation(W * H).astype(np.uint32)
+    _both_forms(plugin, oracle, b, lvl, cam, win, W, H, order, bounces)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(1, 37), (37, 1), (97, 3)], ids=lambda s: "%dx%d" % s)
+def test_one_column_one_row_and_thin_frames(plugin, oracle, size):
+    w, h = size
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, win = brt.cover_camera(w, h, 2, 4)
+    plugin.node.write_buffers(b)
+    order = np.random.default_rng(37).permutation(w * h).astype(np.uint32)
+    _both_forms(plugin, oracle, b, lvl, cam, win, w, h, order, size)
+
+
+@pytest.mark.gpu
+def test_window_of_another_height(plugin, oracle):
+    """The jitter of a sample is sized by the window's height, not the frame's (raytrace.wgsl:139-147)."""
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, _ = brt.cover_camera(W, H, 2, 4)
+    win = brt.WindowExtract.extract_component(2 * H, 0.25)
+    plugin.node.write_buffers(b)
+    order = np.random.default_rng(41).permutation(W * H).astype(np.uint32)
+    want = _both_forms(plugin, oracle, b, lvl, cam, win, W, H, order, "window")
+    same_height = oracle.render(b, lvl, cam, brt.WindowExtract.extract_component(H, 0.25), W, H)[0]
+    assert not _same_bits(want, same_height)                    # (the case is real: the window's height changes the frame)
+
+
+@pytest.mark.gpu
+def test_camera_beyond_the_callee_trees_reach(plugin, oracle):
+    """The list is the call that meets the far camera: it rebuilds the callee's tree (with_tree_reach), and its entries are the oracle's
+    in the CPU twin of the tree the context reports; the other form and a plain frame behind it use that tree as it is."""
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    lvl, cam, win = uniforms(W, H, 2, 4, (13.0 * 25, 2.0 * 25, 3.0 * 25), (0.0, 0.0, 0.0), 0.4 / 25, 0.5, far=1.0e5)
+    plugin.node.write_buffers(brt.generate_scene(brt.SCENE_RTIOW_FINAL, 1))      # (another scene first: the upload below is a real one)
+    plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
+    order = np.random.default_rng(43).permutation(W * H).astype(np.uint32)
+    got = _pixels_dev(plugin, cam, win, W, H, order)
+    st = dict(plugin.node.last_stats)
+    assert st["tree_rebuilt"] == 1 and st["tree_reach"] == brt.tree_reach(b.models, cam)[2] > 0, st
+    twin = brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models, st["tree_reach"]))
+    want, cnt = oracle.render(twin, lvl, cam, win, W, H)
+    assert _same_bits(got, want.reshape(-1, 4)[order]) and st["rays"] == cnt["rays"] and st["kernel_variant"] == STREAM_FORM
+    got = _pixels_dev(plugin, cam, win, W, H, order, brt.FLAG_KERNEL_SIMPLE)
+    st2 = plugin.node.last_stats
+    assert st2["tree_rebuilt"] == 0 and st2["tree_reach"] == st["tree_reach"] and st2["rays"] == cnt["rays"], st2
+    assert _same_bits(got, want.reshape(-1, 4)[order])
+    frame = torch.zeros((H, W, 4), dtype=torch.float32, device="cuda")
+    st3 = plugin.node.render_device(lvl, cam, win, W, H, frame.data_ptr())
+    assert st3["tree_rebuilt"] == 0 and st3["tree_reach"] == st["tree_reach"] and st3["rays"] == cnt["rays"], st3
+    assert _same_bits(frame.cpu().numpy(), want)
+
+
+@pytest.mark.gpu
+def test_a_host_list_behind_a_held_one_grows_the_staging_buffers(oracle, cover):
+    """A device-entry list of 700 is held on a caller's stream; the host entry point then stages 5 000 entries, which a new context has
+    no room for: d_pxlist and d_pxout are allocated behind the held list (whose control words the new one shares).  No host
+    synchronisation between the two calls; the held list's output is read last."""
+    import torch
+    b, lvl, cam, win, want = cover
+    want = want.reshape(-1, 4)
+    rng = np.random.default_rng(47)
+    held, later = rng.integers(0, W * H, 700).astype(np.uint32), rng.integers(0, W * H, 5000).astype(np.uint32)
+    d_held = _dev(held)
+    out = torch.full((700, 4), 7.5, dtype=torch.float32, device="cuda")
+    sa = torch.cuda.Stream()
+    fresh = brt.RaytracePlugin([0])
+    try:
+        fresh.node.write_buffers(b)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sa):
+            torch.cuda._sleep(20_000_000)                       # (a few ms: the held list starts after the second call has been made)
+        fresh.node.render_pixels_device(cam, win, W, H, d_held.data_ptr(), 700, out.data_ptr(), stream=sa.cuda_stream)
+        got = fresh.node.render_pixels(cam, win, W, H, later)
+        st = fresh.node.last_stats
+        assert _same_bits(got, want[later]) and st["paths"] == 5000 * 4 and st["reserved"] == 0
+        again = fresh.node.render_pixels(cam, win, W, H, later[:1234], brt.FLAG_KERNEL_SIMPLE)      # (no growth: the buffers are reused)
+        assert _same_bits(again, want[later[:1234]])
+        torch.cuda.synchronize()
+        assert _same_bits(out.cpu().numpy(), want[held])
+    finally:
+        fresh.close()
 
 
 @pytest.mark.gpu

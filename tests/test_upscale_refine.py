@@ -266,6 +266,44 @@ def test_other_paths_do_not_change(plugin, oracle, cover):
 
 
 @pytest.mark.gpu
+def test_larger_frames_behind_a_held_one_grow_the_buffers(plugin, oracle):
+    """A 32x20 refined frame (from 16x10) is held on stream A of a new context; 64x40 ones (from 32x20) follow on stream B and on the
+    context's own stream with no host synchronisation in between: the list (d_pxbuf), the low frame (d_uplow) and the denoise scratch
+    grow behind the held frame.  Expected: the same calls made one at a time on the session's context, whose refined pixels are the
+    oracle's full-size frames; the held frame is read last."""
+    import torch
+    b = brt.generate_scene(brt.SCENE_COVER, 1)
+    plugin.node.write_buffers(b)
+    views = {}
+    for w, h, lw, lh in ((32, 20, 16, 10), (64, 40, 32, 20)):
+        lvl, cam, win = brt.cover_camera(w, h, 4, 4)
+        want, count = _one_call(plugin, cam, win, lw, lh, w, h, BOTH)
+        full, _ = oracle.render(b, lvl, cam, win, w, h)
+        low, _ = oracle.render(b, lvl, cam, brt.upscale_window(win, h, lh), lw, lh)
+        sel = rr.selected(_mask(plugin, cam, win, lw, lh, low, w, h), BOTH)
+        assert 0 < count == int(sel.sum()) < w * h and _same_bits(want.view(F32)[sel], full[sel])
+        views[w] = (cam, win, lw, lh, w, h, want, count)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    outs = {k: torch.full((views[w][5], views[w][4] * 4), 0x11111111, dtype=torch.int32, device="cuda") for k, w in (("a", 32), ("b", 64), ("c", 64))}
+    counts = {k: torch.full((1,), -1, dtype=torch.int32, device="cuda") for k in outs}
+    fresh = brt.RaytracePlugin([0])
+    try:
+        fresh.node.write_buffers(b)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sa):
+            torch.cuda._sleep(20_000_000)                   # (a few ms: A's kernels start after the later calls have been made)
+        for k, w, stream in (("a", 32, sa.cuda_stream), ("b", 64, sb.cuda_stream), ("c", 64, None)):
+            cam, win, lw, lh, w, h = views[w][:6]
+            fresh.node.render_upscaled_refined_device(cam, win, lw, lh, w, h, outs[k].data_ptr(), BOTH, counts[k].data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        for k, w in (("b", 64), ("c", 64), ("a", 32)):
+            h, want, count = views[w][5], views[w][6], views[w][7]
+            assert _same_bits(_host(outs[k], h, w), want) and int(counts[k].cpu()[0]) == count, k
+    finally:
+        fresh.close()
+
+
+@pytest.mark.gpu
 def test_edge_cases(plugin, oracle):
     w, h, lw, lh = 96, 54, 48, 27
     # an all-sky view: nothing is selected, the frame is the upsampled one
