@@ -15,6 +15,13 @@ namespace brt {
 // 1 / 4: on spheres a few low pixels wide w_n = cos^128 alone leaves one tap, and the frame keeps the noise bilinear averaging removes
 constexpr float kUpscaleBilinearFloor = 0x1p-26f;
 constexpr float kUpscaleEdgeFloor = 0.25f;
+// Every weight of a stage is scaled by a power of two that keeps the stage's weight sum below 1 (stage A: at most 1.25 (1 + 4 x 2^-26),
+// stage B: at most 5.7 x 1.25 over its 16 taps, stage C: at most 1 + 4 x 2^-26), so that no sum of w c' over finite taps passes FLT_MAX:
+// a tap of 3e38 on a refracting sphere (a = 1: c' is finite) at a stage A weight of 1.2 no longer stores +Inf.  The scaling is exact:
+// the quotient sum / weight sum keeps its bits wherever no product is denormal.
+constexpr float kUpscaleScaleA = 0.5f;
+constexpr float kUpscaleScaleB = 0.125f;
+constexpr float kUpscaleScaleC = 0.5f;
 
 // The raster inputs of a frame of a level that blends (1 / 2; DESIGN.md "Upsampling blended frames"): RGBA32F colour and reverse-Z f32
 // depth, both full.width x full.height on the device of the launch, either may be nullptr (zeros).

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
             f3 cd;
             float e;
             if (!tap(ua, pp, qy[j] * lw + qx[i], cd, e)) continue;
-            const float w = (bx[i] * by[j] + kUpscaleBilinearFloor) * (e + kUpscaleEdgeFloor);
+            const float w = ((bx[i] * by[j] + kUpscaleBilinearFloor) * (e + kUpscaleEdgeFloor)) * kUpscaleScaleA;
             sw = sw + w;
             sr = sr + w * cd.x;
             sg = sg + w * cd.y;
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
                 float e;
                 if (!tap(ua, pp, (uint32_t)ty * lw + (uint32_t)tx, cd, e)) continue;
                 const float dx = (float)tx - xl, dy = (float)ty - yl;
-                const float w = (e + kUpscaleEdgeFloor) / (1.0f + (dx * dx + dy * dy));
+                const float w = ((e + kUpscaleEdgeFloor) / (1.0f + (dx * dx + dy * dy))) * kUpscaleScaleB;
                 sw = sw + w;
                 sr = sr + w * cd.x;
                 sg = sg + w * cd.y;
@@ -212,7 +212,11 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
         }
     }
     if (sw != 0.0f) {
-        out[p] = OutPixel<FMT>::make(make_float4((sr / sw) * a.x, (sg / sw) * a.y, (sb / sw) * a.z, 1.0f));
+        // the products are f32 values before the store converts them: without the (empty) barrier the RGBA16F instantiations fuse multiply
+        // and conversion into one v_fma_mixlo_f16 -- one rounding where the store of the f32 result has two (they differ on f16 ties)
+        float r = (sr / sw) * a.x, g = (sg / sw) * a.y, b = (sb / sw) * a.z;
+        asm volatile("" : "+v"(r), "+v"(g), "+v"(b));
+        out[p] = OutPixel<FMT>::make(make_float4(r, g, b, 1.0f));
         return;
     }
     // ---- stage C: p's sphere is thinner than a low pixel -- the bilinear colour of the finite taps, not demodulated
@@ -222,7 +226,7 @@ __global__ __launch_bounds__(256) void k_upscale(DeviceSceneView sv, FrameParams
         for (int i = 0; i < 2; i++) {
             const float4 c = ua.low[qy[j] * lw + qx[i]];
             if (!finite3(c.x, c.y, c.z)) continue;
-            const float w = bx[i] * by[j] + kUpscaleBilinearFloor;
+            const float w = (bx[i] * by[j] + kUpscaleBilinearFloor) * kUpscaleScaleC;
             sw = sw + w;
             sr = sr + w * c.x;
             sg = sg + w * c.y;

@@ -296,6 +296,7 @@ def test_kernel_matches_the_restatement(plugin, oracle, case, size):
     assert _same_bits(got[sky], want[sky])
     if w > 1:
         assert sky.any() and (stage == ur.STAGE_A).any()
+        assert (stage == ur.STAGE_B).any()              # (every rendered case has at least 25 stage B pixels and 3 of stage C)
 
 
 @pytest.mark.gpu

@@ -277,7 +277,9 @@ def test_covered_set_texels_and_uncovered_pixels_are_exact(plugin, oracle, case,
 @pytest.mark.parametrize("shape", SHAPES, ids=SHAPE_IDS)
 def test_frame_matches_the_restatement(plugin, oracle, shape):
     """The whole frame against upscale_blend_ref fed with the device's guides at both sizes, to section 14's 1e-4 max(1, |ref|); the
-    sky and the covered pixels (NaN and Inf texels among them) bitwise."""
+    sky and the covered pixels (NaN and Inf texels among them) bitwise.  Stage B occurs among the uncovered pixels at 96x54 (2 pixels)
+    and at 161x91 (5), and is asserted there; 41x23 from 21x12 has no stage B pixel outside the raster's cover, so that case asserts
+    stage A alone (tests/test_upscale_synthetic.py reaches stages B and C and the zero store under the blend)."""
     w, h, lw, lh = shape
     _upload(plugin, "cover_callee")
     _, cam, win = _view(w, h)
@@ -297,6 +299,8 @@ def test_frame_matches_the_restatement(plugin, oracle, shape):
         if w > 1:
             _assert_shares(stage == ubr.COVERED)
             assert (stage == ur.STAGE_A).any()
+            if shape != (41, 23, 21, 12):
+                assert (stage == ur.STAGE_B).any()
 
 
 @pytest.mark.gpu

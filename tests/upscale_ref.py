@@ -10,6 +10,7 @@ F32 = np.float32
 INF = F32(np.inf)
 BILINEAR_FLOOR = F32(2.0 ** -26)     # kUpscaleBilinearFloor
 EDGE_FLOOR = F32(0.25)               # kUpscaleEdgeFloor
+SCALE_A, SCALE_B, SCALE_C = F32(0.5), F32(0.125), F32(0.5)     # kUpscaleScaleA / B / C: exact, they keep every sum of w c' finite
 SKY, STAGE_A, STAGE_B, STAGE_C, STAGE_NONE = 0, 1, 2, 3, 4     # what upscale() reports per output pixel
 
 
@@ -32,14 +33,16 @@ def sky_colour(dirs):
 
 
 def upscale(low, g_low, g_full, dirs_full, tan_half_fov, sigma_n=128.0, sigma_z=1.0, bilinear_floor=BILINEAR_FLOOR,
-            edge_floor=EDGE_FLOOR):
+            edge_floor=EDGE_FLOOR, scales=(SCALE_A, SCALE_B, SCALE_C)):
     """(out (h, w, 4) f32, stage (h, w) u8) of the low frame `low` (lh, lw, 4) with guides g_low (lh, lw, 8), for the output pixels
-    whose guides are g_full (h, w, 8) and whose unit pixel-centre directions are dirs_full (h, w, 3)."""
+    whose guides are g_full (h, w, 8) and whose unit pixel-centre directions are dirs_full (h, w, 3).  scales: the powers of two the
+    weights of stages A, B, C are multiplied by ((1, 1, 1): the rule before the scaling, for the test that the scaling keeps the bits)."""
     low = low.astype(F32)
     lh, lw = low.shape[:2]
     h, w = g_full.shape[:2]
     sigma_n, sigma_z = F32(sigma_n), F32(sigma_z)
     bilinear_floor, edge_floor = F32(bilinear_floor), F32(edge_floor)
+    scale_a, scale_b, scale_c = (F32(s) for s in scales)
     n_p, t_p, a_p = g_full[..., 0:3], g_full[..., 3], g_full[..., 4:7]
     mat_p = np.ascontiguousarray(g_full[..., 7]).view(np.uint32)
     hit_p = t_p < INF
@@ -86,7 +89,7 @@ def upscale(low, g_low, g_full, dirs_full, tan_half_fov, sigma_n=128.0, sigma_z=
                 qy, qx = np.broadcast_to(qys[j][:, None], (h, w)), np.broadcast_to(qxs[i][None, :], (h, w))
                 el, cd, e = tap(qy, qx, ones)
                 b = (bx[i][None, :] * by[j][:, None]).astype(F32)
-                acc = add(acc, el, (b + bilinear_floor) * (e + edge_floor), cd)
+                acc = add(acc, el, ((b + bilinear_floor) * (e + edge_floor)) * scale_a, cd)
                 n_a += el
         in_a = hit_p & (n_a > 0)
         # stage B: the 4x4 taps x0 - 1 .. x0 + 2, y0 - 1 .. y0 + 2 inside the frame
@@ -98,7 +101,7 @@ def upscale(low, g_low, g_full, dirs_full, tan_half_fov, sigma_n=128.0, sigma_z=
                 inside = (qy >= 0) & (qy < lh) & (qx >= 0) & (qx < lw)
                 el, cd, e = tap(qy, qx, inside)
                 dx, dy = (qx.astype(F32) - xl[None, :]).astype(F32), (qy.astype(F32) - yl[:, None]).astype(F32)
-                acc_b = add(acc_b, el, (e + edge_floor) / (F32(1.0) + (dx * dx + dy * dy)), cd)
+                acc_b = add(acc_b, el, ((e + edge_floor) / (F32(1.0) + (dx * dx + dy * dy))) * scale_b, cd)
                 n_b += el
         in_b = hit_p & ~in_a & (n_b > 0)
         # stage C: the bilinear colour of the finite taps of the footprint, not demodulated
@@ -109,7 +112,7 @@ def upscale(low, g_low, g_full, dirs_full, tan_half_fov, sigma_n=128.0, sigma_z=
                 qy, qx = np.broadcast_to(qys[j][:, None], (h, w)), np.broadcast_to(qxs[i][None, :], (h, w))
                 el = fin_l[qy, qx]
                 b = (bx[i][None, :] * by[j][:, None]).astype(F32)
-                acc_c = add(acc_c, el, np.broadcast_to(b + bilinear_floor, (h, w)), c_l[qy, qx])
+                acc_c = add(acc_c, el, np.broadcast_to((b + bilinear_floor) * scale_c, (h, w)), c_l[qy, qx])
                 n_c += el
         in_c = hit_p & ~in_a & ~in_b & (n_c > 0)
         for mask, (sw, sc), remod, code in ((in_a, acc, True, STAGE_A), (in_b, acc_b, True, STAGE_B), (in_c, acc_c, False, STAGE_C)):
