@@ -33,6 +33,10 @@ bool tree_covers(const brt_ctx* ctx, uint32_t level) {
     return level <= ctx->tree_level || tree_pads_equal(ctx->tree_scene, ctx->tree_reach, tree_reach_of(ctx->tree_scene.scale, level));
 }
 
+}  // namespace
+
+namespace brt {
+
 // the largest origin 1-norm the resident tree covers (+INF: any; < 0: none)
 float query_bound_of(const brt_ctx* ctx) {
     const float inf = std::numeric_limits<float>::infinity();
@@ -69,8 +73,17 @@ int32_t ensure_query_reach(brt_ctx* ctx, float origin_bound, uint32_t* rebuilt) 
     return BRT_OK;
 }
 
-// Which form a batch takes and the streaming form's launch shape (plan_stream).  BRT_QUERY_FORM 1 / 2 force the plain / the streaming
-// form; else a batch of at least BRT_QUERY_STREAM_MIN rays streams (0: none does).
+// The form rule of a list of n rays: knob value 1 / 2 force the plain / the streaming form; else a list of at least stream_min rays
+// streams (0: none does)
+bool list_streams(uint32_t form, uint32_t stream_min, uint32_t n) {
+    return !(form == 1u || (form != 2u && (stream_min == 0u || n < stream_min)));
+}
+
+}  // namespace brt
+
+namespace {
+
+// Which form a batch takes (list_streams under BRT_QUERY_FORM and BRT_QUERY_STREAM_MIN) and the streaming form's launch shape (plan_stream)
 void plan_query(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, QueryLaunch* ql) {
     const Knobs& kn = ctx->knobs;
     ql->scene = dc.view;
@@ -79,8 +92,7 @@ void plan_query(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, QueryL
     ql->scene_mode = SCENE_GLOBAL;
     ql->grid = ql->block = 0u;
     ql->lds_bytes = 0;
-    const uint32_t form = kn[K_QUERY_FORM], stream_min = kn[K_QUERY_STREAM_MIN];
-    if (form == 1u || (form != 2u && (stream_min == 0u || n_rays < stream_min))) return;
+    if (!list_streams(kn[K_QUERY_FORM], kn[K_QUERY_STREAM_MIN], n_rays)) return;
     ql->form = QUERY_STREAM;
     // waves per SIMD: the simple-tree instantiation of 16-bit descriptors holds the hand-written loop's 114 VGPRs (4), the others 60-64 (8)
     const StreamPlan sp = plan_stream(ctx, dc, n_rays, 4u, 8u);
@@ -140,10 +152,6 @@ StreamPlan plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items
     return sp;
 }
 
-}  // namespace brt
-
-namespace {
-
 // the resident -> caller sphere map of the first device for work on `stream` (nullptr: the resident order is the upload order)
 int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32_t** rmap) {
     *rmap = nullptr;
@@ -162,6 +170,10 @@ int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32
     *rmap = dc.d_qmap;
     return BRT_OK;
 }
+
+}  // namespace brt
+
+namespace {
 
 // one batch on `stream`, behind the previous query of the context; counted: the counts are gathered (the caller synchronises and reads d_qctl)
 int32_t query_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits,

@@ -1,0 +1,170 @@
+// brt_api_radiance.cpp -- radiance queries (brt_radiance.hip; DESIGN.md "Radiance queries") on the first device: path-traced colour
+// for a list of the caller's rays.  Reach, refusal bound, sphere numbering and staging buffers are the ray queries' (brt_api_query.cpp).
+#include "brt_frame.h"
+
+using namespace brt;
+
+namespace {
+
+// The default rule streams from this many entries on: below one streaming workgroup's lanes a persistent launch has nothing to refill,
+// and every workgroup of it pays for staging the scene
+constexpr uint32_t kRadianceStreamMin = BRT_BLOCK;
+
+// Which form a list takes and the streaming form's launch shape (plan_stream).  BRT_RADIANCE_FORM 1 / 2 force the plain / the streaming
+// form; else a list of at least kRadianceStreamMin entries streams where the scene or the top of its tree is staged in LDS.
+void plan_radiance(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, RadianceLaunch* rl) {
+    const uint32_t form = ctx->knobs[K_RADIANCE_FORM];
+    rl->scene = dc.view;
+    rl->scene.lds_pairs = 0u;
+    rl->form = RADIANCE_PLAIN;
+    rl->scene_mode = SCENE_GLOBAL;
+    rl->grid = rl->block = 0u;
+    rl->lds_bytes = 0;
+    if (!list_streams(form, kRadianceStreamMin, n_rays)) return;
+    // waves per SIMD where nothing is staged: 114 VGPRs with the hand-written loop (4), 89 without (5)
+    const StreamPlan sp = plan_stream(ctx, dc, n_rays, 4u, 5u);
+    if (form != 2u && sp.scene_mode == SCENE_GLOBAL) return;      // (no LDS form: 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE)
+    rl->form = RADIANCE_STREAM;
+    rl->scene = sp.scene;
+    rl->scene_mode = sp.scene_mode;
+    rl->grid = sp.grid;
+    rl->block = sp.block;
+    rl->lds_bytes = sp.lds_bytes;
+}
+
+// the control words of the first device (DeviceCtx::d_radctl), for work behind ev_q
+int32_t radiance_ctl(brt_ctx* ctx, DeviceCtx& dc) {
+    if (dc.d_radctl) return BRT_OK;
+    return ensure(ctx, &dc.d_radctl, &dc.radctl_cap, 64u);
+}
+
+// one list on `stream`, behind the previous list or query of the context; counted: the counts are gathered (the caller synchronises and
+// reads d_radctl)
+int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t samples,
+                         uint32_t bounces, void* d_out, bool counted, RadianceLaunch* rl) {
+    int32_t rc = radiance_ctl(ctx, dc);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    plan_radiance(ctx, dc, n_rays, rl);
+    const uint32_t* rmap = nullptr;
+    rc = query_rmap(ctx, dc, stream, &rmap);
+    if (rc != BRT_OK) return rc;
+    RadianceArgs& ra = rl->args;
+    ra.rays = static_cast<const float4*>(d_rays);
+    ra.out = static_cast<float4*>(d_out);
+    ra.n_rays = n_rays;
+    ra.samples = samples;
+    ra.bounces = bounces;
+    ra.bound = query_bound_of(ctx);
+    ra.rmap = rmap;
+    ra.stat = counted ? reinterpret_cast<unsigned long long*>(dc.d_radctl) : nullptr;
+    ra.counter = dc.d_radctl + 8;
+    rl->stream = stream;
+    if (counted || rl->form == RADIANCE_STREAM) HIP_TRY(ctx, hipMemsetAsync(dc.d_radctl, 0, 64, stream));
+    HIP_TRY(ctx, launch_radiance(*rl));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+    return BRT_OK;
+}
+
+int32_t radiance_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound,
+                       const void* out) {
+    if (samples < 1u || samples > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "samples must be in [1, 65535]");
+    if (bounces > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "bounces must be in [0, 65535]");
+    if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    if (n_rays > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_rays too large");
+    if (n_rays != 0u && (!rays || !out)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "rays / out is null");
+    if (n_rays != 0u && overlaps(rays, (size_t)n_rays * 32u, out, (size_t)n_rays * 32u))
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "rays and out overlap");
+    if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
+    if (ctx->policy_flags & kPolicyMask)
+        return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "radiance queries implement the default policy only (brt_set_policy)");
+    return BRT_OK;
+}
+
+void radiance_stats(const brt_ctx* ctx, const RadianceLaunch& rl, uint32_t rebuilt, const unsigned long long* counts3, uint64_t* out8) {
+    if (!out8) return;
+    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
+    uint32_t reach_bits;
+    std::memcpy(&reach_bits, &reach, 4);
+    out8[0] = counts3 ? counts3[0] : 0u;
+    out8[1] = counts3 ? counts3[1] : 0u;
+    out8[2] = counts3 ? counts3[2] : 0u;
+    out8[3] = rebuilt;
+    out8[4] = reach_bits;
+    out8[5] = (uint64_t)rl.form;
+    out8[6] = rl.form == RADIANCE_STREAM ? rl.grid : (rl.args.n_rays + 255u) / 256u;
+    out8[7] = 0u;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound,
+                                 void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
+    int32_t rc = radiance_check(ctx, d_rays, n_rays, samples, bounces, origin_bound, d_out);
+    if (rc != BRT_OK) return rc;
+    RadianceLaunch rl{};
+    uint32_t rebuilt = 0u;
+    if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
+    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    const StreamChoice sc = stream_of(dc, hip_stream, flags);
+    unsigned long long counts[3] = {0u, 0u, 0u};
+    auto body = [&]() -> int32_t {
+        int32_t r = radiance_enqueue(ctx, dc, sc.stream, d_rays, n_rays, samples, bounces, d_out, sc.own, &rl);
+        if (r != BRT_OK || !sc.own) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_radctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+        return BRT_OK;
+    };
+    rc = body();
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    radiance_stats(ctx, rl, rebuilt, sc.own ? counts : nullptr, out_stats8);
+    return BRT_OK;
+    });
+}
+
+int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound, void* out,
+                          uint64_t* out_stats8) {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    int32_t rc = radiance_check(ctx, rays, n_rays, samples, bounces, origin_bound, out);
+    if (rc != BRT_OK) return rc;
+    RadianceLaunch rl{};
+    uint32_t rebuilt = 0u;
+    if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
+    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    unsigned long long counts[3] = {0u, 0u, 0u};
+    auto body = [&]() -> int32_t {
+        const size_t bytes = (size_t)n_rays * 32u;
+        if (dc.qrays_cap < bytes || dc.qhits_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));   // (the staging buffers grow only when no list uses them)
+        int32_t r = ensure(ctx, &dc.d_qrays, &dc.qrays_cap, bytes);
+        if (r == BRT_OK) r = ensure(ctx, &dc.d_qhits, &dc.qhits_cap, bytes);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_qrays, rays, bytes, hipMemcpyHostToDevice, dc.stream));
+        r = radiance_enqueue(ctx, dc, dc.stream, dc.d_qrays, n_rays, samples, bounces, dc.d_qhits, true, &rl);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_qhits, bytes, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_radctl, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
+        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
+        return BRT_OK;
+    };
+    rc = body();
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    radiance_stats(ctx, rl, rebuilt, counts, out_stats8);
+    return BRT_OK;
+    });
+}
+
+}  // extern "C"

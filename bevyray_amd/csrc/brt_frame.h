@@ -121,6 +121,14 @@ struct StreamPlan {
     size_t lds_bytes;            // trace_lds_bytes(scene, scene_mode, block, 0)
 };
 StreamPlan plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, uint32_t waves_by_hand, uint32_t waves_other);
+// What lists of caller rays share (ray queries, radiance queries): the largest origin 1-norm the resident tree covers (+INF: any; < 0:
+// none); origin_bound > 0: a callee-built tree's reach raised, if needed, to what origins of that 1-norm need; the form rule of a list
+// of n rays (knob value 1 / 2: plain / streaming, else streaming from stream_min rays on, 0: never); the resident -> caller sphere map
+// of the first device for work on `stream` (nullptr: the identity)
+float query_bound_of(const brt_ctx* ctx);
+int32_t ensure_query_reach(brt_ctx* ctx, float origin_bound, uint32_t* rebuilt);
+bool list_streams(uint32_t form, uint32_t stream_min, uint32_t n);
+int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32_t** rmap);
 
 // ---- brt_api_pixels.cpp ----
 // What a list of pixels is traced into (brt_pixels.h PixelsArgs): packed RGBA32F, or scattered into a frame in a BRT_FLAG_OUT_* format

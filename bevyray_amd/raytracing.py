@@ -331,6 +331,12 @@ RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("t_max", np.float32), ("direct
 HIT_DTYPE = np.dtype([("t", np.float32), ("normal", np.float32, 3), ("sphere", np.uint32), ("material", np.uint32),
                       ("status", np.uint32), ("user", np.uint32)])
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32
+# radiance queries: brt_radiance_rays* (include/bevyray_amd.h): the query ray with `seed` where t_max is, the query hit with the colour
+# where the normal is
+RADIANCE_RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("seed", np.uint32), ("direction", np.float32, 3), ("user", np.uint32)])
+RADIANCE_DTYPE = np.dtype([("t", np.float32), ("rgb", np.float32, 3), ("sphere", np.uint32), ("material", np.uint32),
+                           ("status", np.uint32), ("user", np.uint32)])
+assert RADIANCE_RAY_DTYPE.itemsize == 32 and RADIANCE_DTYPE.itemsize == 32
 
 
 def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.ndarray:
@@ -578,6 +584,7 @@ class RayTracingNode:
         self._p = plugin
         self.last_stats: Optional[dict] = None
         self.last_query_stats: Optional[dict] = None
+        self.last_radiance_stats: Optional[dict] = None
 
     def write_buffers(self, buffers: Buffers) -> None:
         """pipeline.rs:136-138"""
@@ -868,6 +875,37 @@ class RayTracingNode:
         b = C.c_float(0.0)
         _lib.check(p._lib.brt_query_origin_bound(p._ctx, C.byref(b)), p._ctx)
         return float(b.value)
+
+    # -- radiance queries (include/bevyray_amd.h "radiance queries") --------------------------------
+
+    @staticmethod
+    def _radiance_stats(words) -> dict:
+        return {"walks": int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
+                "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
+                "form": int(words[5]), "n_workgroups": int(words[6])}
+
+    def radiance_rays(self, rays, samples: int, bounces: int, origin_bound: float = 0.0, device: bool = False,
+                      stream: Optional[int] = None):
+        """brt_radiance_rays*: path-traced colour for a list of rays -- per entry, seed -> rng_state, `samples` paths of at most
+        `bounces` bounces on (origin, direction), averaged.  device=False: `rays` is an array of RADIANCE_RAY_DTYPE records in host
+        memory -> RADIANCE_DTYPE records (synchronous).  device=True: `rays` is (d_rays, n_rays, d_out), device pointers on the first
+        device -> the call's stats; stream rule as for query_rays_device (on a caller's stream the three counts are 0).
+        origin_bound > 0 first raises the tree's reach for origins of that 1-norm.  last_radiance_stats holds the call's stats."""
+        p = self._p
+        words = (C.c_uint64 * 8)()
+        if device:
+            d_rays, n_rays, d_out = rays
+            _lib.check(p._lib.brt_radiance_rays_device(p._ctx, d_rays or None, int(n_rays), int(samples), int(bounces), float(origin_bound),
+                                                       d_out or None, stream or None, 0 if stream is None else FLAG_CALLER_STREAM, words),
+                       p._ctx)
+            self.last_radiance_stats = self._radiance_stats(words)
+            return self.last_radiance_stats
+        rays = np.ascontiguousarray(rays, RADIANCE_RAY_DTYPE)
+        out = np.empty(rays.shape, RADIANCE_DTYPE)
+        _lib.check(p._lib.brt_radiance_rays(p._ctx, rays.ctypes.data if rays.size else None, rays.size, int(samples), int(bounces),
+                                            float(origin_bound), out.ctypes.data if rays.size else None, words), p._ctx)
+        self.last_radiance_stats = self._radiance_stats(words)
+        return out
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

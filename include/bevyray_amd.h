@@ -467,6 +467,51 @@ int32_t brt_query_origin_bound(brt_ctx* ctx, float* out_bound);
 int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py,
                            void* out_ray32);
 
+/* ---- radiance queries ----------------------------------------------------------------------------------------------------------------
+ * Path-traced colour for batches of the caller's rays (reflection rays from a G-buffer, light probes, cube maps, fisheye or orthographic
+ * views, a host integrator): what a ray SEES, where a ray query answers what it hits.  On the context's first device.  Rule, kernels and
+ * costs: DESIGN.md "Radiance queries".  Deterministic; the default policy only (brt_set_policy: else BRT_ERR_UNSUPPORTED).
+ *   ray, 32 bytes    { origin.xyz, seed, direction.xyz, user }: f32 x 3, u32, f32 x 3, u32 -- the query ray with `seed` where t_max is.
+ *                    The direction is used as given, as in ray queries; raytrace normalises where the shader does.
+ *   result, 32 bytes { t, r, g, b, sphere, material, status, user }: f32 x 4 and u32 x 4 -- the query hit with the colour where the
+ *                    normal is.
+ *   the rule         state = seed; sum = 0; `samples` times: sum += raytrace(Ray(origin, direction), &state).color; rgb = sum /
+ *                    f32(samples).  raytrace is raytrace.wgsl:174-224 at level 3 with camera.bounce_count = `bounces`; state is
+ *                    random.wgsl's rng_state, set to `seed` and threaded through the samples: trace_multisampled (:159-172) with the
+ *                    caller's ray in place of random_ray_from_uv.  No jitter: a caller that wants anti-aliasing varies the ray.  Every
+ *                    operation is a separately rounded f32 operation.  t, sphere, material, status and user are exactly what
+ *                    brt_query_rays reports in BRT_QUERY_CLOSEST mode for { origin, +INF, direction, user }, BRT_QUERY_STATUS_FRONT_FACE
+ *                    and the sphere numbering included; a miss has t = +INF and sphere = material = BRT_QUERY_NONE (and the sky's
+ *                    colour).
+ *   refusals         those of ray queries without the t_max clause: a non-finite component of origin or direction:
+ *                    BRT_QUERY_STATUS_INVALID; (|o.x| + |o.y|) + |o.z| (f32) above the resident tree's bound
+ *                    (brt_query_origin_bound): BRT_QUERY_STATUS_OUT_OF_REACH.  A refused ray is not walked and reads as a miss with
+ *                    rgb = 0.
+ *   samples, bounces samples in [1, 65535], bounces in [0, 65535]; else BRT_ERR_INVALID_ARGUMENT.
+ *   origin_bound     as for brt_query_rays: 0 uses the tree as it stands; > 0 may first raise a callee-built tree's reach to what
+ *                    origins of that 1-norm need, and never lowers it; NaN or < 0: BRT_ERR_INVALID_ARGUMENT.  A path's later bounces
+ *                    start inside the scene, exactly as a frame's do, so the reach rule that covers a camera at that origin covers the
+ *                    query.  The same side effect on later frames applies (they are traced on that tree until the next upload).
+ *   brt_radiance_rays_device   d_rays / d_out: DEVICE buffers of n_rays records on the first device; overlapping ones are
+ *                    BRT_ERR_INVALID_ARGUMENT.  flags: BRT_FLAG_CALLER_STREAM only.  Stream rule as for brt_query_rays_device: on the
+ *                    context's own stream the call returns when the results are there; on a caller's stream it only enqueues.  Radiance
+ *                    lists of one context run one behind the other, and behind its ray queries, pixel lists and post-pass calls, on
+ *                    whatever streams they come; uploads and tree rebuilds wait for them.  A radiance call changes no frame and no frame
+ *                    changes a radiance result.
+ *   brt_radiance_rays   the same for HOST buffers, synchronous.
+ *   out_stats8_or_null   [0] walks performed (an entry's own ray is walked once, whatever `samples` is), [1] entries whose own ray hit,
+ *                    [2] entries refused (these three are counted only by calls that synchronise: the own stream and
+ *                    brt_radiance_rays; 0 on a caller's stream), [3] the tree was rebuilt, [4] its reach (f32 bits in the low word;
+ *                    brt_stats::tree_reach), [5] the kernel form taken (0 plain, 1 streaming), [6] workgroups (both diagnostic), [7]
+ *                    reserved.
+ * n_rays = 0 is BRT_OK and launches nothing.  BRT_ERR_NO_SCENE before an upload; null pointers BRT_ERR_INVALID_ARGUMENT.  A refused call
+ * leaves the context usable.  Which kernel form a call takes is a launch decision (tuning knob BRT_RADIANCE_FORM: 0 the default rule, 1
+ * plain, 2 streaming); the bytes written do not depend on it. */
+int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound,
+                                 void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8_or_null);
+int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound, void* out,
+                          uint64_t* out_stats8_or_null);
+
 /* ---- guide-buffer upsampling ----------------------------------------------------------------------------------------------------------
  * A frame traced at low_width x low_height is presented at width x height: every OUTPUT pixel casts its own pixel-centre ray (the guide
  * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
