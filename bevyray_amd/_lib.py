@@ -100,6 +100,12 @@ _PROTOTYPES = {
     "brt_query_origin_bound": (_I32, [_VP, C.POINTER(_F)]),
     "brt_radiance_rays_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
     "brt_radiance_rays": (_I32, [_VP, _VP, _U32, _U32, _U32, _F, _VP, C.POINTER(C.c_uint64)]),
+    "brt_host_probe_directions": (_I32, [_U32, C.POINTER(_F)]),
+    "brt_host_probe_irradiance": (_I32, [_VP, C.POINTER(_F), C.POINTER(_F)]),
+    "brt_probe_rays_device": (_I32, [_VP, _VP, _U32, _U32, _VP, _VP, _U32]),
+    "brt_probe_project_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _VP, _VP, _U32]),
+    "brt_bake_probes_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
+    "brt_bake_probes": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _F, _VP, C.POINTER(C.c_uint64)]),
     "brt_host_pixel_ray": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP]),
     "brt_upscale_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),

@@ -1,5 +1,5 @@
 // brt_api.cpp -- the extern "C" boundary (include/bevyray_amd.h): context lifecycle, knobs, scene upload, tree builds.  Its other
-// units: brt_api_launch.cpp, brt_api_order.cpp, brt_api_render.cpp, brt_api_post.cpp, brt_api_upscale.cpp, brt_api_query.cpp; brt_frame.h is what they share.
+// units: brt_api_launch.cpp, brt_api_order.cpp, brt_api_render.cpp, brt_api_post.cpp, brt_api_upscale.cpp, brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp; brt_frame.h is what they share.
 //
 // What each export replaces in the reference is cited in the header.  This file holds no ray
 // arithmetic: rays are traced only by the HIP kernels (brt_kernels.hip).  Without a usable
@@ -22,7 +22,7 @@ void free_device(DeviceCtx& dc) {
     for (void* p : std::initializer_list<void*>{dc.d_scene, dc.d_ctrl, dc.d_strip_table, dc.d_tile, dc.d_gather, dc.d_pack, dc.d_raster_rgba,
              dc.d_raster_depth, dc.d_bvh_scratch, dc.d_tile_cost, dc.d_tile_order, dc.d_order_meta, dc.d_order_scratch, dc.d_slice_state,
              dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_uplow, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits,
-             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl})
+             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.d_probe_dirs, dc.d_probe_io})
         if (p) (void)hipFree(p);
     if (dc.h_stage) (void)hipHostFree(dc.h_stage);
     for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack, dc.ev_strip, dc.ev_strip_read, dc.ev_q, dc.ev_dn,
@@ -366,7 +366,7 @@ int32_t brt_set_tuning(brt_ctx* ctx, const char* name, uint32_t value) {
     for (int k = 0; k < K_COUNT; k++)
         if (std::strcmp(name, kKnobs[k].name) == 0) {
             ctx->knobs.v[k] = value;
-            if (k == K_QUERY_FORM || k == K_QUERY_STREAM_MIN || k == K_PIXELS_FORM || k == K_RADIANCE_FORM) return BRT_OK;   // (ray and radiance queries and pixel lists only: no frame's order depends on them)
+            if (k == K_QUERY_FORM || k == K_QUERY_STREAM_MIN || k == K_PIXELS_FORM || k == K_RADIANCE_FORM || k == K_PROBE_CHUNK_RAYS) return BRT_OK;   // (ray and radiance queries, pixel lists and probe bakes only: no frame's order depends on them)
             // a knob may change how the dispatch order is built or used: forget the history of every view (the next frame of
             // a view is a "first frame" again: pre-pass, measuring frame)
             for (auto& dc : ctx->devs) { dc.order_valid = false; dc.view_rays = 0; }

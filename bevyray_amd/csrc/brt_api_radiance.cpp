@@ -38,9 +38,11 @@ int32_t radiance_ctl(brt_ctx* ctx, DeviceCtx& dc) {
     return ensure(ctx, &dc.d_radctl, &dc.radctl_cap, 64u);
 }
 
+}  // namespace
+
 // one list on `stream`, behind the previous list or query of the context; counted: the counts are gathered (the caller synchronises and
-// reads d_radctl)
-int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t samples,
+// reads d_radctl).  Shared with the probe bake (brt_api_probe.cpp).
+int32_t brt::radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t samples,
                          uint32_t bounces, void* d_out, bool counted, RadianceLaunch* rl) {
     int32_t rc = radiance_ctl(ctx, dc);
     if (rc != BRT_OK) return rc;
@@ -65,6 +67,8 @@ int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const 
     HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
     return BRT_OK;
 }
+
+namespace {
 
 int32_t radiance_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound,
                        const void* out) {

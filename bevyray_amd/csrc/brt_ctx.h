@@ -1,5 +1,5 @@
 // brt_ctx.h -- the opaque context of the C ABI (include/bevyray_amd.h) and the helpers its translation units share:
-// brt_api*.cpp (upload, launch, order, render, post-passes, upsampling, queries, radiance queries; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
+// brt_api*.cpp (upload, launch, order, render, post-passes, upsampling, queries, radiance queries, light probes; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
 // gather, external-memory frames).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -149,6 +149,15 @@ struct DeviceCtx {
     // d_qrays / d_qhits, which therefore have one user at a time
     uint32_t* d_radctl = nullptr;
     size_t radctl_cap = 0;
+    // light probes (brt_probe.h), first device only: the direction table {x, y, z, 0} of probe_dirs_n directions (0: none) and the host
+    // copy its upload reads; the probes and records of brt_bake_probes.  A bake stages its lists in d_qrays / d_qhits and is ordered by
+    // ev_q like the radiance lists it launches; the table is rewritten only once every list of the context has ended
+    float* d_probe_dirs = nullptr;
+    size_t probe_dirs_cap = 0;
+    uint32_t probe_dirs_n = 0;
+    std::vector<float> h_probe_dirs;
+    char* d_probe_io = nullptr;
+    size_t probe_io_cap = 0;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;
@@ -165,7 +174,7 @@ struct DeviceCtx {
 enum Knob : int {
     K_BOTTOM_UP, K_REFILL_MIN, K_WALK_EXIT, K_LEAF_VOTE, K_DRAIN_DONATE, K_POOL_ADOPT, K_WGQ_BATCH, K_LPT_LANE_PERMILLE, K_TUNABLE,
     K_FORCE_GLOBAL_SCENE, K_FORCE_LDS_TOP, K_BLOCK_THREADS, K_WG_PER_CU, K_POOL_CAP, K_LPT, K_LPT_SORT, K_LPT_SKY_SLACK, K_CRIT,
-    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_PIXELS_FORM, K_RADIANCE_FORM, K_COUNT
+    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_PIXELS_FORM, K_RADIANCE_FORM, K_PROBE_CHUNK_RAYS, K_COUNT
 };
 struct KnobDef { const char* name; uint32_t dflt; };
 constexpr KnobDef kKnobs[K_COUNT] = {
@@ -180,7 +189,9 @@ constexpr KnobDef kKnobs[K_COUNT] = {
     // sparse pixel tracer: the form of a call (0: streaming unless BRT_FLAG_KERNEL_SIMPLE, 1 plain, 2 streaming)
     {"BRT_PIXELS_FORM", 0},
     // radiance queries: the form of a call (0: streaming from kRadianceStreamMin entries on where the scene has an LDS form, 1 plain, 2 streaming)
-    {"BRT_RADIANCE_FORM", 0}};
+    {"BRT_RADIANCE_FORM", 0},
+    // light probes: the entries of one chunk of a bake (whole probes, at least one; 64 bytes of staging per entry)
+    {"BRT_PROBE_CHUNK_RAYS", 1u << 21}};
 struct Knobs {
     uint32_t v[K_COUNT];
     Knobs() { for (int i = 0; i < K_COUNT; i++) v[i] = kKnobs[i].dflt; }

@@ -130,6 +130,12 @@ int32_t ensure_query_reach(brt_ctx* ctx, float origin_bound, uint32_t* rebuilt);
 bool list_streams(uint32_t form, uint32_t stream_min, uint32_t n);
 int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32_t** rmap);
 
+// ---- brt_api_radiance.cpp ----
+// One radiance list (brt_radiance.h) on `stream` of the first device, behind the previous list or query of the context (ev_q, which it
+// records); the form is plan_radiance's, reported in *rl.  counted: the three counts are gathered in dc.d_radctl.
+int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t samples,
+                         uint32_t bounces, void* d_out, bool counted, RadianceLaunch* rl);
+
 // ---- brt_api_pixels.cpp ----
 // What a list of pixels is traced into (brt_pixels.h PixelsArgs): packed RGBA32F, or scattered into a frame in a BRT_FLAG_OUT_* format
 struct PixelsTarget {

@@ -337,6 +337,30 @@ RADIANCE_RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("seed", np.uint32), (
 RADIANCE_DTYPE = np.dtype([("t", np.float32), ("rgb", np.float32, 3), ("sphere", np.uint32), ("material", np.uint32),
                            ("status", np.uint32), ("user", np.uint32)])
 assert RADIANCE_RAY_DTYPE.itemsize == 32 and RADIANCE_DTYPE.itemsize == 32
+# light probes: brt_bake_probes* (include/bevyray_amd.h): a position with the seed of its first entry; the record of one probe
+PROBE_SH9, PROBE_AMBIENT_CUBE = 0, 1
+PROBE_DTYPE = np.dtype([("position", np.float32, 3), ("seed", np.uint32)])
+PROBE_RECORD_DTYPE = np.dtype([("coeff", np.float32, 27), ("hits", np.uint32), ("status", np.uint32), ("n_dirs", np.uint32),
+                               ("basis", np.uint32), ("reserved", np.uint32)])
+assert PROBE_DTYPE.itemsize == 16 and PROBE_RECORD_DTYPE.itemsize == 128
+
+
+def probe_directions(n_dirs: int) -> np.ndarray:
+    """brt_host_probe_directions: the (n_dirs, 3) f32 direction table of a probe.  Host arithmetic."""
+    n = int(n_dirs)
+    out = np.zeros((n if 0 < n <= 65536 else 0, 3), np.float32)       # (a count out of range is refused before anything is written)
+    _lib.check(_lib.load().brt_host_probe_directions(n, out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def probe_irradiance(record, normal) -> np.ndarray:
+    """brt_host_probe_irradiance: one PROBE_RECORD_DTYPE record evaluated for a unit normal -> rgb (f32 x 3).  Host arithmetic."""
+    rec = np.ascontiguousarray(record, PROBE_RECORD_DTYPE).reshape(1)
+    n = np.ascontiguousarray(normal, np.float32).reshape(3)
+    out = np.zeros(3, np.float32)
+    _lib.check(_lib.load().brt_host_probe_irradiance(rec.ctypes.data, n.ctypes.data_as(C.POINTER(C.c_float)),
+                                                     out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
 
 
 def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.ndarray:
@@ -585,6 +609,7 @@ class RayTracingNode:
         self.last_stats: Optional[dict] = None
         self.last_query_stats: Optional[dict] = None
         self.last_radiance_stats: Optional[dict] = None
+        self.last_probe_stats: Optional[dict] = None
 
     def write_buffers(self, buffers: Buffers) -> None:
         """pipeline.rs:136-138"""
@@ -906,6 +931,50 @@ class RayTracingNode:
                                             float(origin_bound), out.ctypes.data if rays.size else None, words), p._ctx)
         self.last_radiance_stats = self._radiance_stats(words)
         return out
+
+    # -- light probes (include/bevyray_amd.h "light probes") ----------------------------------------
+
+    @staticmethod
+    def _probe_stats(words) -> dict:
+        return {"walks": int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
+                "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
+                "form": int(words[5]), "chunks": int(words[6])}
+
+    def bake_probes(self, probes, n_dirs: int, bounces: int, basis: int = PROBE_SH9, origin_bound: float = 0.0, device: bool = False,
+                    stream: Optional[int] = None):
+        """brt_bake_probes*: irradiance records for a list of probes -- per probe n_dirs radiance entries of one sample and at most
+        `bounces` bounces, made linear and projected onto `basis` (PROBE_SH9 / PROBE_AMBIENT_CUBE).  device=False: `probes` is an array
+        of PROBE_DTYPE records in host memory -> PROBE_RECORD_DTYPE records (synchronous).  device=True: `probes` is (d_probes,
+        n_probes, d_out), device pointers on the first device -> the call's stats; stream rule as for radiance_rays.
+        last_probe_stats holds the call's stats."""
+        p = self._p
+        words = (C.c_uint64 * 8)()
+        if device:
+            d_probes, n_probes, d_out = probes
+            _lib.check(p._lib.brt_bake_probes_device(p._ctx, d_probes or None, int(n_probes), int(n_dirs), int(bounces), int(basis),
+                                                     float(origin_bound), d_out or None, stream or None,
+                                                     0 if stream is None else FLAG_CALLER_STREAM, words), p._ctx)
+            self.last_probe_stats = self._probe_stats(words)
+            return self.last_probe_stats
+        probes = np.ascontiguousarray(probes, PROBE_DTYPE)
+        out = np.empty(probes.shape, PROBE_RECORD_DTYPE)
+        _lib.check(p._lib.brt_bake_probes(p._ctx, probes.ctypes.data if probes.size else None, probes.size, int(n_dirs), int(bounces),
+                                          int(basis), float(origin_bound), out.ctypes.data if probes.size else None, words), p._ctx)
+        self.last_probe_stats = self._probe_stats(words)
+        return out
+
+    def probe_rays_device(self, d_probes: int, n_probes: int, n_dirs: int, d_rays: int, stream: Optional[int] = None):
+        """brt_probe_rays_device: the generation step alone -> n_probes * n_dirs RADIANCE_RAY_DTYPE entries at d_rays, probe-major."""
+        p = self._p
+        _lib.check(p._lib.brt_probe_rays_device(p._ctx, d_probes or None, int(n_probes), int(n_dirs), d_rays or None, stream or None,
+                                                0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+
+    def probe_project_device(self, d_results: int, n_probes: int, n_dirs: int, basis: int, d_out: int, stream: Optional[int] = None):
+        """brt_probe_project_device: the projection step alone, n_probes * n_dirs RADIANCE_DTYPE results (probe-major) ->
+        n_probes PROBE_RECORD_DTYPE records at d_out."""
+        p = self._p
+        _lib.check(p._lib.brt_probe_project_device(p._ctx, d_results or None, int(n_probes), int(n_dirs), int(basis), d_out or None,
+                                                   stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

@@ -512,6 +512,64 @@ int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_ra
 int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound, void* out,
                           uint64_t* out_stats8_or_null);
 
+/* ---- light probes ---------------------------------------------------------------------------------------------------------------------
+ * Irradiance records for a list of positions (the ambient terms of a level-1 / level-2 host: L2 spherical harmonics, or the six colours
+ * of an ambient cube): per probe a fixed direction set is traced as radiance entries, the colours are made linear and projected, all on
+ * the context's first device.  Rule, kernels and costs: DESIGN.md "Light probes".  Deterministic; the default policy only.
+ *   probe, 16 bytes   { position.xyz, seed }: f32 x 3, u32.
+ *   directions        n_dirs = N in [1, 65536]; for k = 0 .. N-1, in float64: y = 1 - (2k+1)/N, r = sqrt(max(0, 1 - y*y)),
+ *                     phi = 2 pi frac(k (sqrt(5)-1)/2), d_k = (f32(r cos phi), f32(y), f32(r sin phi)): a Fibonacci sphere stratified
+ *                     along the up axis, equal weights.  brt_host_probe_directions is the only place that computes it.
+ *   rays              entry k of a probe is the radiance entry { position, seed + k * 0x9E3779B9 (mod 2^32), d_k, user = k }, traced
+ *                     with samples = 1 and the call's `bounces` under the rule of "radiance queries".  More paths: more directions, or
+ *                     the average of bakes with other seeds (the records are linear).
+ *   linear radiance   L_k = rgb_k * rgb_k per channel (the shader returns sqrt(colour) per sample).
+ *   projection        f32, every operation separately rounded; lane l of 64 sums k = l, l + 64, ... in order from +0.0, then for off =
+ *                     32, 16, 8, 4, 2, 1: acc[l] = acc[l] + acc[l + off]; lane 0 holds the sums.
+ *                     BRT_PROBE_SH9: c[j][ch] = (12.566371f / f32(N)) * sum_k Y_j(d_k) * L_k[ch] with Y0 = 0.282095, Y1..3 = 0.488603 *
+ *                     (y, z, x), Y4 = 1.092548 x y, Y5 = 1.092548 y z, Y6 = 0.315392 (3 z z - 1), Y7 = 1.092548 x z, Y8 = 0.546274 (x x -
+ *                     y y).  BRT_PROBE_AMBIENT_CUBE: faces +X, -X, +Y, -Y, +Z, -Z; per face m = max(+-component, 0), m2 = m * m,
+ *                     value = (sum m2 * L) / (sum m2), 0 where the denominator is 0.
+ *   record, 128 bytes { f32 coeff[27], u32 hits, status, n_dirs, basis, reserved = 0 }.  SH9: coeff[3 j + ch]; cube: coeff[3 face + ch],
+ *                     words 18..26 are 0.  hits: the probe's entries whose own ray hit.  status: entry 0's BRT_QUERY_STATUS_INVALID /
+ *                     BRT_QUERY_STATUS_OUT_OF_REACH bits (a probe with a non-finite component; a probe beyond the tree's bound,
+ *                     brt_query_origin_bound); a refused probe has all coefficients 0 and hits 0.
+ *   list layout       the step exports read and write lists of n_probes * n_dirs radiance entries / results in PROBE-MAJOR order: entry
+ *                     k of probe p is record p * n_dirs + k.
+ *   brt_host_probe_directions   host arithmetic, no context: out_xyz[3 k ..] = d_k.  n_dirs 0 or above 65536: BRT_ERR_INVALID_ARGUMENT.
+ *   brt_host_probe_irradiance   host arithmetic, no context: out_rgb3 = the record evaluated for the unit normal normal3.  SH9: E(n) =
+ *                     sum_j A_l c_j Y_j(n) with A = pi, 2 pi / 3, pi / 4 for bands 0, 1, 2 (the irradiance); cube: the n^2-weighted sum of
+ *                     the three faces n points into.  A record of another basis: BRT_ERR_INVALID_ARGUMENT.
+ *   brt_probe_rays_device       the generation kernel alone: n_probes probes at d_probes -> n_probes * n_dirs radiance entries at d_rays
+ *                     (DEVICE buffers; NaN and INF components are copied through).
+ *   brt_probe_project_device    the projection kernel alone, on any list of radiance results in that layout -> n_probes records at d_out
+ *                     (DEVICE buffers).  Needs no scene.
+ *   brt_bake_probes_device      everything in one call on DEVICE buffers: in chunks of whole probes, generate -> the radiance kernels ->
+ *                     project.  A chunk is max(1, BRT_PROBE_CHUNK_RAYS / n_dirs) probes (tuning knob, default 2^21 entries: 128 MiB of
+ *                     staging in the context); the records do not depend on it, nor on BRT_RADIANCE_FORM.  origin_bound: as for
+ *                     brt_radiance_rays.
+ *   brt_bake_probes             the same for HOST buffers, synchronous.
+ *   out_stats8_or_null   [0..2] walks performed, entries whose own ray hit, entries refused, summed over the chunks (counted only by calls
+ *                     that synchronise: the own stream and brt_bake_probes; 0 on a caller's stream), [3] the tree was rebuilt, [4] its
+ *                     reach (f32 bits in the low word), [5] the radiance form of the last chunk (0 plain, 1 streaming), [6] chunks, [7] 0.
+ * flags: BRT_FLAG_CALLER_STREAM only; stream rule as for brt_radiance_rays_device, and the calls run one behind the other with the
+ * context's radiance lists, ray queries and pixel lists on whatever streams they come.  Overlapping buffers, null pointers, bounces above
+ * 65535, a basis other than the two, n_dirs outside [1, 65536] and, for the step exports, n_probes * n_dirs above 0x7fff0000:
+ * BRT_ERR_INVALID_ARGUMENT.  The bakes: BRT_ERR_NO_SCENE before an upload, BRT_ERR_UNSUPPORTED under a set policy.  n_probes = 0 is BRT_OK
+ * and launches nothing.  A refused call leaves the context usable; a bake changes no frame. */
+#define BRT_PROBE_SH9 0u
+#define BRT_PROBE_AMBIENT_CUBE 1u
+int32_t brt_host_probe_directions(uint32_t n_dirs, float* out_xyz);
+int32_t brt_host_probe_irradiance(const void* record128, const float* normal3, float* out_rgb3);
+int32_t brt_probe_rays_device(brt_ctx* ctx, const void* d_probes, uint32_t n_probes, uint32_t n_dirs, void* d_rays, void* hip_stream,
+                              uint32_t flags);
+int32_t brt_probe_project_device(brt_ctx* ctx, const void* d_results, uint32_t n_probes, uint32_t n_dirs, uint32_t basis, void* d_out,
+                                 void* hip_stream, uint32_t flags);
+int32_t brt_bake_probes_device(brt_ctx* ctx, const void* d_probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
+                               float origin_bound, void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8_or_null);
+int32_t brt_bake_probes(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
+                        float origin_bound, void* out, uint64_t* out_stats8_or_null);
+
 /* ---- guide-buffer upsampling ----------------------------------------------------------------------------------------------------------
  * A frame traced at low_width x low_height is presented at width x height: every OUTPUT pixel casts its own pixel-centre ray (the guide
  * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
