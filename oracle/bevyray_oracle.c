@@ -598,6 +598,84 @@ int oracle_pixel_rays(const void* models, uint32_t n_models, const void* materia
     return 0;
 }
 
+/* ---- radiance queries (checker side of brt_radiance_rays*) ----------------------------------------------------------
+ * The 32-byte wire records of a radiance entry and of its result (include/bevyray_amd.h brt_radiance_ray / brt_radiance_result). */
+typedef struct { float ox, oy, oz; uint32_t seed; float dx, dy, dz; uint32_t user; } RadianceRay;
+typedef struct { float t, r, g, b; uint32_t sphere, material, status, user; } RadianceResult;
+_Static_assert(sizeof(RadianceRay) == 32, "radiance ray stride");
+_Static_assert(sizeof(RadianceResult) == 32, "radiance result stride");
+#define RADIANCE_NONE 0xffffffffu
+#define RADIANCE_HIT 1u
+#define RADIANCE_FRONT_FACE 2u
+
+/* Per entry: one raycast of (origin, direction) for the first-hit fields (a miss: t = +inf, material NONE, status 0; a hit: the
+ * distance, the material, HIT | FRONT_FACE; sphere is always NONE -- the tree says nothing about the caller's index); then
+ * state = seed and `samples` calls of raytrace at level 3 with camera.bounce_count = bounces on that ray, summed in f32 and divided
+ * by (float)samples.  counters5 (optional) accumulates the counters of the paths alone: counters5[0] counts `samples` raycasts of
+ * the entry's own ray, not the one for the first-hit fields.  Entries must be valid (finite, within the tree's reach). */
+int oracle_radiance(const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
+                    const void* bvh_nodes, uint32_t n_nodes, const void* rays, uint64_t n_rays,
+                    uint32_t samples, uint32_t bounces, void* out, uint64_t* counters5) {
+    if ((!rays || !out) && n_rays) return -1;
+    if (n_nodes == 0 || !bvh_nodes) return -2;
+    Scene s; memset(&s, 0, sizeof s);
+    s.models = (const Model*)models; s.n_models = n_models;
+    s.materials = (const Material*)materials; s.n_materials = n_materials;
+    s.bvh = (const BVHNode*)bvh_nodes; s.n_nodes = n_nodes;
+    s.camera.sample_count = samples; s.camera.bounce_count = bounces;
+    s.level = 3;
+    const RadianceRay* in = (const RadianceRay*)rays;
+    RadianceResult* res = (RadianceResult*)out;
+    Counters cnt; memset(&cnt, 0, sizeof cnt);
+    for (uint64_t i = 0; i < n_rays; i++) {
+        Ray ray;
+        ray.origin = V(in[i].ox, in[i].oy, in[i].oz);
+        ray.direction = V(in[i].dx, in[i].dy, in[i].dz);
+        Counters first_cnt; memset(&first_cnt, 0, sizeof first_cnt);
+        HitInfo first = raycast(&s, ray, &first_cnt);
+        RadianceResult r;
+        r.sphere = RADIANCE_NONE;
+        r.user = in[i].user;
+        if (first.distance == INF) {
+            r.t = INFINITY; r.material = RADIANCE_NONE; r.status = 0u;
+        } else {
+            r.t = first.distance; r.material = first.material;
+            r.status = RADIANCE_HIT | (first.front_face ? RADIANCE_FRONT_FACE : 0u);
+        }
+        uint32_t state = in[i].seed;
+        vec3 total = V(0.0f, 0.0f, 0.0f);
+        for (uint32_t k = 0; k < samples; k++) total = vadd(total, raytrace(&s, ray, &state, &cnt).color);
+        float n = (float)samples;
+        r.r = total.x / n; r.g = total.y / n; r.b = total.z / n;
+        res[i] = r;
+    }
+    if (counters5) {
+        counters5[0] += cnt.rays; counters5[1] += cnt.node_pops; counters5[2] += cnt.interior;
+        counters5[3] += cnt.sphere_tests; counters5[4] += cnt.hits;
+    }
+    return 0;
+}
+
+/* The ray of the first sample of pixel (px, py) of a W x H frame -- the pixel's seed (oracle_seed), then random_ray_from_uv -- and
+ * the rng state after the two jitter draws: a Pure frame of one sample is the radiance of that ray from that state, one sample. */
+int oracle_first_sample_ray(const void* camera80, const void* window16, uint32_t W, uint32_t H, uint32_t px, uint32_t py,
+                            uint32_t* state_out, float* o3, float* d3) {
+    if (!camera80 || !window16 || !state_out || !o3 || !d3 || W == 0 || H == 0) return -1;
+    Scene s; memset(&s, 0, sizeof s);
+    memcpy(&s.camera, camera80, 80);
+    memcpy(&s.window, window16, 16);
+    s.level = 3;
+    s.tan_half_fov = oracle_tan_half_fov(s.camera.fov);
+    float uvx = ((float)px + 0.5f) / (float)W;
+    float uvy = ((float)py + 0.5f) / (float)H;
+    uint32_t state = oracle_seed(s.window.random_seed, px, py, W, H);
+    Ray r = random_ray_from_uv(&s, uvx, uvy, &state);
+    *state_out = state;
+    o3[0] = r.origin.x; o3[1] = r.origin.y; o3[2] = r.origin.z;
+    d3[0] = r.direction.x; d3[1] = r.direction.y; d3[2] = r.direction.z;
+    return 0;
+}
+
 /* Small probes so tests can pin individual functions against the numpy mirror. */
 uint32_t oracle_rng_next(uint32_t state) { rngNextInt(&state); return state; }
 float oracle_rng_float(uint32_t* state) { return rngNextFloat(state); }

@@ -31,6 +31,19 @@ int oracle_pixel_rays(const void* models, uint32_t n_models, const void* materia
                       const void* bvh_nodes, uint32_t n_nodes, const void* camera80, const void* window16,
                       uint32_t width, uint32_t height, uint32_t* out_rays);
 
+/* Radiance queries, checker side: n_rays 32-byte entries {origin, seed, direction, user} -> 32-byte results {t, rgb, sphere,
+ * material, status, user} (include/bevyray_amd.h brt_radiance_ray / brt_radiance_result).  Per entry one raycast for the first-hit
+ * fields (sphere is always 0xFFFFFFFF), then state = seed and `samples` paths of at most `bounces` bounces at level 3, summed in
+ * f32 and divided by (float)samples.  counters5 (optional) ACCUMULATES the paths' counters; [0] counts `samples` raycasts of the
+ * entry's own ray and not the one for the first-hit fields.  Valid entries only.  One thread.  Returns 0 on success. */
+int oracle_radiance(const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
+                    const void* bvh_nodes, uint32_t n_nodes, const void* rays, uint64_t n_rays,
+                    uint32_t samples, uint32_t bounces, void* out, uint64_t* counters5);
+
+/* The first sample's ray of pixel (px, py) of a W x H frame and the rng state after its two jitter draws. */
+int oracle_first_sample_ray(const void* camera80, const void* window16, uint32_t W, uint32_t H, uint32_t px, uint32_t py,
+                            uint32_t* state_out, float* o3, float* d3);
+
 /* Alternative readings of three implementation-defined points of the shader (bevyray_oracle.c, "alternative
  * policies"); all 0 = the default policy, which is what the product implements.  Process-wide. */
 void oracle_set_policy(int or_short_circuit, int minmax_select, int pow_exp2_log2);

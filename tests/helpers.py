@@ -1,6 +1,7 @@
 """Shared test helpers: hand-made BVHs (single leaf, median split, caterpillar chain, a composer that grafts one onto another),
 a seeded scene large enough for 32-bit tree descriptors with its camera, the upload of a scene whose tree the callee builds,
-uniform builders and a numpy-f32 restatement of the camera/sky arithmetic for analytic checks."""
+uniform builders, the generator of randomized scenes (materials, sizes, cameras, topologies) and a numpy-f32 restatement of the
+camera/sky arithmetic for analytic checks."""
 import os
 
 import numpy as np
@@ -180,6 +181,33 @@ def uniforms(w, h, spp, bounces, pos, target, fov, seed, level=brt.Raytracing.Pu
     proj = brt.PerspectiveProjection(fov=fov, aspect_ratio=w / h, near=near, far=far)
     lvl, cex = brt.CameraExtract.extract_component(cam, brt.Transform(pos, target, up), proj)
     return lvl, cex, brt.WindowExtract.extract_component(h if window_height is None else window_height, seed)
+
+
+def _random_case(rng):
+    n = int(rng.integers(1, 60))
+    data = []
+    for _ in range(n):
+        kind = rng.random()
+        mat = brt.StandardMaterial(base_color=tuple(float(x) for x in rng.random(3)),
+                                   metallic=float(rng.choice([0.0, 1.0, rng.random()])),
+                                   perceptual_roughness=float(rng.choice([0.0, 0.5, rng.random()])),
+                                   ior=float(rng.uniform(0.5, 2.5)),
+                                   specular_transmission=float(rng.choice([0.0, 1.0, rng.random()])))
+        r = float(rng.uniform(0.05, 1.5)) if kind < 0.9 else float(rng.uniform(20, 200))
+        pos = tuple(float(x) for x in rng.uniform(-4, 4, 3)) if kind < 0.9 else (float(rng.uniform(-3, 3)), -r - 1.0, float(rng.uniform(-3, 3)))
+        data.append((pos, r, mat))
+    topo = rng.integers(0, 4)
+    bvh_fn = [None, single_leaf_bvh, lambda m: median_split_bvh(m, int(rng.integers(1, 5))), chain_bvh][topo]
+    if bvh_fn is chain_bvh and n < 2:
+        bvh_fn = single_leaf_bvh
+    b = make_buffers(data, bvh_fn)
+    w, h = int(rng.integers(1, 70)), int(rng.integers(1, 50))
+    pos = tuple(float(x) for x in rng.uniform(-8, 8, 3))
+    lvl, cam, win = uniforms(w, h, spp=int(rng.integers(1, 6)), bounces=int(rng.integers(0, 12)), pos=pos,
+                             target=tuple(float(x) for x in rng.uniform(-1, 1, 3)), fov=float(rng.uniform(0.2, 1.5)),
+                             seed=float(np.float32(rng.random())), level=brt.Raytracing(int(rng.integers(1, 4))),
+                             window_height=int(rng.integers(1, 1200)))
+    return b, lvl, cam, win, w, h
 
 
 def fixture_buffers():

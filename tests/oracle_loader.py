@@ -81,6 +81,42 @@ class Oracle:
         lib.oracle_raycast.restype = C.c_int
         lib.oracle_raycast.argtypes = [VP, U32, VP, U32, C.POINTER(F), C.POINTER(F), C.POINTER(F), C.POINTER(U32),
                                        C.POINTER(C.c_int)]
+        lib.oracle_radiance.restype = C.c_int
+        lib.oracle_radiance.argtypes = [VP, U32, VP, U32, VP, U32, VP, C.c_uint64, U32, U32, VP, VP]
+        lib.oracle_first_sample_ray.restype = C.c_int
+        lib.oracle_first_sample_ray.argtypes = [VP, VP, U32, U32, U32, U32, C.POINTER(U32), C.POINTER(F), C.POINTER(F)]
+
+    def radiance(self, buffers, rays, samples, bounces):
+        """A list of valid 32-byte radiance entries -> (32-byte result records in the dtype of bevyray_amd.RADIANCE_DTYPE, sphere
+        always QUERY_NONE; counters dict of the paths alone: "rays" counts `samples` raycasts of each entry's own ray)."""
+        import bevyray_amd as brt
+        models, materials, bvh = (np.ascontiguousarray(a) for a in (buffers.models, buffers.materials, buffers.bvh))
+        if (models.dtype.itemsize, materials.dtype.itemsize, bvh.dtype.itemsize) != (32, 32, 48):
+            raise ValueError("oracle.radiance: buffers are not in the wire layout")
+        rays = np.ascontiguousarray(rays, brt.RADIANCE_RAY_DTYPE).reshape(-1)
+        out = np.zeros(len(rays), brt.RADIANCE_DTYPE)
+        cnt = (C.c_uint64 * 5)()
+        rc = self.lib.oracle_radiance(models.ctypes.data, len(models), materials.ctypes.data, len(materials), bvh.ctypes.data, len(bvh),
+                                      rays.ctypes.data, len(rays), int(samples), int(bounces), out.ctypes.data, cnt)
+        if rc != 0:
+            raise RuntimeError(f"oracle_radiance failed: {rc}")
+        names = ["rays", "node_pops", "interior_visits", "sphere_tests", "hits"]
+        return out, dict(zip(names, [int(x) for x in cnt]))
+
+    def first_sample_rays(self, camera, window, width, height):
+        """The first sample's ray of every pixel of a width x height frame, raster order -> (origins (N, 3) f32, directions (N, 3) f32,
+        rng states after the jitter draws (N,) u32)."""
+        n = width * height
+        o, d, states = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+        o3, d3, st = (C.c_float * 3)(), (C.c_float * 3)(), C.c_uint32(0)
+        for py in range(height):
+            for px in range(width):
+                rc = self.lib.oracle_first_sample_ray(camera.ctypes.data, window.ctypes.data, width, height, px, py, C.byref(st), o3, d3)
+                if rc != 0:
+                    raise RuntimeError(f"oracle_first_sample_ray failed: {rc}")
+                i = py * width + px
+                o[i], d[i], states[i] = tuple(o3), tuple(d3), st.value
+        return o, d, states
 
     def render(self, buffers, level, camera, window, width, height, raster_rgba=None, raster_depth=None,
                rows=None, threads=None, row_step=1):
