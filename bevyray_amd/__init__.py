@@ -15,6 +15,8 @@ from .raytracing import (  # noqa: F401
     ADAPT_DEFAULT_THRESHOLD, ADAPT_NOISY, ADAPT_SPARSE, HIT_DTYPE, REFINE_EDGES, REFINE_SPECULAR, adaptive_class, QUERY_ANY, QUERY_CLOSEST, QUERY_NONE, QUERY_STATUS_FRONT_FACE, QUERY_STATUS_HIT, QUERY_STATUS_INVALID, QUERY_STATUS_MISS,
     QUERY_STATUS_OUT_OF_REACH, RADIANCE_DTYPE, RADIANCE_RAY_DTYPE, RAY_DTYPE, pixel_ray,
     PROBE_AMBIENT_CUBE, PROBE_DTYPE, PROBE_RECORD_DTYPE, PROBE_SH9, probe_directions, probe_irradiance,
+    VOLUME_DTYPE, VOLUME_POINT_DTYPE, VOLUME_SAMPLE_DTYPE, VOLUME_STATUS_CLAMPED, VOLUME_STATUS_INVALID, VOLUME_STATUS_NO_PROBE, VOLUME_WRAP,
+    make_volume, volume_probes, volume_sample_host,
     blend_covered, prepare_buffers, rtiow_camera, srgb_thresholds, tile_rows, upscale_window, validate_scene,
 )
 

@@ -106,6 +106,13 @@ _PROTOTYPES = {
     "brt_probe_project_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _VP, _VP, _U32]),
     "brt_bake_probes_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
     "brt_bake_probes": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _F, _VP, C.POINTER(C.c_uint64)]),
+    "brt_host_volume_probes": (_I32, [_VP, _VP]),
+    "brt_host_volume_sample": (_I32, [_VP, _VP, _VP, _U32, _VP]),
+    "brt_volume_probes_device": (_I32, [_VP, _VP, _VP, _VP, _U32]),
+    "brt_bake_volume_device": (_I32, [_VP, _VP, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
+    "brt_bake_volume": (_I32, [_VP, _VP, _U32, _U32, _F, _VP, C.POINTER(C.c_uint64)]),
+    "brt_sample_volume_device": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _U32]),
+    "brt_sample_volume": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP]),
     "brt_host_pixel_ray": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP]),
     "brt_upscale_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),

@@ -22,7 +22,8 @@ void free_device(DeviceCtx& dc) {
     for (void* p : std::initializer_list<void*>{dc.d_scene, dc.d_ctrl, dc.d_strip_table, dc.d_tile, dc.d_gather, dc.d_pack, dc.d_raster_rgba,
              dc.d_raster_depth, dc.d_bvh_scratch, dc.d_tile_cost, dc.d_tile_order, dc.d_order_meta, dc.d_order_scratch, dc.d_slice_state,
              dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_uplow, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits,
-             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.d_probe_dirs, dc.d_probe_io})
+             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.d_probe_dirs, dc.d_probe_io, dc.d_volume_probes,
+             dc.d_volume_io})
         if (p) (void)hipFree(p);
     if (dc.h_stage) (void)hipHostFree(dc.h_stage);
     for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack, dc.ev_strip, dc.ev_strip_read, dc.ev_q, dc.ev_dn,

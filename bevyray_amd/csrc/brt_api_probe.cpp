@@ -121,6 +121,10 @@ int32_t step_run(brt_ctx* ctx, uint32_t n_dirs, void* hip_stream, uint32_t flags
     return rc;
 }
 
+}  // namespace
+
+namespace brt {
+
 int32_t bake_check(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
                    float origin_bound, const void* out) {
     int32_t rc = probe_dirs_check(ctx, n_dirs);
@@ -136,12 +140,6 @@ int32_t bake_check(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "light probes implement the default policy only (brt_set_policy)");
     return BRT_OK;
 }
-
-struct BakeRun {
-    RadianceLaunch rl{};
-    uint32_t chunks = 0u;
-    std::vector<unsigned long long> counts;      // 3 per chunk (counted runs)
-};
 
 // The bake of device buffers on `stream`: in chunks of whole probes, generate -> the radiance launch -> project, all behind ev_q, which
 // the last step records.  The lists are staged in d_qrays / d_qhits (one user at a time: they grow only when no list uses them).
@@ -183,6 +181,10 @@ void bake_stats(const brt_ctx* ctx, const BakeRun& run, uint32_t rebuilt, uint64
     out8[6] = run.chunks;
     out8[7] = 0u;
 }
+
+}  // namespace brt
+
+namespace {
 
 // E(n) = sum_j A_l(j) c_j Y_j(n): the cosine lobe's band factors pi, 2 pi / 3, pi / 4
 constexpr double kPi = 3.141592653589793;

@@ -1,5 +1,5 @@
 // brt_ctx.h -- the opaque context of the C ABI (include/bevyray_amd.h) and the helpers its translation units share:
-// brt_api*.cpp (upload, launch, order, render, post-passes, upsampling, queries, radiance queries, light probes; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
+// brt_api*.cpp (upload, launch, order, render, post-passes, upsampling, queries, radiance queries, light probes, irradiance volumes; what only they share: brt_frame.h) and brt_interop.cpp (RCCL
 // gather, external-memory frames).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -158,6 +158,12 @@ struct DeviceCtx {
     std::vector<float> h_probe_dirs;
     char* d_probe_io = nullptr;
     size_t probe_io_cap = 0;
+    // irradiance volumes (brt_volume.h), first device only: the probes k_volume_probes generates for a bake, and the records, points and
+    // samples of the host entry points.  Ordered by ev_q like the probe buffers: each grows only once every list of the context has ended
+    char* d_volume_probes = nullptr;
+    size_t volume_probes_cap = 0;
+    char* d_volume_io = nullptr;
+    size_t volume_io_cap = 0;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;

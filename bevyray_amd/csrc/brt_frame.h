@@ -136,6 +136,21 @@ int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32
 int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t samples,
                          uint32_t bounces, void* d_out, bool counted, RadianceLaunch* rl);
 
+// ---- brt_api_probe.cpp ----
+// What the bakes of light probes share with the bake of an irradiance volume (brt_api_volume.cpp).  bake_check: the arguments of a bake
+// (with n_probes = 0 the two pointers are not looked at).  bake_enqueue: the bake of DEVICE buffers on `stream`, in chunks of whole
+// probes, all behind ev_q, which the last step records.  bake_stats: the call's out_stats8.
+struct BakeRun {
+    RadianceLaunch rl{};
+    uint32_t chunks = 0u;
+    std::vector<unsigned long long> counts;      // 3 per chunk (counted runs)
+};
+int32_t bake_check(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
+                   float origin_bound, const void* out);
+int32_t bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_probes, uint32_t n_probes, uint32_t n_dirs,
+                     uint32_t bounces, uint32_t basis, void* d_out, bool counted, BakeRun* run);
+void bake_stats(const brt_ctx* ctx, const BakeRun& run, uint32_t rebuilt, uint64_t* out8);
+
 // ---- brt_api_pixels.cpp ----
 // What a list of pixels is traced into (brt_pixels.h PixelsArgs): packed RGBA32F, or scattered into a frame in a BRT_FLAG_OUT_* format
 struct PixelsTarget {

@@ -363,6 +363,51 @@ def probe_irradiance(record, normal) -> np.ndarray:
     return out
 
 
+# irradiance volumes: brt_bake_volume* / brt_sample_volume* (include/bevyray_amd.h): a lattice of probes, the points lit from it, the samples
+VOLUME_WRAP = 1
+VOLUME_STATUS_CLAMPED, VOLUME_STATUS_INVALID, VOLUME_STATUS_NO_PROBE = 1, 4, 8
+VOLUME_DTYPE = np.dtype([("origin", np.float32, 3), ("seed", np.uint32), ("spacing", np.float32, 3), ("basis", np.uint32),
+                         ("count", np.uint32, 3), ("flags", np.uint32)])
+VOLUME_POINT_DTYPE = np.dtype([("position", np.float32, 3), ("ignored0", np.uint32), ("normal", np.float32, 3), ("ignored1", np.uint32)])
+VOLUME_SAMPLE_DTYPE = np.dtype([("rgb", np.float32, 3), ("status", np.uint32)])
+assert VOLUME_DTYPE.itemsize == 48 and VOLUME_POINT_DTYPE.itemsize == 32 and VOLUME_SAMPLE_DTYPE.itemsize == 16
+
+
+def make_volume(origin, spacing, count, basis: int = PROBE_SH9, seed: int = 0, flags: int = 0) -> np.ndarray:
+    """One VOLUME_DTYPE descriptor (shape (1,)); nothing is checked here: the library refuses a bad one."""
+    v = np.zeros(1, VOLUME_DTYPE)
+    v["origin"], v["spacing"], v["count"] = origin, spacing, count
+    v["seed"], v["basis"], v["flags"] = seed, basis, flags
+    return v
+
+
+def _volume_probe_count(volume) -> int:
+    c = [int(x) for x in volume["count"].reshape(3)]
+    n = c[0] * c[1] * c[2]
+    return n if all(1 <= x <= 1024 for x in c) and n <= 1 << 20 else 0      # (a bad descriptor is refused before anything is written)
+
+
+def volume_probes(volume) -> np.ndarray:
+    """brt_host_volume_probes: the PROBE_DTYPE records of the lattice, in index order.  Host arithmetic."""
+    v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
+    out = np.zeros(_volume_probe_count(v), PROBE_DTYPE)
+    _lib.check(_lib.load().brt_host_volume_probes(v.ctypes.data, out.ctypes.data if out.size else None))
+    return out
+
+
+def volume_sample_host(volume, records, points) -> np.ndarray:
+    """brt_host_volume_sample: the sampling rule over VOLUME_POINT_DTYPE points on the host -> VOLUME_SAMPLE_DTYPE.  The compiled twin
+    of the kernel behind RayTracingNode.sample_volume."""
+    v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
+    records = np.ascontiguousarray(records, PROBE_RECORD_DTYPE)
+    points = np.ascontiguousarray(points, VOLUME_POINT_DTYPE)
+    out = np.zeros(points.shape, VOLUME_SAMPLE_DTYPE)
+    _lib.check(_lib.load().brt_host_volume_sample(v.ctypes.data, records.ctypes.data if records.size else None,
+                                                  points.ctypes.data if points.size else None, points.size,
+                                                  out.ctypes.data if points.size else None))
+    return out
+
+
 def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.ndarray:
     """brt_host_pixel_ray: the pixel-centre ray of pixel (px, py) as one RAY_DTYPE record (t_max = inf, user = py * width + px): the
     ray the guide buffer casts for that pixel.  Host arithmetic; for picking through RayTracingNode.query_rays."""
@@ -975,6 +1020,52 @@ class RayTracingNode:
         p = self._p
         _lib.check(p._lib.brt_probe_project_device(p._ctx, d_results or None, int(n_probes), int(n_dirs), int(basis), d_out or None,
                                                    stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+
+    # -- irradiance volumes (include/bevyray_amd.h "irradiance volumes") ----------------------------
+
+    def volume_probes_device(self, volume, d_probes: int, stream: Optional[int] = None):
+        """brt_volume_probes_device: the generation kernel alone -> the lattice's PROBE_DTYPE records at d_probes."""
+        p = self._p
+        v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
+        _lib.check(p._lib.brt_volume_probes_device(p._ctx, v.ctypes.data, d_probes or None, stream or None,
+                                                   0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+
+    def bake_volume(self, volume, n_dirs: int, bounces: int, origin_bound: float = 0.0, d_records: Optional[int] = None,
+                    stream: Optional[int] = None):
+        """brt_bake_volume*: the records of the lattice `volume` (VOLUME_DTYPE), baked as bake_probes bakes the lattice's probes.
+        d_records=None: -> PROBE_RECORD_DTYPE records in host memory (synchronous).  d_records=<device pointer>: the records are written
+        there -> the call's stats; stream rule as for bake_probes.  last_probe_stats holds the call's stats."""
+        p = self._p
+        v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
+        words = (C.c_uint64 * 8)()
+        if d_records is not None:
+            _lib.check(p._lib.brt_bake_volume_device(p._ctx, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), d_records or None,
+                                                     stream or None, 0 if stream is None else FLAG_CALLER_STREAM, words), p._ctx)
+            self.last_probe_stats = self._probe_stats(words)
+            return self.last_probe_stats
+        out = np.empty(max(_volume_probe_count(v), 1), PROBE_RECORD_DTYPE)
+        _lib.check(p._lib.brt_bake_volume(p._ctx, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), out.ctypes.data, words), p._ctx)
+        self.last_probe_stats = self._probe_stats(words)
+        return out
+
+    def sample_volume(self, volume, records, points, device: bool = False, stream: Optional[int] = None):
+        """brt_sample_volume*: irradiance at {position, normal} points from the baked records of `volume`.  device=False: `records`
+        (PROBE_RECORD_DTYPE) and `points` (VOLUME_POINT_DTYPE) are host arrays -> VOLUME_SAMPLE_DTYPE (synchronous).  device=True:
+        `records` is a device pointer and `points` is (d_points, n_points, d_out); stream rule as for bake_probes."""
+        p = self._p
+        v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
+        if device:
+            d_points, n_points, d_out = points
+            _lib.check(p._lib.brt_sample_volume_device(p._ctx, v.ctypes.data, records or None, d_points or None, int(n_points), d_out or None,
+                                                       stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+            return None
+        records = np.ascontiguousarray(records, PROBE_RECORD_DTYPE)
+        points = np.ascontiguousarray(points, VOLUME_POINT_DTYPE)
+        out = np.zeros(points.shape, VOLUME_SAMPLE_DTYPE)
+        _lib.check(p._lib.brt_sample_volume(p._ctx, v.ctypes.data, records.ctypes.data if records.size else None,
+                                            points.ctypes.data if points.size else None, points.size,
+                                            out.ctypes.data if points.size else None), p._ctx)
+        return out
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

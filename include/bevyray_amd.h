@@ -570,6 +570,60 @@ int32_t brt_bake_probes_device(brt_ctx* ctx, const void* d_probes, uint32_t n_pr
 int32_t brt_bake_probes(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
                         float origin_bound, void* out, uint64_t* out_stats8_or_null);
 
+/* ---- irradiance volumes --------------------------------------------------------------------------------------------------------------
+ * A regular lattice of light probes over an axis-aligned box, baked in one call, and lists of { position, normal } lit from the baked
+ * records on the device: the ambient term of a level-1 / level-2 host's raster pixels.  On the context's first device.  Rule, kernels and
+ * costs: DESIGN.md "Irradiance volumes".  Deterministic: f32, every operation separately rounded, in the order written here.
+ *   volume, 48 bytes  { f32 origin[3]; u32 seed; f32 spacing[3]; u32 basis; u32 count[3]; u32 flags }.  basis: BRT_PROBE_SH9 or
+ *                     BRT_PROBE_AMBIENT_CUBE; flags: 0 or BRT_VOLUME_WRAP.  Probe (ix, iy, iz) has index i = (iz * count[1] + iy) *
+ *                     count[0] + ix, position origin[a] + f32(i_a) * spacing[a] per axis (a multiply, then an add) and seed
+ *                     seed + i * 0x85EBCA6B (mod 2^32).  Valid: origin finite, spacing finite and > 0, every count in [1, 1024], the
+ *                     product of the counts <= 1 << 20, a known basis and flags; anything else is BRT_ERR_INVALID_ARGUMENT.
+ *   records           the 128-byte records of "light probes", one per probe in index order.
+ *   point, 32 bytes   { f32 position[3]; u32 ignored; f32 normal[3]; u32 ignored }.  The normal is used as given.
+ *   sample, 16 bytes  { f32 rgb[3]; u32 status }, status: BRT_VOLUME_STATUS_* bits.
+ *   the rule          1. a non-finite component of position or normal: rgb = 0, status = INVALID, nothing else.
+ *                     2. per axis a: t = (p_a - origin_a) / spacing_a; hi = f32(count_a - 1); CLAMPED is set if t < 0 or t > hi;
+ *                        t = t > 0 ? t : 0; t = t < hi ? t : hi; i0 = min(u32(floor(t)), max(count_a, 2) - 2); f = t - f32(i0);
+ *                        i1 = min(i0 + 1, count_a - 1).
+ *                     3. SH9: AY_j = A_j * Y_j(n) with the basis of "light probes" and A = 3.1415927f, 2.0943952f, 0.7853982f for
+ *                        bands 0, 1, 2.  Cube: n2_a = n_a * n_a, face_a = 2 a + (n_a < 0).
+ *                     4. corners c = 0 .. 7 in order, bit 0 / 1 / 2 selecting i1 on x / y / z: w = (wx * wy) * wz with w_a = f for a
+ *                        set bit, 1 - f otherwise.  A corner whose record has status != 0 or a basis other than the descriptor's
+ *                        contributes nothing.  Under BRT_VOLUME_WRAP: d = probe position - p; len2 = (dx dx + dy dy) + dz dz;
+ *                        cs = len2 > 0 ? ((dx nx + dy ny) + dz nz) / sqrt(len2) : 1; h = (cs + 1) * 0.5; w = w * (h * h + 0.2).
+ *                        SH9: E_c[ch] from +0.0, E_c = E_c + AY_j * coeff[3 j + ch] for j = 0 .. 8.  Cube: E_c[ch] = (n2_x *
+ *                        c[3 face_x + ch] + n2_y * c[3 face_y + ch]) + n2_z * c[3 face_z + ch].  acc[ch] = acc[ch] + w * E_c[ch];
+ *                        sw = sw + w.
+ *                     5. sw > 0: E = acc / sw, then E = E < 0 ? 0 : E (a NaN stays a NaN).  Otherwise rgb = 0 and NO_PROBE is set.
+ *   brt_host_volume_probes     host arithmetic, no context: the lattice's 16-byte probes in index order.
+ *   brt_host_volume_sample     host arithmetic, no context: the rule over a list of n_points points; the compiled twin of the kernel.
+ *   brt_volume_probes_device   the generation kernel alone: the lattice's probes at d_probes (DEVICE).
+ *   brt_bake_volume_device     the lattice's probes into a buffer of the context, then brt_bake_probes_device's chunked bake of them into
+ *                     d_records (DEVICE, product-of-counts records).  n_dirs, bounces, origin_bound, out_stats8_or_null: as there.
+ *   brt_bake_volume            the same for a HOST buffer, synchronous.
+ *   brt_sample_volume_device   n_points points at d_points -> samples at d_out from the records at d_records (DEVICE).  Needs no scene.
+ *   brt_sample_volume          the same for HOST buffers, synchronous (all three lists are staged in one buffer of the context).
+ * flags: BRT_FLAG_CALLER_STREAM only; stream rule and ordering as for the step exports of "light probes".  A bad descriptor, null
+ * pointers, a DEVICE buffer that is not 16-byte aligned (the kernels move whole 16-byte words), an output that overlaps the points or
+ * the records, n_points above 0x7fff0000: BRT_ERR_INVALID_ARGUMENT.  The bakes add the
+ * probe bakes' refusals (BRT_ERR_NO_SCENE, BRT_ERR_UNSUPPORTED under a set policy, n_dirs, bounces, origin_bound).  n_points = 0 is
+ * BRT_OK and launches nothing.  A refused call leaves the context usable; no call here changes a frame or the dispatch history. */
+#define BRT_VOLUME_WRAP 1u
+#define BRT_VOLUME_STATUS_CLAMPED 1u
+#define BRT_VOLUME_STATUS_INVALID 4u
+#define BRT_VOLUME_STATUS_NO_PROBE 8u
+int32_t brt_host_volume_probes(const void* volume48, void* out_probes);
+int32_t brt_host_volume_sample(const void* volume48, const void* records, const void* points, uint32_t n_points, void* out);
+int32_t brt_volume_probes_device(brt_ctx* ctx, const void* volume48, void* d_probes, void* hip_stream, uint32_t flags);
+int32_t brt_bake_volume_device(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uint32_t bounces, float origin_bound, void* d_records,
+                               void* hip_stream, uint32_t flags, uint64_t* out_stats8_or_null);
+int32_t brt_bake_volume(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uint32_t bounces, float origin_bound, void* records,
+                        uint64_t* out_stats8_or_null);
+int32_t brt_sample_volume_device(brt_ctx* ctx, const void* volume48, const void* d_records, const void* d_points, uint32_t n_points,
+                                 void* d_out, void* hip_stream, uint32_t flags);
+int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* records, const void* points, uint32_t n_points, void* out);
+
 /* ---- guide-buffer upsampling ----------------------------------------------------------------------------------------------------------
  * A frame traced at low_width x low_height is presented at width x height: every OUTPUT pixel casts its own pixel-centre ray (the guide
  * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
