@@ -1,5 +1,6 @@
 // brt_api_pixels.cpp -- the sparse pixel tracer (brt_pixels.hip; DESIGN.md "Refined upsampling") on the first device: a list of pixels
-// of a Pure frame, each traced alone to the value the whole frame holds there.
+// of a Pure frame, each traced alone to the value the whole frame holds there.  The tree follows the call's camera (with_tree_reach),
+// not an origin bound; the launch plan is that of every list kernel (plan_list).
 #include "brt_frame.h"
 
 using namespace brt;
@@ -7,7 +8,7 @@ using namespace brt;
 namespace brt {
 
 // Which form a list takes: BRT_FLAG_KERNEL_SIMPLE or BRT_PIXELS_FORM 1 the plain form (what brt_api_query.cpp hands to k_query_plain
-// goes to it here: every representation and tree), else the streaming form in the launch shape of plan_stream.
+// goes to it here: every representation and tree), else the streaming form (plan_list).
 int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                        const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
                        hipStream_t stream, bool force_plain, PixelsLaunch* pl) {
@@ -16,21 +17,8 @@ int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const 
     if (pl->frame.policy_flags != 0u)
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the pixel tracer implements the default policy only (brt_set_policy)");
     const uint32_t form = ctx->knobs[K_PIXELS_FORM];
-    pl->scene = dc.view;
-    pl->scene.lds_pairs = 0u;
-    pl->form = (form == 1u || (force_plain && form != 2u)) ? PIXELS_PLAIN : PIXELS_STREAM;
-    pl->scene_mode = SCENE_GLOBAL;
-    pl->grid = pl->block = 0u;
-    pl->lds_bytes = 0;
-    if (pl->form == PIXELS_STREAM) {
-        // waves per SIMD where nothing is staged: 114 VGPRs with the hand-written loop (4), 86 without (5)
-        const StreamPlan sp = plan_stream(ctx, dc, n_pixels, 4u, 5u);
-        pl->scene = sp.scene;
-        pl->scene_mode = sp.scene_mode;
-        pl->grid = sp.grid;
-        pl->block = sp.block;
-        pl->lds_bytes = sp.lds_bytes;
-    }
+    // waves per SIMD where nothing is staged: 114 VGPRs with the hand-written loop (4), 86 without (5)
+    plan_list(ctx, dc, n_pixels, !(form == 1u || (force_plain && form != 2u)), 4u, 5u, false, pl);
     PixelsArgs& pa = pl->args;
     pa.pixels = d_pixels;
     pa.n_pixels = n_pixels;
@@ -77,11 +65,11 @@ void pixels_stats(const PixelsLaunch& pl, const unsigned long long* counts2, brt
     // (the tree fields are with_tree_reach's)
     stats->rays = counts2 ? counts2[0] : 0u;
     stats->reserved = counts2 ? (uint32_t)std::min<unsigned long long>(counts2[1], 0xffffffffull) : 0u;      // entries refused
-    stats->n_workgroups = pl.form == PIXELS_STREAM ? pl.grid : (pl.args.n_pixels + 255u) / 256u;
-    stats->threads_per_workgroup = pl.form == PIXELS_STREAM ? pl.block : 256u;
+    stats->n_workgroups = list_groups(pl, pl.args.n_pixels);
+    stats->threads_per_workgroup = pl.form == LIST_STREAM ? pl.block : 256u;
     stats->lds_bytes = (uint32_t)pl.lds_bytes;
-    stats->scene_in_lds = pl.form != PIXELS_STREAM ? 0u : pl.scene_mode == SCENE_LDS ? 1u : (pl.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
-    stats->kernel_variant = pl.form == PIXELS_STREAM ? 32u : 33u;      // (the persistent kernel's variants are below 32)
+    stats->scene_in_lds = pl.form != LIST_STREAM ? 0u : pl.scene_mode == SCENE_LDS ? 1u : (pl.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
+    stats->kernel_variant = pl.form == LIST_STREAM ? 32u : 33u;      // (the persistent kernel's variants are below 32)
 }
 
 }  // namespace
@@ -143,7 +131,8 @@ int32_t brt_render_pixels(brt_ctx* ctx, const void* camera80, const void* window
     const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
         HIP_TRY(ctx, hipSetDevice(dc.device));
         const size_t list_bytes = (size_t)n_pixels * 4u, out_bytes = (size_t)n_pixels * 16u;
-        if (dc.pxlist_cap < list_bytes || dc.pxout_cap < out_bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));   // (the staging buffers grow only when no list uses them)
+        // (the staging rule of `staged`, written out: the control words are allocated between the wait and the buffers)
+        if (dc.pxlist_cap < list_bytes || dc.pxout_cap < out_bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
         int32_t r = pixels_ctl(ctx, dc);
         if (r == BRT_OK) r = ensure(ctx, &dc.d_pxlist, &dc.pxlist_cap, list_bytes);
         if (r == BRT_OK) r = ensure(ctx, &dc.d_pxout, &dc.pxout_cap, out_bytes);

@@ -1,6 +1,7 @@
 // brt_api_probe.cpp -- light probes (brt_probe.hip; DESIGN.md "Light probes") on the first device: irradiance records for a list of
 // positions.  The rays are radiance entries and are traced by the radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue);
-// reach, refusal bound and staging buffers are the ray queries' (brt_api_query.cpp).
+// reach, refusal bound and staging buffers are the ray queries' (brt_api_query.cpp); the skeleton of a list call and the runner of a
+// step export are brt_frame.h's (with_reach, staged, list_step_run, list_stats8).
 #include "brt_frame.h"
 #include "brt_probe.h"
 
@@ -29,11 +30,6 @@ void probe_directions(uint32_t n, float* out, uint32_t stride) {
 
 int32_t probe_dirs_check(brt_ctx* ctx, uint32_t n_dirs) {
     if (n_dirs < 1u || n_dirs > kProbeMaxDirs) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_dirs must be in [1, 65536]");
-    return BRT_OK;
-}
-
-int32_t probe_flags_check(brt_ctx* ctx, uint32_t flags) {
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
     return BRT_OK;
 }
 
@@ -92,7 +88,7 @@ int32_t probe_project_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, c
 // what the two step exports check: flags, the list's size, the basis, and `in` / `out` of in_each / out_each bytes per probe
 int32_t step_check(brt_ctx* ctx, const void* in, size_t in_each, const void* out, size_t out_each, uint32_t n_probes, uint32_t n_dirs,
                    uint32_t basis, uint32_t flags) {
-    int32_t rc = probe_flags_check(ctx, flags);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = probe_list_check(ctx, n_probes, n_dirs);
     if (rc != BRT_OK) return rc;
     if (basis > PROBE_AMBIENT_CUBE) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "basis must be BRT_PROBE_SH9 or BRT_PROBE_AMBIENT_CUBE");
@@ -102,23 +98,10 @@ int32_t step_check(brt_ctx* ctx, const void* in, size_t in_each, const void* out
     return BRT_OK;
 }
 
-// one step kernel alone on the call's stream: behind ev_q with the table of n_dirs, recording ev_q; the own stream synchronises
+// one step kernel alone on the call's stream (list_step_run), behind ev_q with the table of n_dirs
 template <class Enqueue>
 int32_t step_run(brt_ctx* ctx, uint32_t n_dirs, void* hip_stream, uint32_t flags, Enqueue&& enqueue) {
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const StreamChoice sc = stream_of(dc, hip_stream, flags);
-    auto body = [&]() -> int32_t {
-        int32_t r = probe_table(ctx, dc, n_dirs, sc.stream);
-        if (r == BRT_OK) r = enqueue(dc, sc.stream);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));
-        if (sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
-    };
-    const int32_t rc = body();
-    if (rc != BRT_OK) drain_all_streams(ctx);
-    return rc;
+    return list_step_run(ctx, hip_stream, flags, [&](DeviceCtx& dc, hipStream_t stream) { return probe_table(ctx, dc, n_dirs, stream); }, enqueue);
 }
 
 }  // namespace
@@ -131,7 +114,7 @@ int32_t bake_check(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t
     if (rc != BRT_OK) return rc;
     if (basis > PROBE_AMBIENT_CUBE) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "basis must be BRT_PROBE_SH9 or BRT_PROBE_AMBIENT_CUBE");
     if (bounces > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "bounces must be in [0, 65535]");
-    if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    if ((rc = origin_bound_check(ctx, origin_bound)) != BRT_OK) return rc;
     if (n_probes != 0u && (!probes || !out)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "probes / out is null");
     if (n_probes != 0u && overlaps(probes, (size_t)n_probes * 16u, out, (size_t)n_probes * 128u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "probes and out overlap");
@@ -142,15 +125,13 @@ int32_t bake_check(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t
 }
 
 // The bake of device buffers on `stream`: in chunks of whole probes, generate -> the radiance launch -> project, all behind ev_q, which
-// the last step records.  The lists are staged in d_qrays / d_qhits (one user at a time: they grow only when no list uses them).
+// the last step records.  The lists are staged in d_qrays / d_qhits (one user at a time: `staged`).
 int32_t bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_probes, uint32_t n_probes, uint32_t n_dirs,
                      uint32_t bounces, uint32_t basis, void* d_out, bool counted, BakeRun* run) {
     const uint32_t chunk_rays = std::min(std::max(ctx->knobs[K_PROBE_CHUNK_RAYS], 1u), kMaxEntries);
     const uint32_t per_chunk = std::min(std::max(1u, chunk_rays / n_dirs), n_probes);
     const size_t bytes = (size_t)per_chunk * n_dirs * 32u;
-    if (dc.qrays_cap < bytes || dc.qhits_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    int32_t rc = ensure(ctx, &dc.d_qrays, &dc.qrays_cap, bytes);
-    if (rc == BRT_OK) rc = ensure(ctx, &dc.d_qhits, &dc.qhits_cap, bytes);
+    int32_t rc = staged(ctx, dc, {{&dc.d_qrays, &dc.qrays_cap, bytes}, {&dc.d_qhits, &dc.qhits_cap, bytes}});
     if (rc == BRT_OK) rc = probe_table(ctx, dc, n_dirs, stream);
     if (rc != BRT_OK) return rc;
     run->chunks = (n_probes + per_chunk - 1u) / per_chunk;
@@ -169,17 +150,9 @@ int32_t bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void
 }
 
 void bake_stats(const brt_ctx* ctx, const BakeRun& run, uint32_t rebuilt, uint64_t* out8) {
-    if (!out8) return;
-    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
-    uint32_t reach_bits;
-    std::memcpy(&reach_bits, &reach, 4);
-    out8[0] = out8[1] = out8[2] = 0u;
-    for (size_t i = 0; i < run.counts.size(); i++) out8[i % 3u] += run.counts[i];
-    out8[3] = rebuilt;
-    out8[4] = reach_bits;
-    out8[5] = (uint64_t)run.rl.form;
-    out8[6] = run.chunks;
-    out8[7] = 0u;
+    uint64_t sums[3] = {0u, 0u, 0u};
+    for (size_t i = 0; i < run.counts.size(); i++) sums[i % 3u] += run.counts[i];
+    list_stats8(ctx, sums, rebuilt, run.rl.form, run.chunks, out8);
 }
 
 }  // namespace brt
@@ -260,27 +233,20 @@ int32_t brt_bake_probes_device(brt_ctx* ctx, const void* d_probes, uint32_t n_pr
                                float origin_bound, void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    int32_t rc = probe_flags_check(ctx, flags);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = bake_check(ctx, d_probes, n_probes, n_dirs, bounces, basis, origin_bound, d_out);
     if (rc != BRT_OK) return rc;
     BakeRun run;
     uint32_t rebuilt = 0u;
     if (n_probes == 0u) { bake_stats(ctx, run, 0u, out_stats8); return BRT_OK; }
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const StreamChoice sc = stream_of(dc, hip_stream, flags);
-    auto body = [&]() -> int32_t {
+    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         const int32_t r = bake_enqueue(ctx, dc, sc.stream, d_probes, n_probes, n_dirs, bounces, basis, d_out, sc.own, &run);
         if (r != BRT_OK || !sc.own) return r;
         HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    bake_stats(ctx, run, rebuilt, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
+    return rc;
     });
 }
 
@@ -293,15 +259,10 @@ int32_t brt_bake_probes(brt_ctx* ctx, const void* probes, uint32_t n_probes, uin
     BakeRun run;
     uint32_t rebuilt = 0u;
     if (n_probes == 0u) { bake_stats(ctx, run, 0u, out_stats8); return BRT_OK; }
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    auto body = [&]() -> int32_t {
-        // the probes and the records on the device: one buffer, 16 + 128 bytes per probe; it grows only when no list uses it
+    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
+        // the probes and the records on the device: one buffer, 16 + 128 bytes per probe
         const size_t in_bytes = align256((size_t)n_probes * 16u), bytes = in_bytes + (size_t)n_probes * 128u;
-        if (dc.probe_io_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-        int32_t r = ensure(ctx, &dc.d_probe_io, &dc.probe_io_cap, bytes);
+        int32_t r = staged(ctx, dc, {{&dc.d_probe_io, &dc.probe_io_cap, bytes}});
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
         HIP_TRY(ctx, hipMemcpyAsync(dc.d_probe_io, probes, (size_t)n_probes * 16u, hipMemcpyHostToDevice, dc.stream));
@@ -311,11 +272,9 @@ int32_t brt_bake_probes(brt_ctx* ctx, const void* probes, uint32_t n_probes, uin
         HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the buffer)
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    bake_stats(ctx, run, rebuilt, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
+    return rc;
     });
 }
 

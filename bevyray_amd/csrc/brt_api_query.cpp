@@ -1,4 +1,6 @@
-// brt_api_query.cpp -- ray queries (brt_query.hip; DESIGN.md "Ray queries") on the first device.
+// brt_api_query.cpp -- ray queries (brt_query.hip; DESIGN.md "Ray queries") on the first device, and the launch plan of every list
+// kernel (plan_list).  The skeleton of a list call -- flags, staging, reach, stream, drain, stats -- is brt_frame.h's (with_reach,
+// staged, list_stats8).
 #include "brt_frame.h"
 
 using namespace brt;
@@ -83,73 +85,62 @@ bool list_streams(uint32_t form, uint32_t stream_min, uint32_t n) {
 
 namespace {
 
-// Which form a batch takes (list_streams under BRT_QUERY_FORM and BRT_QUERY_STREAM_MIN) and the streaming form's launch shape (plan_stream)
-void plan_query(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, QueryLaunch* ql) {
-    const Knobs& kn = ctx->knobs;
-    ql->scene = dc.view;
-    ql->scene.lds_pairs = 0u;
-    ql->form = QUERY_PLAIN;
-    ql->scene_mode = SCENE_GLOBAL;
-    ql->grid = ql->block = 0u;
-    ql->lds_bytes = 0;
-    if (!list_streams(kn[K_QUERY_FORM], kn[K_QUERY_STREAM_MIN], n_rays)) return;
-    ql->form = QUERY_STREAM;
-    // waves per SIMD: the simple-tree instantiation of 16-bit descriptors holds the hand-written loop's 114 VGPRs (4), the others 60-64 (8)
-    const StreamPlan sp = plan_stream(ctx, dc, n_rays, 4u, 8u);
-    ql->scene = sp.scene;
-    ql->scene_mode = sp.scene_mode;
-    ql->grid = sp.grid;
-    ql->block = sp.block;
-    ql->lds_bytes = sp.lds_bytes;
-}
-
-}  // namespace
-
-namespace brt {
-
 // The streaming forms stage what k_trace_persistent would (plan_launch): the whole scene where it fits a workgroup's LDS beside the
 // stacks, else the top of the tree, else nothing (scenes of 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE); BRT_FORCE_LDS_TOP=<records> as
 // there.
-StreamPlan plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, uint32_t waves_by_hand, uint32_t waves_other) {
+void plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, uint32_t waves_by_hand, uint32_t waves_other, StreamLaunch* sp) {
     const Knobs& kn = ctx->knobs;
-    StreamPlan sp{};
-    sp.scene = dc.view;
-    sp.scene.lds_pairs = 0u;
-    sp.scene_mode = SCENE_GLOBAL;
+    sp->form = LIST_STREAM;
     const bool force_global = kn[K_FORCE_GLOBAL_SCENE] != 0u;
     const uint32_t force_top = kn[K_FORCE_LDS_TOP];
     uint32_t per_cu = 1u;
     if (!force_global && !force_top && dc.view.desc16) {
         for (uint32_t block : {1024u, 512u, 256u}) {
             const size_t need = trace_lds_bytes(dc.view, SCENE_LDS, block, 0u);
-            if (need <= dc.max_lds) { sp.scene_mode = SCENE_LDS; sp.block = block; sp.lds_bytes = need; break; }
+            if (need <= dc.max_lds) { sp->scene_mode = SCENE_LDS; sp->block = block; sp->lds_bytes = need; break; }
         }
     }
-    if (sp.scene_mode != SCENE_LDS && !force_global && dc.view.desc16) {
-        const size_t fixed = trace_lds_bytes(sp.scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);       // (lds_pairs = 0: stacks only)
+    if (sp->scene_mode != SCENE_LDS && !force_global && dc.view.desc16) {
+        const size_t fixed = trace_lds_bytes(sp->scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);       // (lds_pairs = 0: stacks only)
         if (fixed + 64 * PAIR_BYTES <= dc.max_lds) {
             uint32_t k = (uint32_t)((dc.max_lds - fixed) / PAIR_BYTES);
             if (k > dc.view.n_pairs) k = dc.view.n_pairs;
             if (force_top && force_top < k) k = force_top;
-            sp.scene.lds_pairs = k;
-            sp.scene_mode = SCENE_LDS_TOP;
-            sp.block = BRT_BLOCK;
-            sp.lds_bytes = trace_lds_bytes(sp.scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);
+            sp->scene.lds_pairs = k;
+            sp->scene_mode = SCENE_LDS_TOP;
+            sp->block = BRT_BLOCK;
+            sp->lds_bytes = trace_lds_bytes(sp->scene, SCENE_LDS_TOP, BRT_BLOCK, 0u);
         }
     }
-    if (sp.scene_mode == SCENE_GLOBAL) {
-        sp.block = 256u;
-        sp.lds_bytes = trace_lds_bytes(dc.view, SCENE_GLOBAL, 256u, 0u);
-        per_cu = (uint32_t)(dc.max_lds / (sp.lds_bytes ? sp.lds_bytes : 1));
+    if (sp->scene_mode == SCENE_GLOBAL) {
+        sp->block = 256u;
+        sp->lds_bytes = trace_lds_bytes(dc.view, SCENE_GLOBAL, 256u, 0u);
+        per_cu = (uint32_t)(dc.max_lds / (sp->lds_bytes ? sp->lds_bytes : 1));
         const uint32_t by_regs = (dc.view.desc16 && dc.view.simple_tree) ? waves_by_hand : waves_other;
         if (per_cu > by_regs) per_cu = by_regs;
         if (per_cu < 1u) per_cu = 1u;
     }
-    sp.grid = (uint32_t)dc.num_cus * per_cu;
-    const uint32_t useful = (n_items + sp.block - 1u) / sp.block;
-    if (sp.grid > useful) sp.grid = useful;
-    if (sp.grid < 1u) sp.grid = 1u;
-    return sp;
+    sp->grid = (uint32_t)dc.num_cus * per_cu;
+    const uint32_t useful = (n_items + sp->block - 1u) / sp->block;
+    if (sp->grid > useful) sp->grid = useful;
+    if (sp->grid < 1u) sp->grid = 1u;
+}
+
+}  // namespace
+
+namespace brt {
+
+void plan_list(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, bool streams, uint32_t waves_by_hand, uint32_t waves_other,
+               bool need_lds, StreamLaunch* sl) {
+    StreamLaunch plain{};
+    plain.scene = dc.view;
+    plain.scene.lds_pairs = 0u;
+    plain.form = LIST_PLAIN;
+    plain.scene_mode = SCENE_GLOBAL;
+    *sl = plain;
+    if (!streams) return;
+    plan_stream(ctx, dc, n_items, waves_by_hand, waves_other, sl);
+    if (need_lds && sl->scene_mode == SCENE_GLOBAL) *sl = plain;
 }
 
 // the resident -> caller sphere map of the first device for work on `stream` (nullptr: the resident order is the upload order)
@@ -179,7 +170,10 @@ namespace {
 int32_t query_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits,
                       bool counted, QueryLaunch* ql) {
     HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    plan_query(ctx, dc, n_rays, ql);
+    // the form: list_streams under BRT_QUERY_FORM and BRT_QUERY_STREAM_MIN.  Waves per SIMD: the simple-tree instantiation of 16-bit
+    // descriptors holds the hand-written loop's 114 VGPRs (4), the others 60-64 (8)
+    const Knobs& kn = ctx->knobs;
+    plan_list(ctx, dc, n_rays, list_streams(kn[K_QUERY_FORM], kn[K_QUERY_STREAM_MIN], n_rays), 4u, 8u, false, ql);
     const uint32_t* rmap = nullptr;
     int32_t rc = query_rmap(ctx, dc, stream, &rmap);
     if (rc != BRT_OK) return rc;
@@ -193,7 +187,7 @@ int32_t query_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const voi
     qa.stat = counted ? dc.d_qctl : nullptr;
     qa.counter = dc.d_qctl + 4;
     ql->stream = stream;
-    if (counted || ql->form == QUERY_STREAM) HIP_TRY(ctx, hipMemsetAsync(dc.d_qctl, 0, 32, stream));
+    if (counted || ql->form == LIST_STREAM) HIP_TRY(ctx, hipMemsetAsync(dc.d_qctl, 0, 32, stream));
     HIP_TRY(ctx, launch_query(*ql));
     HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
     return BRT_OK;
@@ -201,7 +195,7 @@ int32_t query_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const voi
 
 int32_t query_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mode, float origin_bound, const void* hits) {
     if (mode != BRT_QUERY_CLOSEST && mode != BRT_QUERY_ANY) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "mode must be BRT_QUERY_CLOSEST or BRT_QUERY_ANY");
-    if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    if (const int32_t rc = origin_bound_check(ctx, origin_bound)) return rc;
     if (n_rays > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_rays too large");
     if (n_rays != 0u && (!rays || !hits)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "rays / hits is null");
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
@@ -209,18 +203,7 @@ int32_t query_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mo
 }
 
 void query_stats(const brt_ctx* ctx, const QueryLaunch& ql, uint32_t rebuilt, const uint32_t* counts3, uint64_t* out8) {
-    if (!out8) return;
-    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
-    uint32_t reach_bits;
-    std::memcpy(&reach_bits, &reach, 4);
-    out8[0] = counts3 ? counts3[0] : 0u;
-    out8[1] = counts3 ? counts3[1] : 0u;
-    out8[2] = counts3 ? counts3[2] : 0u;
-    out8[3] = rebuilt;
-    out8[4] = reach_bits;
-    out8[5] = (uint64_t)ql.form;
-    out8[6] = ql.form == QUERY_STREAM ? ql.grid : (ql.args.n_rays + 255u) / 256u;
-    out8[7] = 0u;
+    list_stats8(ctx, counts3, rebuilt, ql.form, list_groups(ql, ql.args.n_rays), out8);
 }
 
 }  // namespace
@@ -231,29 +214,21 @@ int32_t brt_query_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays,
                               void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
-    int32_t rc = query_check(ctx, d_rays, n_rays, mode, origin_bound, d_hits);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
+    if (rc == BRT_OK) rc = query_check(ctx, d_rays, n_rays, mode, origin_bound, d_hits);
     if (rc != BRT_OK) return rc;
     QueryLaunch ql{};
-    uint32_t rebuilt = 0u;
+    uint32_t rebuilt = 0u, counts[3] = {0u, 0u, 0u};      // (a caller's stream is not waited for: its counts stay 0)
     if (n_rays == 0u) { query_stats(ctx, ql, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const StreamChoice sc = stream_of(dc, hip_stream, flags);
-    uint32_t counts[3] = {0u, 0u, 0u};
-    auto body = [&]() -> int32_t {
+    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         int32_t r = query_enqueue(ctx, dc, sc.stream, d_rays, n_rays, mode, d_hits, sc.own, &ql);
         if (r != BRT_OK || !sc.own) return r;
         HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
         HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    query_stats(ctx, ql, rebuilt, sc.own ? counts : nullptr, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) query_stats(ctx, ql, rebuilt, counts, out_stats8);
+    return rc;
     });
 }
 
@@ -263,18 +238,11 @@ int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t
     int32_t rc = query_check(ctx, rays, n_rays, mode, origin_bound, hits);
     if (rc != BRT_OK) return rc;
     QueryLaunch ql{};
-    uint32_t rebuilt = 0u;
+    uint32_t rebuilt = 0u, counts[3] = {0u, 0u, 0u};
     if (n_rays == 0u) { query_stats(ctx, ql, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    uint32_t counts[3] = {0u, 0u, 0u};
-    auto body = [&]() -> int32_t {
+    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
         const size_t bytes = (size_t)n_rays * 32u;
-        if (dc.qrays_cap < bytes || dc.qhits_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));   // (the staging buffers grow only when no query uses them)
-        int32_t r = ensure(ctx, &dc.d_qrays, &dc.qrays_cap, bytes);
-        if (r == BRT_OK) r = ensure(ctx, &dc.d_qhits, &dc.qhits_cap, bytes);
+        int32_t r = staged(ctx, dc, {{&dc.d_qrays, &dc.qrays_cap, bytes}, {&dc.d_qhits, &dc.qhits_cap, bytes}});
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
         HIP_TRY(ctx, hipMemcpyAsync(dc.d_qrays, rays, bytes, hipMemcpyHostToDevice, dc.stream));
@@ -285,11 +253,9 @@ int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t
         HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    query_stats(ctx, ql, rebuilt, counts, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) query_stats(ctx, ql, rebuilt, counts, out_stats8);
+    return rc;
     });
 }
 

@@ -1,5 +1,6 @@
 // brt_api_radiance.cpp -- radiance queries (brt_radiance.hip; DESIGN.md "Radiance queries") on the first device: path-traced colour
-// for a list of the caller's rays.  Reach, refusal bound, sphere numbering and staging buffers are the ray queries' (brt_api_query.cpp).
+// for a list of the caller's rays.  Reach, refusal bound, sphere numbering, staging buffers and launch plan are the ray queries'
+// (brt_api_query.cpp); the skeleton of a list call is brt_frame.h's (with_reach, staged, list_stats8).
 #include "brt_frame.h"
 
 using namespace brt;
@@ -9,28 +10,6 @@ namespace {
 // The default rule streams from this many entries on: below one streaming workgroup's lanes a persistent launch has nothing to refill,
 // and every workgroup of it pays for staging the scene
 constexpr uint32_t kRadianceStreamMin = BRT_BLOCK;
-
-// Which form a list takes and the streaming form's launch shape (plan_stream).  BRT_RADIANCE_FORM 1 / 2 force the plain / the streaming
-// form; else a list of at least kRadianceStreamMin entries streams where the scene or the top of its tree is staged in LDS.
-void plan_radiance(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_rays, RadianceLaunch* rl) {
-    const uint32_t form = ctx->knobs[K_RADIANCE_FORM];
-    rl->scene = dc.view;
-    rl->scene.lds_pairs = 0u;
-    rl->form = RADIANCE_PLAIN;
-    rl->scene_mode = SCENE_GLOBAL;
-    rl->grid = rl->block = 0u;
-    rl->lds_bytes = 0;
-    if (!list_streams(form, kRadianceStreamMin, n_rays)) return;
-    // waves per SIMD where nothing is staged: 114 VGPRs with the hand-written loop (4), 89 without (5)
-    const StreamPlan sp = plan_stream(ctx, dc, n_rays, 4u, 5u);
-    if (form != 2u && sp.scene_mode == SCENE_GLOBAL) return;      // (no LDS form: 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE)
-    rl->form = RADIANCE_STREAM;
-    rl->scene = sp.scene;
-    rl->scene_mode = sp.scene_mode;
-    rl->grid = sp.grid;
-    rl->block = sp.block;
-    rl->lds_bytes = sp.lds_bytes;
-}
 
 // the control words of the first device (DeviceCtx::d_radctl), for work behind ev_q
 int32_t radiance_ctl(brt_ctx* ctx, DeviceCtx& dc) {
@@ -47,7 +26,11 @@ int32_t brt::radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, c
     int32_t rc = radiance_ctl(ctx, dc);
     if (rc != BRT_OK) return rc;
     HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    plan_radiance(ctx, dc, n_rays, rl);
+    // The form: BRT_RADIANCE_FORM 1 / 2 force the plain / the streaming form; else a list of at least kRadianceStreamMin entries streams
+    // where the scene or the top of its tree is staged in LDS (no LDS form: 32-bit descriptors, BRT_FORCE_GLOBAL_SCENE).  Waves per SIMD
+    // where nothing is staged: 114 VGPRs with the hand-written loop (4), 89 without (5)
+    const uint32_t form = ctx->knobs[K_RADIANCE_FORM];
+    plan_list(ctx, dc, n_rays, list_streams(form, kRadianceStreamMin, n_rays), 4u, 5u, form != 2u, rl);
     const uint32_t* rmap = nullptr;
     rc = query_rmap(ctx, dc, stream, &rmap);
     if (rc != BRT_OK) return rc;
@@ -62,7 +45,7 @@ int32_t brt::radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, c
     ra.stat = counted ? reinterpret_cast<unsigned long long*>(dc.d_radctl) : nullptr;
     ra.counter = dc.d_radctl + 8;
     rl->stream = stream;
-    if (counted || rl->form == RADIANCE_STREAM) HIP_TRY(ctx, hipMemsetAsync(dc.d_radctl, 0, 64, stream));
+    if (counted || rl->form == LIST_STREAM) HIP_TRY(ctx, hipMemsetAsync(dc.d_radctl, 0, 64, stream));
     HIP_TRY(ctx, launch_radiance(*rl));
     HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
     return BRT_OK;
@@ -74,7 +57,7 @@ int32_t radiance_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t
                        const void* out) {
     if (samples < 1u || samples > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "samples must be in [1, 65535]");
     if (bounces > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "bounces must be in [0, 65535]");
-    if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    if (const int32_t rc = origin_bound_check(ctx, origin_bound)) return rc;
     if (n_rays > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_rays too large");
     if (n_rays != 0u && (!rays || !out)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "rays / out is null");
     if (n_rays != 0u && overlaps(rays, (size_t)n_rays * 32u, out, (size_t)n_rays * 32u))
@@ -86,18 +69,7 @@ int32_t radiance_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t
 }
 
 void radiance_stats(const brt_ctx* ctx, const RadianceLaunch& rl, uint32_t rebuilt, const unsigned long long* counts3, uint64_t* out8) {
-    if (!out8) return;
-    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
-    uint32_t reach_bits;
-    std::memcpy(&reach_bits, &reach, 4);
-    out8[0] = counts3 ? counts3[0] : 0u;
-    out8[1] = counts3 ? counts3[1] : 0u;
-    out8[2] = counts3 ? counts3[2] : 0u;
-    out8[3] = rebuilt;
-    out8[4] = reach_bits;
-    out8[5] = (uint64_t)rl.form;
-    out8[6] = rl.form == RADIANCE_STREAM ? rl.grid : (rl.args.n_rays + 255u) / 256u;
-    out8[7] = 0u;
+    list_stats8(ctx, counts3, rebuilt, rl.form, list_groups(rl, rl.args.n_rays), out8);
 }
 
 }  // namespace
@@ -108,29 +80,22 @@ int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_ra
                                  void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
     return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
-    int32_t rc = radiance_check(ctx, d_rays, n_rays, samples, bounces, origin_bound, d_out);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
+    if (rc == BRT_OK) rc = radiance_check(ctx, d_rays, n_rays, samples, bounces, origin_bound, d_out);
     if (rc != BRT_OK) return rc;
     RadianceLaunch rl{};
     uint32_t rebuilt = 0u;
+    unsigned long long counts[3] = {0u, 0u, 0u};      // (a caller's stream is not waited for: its counts stay 0)
     if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const StreamChoice sc = stream_of(dc, hip_stream, flags);
-    unsigned long long counts[3] = {0u, 0u, 0u};
-    auto body = [&]() -> int32_t {
+    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         int32_t r = radiance_enqueue(ctx, dc, sc.stream, d_rays, n_rays, samples, bounces, d_out, sc.own, &rl);
         if (r != BRT_OK || !sc.own) return r;
         HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_radctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
         HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    radiance_stats(ctx, rl, rebuilt, sc.own ? counts : nullptr, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) radiance_stats(ctx, rl, rebuilt, counts, out_stats8);
+    return rc;
     });
 }
 
@@ -142,17 +107,11 @@ int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint3
     if (rc != BRT_OK) return rc;
     RadianceLaunch rl{};
     uint32_t rebuilt = 0u;
-    if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
     unsigned long long counts[3] = {0u, 0u, 0u};
-    auto body = [&]() -> int32_t {
+    if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
+    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
         const size_t bytes = (size_t)n_rays * 32u;
-        if (dc.qrays_cap < bytes || dc.qhits_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));   // (the staging buffers grow only when no list uses them)
-        int32_t r = ensure(ctx, &dc.d_qrays, &dc.qrays_cap, bytes);
-        if (r == BRT_OK) r = ensure(ctx, &dc.d_qhits, &dc.qhits_cap, bytes);
+        int32_t r = staged(ctx, dc, {{&dc.d_qrays, &dc.qrays_cap, bytes}, {&dc.d_qhits, &dc.qhits_cap, bytes}});
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
         HIP_TRY(ctx, hipMemcpyAsync(dc.d_qrays, rays, bytes, hipMemcpyHostToDevice, dc.stream));
@@ -163,11 +122,9 @@ int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint3
         HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    radiance_stats(ctx, rl, rebuilt, counts, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) radiance_stats(ctx, rl, rebuilt, counts, out_stats8);
+    return rc;
     });
 }
 

@@ -1,18 +1,13 @@
 // brt_api_volume.cpp -- irradiance volumes (brt_volume.h, brt_volume.hip; DESIGN.md "Irradiance volumes") on the first device: a regular
 // lattice of light probes baked in one call, and lists of {position, normal} shaded from the baked records.  The bake is the light
 // probes' (brt_api_probe.cpp bake_enqueue) over probes that k_volume_probes writes; streams, ordering behind ev_q and the staging rule
-// are those of the probe step exports.
+// are those of every list call (brt_frame.h: with_reach, with_list_call, staged, list_step_run).
 #include "brt_frame.h"
 #include "brt_volume.h"
 
 using namespace brt;
 
 namespace {
-
-int32_t volume_flags_check(brt_ctx* ctx, uint32_t flags) {
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
-    return BRT_OK;
-}
 
 // the kernels read and write whole 16-byte words: a DEVICE buffer of the caller's must be 16-byte aligned (hipMalloc's are)
 int32_t device_aligned(brt_ctx* ctx, std::initializer_list<const void*> ptrs) {
@@ -83,31 +78,10 @@ int32_t volume_sample_enqueue(brt_ctx* ctx, hipStream_t stream, const VolumeDesc
     return BRT_OK;
 }
 
-// one kernel alone on the call's stream: behind ev_q, recording ev_q; the own stream synchronises
-template <class Enqueue>
-int32_t volume_step_run(brt_ctx* ctx, void* hip_stream, uint32_t flags, Enqueue&& enqueue) {
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const StreamChoice sc = stream_of(dc, hip_stream, flags);
-    auto body = [&]() -> int32_t {
-        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_q, 0));
-        const int32_t r = enqueue(sc.stream);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));
-        if (sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
-    };
-    const int32_t rc = body();
-    if (rc != BRT_OK) drain_all_streams(ctx);
-    return rc;
-}
-
-// the lattice's probes in the context's buffer for work on `stream`, behind ev_q and recorded in it; the buffer grows only when no list
-// uses it
+// the lattice's probes in the context's buffer (`staged`) for work on `stream`, behind ev_q and recorded in it
 int32_t volume_probes_staged(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const VolumeDesc& v, uint32_t n_probes) {
     const size_t bytes = (size_t)n_probes * 16u;
-    if (dc.volume_probes_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    int32_t rc = ensure(ctx, &dc.d_volume_probes, &dc.volume_probes_cap, bytes);
+    int32_t rc = staged(ctx, dc, {{&dc.d_volume_probes, &dc.volume_probes_cap, bytes}});
     if (rc != BRT_OK) return rc;
     HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
     rc = volume_probes_enqueue(ctx, stream, v, n_probes, dc.d_volume_probes);
@@ -168,13 +142,13 @@ int32_t brt_volume_probes_device(brt_ctx* ctx, const void* volume48, void* d_pro
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     VolumeDesc v;
     uint32_t n_probes = 0u;
-    int32_t rc = volume_flags_check(ctx, flags);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = volume_check(ctx, volume48, &v, &n_probes);
     if (rc != BRT_OK) return rc;
     if (!d_probes) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null device pointer");
     rc = device_aligned(ctx, {d_probes});
     if (rc != BRT_OK) return rc;
-    return volume_step_run(ctx, hip_stream, flags, [&](hipStream_t stream) { return volume_probes_enqueue(ctx, stream, v, n_probes, d_probes); });
+    return list_step_run(ctx, hip_stream, flags, [&](DeviceCtx&, hipStream_t stream) { return volume_probes_enqueue(ctx, stream, v, n_probes, d_probes); });
     });
 }
 
@@ -184,27 +158,20 @@ int32_t brt_bake_volume_device(brt_ctx* ctx, const void* volume48, uint32_t n_di
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     VolumeDesc v;
     uint32_t n_probes = 0u, rebuilt = 0u;
-    int32_t rc = volume_flags_check(ctx, flags);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = volume_bake_check(ctx, volume48, n_dirs, bounces, origin_bound, d_records, &v, &n_probes);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_records});
     if (rc != BRT_OK) return rc;
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const StreamChoice sc = stream_of(dc, hip_stream, flags);
     BakeRun run;
-    auto body = [&]() -> int32_t {
+    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         int32_t r = volume_probes_staged(ctx, dc, sc.stream, v, n_probes);
         if (r == BRT_OK) r = bake_enqueue(ctx, dc, sc.stream, dc.d_volume_probes, n_probes, n_dirs, bounces, v.basis, d_records, sc.own, &run);
         if (r != BRT_OK || !sc.own) return r;
         HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    bake_stats(ctx, run, rebuilt, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
+    return rc;
     });
 }
 
@@ -216,15 +183,10 @@ int32_t brt_bake_volume(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uin
     uint32_t n_probes = 0u, rebuilt = 0u;
     int32_t rc = volume_bake_check(ctx, volume48, n_dirs, bounces, origin_bound, records, &v, &n_probes);
     if (rc != BRT_OK) return rc;
-    rc = ensure_query_reach(ctx, origin_bound, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
     BakeRun run;
-    auto body = [&]() -> int32_t {
+    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
         const size_t bytes = (size_t)n_probes * 128u;
-        if (dc.volume_io_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-        int32_t r = ensure(ctx, &dc.d_volume_io, &dc.volume_io_cap, bytes);
+        int32_t r = staged(ctx, dc, {{&dc.d_volume_io, &dc.volume_io_cap, bytes}});
         if (r == BRT_OK) r = volume_probes_staged(ctx, dc, dc.stream, v, n_probes);
         if (r == BRT_OK) r = bake_enqueue(ctx, dc, dc.stream, dc.d_volume_probes, n_probes, n_dirs, bounces, v.basis, dc.d_volume_io, true, &run);
         if (r != BRT_OK) return r;
@@ -232,11 +194,9 @@ int32_t brt_bake_volume(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uin
         HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the buffer)
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    bake_stats(ctx, run, rebuilt, out_stats8);
-    return BRT_OK;
+    });
+    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
+    return rc;
     });
 }
 
@@ -246,12 +206,12 @@ int32_t brt_sample_volume_device(brt_ctx* ctx, const void* volume48, const void*
     if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     VolumeDesc v;
     uint32_t n_probes = 0u;
-    int32_t rc = volume_flags_check(ctx, flags);
+    int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = volume_check(ctx, volume48, &v, &n_probes);
     if (rc == BRT_OK) rc = sample_check(ctx, n_probes, d_records, d_points, n_points, d_out);
     if (rc == BRT_OK && n_points != 0u) rc = device_aligned(ctx, {d_records, d_points, d_out});
     if (rc != BRT_OK || n_points == 0u) return rc;
-    return volume_step_run(ctx, hip_stream, flags, [&](hipStream_t stream) {
+    return list_step_run(ctx, hip_stream, flags, [&](DeviceCtx&, hipStream_t stream) {
         return volume_sample_enqueue(ctx, stream, v, d_records, d_points, n_points, d_out);
     });
     });
@@ -265,14 +225,11 @@ int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* record
     int32_t rc = volume_check(ctx, volume48, &v, &n_probes);
     if (rc == BRT_OK) rc = sample_check(ctx, n_probes, records, points, n_points, out);
     if (rc != BRT_OK || n_points == 0u) return rc;
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    auto body = [&]() -> int32_t {
-        // the records, the points and the samples on the device: one buffer; it grows only when no list uses it
+    return with_list_call(ctx, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
+        // the records, the points and the samples on the device: one buffer
         const size_t rec_bytes = (size_t)n_probes * 128u, pt_bytes = (size_t)n_points * 32u, out_bytes_ = (size_t)n_points * 16u;
         const size_t pt_off = align256(rec_bytes), out_off = pt_off + align256(pt_bytes), bytes = out_off + out_bytes_;
-        if (dc.volume_io_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-        int32_t r = ensure(ctx, &dc.d_volume_io, &dc.volume_io_cap, bytes);
+        int32_t r = staged(ctx, dc, {{&dc.d_volume_io, &dc.volume_io_cap, bytes}});
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
         HIP_TRY(ctx, hipMemcpyAsync(dc.d_volume_io, records, rec_bytes, hipMemcpyHostToDevice, dc.stream));
@@ -283,10 +240,7 @@ int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* record
         HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;
-    };
-    rc = body();
-    if (rc != BRT_OK) drain_all_streams(ctx);
-    return rc;
+    });
     });
 }
 

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <string>
 #include <vector>
@@ -111,16 +112,12 @@ int32_t render_frame_device(brt_ctx* ctx, const void* camera80, const void* wind
                             brt_stats* stats);
 
 // ---- brt_api_query.cpp ----
-// The launch shape of a streaming kernel (k_query_stream, k_trace_pixels_stream) over n_items: what it stages in LDS, its block and its
-// fixed grid.  waves_by_hand / waves_other: the waves per SIMD its registers admit where nothing is staged -- of the instantiation that
-// holds the hand-written walk loop (16-bit descriptors, simple tree) and of the others.
-struct StreamPlan {
-    DeviceSceneView scene;       // (lds_pairs set for SCENE_LDS_TOP)
-    int scene_mode;              // SceneMode
-    uint32_t grid, block;
-    size_t lds_bytes;            // trace_lds_bytes(scene, scene_mode, block, 0)
-};
-StreamPlan plan_stream(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, uint32_t waves_by_hand, uint32_t waves_other);
+// The launch of a list kernel over n_items (brt_kernels.h StreamLaunch): the plain form, or -- with `streams` -- the streaming form in the
+// launch shape of plan_stream: what it stages in LDS, its block and its fixed grid.  waves_by_hand / waves_other: the waves per SIMD the
+// kernel's registers admit where nothing is staged -- of the instantiation that holds the hand-written walk loop (16-bit descriptors,
+// simple tree) and of the others.  need_lds: where nothing can be staged the list takes the plain form after all.
+void plan_list(const brt_ctx* ctx, const DeviceCtx& dc, uint32_t n_items, bool streams, uint32_t waves_by_hand, uint32_t waves_other,
+               bool need_lds, StreamLaunch* sl);
 // What lists of caller rays share (ray queries, radiance queries): the largest origin 1-norm the resident tree covers (+INF: any; < 0:
 // none); origin_bound > 0: a callee-built tree's reach raised, if needed, to what origins of that 1-norm need; the form rule of a list
 // of n rays (knob value 1 / 2: plain / streaming, else streaming from stream_min rays on, 0: never); the resident -> caller sphere map
@@ -132,7 +129,7 @@ int32_t query_rmap(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const uint32
 
 // ---- brt_api_radiance.cpp ----
 // One radiance list (brt_radiance.h) on `stream` of the first device, behind the previous list or query of the context (ev_q, which it
-// records); the form is plan_radiance's, reported in *rl.  counted: the three counts are gathered in dc.d_radctl.
+// records); the form is reported in *rl.  counted: the three counts are gathered in dc.d_radctl.
 int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_rays, uint32_t n_rays, uint32_t samples,
                          uint32_t bounces, void* d_out, bool counted, RadianceLaunch* rl);
 
@@ -180,5 +177,83 @@ int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const De
                     uint32_t out_format, hipStream_t stream, uint32_t flags, const BlendPost& bp);
 bool blend_post_on(uint32_t level, uint32_t flags);
 int32_t post_flags_check(brt_ctx* ctx, uint32_t level, uint32_t flags);
+
+// ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp, brt_api_pixels.cpp) ----
+inline int32_t caller_stream_flags_check(brt_ctx* ctx, uint32_t flags) {
+    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
+    return BRT_OK;
+}
+inline int32_t origin_bound_check(brt_ctx* ctx, float origin_bound) {
+    if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    return BRT_OK;
+}
+
+// The context's staging buffers of a call, each of at least its `bytes`.  Their users run one behind the other, ordered by ev_q, so a
+// buffer grows only once no list uses it: ev_q is waited for on the host if any of them is short.
+struct StagedBuf { char** ptr; size_t* cap; size_t bytes; };
+inline int32_t staged(brt_ctx* ctx, DeviceCtx& dc, std::initializer_list<StagedBuf> bufs) {
+    for (const StagedBuf& b : bufs)
+        if (*b.cap < b.bytes) { HIP_TRY(ctx, hipEventSynchronize(dc.ev_q)); break; }
+    for (const StagedBuf& b : bufs) {
+        const int32_t rc = ensure(ctx, b.ptr, b.cap, b.bytes);
+        if (rc != BRT_OK) return rc;
+    }
+    return BRT_OK;
+}
+
+// A call on the first device: body(dc, sc) with the call's stream (stream_of; the host forms pass nullptr, 0: the context's own).  A
+// failed call leaves nothing in flight on the context's own streams.  with_reach: behind ensure_query_reach, for the calls that trace.
+template <class Body>
+int32_t with_list_call(brt_ctx* ctx, void* hip_stream, uint32_t flags, Body&& body) {
+    DeviceCtx& dc = ctx->devs[0];
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    const int32_t rc = body(dc, stream_of(dc, hip_stream, flags));
+    if (rc != BRT_OK) drain_all_streams(ctx);
+    return rc;
+}
+template <class Body>
+int32_t with_reach(brt_ctx* ctx, float origin_bound, uint32_t* rebuilt, void* hip_stream, uint32_t flags, Body&& body) {
+    const int32_t rc = ensure_query_reach(ctx, origin_bound, rebuilt);
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    return with_list_call(ctx, hip_stream, flags, body);
+}
+
+// One kernel alone on the call's stream: behind(dc, stream) puts the stream behind ev_q (without one: a wait for ev_q; the probe steps
+// pass probe_table), enqueue(dc, stream) launches, ev_q is recorded; the own stream synchronises.
+template <class Behind, class Enqueue>
+int32_t list_step_run(brt_ctx* ctx, void* hip_stream, uint32_t flags, Behind&& behind, Enqueue&& enqueue) {
+    return with_list_call(ctx, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        int32_t r = behind(dc, sc.stream);
+        if (r == BRT_OK) r = enqueue(dc, sc.stream);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));
+        if (sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+        return BRT_OK;
+    });
+}
+template <class Enqueue>
+int32_t list_step_run(brt_ctx* ctx, void* hip_stream, uint32_t flags, Enqueue&& enqueue) {
+    return list_step_run(ctx, hip_stream, flags, [&](DeviceCtx& dc, hipStream_t stream) -> int32_t {
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+        return BRT_OK;
+    }, enqueue);
+}
+
+// The out_stats8 of a list call: three counts (nullptr: not gathered), tree rebuilt, the callee-built tree's reach (bits), the form, and
+// the family's word 6.  list_groups: the workgroups of a launch over n items.
+inline uint32_t list_groups(const StreamLaunch& sl, uint32_t n) { return sl.form == LIST_STREAM ? sl.grid : (n + 255u) / 256u; }
+template <class Count>
+void list_stats8(const brt_ctx* ctx, const Count* counts3, uint32_t rebuilt, int form, uint64_t word6, uint64_t* out8) {
+    if (!out8) return;
+    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
+    uint32_t reach_bits;
+    std::memcpy(&reach_bits, &reach, 4);
+    for (uint32_t i = 0; i < 3u; i++) out8[i] = counts3 ? counts3[i] : 0u;
+    out8[3] = rebuilt;
+    out8[4] = reach_bits;
+    out8[5] = (uint64_t)form;
+    out8[6] = word6;
+    out8[7] = 0u;
+}
 
 }  // namespace brt

@@ -29,6 +29,18 @@ struct TraceLaunch {
     hipStream_t stream;
 };
 
+// What the launches of the list kernels share (brt_query.h, brt_radiance.h, brt_pixels.h): the form, and the streaming form's shape
+// (plan_list, brt_api_query.cpp; launch_stream, brt_stream.h).  The form's values are reported in stats.
+enum ListForm : int { LIST_PLAIN = 0, LIST_STREAM = 1 };
+struct StreamLaunch {
+    DeviceSceneView scene;      // (lds_pairs set for SCENE_LDS_TOP)
+    int form;                   // ListForm
+    int scene_mode;             // streaming form: SceneMode
+    uint32_t grid, block;       // streaming form
+    size_t lds_bytes;           // streaming form: trace_lds_bytes(scene, scene_mode, block, 0)
+    hipStream_t stream;
+};
+
 // rows: with the scratch of the row-mode walk of thin waves (SCENE_LDS only; FrameParams::rows_on)
 size_t trace_lds_bytes(const DeviceSceneView& sv, int scene_mode, uint32_t block, uint32_t pool_cap, uint32_t hist_words = 0, bool rows = false);
 constexpr uint32_t POOL_RECORD_BYTES = 96;   // one path in the drain pool (k_trace_persistent)

@@ -5,7 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "brt_layout.h"
+#include "brt_kernels.h"
 
 namespace brt {
 
@@ -23,17 +23,9 @@ struct PixelsArgs {
     uint32_t* counter;          // streaming form: the batch counter, zeroed by the caller
 };
 
-enum PixelsForm : int { PIXELS_PLAIN = 0, PIXELS_STREAM = 1 };
-
-struct PixelsLaunch {
-    DeviceSceneView scene;      // (lds_pairs set for SCENE_LDS_TOP)
+struct PixelsLaunch : StreamLaunch {
     FrameParams frame;          // one part, level 3, the default policy
     PixelsArgs args;
-    int form;                   // PixelsForm
-    int scene_mode;             // streaming form: SceneMode
-    uint32_t grid, block;       // streaming form
-    size_t lds_bytes;           // streaming form: trace_lds_bytes(scene, scene_mode, block, 0)
-    hipStream_t stream;
 };
 hipError_t launch_trace_pixels(const PixelsLaunch& pl);
 

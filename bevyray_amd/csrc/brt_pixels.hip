@@ -6,18 +6,19 @@
 // k_trace_pixels_plain<D16>                one thread per entry: k_trace_simple's loop over a list, the scene in global memory, a private
 //                                          stack.  Every scene representation and tree.
 // k_trace_pixels_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in
-//                                          LDS as k_query_stream stages it, the stacks in LDS, so the hand-written walk loops serve it.
+//                                          LDS (stream_stage, brt_stream.h), the stacks in LDS, so the hand-written walk loops serve it.
 //                                          A lane carries one path.  A round: the wave takes entries from the batch counter (one
 //                                          fetch-add) for the lanes whose pixel has ended, walk_run for all lanes, and the lanes whose
 //                                          walk has ended shade their segment and begin the next one, end the sample or end the pixel.
 // Both forms write the same bytes: an entry's result depends on its pixel alone.  No atomic touches a result.
+// What the streaming form shares with k_query_stream and k_radiance_stream, its launch included: brt_stream.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
 #include "brt_pixels.h"
 #include "brt_store.h"
-#include "brt_trace.h"
+#include "brt_stream.h"
 
 namespace brt {
 
@@ -75,19 +76,6 @@ BRT_DEV float4 pixels_value(const FrameParams& fp, const PixelState& ps) {
     return make_float4(ps.sum.x / fp.spp_f, ps.sum.y / fp.spp_f, ps.sum.z / fp.spp_f, 1.0f);
 }
 
-BRT_DEV ScenePtrs pixels_scene_global(const DeviceSceneView& sv) {      // the scene in global memory, as k_trace_simple walks it
-    ScenePtrs sc = {};
-    sc.pairs = reinterpret_cast<const char*>(sv.pairs);
-    sc.pairs_far = sc.pairs;
-    sc.boxes_ordered = sv.boxes_ordered != 0u;
-    sc.spheres = reinterpret_cast<const float4*>(sv.spheres);
-    sc.sphere_material = sv.sphere_material;
-    sc.materials = reinterpret_cast<const float4*>(sv.materials);
-    sc.sphere_mats = reinterpret_cast<const float4*>(sv.sphere_mats);
-    sc.leaf_table = reinterpret_cast<const uint2*>(sv.leaf_table);
-    return sc;
-}
-
 }  // namespace
 
 // ---- plain form ----------------------------------------------------------------------------------------------------------------------
@@ -102,7 +90,7 @@ __global__ __launch_bounds__(256) void k_trace_pixels_plain(DeviceSceneView sv, 
             pixels_refuse(pa, i);
             refused = 1u;
         } else {
-            const ScenePtrs sc = pixels_scene_global(sv);
+            const ScenePtrs sc = scene_global(sv);
             HitCounters hc = {};
             PixelState ps;
             pixels_begin(fp, p, ps);
@@ -136,53 +124,14 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneVi
     static_assert(MODE == SCENE_GLOBAL || D16, "a scene staged in LDS always uses 16-bit descriptors");
     using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
     using DS = Desc<D16>;
-    // one dynamic array, carved as k_trace_persistent and k_query_stream carve it: the hand-written loops address the pair records from
-    // LDS address 0, so they come first (every carve offset is a multiple of 16), then spheres, leaf table and the stacks
     extern __shared__ uint4 smem[];
-    ScenePtrs sc = pixels_scene_global(sv);
-    StackT* stacks;
-    if (MODE == SCENE_LDS) {
-        const uint32_t pair_granules = (uint32_t)(pair_array_bytes(sv.n_pairs) / 16);
-        float4* p = reinterpret_cast<float4*>(smem);
-        float4* l_pairs = p; p += pair_granules;
-        float4* l_sp = p; p += sv.n_models;
-        uint2* l_lt = reinterpret_cast<uint2*>(p);
-        stacks = reinterpret_cast<StackT*>(l_lt + sv.n_leaf_table);
-        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
-        const float4* g_sp = reinterpret_cast<const float4*>(sv.spheres);
-        const uint2* g_lt = reinterpret_cast<const uint2*>(sv.leaf_table);
-        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
-        for (uint32_t i = threadIdx.x; i < sv.n_models; i += blockDim.x) l_sp[i] = g_sp[i];
-        for (uint32_t i = threadIdx.x; i < sv.n_leaf_table; i += blockDim.x) l_lt[i] = g_lt[i];
-        sc.pairs = reinterpret_cast<const char*>(l_pairs);
-        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
-        sc.sph_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_sp);
-        sc.spheres = l_sp;
-        sc.leaf_table = l_lt;
-    } else if (MODE == SCENE_LDS_TOP) {
-        const uint32_t pair_granules = sv.lds_pairs * PAIR_UNITS;
-        float4* l_pairs = reinterpret_cast<float4*>(smem);
-        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
-        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
-        sc.pairs = reinterpret_cast<const char*>(l_pairs);
-        sc.near_bytes = sv.lds_pairs * PAIR_BYTES;
-        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
-        stacks = reinterpret_cast<StackT*>(l_pairs + pair_granules);
-    } else {
-        stacks = reinterpret_cast<StackT*>(smem);
-    }
-    __syncthreads();
+    ScenePtrs sc = scene_global(sv);
+    StackT* stacks = stream_stage<MODE, StackT>(sv, smem, sc);
     const uint32_t lane = lane_id();
-    const uint32_t wave = threadIdx.x >> 6;
-    // this lane's column of the wave's [entry][64] stack array (16-bit entries: lanes l and l + 32 share a dword, brt_trace.h)
-    const uint32_t stack_col = D16 ? ((lane & 31u) * 2u + (lane >> 5)) : lane;
-    StackT* stk = stacks + wave * ((sv.stack_entries + 2u) * 64u) + stack_col;
+    StackT* stk = stream_stack<D16>(sv, stacks, lane);
     const uint32_t n = pixels_n(pa), frame_px = fp.width * fp.height;
 
-    WalkState<StackT> walk;
-    walk.a = 0.0f; walk.inv = mk3(0.0f, 0.0f, 0.0f); walk.closest = kInf; walk.closest_idx = 0xffffffffu;
-    walk.cur = DS::DONE; walk.sp = stk; walk.n = 0;
-    walk.ox = walk.oy = walk.oz = 0u;
+    WalkState<StackT> walk = walk_idle<D16>(stk);
     PixelState ps = {};
     f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f), tput = mk3(1.0f, 1.0f, 1.0f);
     uint32_t bounce = 0u;
@@ -253,48 +202,21 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneVi
 
 // ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
 
-template <int MODE, bool D, bool S>
-static hipError_t launch_stream_t(const PixelsLaunch& pl) {
-    auto kern = k_trace_pixels_stream<MODE, D, S>;
-    if (MODE == SCENE_LDS || MODE == SCENE_LDS_TOP) {
-        // the hand-written walk loops address the pair records from LDS address 0: the dynamic LDS must start there
-        static const size_t static_lds = [&] {
-            hipFuncAttributes at{};
-            return hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kern)) == hipSuccess ? at.sharedSizeBytes : (size_t)1;
-        }();
-        if (static_lds != 0) return hipErrorInvalidConfiguration;
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.block), pl.lds_bytes, pl.stream, pl.scene, pl.frame, pl.args);
-    return hipGetLastError();
-}
-
-template <int MODE, bool D>
-static hipError_t launch_stream_md(const PixelsLaunch& pl) {
-    return pl.scene.simple_tree ? launch_stream_t<MODE, D, true>(pl) : launch_stream_t<MODE, D, false>(pl);
-}
+struct PixelsStream {
+    template <int MODE, bool D16, bool SIMPLE>
+    static auto kernel() { return k_trace_pixels_stream<MODE, D16, SIMPLE>; }
+};
 
 hipError_t launch_trace_pixels(const PixelsLaunch& pl) {
     if (pl.args.n_pixels == 0u) return hipSuccess;
     if (!pl.args.pixels || !pl.args.out || pl.frame.policy_flags != 0u) return hipErrorInvalidValue;
-    if (pl.form == PIXELS_PLAIN) {
+    if (pl.form == LIST_PLAIN) {
         const dim3 grid((pl.args.n_pixels + 255u) / 256u);
         if (pl.scene.desc16) hipLaunchKernelGGL(k_trace_pixels_plain<true>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
         else hipLaunchKernelGGL(k_trace_pixels_plain<false>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
         return hipGetLastError();
     }
-    if (pl.grid == 0u || pl.block == 0u || (pl.block & 63u) != 0u || pl.block > BRT_BLOCK || !pl.args.counter) return hipErrorInvalidValue;
-    switch (pl.scene_mode) {
-        case SCENE_LDS:
-            if (!pl.scene.desc16) return hipErrorInvalidValue;
-            return launch_stream_md<SCENE_LDS, true>(pl);
-        case SCENE_LDS_TOP:
-            if (!pl.scene.desc16) return hipErrorInvalidValue;
-            return launch_stream_md<SCENE_LDS_TOP, true>(pl);
-        default:
-            return pl.scene.desc16 ? launch_stream_md<SCENE_GLOBAL, true>(pl) : launch_stream_md<SCENE_GLOBAL, false>(pl);
-    }
+    return launch_stream<PixelsStream>(pl, pl.args.counter, pl.frame, pl.args);
 }
 
 }  // namespace brt

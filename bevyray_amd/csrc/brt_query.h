@@ -5,7 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "brt_layout.h"
+#include "brt_kernels.h"
 
 namespace brt {
 
@@ -24,16 +24,8 @@ struct QueryArgs {
 // entered) still walk
 constexpr uint32_t kQueryExitLanes = 32;
 
-enum QueryForm : int { QUERY_PLAIN = 0, QUERY_STREAM = 1 };
-
-struct QueryLaunch {
-    DeviceSceneView scene;      // (lds_pairs set for SCENE_LDS_TOP)
+struct QueryLaunch : StreamLaunch {
     QueryArgs args;
-    int form;                   // QueryForm
-    int scene_mode;             // streaming form: SceneMode
-    uint32_t grid, block;       // streaming form
-    size_t lds_bytes;           // streaming form: trace_lds_bytes(scene, scene_mode, block, 0)
-    hipStream_t stream;
 };
 hipError_t launch_query(const QueryLaunch& ql);
 

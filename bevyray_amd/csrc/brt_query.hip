@@ -5,19 +5,19 @@
 // k_query_plain<D16>                one thread per ray, the scene in global memory, a private stack: what k_denoise_guides does per pixel.
 //                                   Every scene representation and tree.  ANY mode leaves the walk at the first step after which
 //                                   closest < t_max.
-// k_query_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in LDS as
-//                                   k_trace_persistent stages it, the stacks in LDS, so the hand-written walk loops serve it.  A wave takes
+// k_query_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in LDS
+//                                   (stream_stage, brt_stream.h), the stacks in LDS, so the hand-written walk loops serve it.  A wave takes
 //                                   rays from the batch counter for the lanes whose walk has ended and walks on next to the lanes that
 //                                   are still under way (walk_run's early exit and WalkState), instead of waiting for its longest walk.
 //                                   ANY mode ends a lane's walk at the first return of walk_run at which closest < t_max.
 // Both forms write the same bytes: a lane's result depends on its own ray alone.  No atomics touch a result.
+// What the streaming form shares with k_radiance_stream and k_trace_pixels_stream, its launch included: brt_stream.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "brt_device.h"
-#include "brt_kernels.h"
 #include "brt_query.h"
+#include "brt_stream.h"
 
 namespace brt {
 
@@ -30,9 +30,6 @@ struct QueryRay {
     float t_max;
     uint32_t user;
 };
-
-BRT_DEV uint32_t q_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-BRT_DEV uint32_t q_rank(uint64_t mask) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u)); }
 
 BRT_DEV QueryRay query_load(const QueryArgs& qa, uint32_t i) {
     const float4 r0 = qa.rays[2 * (size_t)i], r1 = qa.rays[2 * (size_t)i + 1];
@@ -78,6 +75,7 @@ BRT_DEV bool query_store(const QueryArgs& qa, const DeviceSceneView& sv, const f
     return hit;
 }
 
+// (wave_sum of brt_trace.h sums downwards: lane 0 would hold the same value, from other instructions)
 BRT_DEV uint32_t q_wave_sum(uint32_t v) {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s, 64);
@@ -90,24 +88,11 @@ BRT_DEV void query_count(const QueryArgs& qa, uint32_t walked, uint32_t hits, ui
     walked = q_wave_sum(walked);
     hits = q_wave_sum(hits);
     refused = q_wave_sum(refused);
-    if (q_lane() == 0u) {
+    if (lane_id() == 0u) {
         if (walked) atomicAdd(qa.stat + 0, walked);
         if (hits) atomicAdd(qa.stat + 1, hits);
         if (refused) atomicAdd(qa.stat + 2, refused);
     }
-}
-
-BRT_DEV ScenePtrs query_scene_global(const DeviceSceneView& sv) {      // the scene in global memory, as k_trace_simple walks it
-    ScenePtrs sc = {};
-    sc.pairs = reinterpret_cast<const char*>(sv.pairs);
-    sc.pairs_far = sc.pairs;
-    sc.boxes_ordered = sv.boxes_ordered != 0u;
-    sc.spheres = reinterpret_cast<const float4*>(sv.spheres);
-    sc.sphere_material = sv.sphere_material;
-    sc.materials = reinterpret_cast<const float4*>(sv.materials);
-    sc.sphere_mats = reinterpret_cast<const float4*>(sv.sphere_mats);
-    sc.leaf_table = reinterpret_cast<const uint2*>(sv.leaf_table);
-    return sc;
 }
 
 }  // namespace
@@ -125,7 +110,7 @@ __global__ __launch_bounds__(256) void k_query_plain(DeviceSceneView sv, QueryAr
             query_store_miss(qa, i, refusal, r.user);
             refused = 1u;
         } else {
-            const ScenePtrs sc = query_scene_global(sv);
+            const ScenePtrs sc = scene_global(sv);
             uint32_t stack[34];   // DONE sentinel + 32 entries + one spare
             HitCounters hc = {};
             float t;
@@ -166,50 +151,12 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_query_stream(DeviceSceneView sv, 
     using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
     using DS = Desc<D16>;
     extern __shared__ uint4 smem[];
-    // the carve of k_trace_persistent (brt_trace.h): the hand-written loops address the pair records from LDS address 0
-    ScenePtrs sc = query_scene_global(sv);
-    StackT* stacks;
-    if (MODE == SCENE_LDS) {
-        const uint32_t pair_granules = (uint32_t)(pair_array_bytes(sv.n_pairs) / 16);
-        float4* p = reinterpret_cast<float4*>(smem);
-        float4* l_pairs = p; p += pair_granules;
-        float4* l_sp = p; p += sv.n_models;
-        uint2* l_lt = reinterpret_cast<uint2*>(p);
-        stacks = reinterpret_cast<StackT*>(l_lt + sv.n_leaf_table);
-        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
-        const float4* g_sp = reinterpret_cast<const float4*>(sv.spheres);
-        const uint2* g_lt = reinterpret_cast<const uint2*>(sv.leaf_table);
-        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
-        for (uint32_t i = threadIdx.x; i < sv.n_models; i += blockDim.x) l_sp[i] = g_sp[i];
-        for (uint32_t i = threadIdx.x; i < sv.n_leaf_table; i += blockDim.x) l_lt[i] = g_lt[i];
-        sc.pairs = reinterpret_cast<const char*>(l_pairs);
-        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
-        sc.sph_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_sp);
-        sc.spheres = l_sp;
-        sc.leaf_table = l_lt;
-    } else if (MODE == SCENE_LDS_TOP) {
-        const uint32_t pair_granules = sv.lds_pairs * PAIR_UNITS;
-        float4* l_pairs = reinterpret_cast<float4*>(smem);
-        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
-        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
-        sc.pairs = reinterpret_cast<const char*>(l_pairs);
-        sc.near_bytes = sv.lds_pairs * PAIR_BYTES;
-        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
-        stacks = reinterpret_cast<StackT*>(l_pairs + pair_granules);
-    } else {
-        stacks = reinterpret_cast<StackT*>(smem);
-    }
-    __syncthreads();
-    const uint32_t lane = q_lane();
-    const uint32_t wave = threadIdx.x >> 6;
-    // this lane's column of the wave's [entry][64] stack array (16-bit entries: lanes l and l + 32 share a dword, brt_trace.h)
-    const uint32_t stack_col = D16 ? ((lane & 31u) * 2u + (lane >> 5)) : lane;
-    StackT* stk = stacks + wave * ((sv.stack_entries + 2u) * 64u) + stack_col;
+    ScenePtrs sc = scene_global(sv);
+    StackT* stacks = stream_stage<MODE, StackT>(sv, smem, sc);
+    const uint32_t lane = lane_id();
+    StackT* stk = stream_stack<D16>(sv, stacks, lane);
 
-    WalkState<StackT> walk;
-    walk.a = 0.0f; walk.inv = mk3(0.0f, 0.0f, 0.0f); walk.closest = kInf; walk.closest_idx = 0xffffffffu;
-    walk.cur = DS::DONE; walk.sp = stk; walk.n = 0;
-    walk.ox = walk.oy = walk.oz = 0u;
+    WalkState<StackT> walk = walk_idle<D16>(stk);
     QueryRay r;
     r.o = mk3(0.0f, 0.0f, 0.0f); r.d = mk3(0.0f, 0.0f, 1.0f); r.t_max = kPosInf; r.user = 0u;
     uint32_t ray_i = 0u;
@@ -226,7 +173,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_query_stream(DeviceSceneView sv, 
             if (lane == 0u) base = atomicAdd(qa.counter, cnt);
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
             exhausted = base >= qa.n_rays || qa.n_rays - base <= cnt;
-            const uint32_t mine = base + q_rank(idle);
+            const uint32_t mine = base + mbcnt64(idle);
             if (!in_flight && base < qa.n_rays && mine < qa.n_rays) {
                 r = query_load(qa, mine);
                 ray_i = mine;
@@ -257,47 +204,20 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_query_stream(DeviceSceneView sv, 
 
 // ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
 
-template <int MODE, bool D, bool S>
-static hipError_t launch_stream_t(const QueryLaunch& ql) {
-    auto kern = k_query_stream<MODE, D, S>;
-    if (MODE == SCENE_LDS || MODE == SCENE_LDS_TOP) {
-        // the hand-written walk loops address the pair records from LDS address 0: the dynamic LDS must start there
-        static const size_t static_lds = [&] {
-            hipFuncAttributes at{};
-            return hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kern)) == hipSuccess ? at.sharedSizeBytes : (size_t)1;
-        }();
-        if (static_lds != 0) return hipErrorInvalidConfiguration;
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ql.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ql.grid), dim3(ql.block), ql.lds_bytes, ql.stream, ql.scene, ql.args);
-    return hipGetLastError();
-}
-
-template <int MODE, bool D>
-static hipError_t launch_stream_md(const QueryLaunch& ql) {
-    return ql.scene.simple_tree ? launch_stream_t<MODE, D, true>(ql) : launch_stream_t<MODE, D, false>(ql);
-}
+struct QueryStream {
+    template <int MODE, bool D16, bool SIMPLE>
+    static auto kernel() { return k_query_stream<MODE, D16, SIMPLE>; }
+};
 
 hipError_t launch_query(const QueryLaunch& ql) {
     if (ql.args.n_rays == 0u) return hipSuccess;
-    if (ql.form == QUERY_PLAIN) {
+    if (ql.form == LIST_PLAIN) {
         const dim3 grid((ql.args.n_rays + 255u) / 256u);
         if (ql.scene.desc16) hipLaunchKernelGGL(k_query_plain<true>, grid, dim3(256), 0, ql.stream, ql.scene, ql.args);
         else hipLaunchKernelGGL(k_query_plain<false>, grid, dim3(256), 0, ql.stream, ql.scene, ql.args);
         return hipGetLastError();
     }
-    if (ql.grid == 0u || ql.block == 0u || (ql.block & 63u) != 0u || ql.block > BRT_BLOCK || !ql.args.counter) return hipErrorInvalidValue;
-    switch (ql.scene_mode) {
-        case SCENE_LDS:
-            if (!ql.scene.desc16) return hipErrorInvalidValue;
-            return launch_stream_md<SCENE_LDS, true>(ql);
-        case SCENE_LDS_TOP:
-            if (!ql.scene.desc16) return hipErrorInvalidValue;
-            return launch_stream_md<SCENE_LDS_TOP, true>(ql);
-        default:
-            return ql.scene.desc16 ? launch_stream_md<SCENE_GLOBAL, true>(ql) : launch_stream_md<SCENE_GLOBAL, false>(ql);
-    }
+    return launch_stream<QueryStream>(ql, ql.args.counter, ql.args);
 }
 
 }  // namespace brt

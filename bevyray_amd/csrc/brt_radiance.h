@@ -5,7 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "brt_layout.h"
+#include "brt_kernels.h"
 
 namespace brt {
 
@@ -22,16 +22,8 @@ struct RadianceArgs {
     uint32_t* counter;          // streaming form: the batch counter, zeroed by the caller
 };
 
-enum RadianceForm : int { RADIANCE_PLAIN = 0, RADIANCE_STREAM = 1 };
-
-struct RadianceLaunch {
-    DeviceSceneView scene;      // (lds_pairs set for SCENE_LDS_TOP)
+struct RadianceLaunch : StreamLaunch {
     RadianceArgs args;
-    int form;                   // RadianceForm
-    int scene_mode;             // streaming form: SceneMode
-    uint32_t grid, block;       // streaming form
-    size_t lds_bytes;           // streaming form: trace_lds_bytes(scene, scene_mode, block, 0)
-    hipStream_t stream;
 };
 hipError_t launch_radiance(const RadianceLaunch& rl);
 

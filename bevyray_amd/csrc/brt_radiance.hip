@@ -11,18 +11,19 @@
 // k_radiance_plain<D16>                one thread per entry, the scene in global memory, a private 34-entry stack: the thread's column
 //                                      of a [34][256] LDS array (no scratch).  Every scene representation and tree.
 // k_radiance_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in LDS
-//                                      as k_trace_pixels_stream / k_query_stream stage it, the stacks in LDS, so the hand-written walk
+//                                      (stream_stage, brt_stream.h), the stacks in LDS, so the hand-written walk
 //                                      loops serve it.  A lane carries one path.  A round: the wave takes entries from the batch counter
 //                                      (one fetch-add) for the lanes whose entry has ended, walk_run for all lanes, and the lanes whose
 //                                      walk has ended shade their segment and begin the next one, end the sample or end the entry.
 // Both forms write the same bytes: an entry's result depends on its own record alone.  No atomic touches a result; a result goes out as
 // two float4 stores.
+// What the streaming form shares with k_query_stream and k_trace_pixels_stream, its launch included: brt_stream.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
 #include "brt_radiance.h"
-#include "brt_trace.h"
+#include "brt_stream.h"
 
 namespace brt {
 
@@ -104,19 +105,6 @@ BRT_DEV FrameParams radiance_frame(const RadianceArgs& ra) {
     return fp;
 }
 
-BRT_DEV ScenePtrs radiance_scene_global(const DeviceSceneView& sv) {      // the scene in global memory, as k_trace_simple walks it
-    ScenePtrs sc = {};
-    sc.pairs = reinterpret_cast<const char*>(sv.pairs);
-    sc.pairs_far = sc.pairs;
-    sc.boxes_ordered = sv.boxes_ordered != 0u;
-    sc.spheres = reinterpret_cast<const float4*>(sv.spheres);
-    sc.sphere_material = sv.sphere_material;
-    sc.materials = reinterpret_cast<const float4*>(sv.materials);
-    sc.sphere_mats = reinterpret_cast<const float4*>(sv.sphere_mats);
-    sc.leaf_table = reinterpret_cast<const uint2*>(sv.leaf_table);
-    return sc;
-}
-
 }  // namespace
 
 // ---- plain form ----------------------------------------------------------------------------------------------------------------------
@@ -136,7 +124,7 @@ __global__ __launch_bounds__(256) void k_radiance_plain(DeviceSceneView sv, Radi
             radiance_store_refused(ra, i, refusal, r.user);
             refused = 1u;
         } else {
-            const ScenePtrs sc = radiance_scene_global(sv);
+            const ScenePtrs sc = scene_global(sv);
             const FrameParams fp = radiance_frame(ra);
             HitCounters hc = {};
             uint32_t* stack = stacks + threadIdx.x;
@@ -170,53 +158,14 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_radiance_stream(DeviceSceneView s
     static_assert(MODE == SCENE_GLOBAL || D16, "a scene staged in LDS always uses 16-bit descriptors");
     using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
     using DS = Desc<D16>;
-    // one dynamic array, carved as k_trace_pixels_stream and k_query_stream carve it: the hand-written loops address the pair records
-    // from LDS address 0, so they come first (every carve offset is a multiple of 16), then spheres, leaf table and the stacks
     extern __shared__ uint4 smem[];
-    ScenePtrs sc = radiance_scene_global(sv);
-    StackT* stacks;
-    if (MODE == SCENE_LDS) {
-        const uint32_t pair_granules = (uint32_t)(pair_array_bytes(sv.n_pairs) / 16);
-        float4* p = reinterpret_cast<float4*>(smem);
-        float4* l_pairs = p; p += pair_granules;
-        float4* l_sp = p; p += sv.n_models;
-        uint2* l_lt = reinterpret_cast<uint2*>(p);
-        stacks = reinterpret_cast<StackT*>(l_lt + sv.n_leaf_table);
-        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
-        const float4* g_sp = reinterpret_cast<const float4*>(sv.spheres);
-        const uint2* g_lt = reinterpret_cast<const uint2*>(sv.leaf_table);
-        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
-        for (uint32_t i = threadIdx.x; i < sv.n_models; i += blockDim.x) l_sp[i] = g_sp[i];
-        for (uint32_t i = threadIdx.x; i < sv.n_leaf_table; i += blockDim.x) l_lt[i] = g_lt[i];
-        sc.pairs = reinterpret_cast<const char*>(l_pairs);
-        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
-        sc.sph_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_sp);
-        sc.spheres = l_sp;
-        sc.leaf_table = l_lt;
-    } else if (MODE == SCENE_LDS_TOP) {
-        const uint32_t pair_granules = sv.lds_pairs * PAIR_UNITS;
-        float4* l_pairs = reinterpret_cast<float4*>(smem);
-        const float4* g_pairs = reinterpret_cast<const float4*>(sv.pairs);
-        for (uint32_t i = threadIdx.x; i < pair_granules; i += blockDim.x) l_pairs[i] = g_pairs[i];
-        sc.pairs = reinterpret_cast<const char*>(l_pairs);
-        sc.near_bytes = sv.lds_pairs * PAIR_BYTES;
-        sc.near_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)reinterpret_cast<char*>(l_pairs);
-        stacks = reinterpret_cast<StackT*>(l_pairs + pair_granules);
-    } else {
-        stacks = reinterpret_cast<StackT*>(smem);
-    }
-    __syncthreads();
+    ScenePtrs sc = scene_global(sv);
+    StackT* stacks = stream_stage<MODE, StackT>(sv, smem, sc);
     const uint32_t lane = lane_id();
-    const uint32_t wave = threadIdx.x >> 6;
-    // this lane's column of the wave's [entry][64] stack array (16-bit entries: lanes l and l + 32 share a dword, brt_trace.h)
-    const uint32_t stack_col = D16 ? ((lane & 31u) * 2u + (lane >> 5)) : lane;
-    StackT* stk = stacks + wave * ((sv.stack_entries + 2u) * 64u) + stack_col;
+    StackT* stk = stream_stack<D16>(sv, stacks, lane);
     const FrameParams fp = radiance_frame(ra);
 
-    WalkState<StackT> walk;
-    walk.a = 0.0f; walk.inv = mk3(0.0f, 0.0f, 0.0f); walk.closest = kInf; walk.closest_idx = 0xffffffffu;
-    walk.cur = DS::DONE; walk.sp = stk; walk.n = 0;
-    walk.ox = walk.oy = walk.oz = 0u;
+    WalkState<StackT> walk = walk_idle<D16>(stk);
     // the entry: its own ray and the walk of it (kept for every sample), its random state, sum and sample number
     f3 o0 = mk3(0.0f, 0.0f, 0.0f), d0 = mk3(0.0f, 0.0f, 1.0f);
     float t0 = kInf;
@@ -298,48 +247,21 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_radiance_stream(DeviceSceneView s
 
 // ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
 
-template <int MODE, bool D, bool S>
-static hipError_t launch_stream_t(const RadianceLaunch& rl) {
-    auto kern = k_radiance_stream<MODE, D, S>;
-    if (MODE == SCENE_LDS || MODE == SCENE_LDS_TOP) {
-        // the hand-written walk loops address the pair records from LDS address 0: the dynamic LDS must start there
-        static const size_t static_lds = [&] {
-            hipFuncAttributes at{};
-            return hipFuncGetAttributes(&at, reinterpret_cast<const void*>(kern)) == hipSuccess ? at.sharedSizeBytes : (size_t)1;
-        }();
-        if (static_lds != 0) return hipErrorInvalidConfiguration;
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl.lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(rl.grid), dim3(rl.block), rl.lds_bytes, rl.stream, rl.scene, rl.args);
-    return hipGetLastError();
-}
-
-template <int MODE, bool D>
-static hipError_t launch_stream_md(const RadianceLaunch& rl) {
-    return rl.scene.simple_tree ? launch_stream_t<MODE, D, true>(rl) : launch_stream_t<MODE, D, false>(rl);
-}
+struct RadianceStream {
+    template <int MODE, bool D16, bool SIMPLE>
+    static auto kernel() { return k_radiance_stream<MODE, D16, SIMPLE>; }
+};
 
 hipError_t launch_radiance(const RadianceLaunch& rl) {
     if (rl.args.n_rays == 0u) return hipSuccess;
     if (!rl.args.rays || !rl.args.out || rl.args.samples == 0u) return hipErrorInvalidValue;
-    if (rl.form == RADIANCE_PLAIN) {
+    if (rl.form == LIST_PLAIN) {
         const dim3 grid((rl.args.n_rays + 255u) / 256u);
         if (rl.scene.desc16) hipLaunchKernelGGL(k_radiance_plain<true>, grid, dim3(256), 0, rl.stream, rl.scene, rl.args);
         else hipLaunchKernelGGL(k_radiance_plain<false>, grid, dim3(256), 0, rl.stream, rl.scene, rl.args);
         return hipGetLastError();
     }
-    if (rl.grid == 0u || rl.block == 0u || (rl.block & 63u) != 0u || rl.block > BRT_BLOCK || !rl.args.counter) return hipErrorInvalidValue;
-    switch (rl.scene_mode) {
-        case SCENE_LDS:
-            if (!rl.scene.desc16) return hipErrorInvalidValue;
-            return launch_stream_md<SCENE_LDS, true>(rl);
-        case SCENE_LDS_TOP:
-            if (!rl.scene.desc16) return hipErrorInvalidValue;
-            return launch_stream_md<SCENE_LDS_TOP, true>(rl);
-        default:
-            return rl.scene.desc16 ? launch_stream_md<SCENE_GLOBAL, true>(rl) : launch_stream_md<SCENE_GLOBAL, false>(rl);
-    }
+    return launch_stream<RadianceStream>(rl, rl.args.counter, rl.args);
 }
 
 }  // namespace brt

@@ -129,6 +129,19 @@ def _trim(arr: np.ndarray, n: int) -> np.ndarray:
     return raw.view(arr.dtype).reshape(n)
 
 
+def _stream_args(stream: Optional[int], flags: int = 0):
+    """The (hip_stream, flags) pair of a device entry point: stream=None is the context's own stream, a handle (0 = the default
+    stream) the caller's, with FLAG_CALLER_STREAM added to `flags`."""
+    return stream or None, flags | (0 if stream is None else FLAG_CALLER_STREAM)
+
+
+def _stats8(words, names) -> dict:
+    """The out_stats8 words of a list call; names: the keys of word 0 and of word 6, which differ by family."""
+    return {names[0]: int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
+            "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
+            "form": int(words[5]), names[1]: int(words[6])}
+
+
 class CameraExtract:
     """extract.rs:83-158"""
 
@@ -705,11 +718,9 @@ class RayTracingNode:
         (0 = the default stream): asynchronous on that stream (FLAG_CALLER_STREAM is added)."""
         p = self._p
         stats = BrtStats()
-        if stream is not None:
-            flags |= FLAG_CALLER_STREAM
         _lib.check(p._lib.brt_render_part_device(p._ctx, camera.ctypes.data, window.ctypes.data, int(level["level"][0]),
                                                  width, height, part, n_parts, d_raster_rgba or None,
-                                                 d_raster_depth or None, d_out_tile, stream or None, flags,
+                                                 d_raster_depth or None, d_out_tile, *_stream_args(stream, flags),
                                                  C.byref(stats)), p._ctx)
         return stats.as_dict()
 
@@ -720,10 +731,8 @@ class RayTracingNode:
         render_part_device."""
         p = self._p
         stats = BrtStats()
-        if stream is not None:
-            flags |= FLAG_CALLER_STREAM
         _lib.check(p._lib.brt_render_device(p._ctx, camera.ctypes.data, window.ctypes.data, int(level["level"][0]), width, height,
-                                            d_raster_rgba or None, d_raster_depth or None, d_frame, stream or None, flags,
+                                            d_raster_rgba or None, d_raster_depth or None, d_frame, *_stream_args(stream, flags),
                                             C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
@@ -736,7 +745,7 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_denoise_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_frame, d_out,
-                                             stream or None, (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                             *_stream_args(stream, out_format | flags),
                                              C.byref(stats)), p._ctx)
         return stats.as_dict()
 
@@ -749,8 +758,8 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_blend_post_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_coverage,
-                                                d_raster_rgba or None, d_out, stream or None,
-                                                (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags, C.byref(stats)), p._ctx)
+                                                d_raster_rgba or None, d_out,
+                                                *_stream_args(stream, out_format | flags), C.byref(stats)), p._ctx)
         return stats.as_dict()
 
     # -- guide-buffer upsampling (include/bevyray_amd.h "guide-buffer upsampling") ------------------
@@ -763,8 +772,7 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_upscale_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, d_low or None, width,
-                                             height, d_out or None, stream or None,
-                                             (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+                                             height, d_out or None, *_stream_args(stream, out_format), C.byref(stats)), p._ctx)
         return stats.as_dict()
 
     def render_upscaled_device(self, camera, window, low_width: int, low_height: int, width: int, height: int, d_frame: int,
@@ -776,8 +784,7 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_render_upscaled_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, width, height,
-                                                     d_frame or None, stream or None,
-                                                     (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                                     d_frame or None, *_stream_args(stream, out_format | flags),
                                                      C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
@@ -794,8 +801,7 @@ class RayTracingNode:
         stats = BrtStats()
         _lib.check(p._lib.brt_upscale_blend_device(p._ctx, camera.ctypes.data, window.ctypes.data, int(level["level"][0]), low_width,
                                                    low_height, d_low or None, width, height, d_raster_rgba or None, d_raster_depth or None,
-                                                   d_out or None, stream or None,
-                                                   (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+                                                   d_out or None, *_stream_args(stream, out_format), C.byref(stats)), p._ctx)
         return stats.as_dict()
 
     def render_upscaled_blend_device(self, level, camera, window, low_width: int, low_height: int, width: int, height: int, d_frame: int,
@@ -808,8 +814,7 @@ class RayTracingNode:
         stats = BrtStats()
         _lib.check(p._lib.brt_render_upscaled_blend_device(p._ctx, camera.ctypes.data, window.ctypes.data, int(level["level"][0]), low_width,
                                                            low_height, width, height, d_raster_rgba or None, d_raster_depth or None,
-                                                           d_frame or None, stream or None,
-                                                           (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                                           d_frame or None, *_stream_args(stream, out_format | flags),
                                                            C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
@@ -837,8 +842,7 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_render_pixels_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_pixels or None,
-                                                   int(n_pixels), d_out or None, stream or None,
-                                                   (0 if stream is None else FLAG_CALLER_STREAM) | flags, C.byref(stats)), p._ctx)
+                                                   int(n_pixels), d_out or None, *_stream_args(stream, flags), C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
 
@@ -850,8 +854,8 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_upscale_refine_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, d_low or None,
-                                                    width, height, d_out or None, int(classes), d_refined_count or None, stream or None,
-                                                    (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+                                                    width, height, d_out or None, int(classes), d_refined_count or None,
+                                                    *_stream_args(stream, out_format), C.byref(stats)), p._ctx)
         return stats.as_dict()
 
     def render_upscaled_refined_device(self, camera, window, low_width: int, low_height: int, width: int, height: int, d_frame: int,
@@ -862,8 +866,7 @@ class RayTracingNode:
         stats = BrtStats()
         _lib.check(p._lib.brt_render_upscaled_refined_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height, width,
                                                              height, d_frame or None, int(classes), d_refined_count or None,
-                                                             stream or None,
-                                                             (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags,
+                                                             *_stream_args(stream, out_format | flags),
                                                              C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
@@ -873,8 +876,7 @@ class RayTracingNode:
         """brt_upscale_refine_mask_device: the REFINE_* class bits of every output pixel into the width x height bytes at d_mask."""
         p = self._p
         _lib.check(p._lib.brt_upscale_refine_mask_device(p._ctx, camera.ctypes.data, window.ctypes.data, low_width, low_height,
-                                                         d_low or None, width, height, d_mask or None, stream or None,
-                                                         0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+                                                         d_low or None, width, height, d_mask or None, *_stream_args(stream)), p._ctx)
 
     # -- adaptive sampling (include/bevyray_amd.h "adaptive sampling") -------------------------------
 
@@ -886,8 +888,8 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_render_adaptive_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_frame or None,
-                                                     d_selected_count or None, stream or None,
-                                                     (0 if stream is None else FLAG_CALLER_STREAM) | out_format | flags, C.byref(stats)), p._ctx)
+                                                     d_selected_count or None,
+                                                     *_stream_args(stream, out_format | flags), C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
 
@@ -897,23 +899,17 @@ class RayTracingNode:
         p = self._p
         stats = BrtStats()
         _lib.check(p._lib.brt_adaptive_refine_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_base or None,
-                                                     d_out or None, d_selected_count or None, stream or None,
-                                                     (0 if stream is None else FLAG_CALLER_STREAM) | out_format, C.byref(stats)), p._ctx)
+                                                     d_out or None, d_selected_count or None,
+                                                     *_stream_args(stream, out_format), C.byref(stats)), p._ctx)
         return stats.as_dict()
 
     def adaptive_mask_device(self, camera, window, width: int, height: int, d_base: int, d_mask: int, stream: Optional[int] = None) -> None:
         """brt_adaptive_mask_device: the ADAPT_* class of every pixel into the width x height bytes at d_mask; traces nothing."""
         p = self._p
         _lib.check(p._lib.brt_adaptive_mask_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_base or None,
-                                                   d_mask or None, stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+                                                   d_mask or None, *_stream_args(stream)), p._ctx)
 
     # -- ray queries (include/bevyray_amd.h "ray queries") ------------------------------------------
-
-    @staticmethod
-    def _query_stats(words) -> dict:
-        return {"rays_walked": int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
-                "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
-                "form": int(words[5]), "n_workgroups": int(words[6])}
 
     def query_rays(self, rays: np.ndarray, mode: int = QUERY_CLOSEST, origin_bound: float = 0.0) -> np.ndarray:
         """brt_query_rays: a batch of RAY_DTYPE records (host memory) against the resident scene -> HIT_DTYPE records.  mode:
@@ -925,7 +921,7 @@ class RayTracingNode:
         words = (C.c_uint64 * 8)()
         _lib.check(p._lib.brt_query_rays(p._ctx, rays.ctypes.data if rays.size else None, rays.size, int(mode), float(origin_bound),
                                          hits.ctypes.data if rays.size else None, words), p._ctx)
-        self.last_query_stats = self._query_stats(words)
+        self.last_query_stats = _stats8(words, ("rays_walked", "n_workgroups"))
         return hits
 
     def query_rays_device(self, d_rays: int, n_rays: int, d_hits: int, mode: int = QUERY_CLOSEST, origin_bound: float = 0.0,
@@ -935,8 +931,8 @@ class RayTracingNode:
         p = self._p
         words = (C.c_uint64 * 8)()
         _lib.check(p._lib.brt_query_rays_device(p._ctx, d_rays or None, int(n_rays), int(mode), float(origin_bound), d_hits or None,
-                                                stream or None, 0 if stream is None else FLAG_CALLER_STREAM, words), p._ctx)
-        self.last_query_stats = self._query_stats(words)
+                                                *_stream_args(stream), words), p._ctx)
+        self.last_query_stats = _stats8(words, ("rays_walked", "n_workgroups"))
         return self.last_query_stats
 
     def query_origin_bound(self) -> float:
@@ -947,12 +943,6 @@ class RayTracingNode:
         return float(b.value)
 
     # -- radiance queries (include/bevyray_amd.h "radiance queries") --------------------------------
-
-    @staticmethod
-    def _radiance_stats(words) -> dict:
-        return {"walks": int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
-                "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
-                "form": int(words[5]), "n_workgroups": int(words[6])}
 
     def radiance_rays(self, rays, samples: int, bounces: int, origin_bound: float = 0.0, device: bool = False,
                       stream: Optional[int] = None):
@@ -966,24 +956,18 @@ class RayTracingNode:
         if device:
             d_rays, n_rays, d_out = rays
             _lib.check(p._lib.brt_radiance_rays_device(p._ctx, d_rays or None, int(n_rays), int(samples), int(bounces), float(origin_bound),
-                                                       d_out or None, stream or None, 0 if stream is None else FLAG_CALLER_STREAM, words),
+                                                       d_out or None, *_stream_args(stream), words),
                        p._ctx)
-            self.last_radiance_stats = self._radiance_stats(words)
+            self.last_radiance_stats = _stats8(words, ("walks", "n_workgroups"))
             return self.last_radiance_stats
         rays = np.ascontiguousarray(rays, RADIANCE_RAY_DTYPE)
         out = np.empty(rays.shape, RADIANCE_DTYPE)
         _lib.check(p._lib.brt_radiance_rays(p._ctx, rays.ctypes.data if rays.size else None, rays.size, int(samples), int(bounces),
                                             float(origin_bound), out.ctypes.data if rays.size else None, words), p._ctx)
-        self.last_radiance_stats = self._radiance_stats(words)
+        self.last_radiance_stats = _stats8(words, ("walks", "n_workgroups"))
         return out
 
     # -- light probes (include/bevyray_amd.h "light probes") ----------------------------------------
-
-    @staticmethod
-    def _probe_stats(words) -> dict:
-        return {"walks": int(words[0]), "hits": int(words[1]), "refused": int(words[2]), "tree_rebuilt": int(words[3]),
-                "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
-                "form": int(words[5]), "chunks": int(words[6])}
 
     def bake_probes(self, probes, n_dirs: int, bounces: int, basis: int = PROBE_SH9, origin_bound: float = 0.0, device: bool = False,
                     stream: Optional[int] = None):
@@ -997,29 +981,28 @@ class RayTracingNode:
         if device:
             d_probes, n_probes, d_out = probes
             _lib.check(p._lib.brt_bake_probes_device(p._ctx, d_probes or None, int(n_probes), int(n_dirs), int(bounces), int(basis),
-                                                     float(origin_bound), d_out or None, stream or None,
-                                                     0 if stream is None else FLAG_CALLER_STREAM, words), p._ctx)
-            self.last_probe_stats = self._probe_stats(words)
+                                                     float(origin_bound), d_out or None, *_stream_args(stream), words), p._ctx)
+            self.last_probe_stats = _stats8(words, ("walks", "chunks"))
             return self.last_probe_stats
         probes = np.ascontiguousarray(probes, PROBE_DTYPE)
         out = np.empty(probes.shape, PROBE_RECORD_DTYPE)
         _lib.check(p._lib.brt_bake_probes(p._ctx, probes.ctypes.data if probes.size else None, probes.size, int(n_dirs), int(bounces),
                                           int(basis), float(origin_bound), out.ctypes.data if probes.size else None, words), p._ctx)
-        self.last_probe_stats = self._probe_stats(words)
+        self.last_probe_stats = _stats8(words, ("walks", "chunks"))
         return out
 
     def probe_rays_device(self, d_probes: int, n_probes: int, n_dirs: int, d_rays: int, stream: Optional[int] = None):
         """brt_probe_rays_device: the generation step alone -> n_probes * n_dirs RADIANCE_RAY_DTYPE entries at d_rays, probe-major."""
         p = self._p
-        _lib.check(p._lib.brt_probe_rays_device(p._ctx, d_probes or None, int(n_probes), int(n_dirs), d_rays or None, stream or None,
-                                                0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+        _lib.check(p._lib.brt_probe_rays_device(p._ctx, d_probes or None, int(n_probes), int(n_dirs), d_rays or None,
+        *_stream_args(stream)), p._ctx)
 
     def probe_project_device(self, d_results: int, n_probes: int, n_dirs: int, basis: int, d_out: int, stream: Optional[int] = None):
         """brt_probe_project_device: the projection step alone, n_probes * n_dirs RADIANCE_DTYPE results (probe-major) ->
         n_probes PROBE_RECORD_DTYPE records at d_out."""
         p = self._p
         _lib.check(p._lib.brt_probe_project_device(p._ctx, d_results or None, int(n_probes), int(n_dirs), int(basis), d_out or None,
-                                                   stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+                                                   *_stream_args(stream)), p._ctx)
 
     # -- irradiance volumes (include/bevyray_amd.h "irradiance volumes") ----------------------------
 
@@ -1027,8 +1010,7 @@ class RayTracingNode:
         """brt_volume_probes_device: the generation kernel alone -> the lattice's PROBE_DTYPE records at d_probes."""
         p = self._p
         v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
-        _lib.check(p._lib.brt_volume_probes_device(p._ctx, v.ctypes.data, d_probes or None, stream or None,
-                                                   0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+        _lib.check(p._lib.brt_volume_probes_device(p._ctx, v.ctypes.data, d_probes or None, *_stream_args(stream)), p._ctx)
 
     def bake_volume(self, volume, n_dirs: int, bounces: int, origin_bound: float = 0.0, d_records: Optional[int] = None,
                     stream: Optional[int] = None):
@@ -1040,12 +1022,12 @@ class RayTracingNode:
         words = (C.c_uint64 * 8)()
         if d_records is not None:
             _lib.check(p._lib.brt_bake_volume_device(p._ctx, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), d_records or None,
-                                                     stream or None, 0 if stream is None else FLAG_CALLER_STREAM, words), p._ctx)
-            self.last_probe_stats = self._probe_stats(words)
+                                                     *_stream_args(stream), words), p._ctx)
+            self.last_probe_stats = _stats8(words, ("walks", "chunks"))
             return self.last_probe_stats
         out = np.empty(max(_volume_probe_count(v), 1), PROBE_RECORD_DTYPE)
         _lib.check(p._lib.brt_bake_volume(p._ctx, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), out.ctypes.data, words), p._ctx)
-        self.last_probe_stats = self._probe_stats(words)
+        self.last_probe_stats = _stats8(words, ("walks", "chunks"))
         return out
 
     def sample_volume(self, volume, records, points, device: bool = False, stream: Optional[int] = None):
@@ -1057,7 +1039,7 @@ class RayTracingNode:
         if device:
             d_points, n_points, d_out = points
             _lib.check(p._lib.brt_sample_volume_device(p._ctx, v.ctypes.data, records or None, d_points or None, int(n_points), d_out or None,
-                                                       stream or None, 0 if stream is None else FLAG_CALLER_STREAM), p._ctx)
+                                                       *_stream_args(stream)), p._ctx)
             return None
         records = np.ascontiguousarray(records, PROBE_RECORD_DTYPE)
         points = np.ascontiguousarray(points, VOLUME_POINT_DTYPE)
@@ -1072,8 +1054,8 @@ class RayTracingNode:
         """stream=None: own stream, synchronous.  stream=<handle> (0 = default stream): asynchronous there --
         pass the stream the gather was enqueued on so that the copy kernel runs behind it.  out_format: FLAG_OUT_*."""
         p = self._p
-        _lib.check(p._lib.brt_deinterleave_device(p._ctx, d_tiles, n_parts, width, height, d_frame, stream or None,
-                                                  (0 if stream is None else FLAG_CALLER_STREAM) | out_format), p._ctx)
+        _lib.check(p._lib.brt_deinterleave_device(p._ctx, d_tiles, n_parts, width, height, d_frame,
+        *_stream_args(stream, out_format)), p._ctx)
 
     def gather_rccl(self, comm: int, rank: int, world: int, d_tile: int, d_tiles_on_root: int, width: int, height: int,
                     d_frame_on_root: int = 0, stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):
@@ -1081,5 +1063,4 @@ class RayTracingNode:
         same stream.  Stream rule as for render_part_device."""
         p = self._p
         _lib.check(p._lib.brt_gather_rccl(p._ctx, comm, rank, world, d_tile, d_tiles_on_root or None, width, height,
-                                          d_frame_on_root or None, stream or None,
-                                          (0 if stream is None else FLAG_CALLER_STREAM) | out_format), p._ctx)
+                                          d_frame_on_root or None, *_stream_args(stream, out_format)), p._ctx)

@@ -1,24 +1,39 @@
 #!/usr/bin/env python3
 """Are the kernels of two builds of one .hip file the same instructions?  Takes two device assembly files
 (hipcc --offload-arch=gfx950 <the Makefile's CXXFLAGS> -S --cuda-device-only -o X.s X.hip, e.g. of a parent checkout and of this tree)
-and prints, per kernel of the first, SAME or DIFF with the instruction counts (gone: the second has no such kernel); kernels only the second has
-are listed as new.  Comments,
+and prints, per kernel of the first, SAME, REGS or DIFF with the instruction counts (gone: the second has no such kernel); kernels only the second has
+are listed as new.  REGS: not the same, but as many instructions, the same mnemonics and the same operands wherever an operand is no
+register, and the same "Kernel info" block behind the kernel (the figures -Rpass-analysis=kernel-resource-usage prints: registers,
+scratch, LDS, occupancy): the register allocator named the same values differently.  Comments,
 directives and the numbering of local labels are ignored; an empty template parameter pack in a mangled name counts as no pack (the
 instantiation of a kernel template that gained an optional trailing argument), and a seventh argument `false` of k_trace_persistent
 counts as no argument (the template lost that parameter; its `true` instantiation has no namesake and is reported missing).  Exit
-status 1 if a kernel differs or is missing."""
+status 1 if a kernel is DIFF or missing."""
 import re
 import sys
 
 
-def kernels(path):
-    out, cur = {}, None
+REG = re.compile(r"\b[vsa](?:\d+|\[\d+:\d+\])|\bvcc(?:_lo|_hi)?\b")
+
+
+def kernels(path, info=None):
+    """kernel -> its instructions; info (if given): kernel -> the lines of the "Kernel info" block behind it"""
+    out, cur, last, block = {}, None, None, None
     for ln in open(path):
+        if ln.startswith("; Kernel info:") and info is not None:
+            block = info.setdefault(last, [])
+            continue
+        if block is not None:
+            if ln.startswith("; "):
+                block.append(ln.strip())
+                continue
+            block = None
         m = re.match(r"^(_Z\w+):", ln)
         if m:
             cur = m.group(1).replace("EJEEEv", "EEEv").replace("DpT1_", "")
             cur = re.sub(r"(k_trace_persistentI(?:L[ib]\dE){6})Lb0E(EEv)", r"\1\2", cur)
             out[cur] = []
+            last = cur
         elif cur is not None:
             if ln.startswith(".Lfunc_end"):
                 cur = None
@@ -30,12 +45,14 @@ def kernels(path):
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    ia, ib = {}, {}
+    a, b = kernels(sys.argv[1], ia), kernels(sys.argv[2], ib)
     bad = 0
     for k, body in a.items():
         same = body == b.get(k)
-        bad += not same
-        print(f"{'SAME' if same else 'DIFF' if k in b else 'gone'} {len(body):6d} {len(b.get(k, [])):6d}  {k}")
+        regs = not same and k in b and ia.get(k) == ib.get(k) and [REG.sub("r", x) for x in body] == [REG.sub("r", x) for x in b[k]]
+        bad += not (same or regs)
+        print(f"{'SAME' if same else 'REGS' if regs else 'DIFF' if k in b else 'gone'} {len(body):6d} {len(b.get(k, [])):6d}  {k}")
     for k in b:
         if k not in a:
             print(f"new  {'':6s} {len(b[k]):6d}  {k}")

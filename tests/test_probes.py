@@ -2,7 +2,7 @@
 the exports, the direction table, the restatement (tests/probe_ref.py) against the closed-form sky and against float64, the host
 evaluation, rejections.  GPU: the two kernels bitwise against the restatement on generated and synthetic lists; bakes bitwise against
 radiance_ref + the restatement on both trees, both bases, both entry points and both radiance forms; one call against its three steps
-under three chunkings; an empty sky against the analytic coefficients; refusals; streams; frames do not move; 32-bit descriptors."""
+under three chunkings; an empty sky against the analytic coefficients; refusals; streams; host queries growing the shared staging buffers behind a held bake; frames do not move; 32-bit descriptors."""
 import functools
 import os
 import subprocess
@@ -571,6 +571,59 @@ def test_bakes_on_two_caller_streams_and_across_an_upload(plugin):
     after = _host(d_out[100], brt.PROBE_RECORD_DTYPE)
     assert after.tobytes() == _bake(plugin, probes, 100, 4, SH9, device=True).tobytes()
     assert after.tobytes() != serial[100].tobytes()
+
+
+def _list_rays(n, dtype, seed):
+    """n rays from inside the cover scene's box of probes, in the ray queries' or the radiance queries' record"""
+    rng = np.random.default_rng(seed)
+    rays = np.zeros(n, dtype)
+    rays["origin"] = rng.uniform((-5.0, 0.1, -5.0), (5.0, 3.0, 5.0), size=(n, 3)).astype(F32)
+    d = rng.normal(size=(n, 3))
+    rays["direction"] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F32)
+    rays["user"] = np.arange(n, dtype=np.uint32)
+    if "seed" in dtype.names:
+        rays["seed"] = rng.integers(0, 2 ** 32, size=n, dtype=np.uint32)
+    else:
+        rays["t_max"] = np.inf
+    return rays
+
+
+@pytest.mark.gpu
+def test_host_queries_behind_a_held_bake_grow_the_shared_staging_buffers(plugin):
+    """d_qrays / d_qhits serve three families.  A device bake of 27 probes x 64 directions in chunks of 640 entries (three chunks, each
+    staged in the pair: 20 480 bytes) is held on a caller's stream of a new context; with no host synchronisation the host ray query then
+    stages 5 000 rays (160 000 bytes: the pair grows behind the held bake) and the host radiance query 1 234 entries (no growth).  The
+    smallest sizes at which the new context must allocate and the bake must chunk.  Expectations: the same three calls one at a time on
+    the module's context, whose buffers other tests have grown already."""
+    import torch
+    b, _ = _upload_cover(plugin, "caller")
+    probes = _lattice(27)
+    q_rays, r_rays = _list_rays(5000, brt.RAY_DTYPE, 61), _list_rays(1234, brt.RADIANCE_RAY_DTYPE, 62)
+    want_bake = _bake(plugin, probes, 64, 4, SH9, device=True, BRT_PROBE_CHUNK_RAYS=640).copy()
+    assert plugin.node.last_probe_stats["chunks"] == 3
+    want_q = plugin.node.query_rays(q_rays).copy()
+    want_r = plugin.node.radiance_rays(r_rays, 2, 4).copy()
+    assert 0 < np.isfinite(want_q["t"]).sum() < 5000 and 0 < np.isfinite(want_r["t"]).sum() < 1234 and (want_r["rgb"] > 0).any()
+    d_probes = _dev(probes)
+    d_out = torch.zeros(len(probes) * 128, dtype=torch.uint8, device="cuda")
+    sa = torch.cuda.Stream()
+    fresh = brt.RaytracePlugin([0])
+    try:
+        fresh.node.write_buffers(b)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sa):
+            torch.cuda._sleep(20_000_000)                       # (a few ms: the held bake starts after the later calls have been made)
+        with fresh.tuning(BRT_PROBE_CHUNK_RAYS=640):
+            st = fresh.node.bake_probes((d_probes.data_ptr(), len(probes), d_out.data_ptr()), 64, 4, SH9, device=True, stream=sa.cuda_stream)
+        assert st["chunks"] == 3
+        got_q = fresh.node.query_rays(q_rays)
+        assert got_q.tobytes() == want_q.tobytes() and fresh.node.last_query_stats["rays_walked"] == 5000
+        got_r = fresh.node.radiance_rays(r_rays, 2, 4)                # (no growth: the buffers are reused)
+        assert got_r.tobytes() == want_r.tobytes() and fresh.node.last_radiance_stats["refused"] == 0
+        torch.cuda.synchronize()
+        assert _host(d_out, brt.PROBE_RECORD_DTYPE).tobytes() == want_bake.tobytes()
+    finally:
+        fresh.close()
 
 
 @pytest.mark.gpu
