@@ -17,6 +17,8 @@ from .raytracing import (  # noqa: F401
     PROBE_AMBIENT_CUBE, PROBE_DTYPE, PROBE_RECORD_DTYPE, PROBE_SH9, probe_directions, probe_irradiance,
     VOLUME_DTYPE, VOLUME_POINT_DTYPE, VOLUME_SAMPLE_DTYPE, VOLUME_STATUS_CLAMPED, VOLUME_STATUS_INVALID, VOLUME_STATUS_NO_PROBE, VOLUME_WRAP,
     make_volume, volume_probes, volume_sample_host,
+    ENVMAP_TAP_DTYPE, ENVMAP_TAPS_COSINE, ENVMAP_TAPS_GGX, ENVMAP_TEXEL16_DTYPE, ENVMAP_TEXEL_DTYPE, envmap_directions,
+    envmap_downsample_host, envmap_filter_host, envmap_level_offsets, envmap_taps,
     blend_covered, prepare_buffers, rtiow_camera, srgb_thresholds, tile_rows, upscale_window, validate_scene,
 )
 

@@ -113,6 +113,16 @@ _PROTOTYPES = {
     "brt_bake_volume": (_I32, [_VP, _VP, _U32, _U32, _F, _VP, C.POINTER(C.c_uint64)]),
     "brt_sample_volume_device": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP, _VP, _U32]),
     "brt_sample_volume": (_I32, [_VP, _VP, _VP, _VP, _U32, _VP]),
+    "brt_host_envmap_directions": (_I32, [_U32, C.POINTER(_F)]),
+    "brt_host_envmap_taps": (_I32, [_U32, _F, _U32, _VP]),
+    "brt_host_envmap_downsample": (_I32, [_VP, _U32, _VP]),
+    "brt_host_envmap_filter": (_I32, [_VP, _U32, _VP, _U32, _U32, _VP]),
+    "brt_envmap_rays_device": (_I32, [_VP, C.POINTER(_F), _U32, _U32, _VP, _VP, _U32]),
+    "brt_envmap_resolve_device": (_I32, [_VP, _VP, _U32, _VP, _VP, _U32]),
+    "brt_envmap_downsample_device": (_I32, [_VP, _VP, _U32, _VP, _VP, _U32]),
+    "brt_envmap_filter_device": (_I32, [_VP, _VP, _U32, _VP, _U32, _U32, _VP, _VP, _U32]),
+    "brt_bake_envmap_device": (_I32, [_VP, C.POINTER(_F), _U32, _U32, _U32, _U32, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
+    "brt_bake_envmap": (_I32, [_VP, C.POINTER(_F), _U32, _U32, _U32, _U32, _U32, _U32, _F, _VP, _U32, C.POINTER(C.c_uint64)]),
     "brt_host_pixel_ray": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP]),
     "brt_upscale_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),

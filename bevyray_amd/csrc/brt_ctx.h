@@ -164,6 +164,17 @@ struct DeviceCtx {
     size_t volume_probes_cap = 0;
     char* d_volume_io = nullptr;
     size_t volume_io_cap = 0;
+    // reflection probes (brt_envmap.h), first device only: the box levels of a bake (and the f32 level 0 of an RGBA16F one), the chain
+    // of brt_bake_envmap, and the tap tables of the levels 1 .. envmap_taps_levels - 1 (envmap_taps_n taps each; 0: none) with the host
+    // copy their upload reads.  Ordered by ev_q like the probe buffers: each grows only once every list of the context has ended
+    char* d_envmap = nullptr;
+    size_t envmap_cap = 0;
+    char* d_envmap_io = nullptr;
+    size_t envmap_io_cap = 0;
+    float* d_envmap_taps = nullptr;
+    size_t envmap_taps_cap = 0;
+    uint32_t envmap_taps_levels = 0, envmap_taps_n = 0;
+    std::vector<float> h_envmap_taps;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;

@@ -421,6 +421,61 @@ def volume_sample_host(volume, records, points) -> np.ndarray:
     return out
 
 
+# reflection probes: brt_bake_envmap* / brt_envmap_*_device (include/bevyray_amd.h): a cube map [face][y][x] of RGBA f32 texels, its
+# roughness mip chain, and the tap tables of the filter
+ENVMAP_TAPS_GGX, ENVMAP_TAPS_COSINE = 0, 1
+ENVMAP_TEXEL_DTYPE = np.dtype([("rgba", np.float32, 4)])
+ENVMAP_TEXEL16_DTYPE = np.dtype([("rgba", np.float16, 4)])
+ENVMAP_TAP_DTYPE = np.dtype([("l", np.float32, 3), ("w", np.float32)])
+assert ENVMAP_TEXEL_DTYPE.itemsize == 16 and ENVMAP_TEXEL16_DTYPE.itemsize == 8 and ENVMAP_TAP_DTYPE.itemsize == 16
+
+
+def envmap_level_offsets(size: int, levels: int) -> list:
+    """The texel offsets of the levels of a chain, level 0 first, and the chain's total as the last entry (levels + 1 entries): level l
+    has edge size >> l and begins at the sum over j < l of 6 * (size >> j) ** 2."""
+    offs = [0]
+    for l in range(int(levels)):
+        offs.append(offs[-1] + 6 * (int(size) >> l) ** 2)
+    return offs
+
+
+def envmap_directions(size: int) -> np.ndarray:
+    """brt_host_envmap_directions: the (6, size, size, 3) f32 texel directions of a cube, faces +X, -X, +Y, -Y, +Z, -Z.  Host arithmetic."""
+    s = int(size)
+    out = np.zeros((6, s, s, 3) if 0 < s <= 4096 else (0, 3), np.float32)   # (a size out of range is refused before anything is written)
+    _lib.check(_lib.load().brt_host_envmap_directions(s, out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def envmap_taps(kind: int, roughness: float, n_taps: int) -> np.ndarray:
+    """brt_host_envmap_taps: the (n_taps, 4) f32 table {lx, ly, lz, w} of ENVMAP_TAPS_GGX at `roughness` or of ENVMAP_TAPS_COSINE."""
+    n = int(n_taps)
+    out = np.zeros((n if 0 < n <= 4096 else 0, 4), np.float32)
+    _lib.check(_lib.load().brt_host_envmap_taps(int(kind), float(roughness), n, out.ctypes.data if out.size else None))
+    return out
+
+
+def envmap_downsample_host(src) -> np.ndarray:
+    """brt_host_envmap_downsample: the box level of a (6, S, S, 4) f32 cube -> (6, S / 2, S / 2, 4).  Host arithmetic."""
+    src = np.ascontiguousarray(src, np.float32)
+    s = src.shape[1]
+    out = np.zeros((6, s // 2, s // 2, 4), np.float32)
+    _lib.check(_lib.load().brt_host_envmap_downsample(src.ctypes.data, s, out.ctypes.data if out.size else None))
+    return out
+
+
+def envmap_filter_host(src, taps, dst_size: int) -> np.ndarray:
+    """brt_host_envmap_filter: the filter rule on the host, a (6, S, S, 4) f32 cube and an (n, 4) table -> (6, dst_size, dst_size, 4).
+    The compiled twin of the kernel behind RayTracingNode.envmap_filter_device."""
+    src = np.ascontiguousarray(src, np.float32)
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1, 4)
+    d = int(dst_size)
+    out = np.zeros((6, d, d, 4) if 0 < d <= 4096 else (0, 4), np.float32)
+    _lib.check(_lib.load().brt_host_envmap_filter(src.ctypes.data, src.shape[1], taps.ctypes.data if taps.size else None, len(taps), d,
+                                                  out.ctypes.data if out.size else None))
+    return out
+
+
 def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.ndarray:
     """brt_host_pixel_ray: the pixel-centre ray of pixel (px, py) as one RAY_DTYPE record (t_max = inf, user = py * width + px): the
     ray the guide buffer casts for that pixel.  Host arithmetic; for picking through RayTracingNode.query_rays."""
@@ -1048,6 +1103,53 @@ class RayTracingNode:
                                             points.ctypes.data if points.size else None, points.size,
                                             out.ctypes.data if points.size else None), p._ctx)
         return out
+
+    # -- reflection probes (include/bevyray_amd.h "reflection probes") ------------------------------
+
+    def bake_envmap(self, position, size: int, levels: int, samples: int, bounces: int, n_taps: int = 64, seed: int = 0,
+                    origin_bound: float = 0.0, d_out: Optional[int] = None, stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):
+        """brt_bake_envmap*: the cube map seen from `position` (edge `size`, a power of two) and its `levels` roughness levels, the
+        levels concatenated (envmap_level_offsets).  d_out=None: -> the chain's texels in host memory, (n, 4) f32 or, with
+        out_format=FLAG_OUT_RGBA16F, f16 (synchronous).  d_out=<device pointer>: the chain is written there -> the call's stats; stream
+        rule as for bake_probes.  last_probe_stats holds the call's stats."""
+        p = self._p
+        words = (C.c_uint64 * 8)()
+        pos = _f3(position)
+        if d_out is not None:
+            hs, flags = _stream_args(stream, int(out_format))
+            _lib.check(p._lib.brt_bake_envmap_device(p._ctx, pos, int(seed), int(size), int(levels), int(samples), int(bounces), int(n_taps),
+                                                     float(origin_bound), d_out or None, hs, flags, words), p._ctx)
+            self.last_probe_stats = _stats8(words, ("walks", "chunks"))
+            return self.last_probe_stats
+        n = envmap_level_offsets(size, levels)[-1] if 0 < int(size) <= 1024 and 0 < int(levels) <= 11 else 1
+        out = np.zeros((max(n, 1), 4), np.float16 if out_format == FLAG_OUT_RGBA16F else np.float32)
+        _lib.check(p._lib.brt_bake_envmap(p._ctx, pos, int(seed), int(size), int(levels), int(samples), int(bounces), int(n_taps),
+                                          float(origin_bound), out.ctypes.data, int(out_format), words), p._ctx)
+        self.last_probe_stats = _stats8(words, ("walks", "chunks"))
+        return out
+
+    def envmap_rays_device(self, position, seed: int, size: int, d_rays: int, stream: Optional[int] = None):
+        """brt_envmap_rays_device: the generation step alone -> the 6 * size * size RADIANCE_RAY_DTYPE entries of a cube at d_rays."""
+        p = self._p
+        _lib.check(p._lib.brt_envmap_rays_device(p._ctx, _f3(position), int(seed), int(size), d_rays or None, *_stream_args(stream)), p._ctx)
+
+    def envmap_resolve_device(self, d_results: int, size: int, d_out: int, stream: Optional[int] = None):
+        """brt_envmap_resolve_device: 6 * size * size RADIANCE_DTYPE results -> the level-0 texels (linear rgb, alpha = hit) at d_out."""
+        p = self._p
+        _lib.check(p._lib.brt_envmap_resolve_device(p._ctx, d_results or None, int(size), d_out or None, *_stream_args(stream)), p._ctx)
+
+    def envmap_downsample_device(self, d_src: int, src_size: int, d_out: int, stream: Optional[int] = None):
+        """brt_envmap_downsample_device: the box level of the cube at d_src (edge src_size, even) -> d_out (edge src_size / 2)."""
+        p = self._p
+        _lib.check(p._lib.brt_envmap_downsample_device(p._ctx, d_src or None, int(src_size), d_out or None, *_stream_args(stream)), p._ctx)
+
+    def envmap_filter_device(self, d_src: int, src_size: int, d_taps: int, n_taps: int, dst_size: int, d_out: int,
+                             stream: Optional[int] = None):
+        """brt_envmap_filter_device: the filter rule, the cube at d_src and the table at d_taps -> the cube of edge dst_size at d_out.  A
+        cosine table (envmap_taps(ENVMAP_TAPS_COSINE, ...)) gives the diffuse map."""
+        p = self._p
+        _lib.check(p._lib.brt_envmap_filter_device(p._ctx, d_src or None, int(src_size), d_taps or None, int(n_taps), int(dst_size),
+                                                   d_out or None, *_stream_args(stream)), p._ctx)
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

@@ -624,6 +624,97 @@ int32_t brt_sample_volume_device(brt_ctx* ctx, const void* volume48, const void*
                                  void* d_out, void* hip_stream, uint32_t flags);
 int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* records, const void* points, uint32_t n_points, void* out);
 
+/* ---- reflection probes ----------------------------------------------------------------------------------------------------------------
+ * A cube map traced from one position and its mip chain prefiltered by roughness: the specular map of a level-1 / level-2 host's
+ * environment light (Bevy's EnvironmentMapLight), and -- through the filter step with a cosine table -- its diffuse map.  On the
+ * context's first device.  Rule, kernels and costs: DESIGN.md "Reflection probes".  Deterministic: f32, every operation separately
+ * rounded, in the order written here.
+ *   cube              6 faces of size x size texels, stored [face][y][x]; a texel is 16 bytes { f32 r, g, b, a }.  Faces in the order +X,
+ *                     -X, +Y, -Y, +Z, -Z (wgpu, Vulkan, D3D).
+ *   texel direction   u = f32(2x+1) / f32(size) - 1, v = f32(2y+1) / f32(size) - 1; raw = +X (1, -v, -u), -X (-1, -v, u), +Y (u, 1, v),
+ *                     -Y (u, -1, -v), +Z (u, -v, 1), -Z (-u, -v, -1); len = sqrt((x x + y y) + z z); d = raw / len (three divides).
+ *   texel index       i = (face * size + y) * size + x.  Its radiance entry is { position, seed + i * 0x9E3779B9 (mod 2^32), d_i,
+ *                     user = i }, traced with the call's `samples` and `bounces` under the rule of "radiance queries".
+ *   resolve           rgb_linear = rgb * rgb per channel (as "light probes"); a = 1.0 where the texel's own ray hit
+ *                     (BRT_QUERY_STATUS_HIT), 0.0 where it missed or was refused: a host composites its own skybox there.
+ *   box level         a texel of the next smaller level (edge size / 2) is ((t00 + t01) + (t10 + t11)) * 0.25 per channel, alpha
+ *                     included, t_yx the four texels it covers.  The edge of the larger level must be even.
+ *   tap table         n_taps in [1, 4096] records of 16 bytes { f32 lx, ly, lz, w } in the tangent space of the lobe axis.
+ *                     brt_host_envmap_taps is the only place that computes one: in float64, rounded once to f32.  For tap i:
+ *                     xi1 = (i + 0.5) / n, xi2 = the base-2 radical inverse of i, phi = 2 pi xi1.
+ *                     BRT_ENVMAP_TAPS_GGX, roughness in [0, 1]: a = roughness^2 (the f32 argument squared in float64); cos t = sqrt((1 -
+ *                     xi2) / (1 + (a a - 1) xi2)); sin t = sqrt(max(0, 1 - cos t cos t)); h = (sin t cos phi, sin t sin phi, cos t);
+ *                     l = (2 h.z h.x, 2 h.z h.y, 2 h.z h.z - 1); w = max(l.z, 0).
+ *                     BRT_ENVMAP_TAPS_COSINE (roughness is not read): r = sqrt(xi2); l = (r cos phi, r sin phi, sqrt(1 - xi2)); w = 1.
+ *                     The kernel takes the table as data and does no trigonometry; a caller may pass a table of its own.
+ *   the filter rule   the source cube (edge src_size) -> the destination cube (edge dst_size).  Per destination texel:
+ *                     1. N = the texel's direction (dst_size).
+ *                     2. |N.z| < 0.999f: t = (-N.y, N.x, 0) [= (0, 0, 1) x N]; otherwise t = (0, -N.z, N.y) [= (1, 0, 0) x N].
+ *                     3. T = t / sqrt((t.x t.x + t.y t.y) + t.z t.z) (three divides); B = N x T = (N.y T.z - N.z T.y, N.z T.x - N.x T.z,
+ *                        N.x T.y - N.y T.x).
+ *                     4. acc[4] = +0.0, sw = +0.0; the taps k = 0 .. n_taps - 1 in order; a tap with w <= 0 is skipped (a NaN w is not).
+ *                     5. L = (lx * T + ly * B) + lz * N per component.
+ *                     6. the face by the major axis, ties to X, then Y: ax >= ay && ax >= az: X (ma = ax; L.x < 0: face -X, sc = L.z,
+ *                        else face +X, sc = -L.z; tc = -L.y); else ay >= az: Y (ma = ay; sc = L.x; L.y < 0: face -Y, tc = -L.z, else
+ *                        face +Y, tc = L.z); else Z (ma = az; tc = -L.y; L.z < 0: face -Z, sc = -L.x, else face +Z, sc = L.x).
+ *                     7. u = sc / ma, v = tc / ma.
+ *                     8. with S = src_size: px = ((u + 1) * 0.5) * f32(S) - 0.5; px = px > 0 ? px : 0 (a NaN becomes 0); px = px <
+ *                        f32(S - 1) ? px : f32(S - 1).
+ *                     9. i0 = min(u32(floor(px)), max(S, 2) - 2); i1 = min(i0 + 1, S - 1); g = px - f32(i0).  The same for v -> j0, j1, gy.
+ *                     10. inside that face: c = (c00 * (1 - gx) + c01 * gx) * (1 - gy) + (c10 * (1 - gx) + c11 * gx) * gy per channel,
+ *                        c_ji the texel (x = i_i, y = j_j).
+ *                     11. acc = acc + w * c for all four channels; sw = sw + w.
+ *                     12. sw > 0: acc / sw; otherwise 0 in all four channels.
+ *                     A NaN or INF texel propagates as the arithmetic says.  LIMITATION: a tap's four texels are taken inside the face
+ *                     its direction falls on (clamped at the face's edge): taps do not filter across face edges.
+ *   the chain         `levels` in [1, log2(size) + 1]; level l has edge size >> l.  The levels are concatenated, level 0 first, each a
+ *                     cube: level l begins at texel offset(l) = sum over j < l of 6 * (size >> j)^2.  Level 0 is the resolved cube.
+ *                     Box level 0 is level 0; box level l >= 1 is the box level of box level l - 1.  Level l >= 1 is the filter of box
+ *                     level l at its own resolution (src_size = dst_size = size >> l) with the GGX table of roughness f32(l) / f32(levels
+ *                     - 1) (an f32 divide) and the call's n_taps.
+ *   brt_host_envmap_directions   host arithmetic, no context: out_xyz[3 i ..] = d_i for the 6 size^2 texels.  size in [1, 4096].
+ *   brt_host_envmap_taps         host arithmetic, no context: the table of `kind` at `out` (16 n_taps bytes).
+ *   brt_host_envmap_downsample   host arithmetic, no context: the box level of the cube at `src` (src_size even, in [2, 4096]).
+ *   brt_host_envmap_filter       host arithmetic, no context: the filter rule; the compiled twin of the kernel.  Sizes in [1, 4096].
+ *   brt_envmap_rays_device       the generation kernel alone: the 6 size^2 radiance entries of a cube at d_rays (DEVICE), size in [1, 4096].
+ *   brt_envmap_resolve_device    the resolve kernel alone: 6 size^2 radiance results at d_results -> texels at d_out.  Needs no scene.
+ *   brt_envmap_downsample_device the box-level kernel alone.  Needs no scene.
+ *   brt_envmap_filter_device     the filter kernel alone (RGBA32F texels).  Needs no scene.  With a BRT_ENVMAP_TAPS_COSINE table over the
+ *                     resolved cube (or a box level of it) the result is the diffuse map: the cosine-weighted mean radiance per direction.
+ *   brt_bake_envmap_device       everything in one call: the texels in chunks of BRT_PROBE_CHUNK_RAYS entries (the light probes' tuning
+ *                     knob), generate -> the radiance kernels -> resolve; then per level the box level and its filter.  d_out: DEVICE,
+ *                     offset(levels) texels of 16 bytes, or of 8 bytes { f16 r, g, b, a } with BRT_FLAG_OUT_RGBA16F (every level is
+ *                     computed in f32 and rounded to nearest even once, when it is written).  size: a power of two in [1, 1024];
+ *                     samples, bounces, origin_bound: as for brt_radiance_rays.  The bytes written depend neither on the chunk size
+ *                     nor on BRT_RADIANCE_FORM.  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_RGBA16F.
+ *   brt_bake_envmap              the same for a HOST buffer, synchronous.  flags: BRT_FLAG_OUT_RGBA16F only.
+ *   out_stats8_or_null   as for brt_bake_probes: [0..2] walks, entries whose own ray hit, entries refused, summed over the chunks (only
+ *                     calls that synchronise count), [3] the tree was rebuilt, [4] its reach, [5] the radiance form of the last chunk,
+ *                     [6] chunks, [7] 0.
+ * The step exports' flags: BRT_FLAG_CALLER_STREAM only; stream rule and ordering as for the step exports of "light probes".  Refused with
+ * BRT_ERR_INVALID_ARGUMENT and nothing written: a non-finite position; a bake position whose 1-norm (|x| + |y|) + |z| exceeds the tree's
+ * bound (brt_query_origin_bound) after the reach step of origin_bound; null pointers; a DEVICE buffer that is not 16-byte aligned; an
+ * output that overlaps an input; a size, n_taps, kind, roughness, levels, samples or bounces out of range; unknown flags.  The bakes:
+ * BRT_ERR_NO_SCENE before an upload, BRT_ERR_UNSUPPORTED under a set policy.  A refused call leaves the context usable; no call here
+ * changes a frame or the dispatch history. */
+#define BRT_ENVMAP_TAPS_GGX 0u
+#define BRT_ENVMAP_TAPS_COSINE 1u
+int32_t brt_host_envmap_directions(uint32_t size, float* out_xyz);
+int32_t brt_host_envmap_taps(uint32_t kind, float roughness, uint32_t n_taps, void* out);
+int32_t brt_host_envmap_downsample(const void* src, uint32_t src_size, void* out);
+int32_t brt_host_envmap_filter(const void* src, uint32_t src_size, const void* taps, uint32_t n_taps, uint32_t dst_size, void* out);
+int32_t brt_envmap_rays_device(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, void* d_rays, void* hip_stream,
+                               uint32_t flags);
+int32_t brt_envmap_resolve_device(brt_ctx* ctx, const void* d_results, uint32_t size, void* d_out, void* hip_stream, uint32_t flags);
+int32_t brt_envmap_downsample_device(brt_ctx* ctx, const void* d_src, uint32_t src_size, void* d_out, void* hip_stream, uint32_t flags);
+int32_t brt_envmap_filter_device(brt_ctx* ctx, const void* d_src, uint32_t src_size, const void* d_taps, uint32_t n_taps, uint32_t dst_size,
+                                 void* d_out, void* hip_stream, uint32_t flags);
+int32_t brt_bake_envmap_device(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, uint32_t levels, uint32_t samples,
+                               uint32_t bounces, uint32_t n_taps, float origin_bound, void* d_out, void* hip_stream, uint32_t flags,
+                               uint64_t* out_stats8_or_null);
+int32_t brt_bake_envmap(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, uint32_t levels, uint32_t samples,
+                        uint32_t bounces, uint32_t n_taps, float origin_bound, void* out, uint32_t flags, uint64_t* out_stats8_or_null);
+
 /* ---- guide-buffer upsampling ----------------------------------------------------------------------------------------------------------
  * A frame traced at low_width x low_height is presented at width x height: every OUTPUT pixel casts its own pixel-centre ray (the guide
  * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
