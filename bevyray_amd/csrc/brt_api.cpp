@@ -22,8 +22,8 @@ void free_device(DeviceCtx& dc) {
     for (void* p : std::initializer_list<void*>{dc.d_scene, dc.d_ctrl, dc.d_strip_table, dc.d_tile, dc.d_gather, dc.d_pack, dc.d_raster_rgba,
              dc.d_raster_depth, dc.d_bvh_scratch, dc.d_tile_cost, dc.d_tile_order, dc.d_order_meta, dc.d_order_scratch, dc.d_slice_state,
              dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_uplow, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits,
-             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.d_probe_dirs, dc.d_probe_io, dc.d_volume_probes,
-             dc.d_volume_io, dc.d_envmap, dc.d_envmap_io, dc.d_envmap_taps})
+             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.probe_dirs.d, dc.d_list_io, dc.d_volume_probes,
+             dc.d_envmap, dc.envmap_taps.d})
         if (p) (void)hipFree(p);
     if (dc.h_stage) (void)hipHostFree(dc.h_stage);
     for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack, dc.ev_strip, dc.ev_strip_read, dc.ev_q, dc.ev_dn,
@@ -353,8 +353,7 @@ int32_t brt_create(const int32_t* device_ids, int32_t n_devices, brt_ctx** out_c
 }
 
 int32_t brt_set_policy(brt_ctx* ctx, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (flags & ~kPolicyMask) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "unknown policy flag");
     ctx->policy_flags = flags;
     return BRT_OK;
@@ -406,8 +405,7 @@ int32_t brt_host_alloc(brt_ctx* ctx, uint64_t bytes, void** out_ptr) {
 }
 
 int32_t brt_host_free(brt_ctx* ctx, void* ptr) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     for (size_t i = 0; i < ctx->pinned.size(); i++)
         if (ctx->pinned[i].first == ptr) {
             HIP_TRY(ctx, hipHostFree(ptr));
@@ -431,8 +429,7 @@ int32_t brt_destroy(brt_ctx* ctx) {
 
 int32_t brt_upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
                          const void* bvh_nodes, uint32_t n_nodes) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     return upload_scene(ctx, models, n_models, materials, n_materials, bvh_nodes, n_nodes, 0u, false);
     });
 }
@@ -473,8 +470,7 @@ int32_t brt_debug_profile(brt_ctx* ctx, uint64_t* out64) {
 }
 
 int32_t brt_debug_eval(brt_ctx* ctx, uint32_t op, const float* in16, float* out8, uint32_t n) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!in16 || !out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null buffer");
     if (n == 0) return BRT_OK;
     DeviceCtx& dc = ctx->devs[0];

@@ -102,8 +102,7 @@ int32_t retrace_rays(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, unsigned l
 extern "C" {
 
 int32_t brt_set_adaptive(brt_ctx* ctx, uint32_t base_spp, float threshold, uint32_t min_taps) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (base_spp < 1u || base_spp > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "base_spp must be in [1, 65535]");
     if (!adapt_finite(threshold) || !(threshold > 0.0f)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "threshold must be finite and > 0");
     if (min_taps < 1u || min_taps > 25u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "min_taps must be in [1, 25]");
@@ -205,8 +204,7 @@ int32_t brt_adaptive_refine_device(brt_ctx* ctx, const void* camera80, const voi
 
 int32_t brt_adaptive_mask_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                                  const float* d_base_rgba, void* d_mask_u8, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_base_rgba || !d_mask_u8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_base_rgba / d_mask_u8 is null");
     if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
     if (const int32_t bad = adaptive_check(ctx, camera80, window16, width, height)) return bad;

@@ -1,21 +1,15 @@
 // brt_api_envmap.cpp -- reflection probes (brt_envmap.h, brt_envmap.hip; DESIGN.md "Reflection probes") on the first device: a cube map
 // traced from one position and its mip chain prefiltered by roughness.  The texels' rays are radiance entries and are traced by the
-// radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue); streams, ordering behind ev_q and the staging rule are those of
-// every list call (brt_frame.h: with_reach, with_list_call, staged, list_step_run); the stats are the probe bakes' (bake_stats).
+// radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue); the skeleton of a bake export, its chunk loop, the cached tap
+// tables, streams, ordering behind ev_q and the staging rule are those of every list call (brt_frame.h: bake_call, bake_call_host,
+// bake_chunks, cached_table, staged, list_step_run, device_aligned); the stats are the probe bakes' (bake_stats).  Here: the checks, the
+// tap tables' maths, the argument packing, the level loop and the host twins.
 #include "brt_envmap.h"
 #include "brt_frame.h"
 
 using namespace brt;
 
 namespace {
-
-constexpr double kTwoPi = 6.283185307179586;
-
-int32_t device_aligned(brt_ctx* ctx, std::initializer_list<const void*> ptrs) {
-    for (const void* p : ptrs)
-        if (reinterpret_cast<uintptr_t>(p) & 15u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "device buffers must be 16-byte aligned");
-    return BRT_OK;
-}
 
 int32_t size_check(brt_ctx* ctx, uint32_t size, const char* what) {
     if (size < 1u || size > kEnvmapMaxSize) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, std::string(what) + " must be in [1, 4096]");
@@ -163,24 +157,15 @@ int32_t envmap_bake_check(brt_ctx* ctx, const float* position3, uint32_t size, u
 }
 
 // The device tables of the levels 1 .. levels - 1 of a chain (GGX, roughness l / (levels - 1), n_taps taps each, level l at record
-// (l - 1) * n_taps) for work on `stream`, which is then behind ev_q.  Kept per context by (levels, n_taps); another pair rewrites the
-// host copy and the device copy only once every list of the context has ended, and the upload is recorded in ev_q (as probe_table).
+// (l - 1) * n_taps) for work on `stream`, which is then behind ev_q.  Kept per context by (levels, n_taps) (cached_table); a chain of
+// one level has no table.
 int32_t envmap_tables(brt_ctx* ctx, DeviceCtx& dc, uint32_t levels, uint32_t n_taps, hipStream_t stream) {
-    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    if (levels < 2u || (dc.envmap_taps_levels == levels && dc.envmap_taps_n == n_taps && dc.d_envmap_taps)) return BRT_OK;
-    HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    dc.envmap_taps_levels = dc.envmap_taps_n = 0u;
-    dc.h_envmap_taps.resize((size_t)(levels - 1u) * n_taps * 4u);
-    for (uint32_t l = 1; l < levels; l++)
-        envmap_taps(ENVMAP_TAPS_GGX, level_roughness(l, levels), n_taps, dc.h_envmap_taps.data() + (size_t)(l - 1u) * n_taps * 4u);
-    const size_t bytes = dc.h_envmap_taps.size() * sizeof(float);
-    const int32_t rc = ensure(ctx, &dc.d_envmap_taps, &dc.envmap_taps_cap, bytes);
-    if (rc != BRT_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(dc.d_envmap_taps, dc.h_envmap_taps.data(), bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    dc.envmap_taps_levels = levels;
-    dc.envmap_taps_n = n_taps;
-    return BRT_OK;
+    if (levels < 2u) { HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0)); return BRT_OK; }
+    return cached_table(ctx, dc, dc.envmap_taps, (uint64_t)levels << 32 | n_taps, stream, [&](std::vector<float>& h) {
+        h.resize((size_t)(levels - 1u) * n_taps * 4u);
+        for (uint32_t l = 1; l < levels; l++)
+            envmap_taps(ENVMAP_TAPS_GGX, level_roughness(l, levels), n_taps, h.data() + (size_t)(l - 1u) * n_taps * 4u);
+    });
 }
 
 // The bake into the DEVICE buffer d_out on `stream`: the texels in chunks of BRT_PROBE_CHUNK_RAYS entries, generate -> the radiance
@@ -202,25 +187,20 @@ int32_t envmap_bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, con
     if (rc == BRT_OK) rc = envmap_tables(ctx, dc, levels, n_taps, stream);
     if (rc != BRT_OK) return rc;
     char* lvl0 = half ? dc.d_envmap : static_cast<char*>(d_out);
-    run->chunks = (n0 + per_chunk - 1u) / per_chunk;
-    if (counted) run->counts.assign((size_t)run->chunks * 3u, 0u);
-    for (uint32_t c = 0; c < run->chunks; c++) {
-        const uint32_t first = c * per_chunk, n = std::min(per_chunk, n0 - first);
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-        rc = rays_enqueue(ctx, stream, position3, seed, size, first, n, dc.d_qrays);
-        if (rc == BRT_OK) rc = radiance_enqueue(ctx, dc, stream, dc.d_qrays, n, samples, bounces, dc.d_qhits, counted, &run->rl);
-        if (rc == BRT_OK) rc = resolve_enqueue(ctx, stream, dc.d_qhits, n, lvl0 + (size_t)first * 16u,
-                                               half ? static_cast<char*>(d_out) + (size_t)first * 8u : nullptr);
-        if (rc != BRT_OK) return rc;
-        if (counted) HIP_TRY(ctx, hipMemcpyAsync(&run->counts[(size_t)c * 3u], dc.d_radctl, 24u, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    }
+    rc = bake_chunks(ctx, dc, stream, n0, per_chunk, counted, run, [&](uint32_t first, uint32_t n) {
+        int32_t r = rays_enqueue(ctx, stream, position3, seed, size, first, n, dc.d_qrays);
+        if (r == BRT_OK) r = radiance_enqueue(ctx, dc, stream, dc.d_qrays, n, samples, bounces, dc.d_qhits, counted, &run->rl);
+        if (r == BRT_OK) r = resolve_enqueue(ctx, stream, dc.d_qhits, n, lvl0 + (size_t)first * 16u,
+                                             half ? static_cast<char*>(d_out) + (size_t)first * 8u : nullptr);
+        return r;
+    });
+    if (rc != BRT_OK) return rc;
     const char* box = lvl0;
     char* next = dc.d_envmap + lvl0_bytes;
     for (uint32_t l = 1; l < levels; l++) {
         const uint32_t s = size >> l;
         rc = downsample_enqueue(ctx, stream, box, s * 2u, next);
-        if (rc == BRT_OK) rc = filter_enqueue(ctx, stream, next, s, dc.d_envmap_taps + (size_t)(l - 1u) * n_taps * 4u, n_taps, s,
+        if (rc == BRT_OK) rc = filter_enqueue(ctx, stream, next, s, dc.envmap_taps.d + (size_t)(l - 1u) * n_taps * 4u, n_taps, s,
                                               static_cast<char*>(d_out) + (size_t)envmap_level_offset(size, l) * texel, out_format);
         if (rc != BRT_OK) return rc;
         box = next;
@@ -295,8 +275,7 @@ int32_t brt_host_envmap_filter(const void* src, uint32_t src_size, const void* t
 
 int32_t brt_envmap_rays_device(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, void* d_rays, void* hip_stream,
                                uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = position_check(ctx, position3);
     if (rc == BRT_OK) rc = size_check(ctx, size, "size");
@@ -310,8 +289,7 @@ int32_t brt_envmap_rays_device(brt_ctx* ctx, const float* position3, uint32_t se
 }
 
 int32_t brt_envmap_resolve_device(brt_ctx* ctx, const void* d_results, uint32_t size, void* d_out, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = size_check(ctx, size, "size");
     if (rc != BRT_OK) return rc;
@@ -326,8 +304,7 @@ int32_t brt_envmap_resolve_device(brt_ctx* ctx, const void* d_results, uint32_t 
 }
 
 int32_t brt_envmap_downsample_device(brt_ctx* ctx, const void* d_src, uint32_t src_size, void* d_out, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = downsample_check(ctx, d_src, src_size, d_out);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_src, d_out});
@@ -340,8 +317,7 @@ int32_t brt_envmap_downsample_device(brt_ctx* ctx, const void* d_src, uint32_t s
 
 int32_t brt_envmap_filter_device(brt_ctx* ctx, const void* d_src, uint32_t src_size, const void* d_taps, uint32_t n_taps, uint32_t dst_size,
                                  void* d_out, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = filter_check(ctx, d_src, src_size, d_taps, n_taps, dst_size, d_out);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_src, d_taps, d_out});
@@ -355,53 +331,35 @@ int32_t brt_envmap_filter_device(brt_ctx* ctx, const void* d_src, uint32_t src_s
 int32_t brt_bake_envmap_device(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, uint32_t levels, uint32_t samples,
                                uint32_t bounces, uint32_t n_taps, float origin_bound, void* d_out, void* hip_stream, uint32_t flags,
                                uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
     int32_t rc = envmap_bake_check(ctx, position3, size, levels, samples, bounces, n_taps, origin_bound, d_out);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_out});
     if (rc != BRT_OK) return rc;
     const float pos[3] = {position3[0], position3[1], position3[2]};
-    BakeRun run;
-    uint32_t rebuilt = 0u;
-    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags & BRT_FLAG_CALLER_STREAM, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = position_reach_check(ctx, pos);
-        if (r == BRT_OK) r = envmap_bake_enqueue(ctx, dc, sc.stream, pos, seed, size, levels, samples, bounces, n_taps, d_out,
-                                                 flags & BRT_FLAG_OUT_MASK, sc.own, &run);
-        if (r != BRT_OK || !sc.own) return r;
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
+    return bake_call(ctx, origin_bound, hip_stream, flags & BRT_FLAG_CALLER_STREAM, out_stats8,
+                     [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
+        const int32_t r = position_reach_check(ctx, pos);
+        if (r != BRT_OK) return r;
+        return envmap_bake_enqueue(ctx, dc, stream, pos, seed, size, levels, samples, bounces, n_taps, d_out, flags & BRT_FLAG_OUT_MASK,
+                                   counted, run);
     });
-    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
-    return rc;
     });
 }
 
 int32_t brt_bake_envmap(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, uint32_t levels, uint32_t samples,
                         uint32_t bounces, uint32_t n_taps, float origin_bound, void* out, uint32_t flags, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (flags & ~(uint32_t)BRT_FLAG_OUT_RGBA16F) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_OUT_RGBA16F only");
-    int32_t rc = envmap_bake_check(ctx, position3, size, levels, samples, bounces, n_taps, origin_bound, out);
+    const int32_t rc = envmap_bake_check(ctx, position3, size, levels, samples, bounces, n_taps, origin_bound, out);
     if (rc != BRT_OK) return rc;
     const float pos[3] = {position3[0], position3[1], position3[2]};
-    BakeRun run;
-    uint32_t rebuilt = 0u;
-    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        const size_t bytes = (size_t)envmap_level_offset(size, levels) * (flags == BRT_FLAG_OUT_RGBA16F ? 8u : 16u);
-        int32_t r = position_reach_check(ctx, pos);
-        if (r == BRT_OK) r = staged(ctx, dc, {{&dc.d_envmap_io, &dc.envmap_io_cap, bytes}});
-        if (r == BRT_OK) r = envmap_bake_enqueue(ctx, dc, dc.stream, pos, seed, size, levels, samples, bounces, n_taps, dc.d_envmap_io, flags,
-                                                 true, &run);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_envmap_io, bytes, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
-    });
-    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
-    return rc;
+    const size_t bytes = (size_t)envmap_level_offset(size, levels) * (flags == BRT_FLAG_OUT_RGBA16F ? 8u : 16u);
+    return bake_call_host(ctx, origin_bound, bytes, {0u, out, bytes}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
+        return envmap_bake_enqueue(ctx, dc, stream, pos, seed, size, levels, samples, bounces, n_taps, dc.d_list_io, flags, counted, run);
+    }, [&] { return position_reach_check(ctx, pos); });
     });
 }
 

@@ -521,8 +521,7 @@ uint32_t brt_tile_rows(uint32_t height, uint32_t n_parts) {
 }
 
 int32_t brt_set_strip_table(brt_ctx* ctx, uint32_t n_parts, uint32_t n_strips, const uint32_t* part_of_strip) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!part_of_strip) { ctx->strip_epoch++; ctx->strip_part.clear(); ctx->strip_n_parts = 0u; return BRT_OK; }
     // (a refused table changes nothing: the table in force stays)
     if (n_parts < 1u || n_strips < 1u || n_strips > 4096u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_parts / n_strips out of range");
@@ -537,8 +536,7 @@ int32_t brt_set_strip_table(brt_ctx* ctx, uint32_t n_parts, uint32_t n_strips, c
 
 int32_t brt_plan_strips(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t width, uint32_t height,
                         uint32_t n_parts, uint32_t probe_spp, uint32_t* out_part_of_strip) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "no scene uploaded");
     if (n_parts < 1u || n_parts > 64u || probe_spp < 1u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_parts must be 1..64, probe_spp >= 1");
     FrameParams fp;
@@ -577,8 +575,7 @@ int32_t brt_plan_strips(brt_ctx* ctx, const void* camera80, const void* window16
 int32_t brt_debug_tile_order(brt_ctx* ctx, const uint32_t* ray_sum, const uint32_t* longest_pixel, uint32_t n_tiles,
                              uint32_t sample_count, uint64_t grid_lanes, uint32_t tiles_x, uint32_t dilate, uint32_t split_tail,
                              uint32_t* out_order, uint32_t* out_info4) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!ray_sum || !longest_pixel || !out_order || !out_info4 || n_tiles == 0) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null buffer / no tiles");
     if (dilate != 0u && (tiles_x == 0u || n_tiles % tiles_x != 0u)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "dilate needs a tiles_x that divides n_tiles");
     DeviceCtx& dc = ctx->devs[0];

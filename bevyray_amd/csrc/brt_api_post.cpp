@@ -185,8 +185,7 @@ int32_t denoise_device(brt_ctx* ctx, const void* camera80, const void* window16,
 extern "C" {
 
 int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance, float sigma_normal, float sigma_depth) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (iterations < 1u || iterations > 6u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "iterations must be in [1, 6]");
     for (float v : {sigma_luminance, sigma_normal, sigma_depth})
         if (!std::isfinite(v) || !(v > 0.0f)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "the sigmas must be finite and > 0");
@@ -217,8 +216,7 @@ int32_t brt_blend_post_device(brt_ctx* ctx, const void* camera80, const void* wi
 }
 
 int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, float* out8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out8 is null");
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     uint32_t rebuilt = 0u;
@@ -241,8 +239,7 @@ int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void*
 }
 
 int32_t brt_set_temporal(brt_ctx* ctx, uint32_t max_history) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (max_history < 1u || max_history > 65535u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "max_history must be in [1, 65535]");
     ctx->temporal.max_history = max_history;
     ctx->temporal.valid = false;
@@ -251,16 +248,14 @@ int32_t brt_set_temporal(brt_ctx* ctx, uint32_t max_history) {
 }
 
 int32_t brt_reset_temporal(brt_ctx* ctx) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     ctx->temporal.valid = false;
     return BRT_OK;
     });
 }
 
 int32_t brt_debug_temporal_state(brt_ctx* ctx, uint32_t width, uint32_t height, float* out8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out8 is null");
     if (width == 0 || height == 0 || width > 32768u || height > 32768u)
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");

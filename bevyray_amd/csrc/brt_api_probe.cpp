@@ -1,7 +1,8 @@
 // brt_api_probe.cpp -- light probes (brt_probe.hip; DESIGN.md "Light probes") on the first device: irradiance records for a list of
 // positions.  The rays are radiance entries and are traced by the radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue);
-// reach, refusal bound and staging buffers are the ray queries' (brt_api_query.cpp); the skeleton of a list call and the runner of a
-// step export are brt_frame.h's (with_reach, staged, list_step_run, list_stats8).
+// reach, refusal bound and staging buffers are the ray queries' (brt_api_query.cpp); the skeleton of a bake export, its chunk loop, the
+// cached direction table and the runner of a step export are brt_frame.h's (bake_call, bake_call_host, bake_chunks, cached_table,
+// staged, list_step_run, list_stats8).  Here: the checks, the direction table's maths, the argument packing and the host twins.
 #include "brt_frame.h"
 #include "brt_probe.h"
 
@@ -11,7 +12,6 @@ namespace {
 
 constexpr uint32_t kMaxEntries = 0x7fff0000u;        // of one radiance list (radiance_check)
 constexpr double kGolden = 0.6180339887498949;       // (sqrt(5) - 1) / 2
-constexpr double kTwoPi = 6.283185307179586;
 
 // The direction table: a Fibonacci sphere stratified along the up axis, equal weights.  float64, rounded to f32 at the end; the only
 // place that computes it (the device reads a table uploaded from here).
@@ -41,30 +41,19 @@ int32_t probe_list_check(brt_ctx* ctx, uint32_t n_probes, uint32_t n_dirs) {
     return BRT_OK;
 }
 
-// The device table of n_dirs directions for work on `stream`, which is then behind ev_q.  The table is kept per context by n_dirs;
-// another n_dirs rewrites the host copy and the device copy only once every list of the context has ended (the upload of the old table
-// among them), and the upload is recorded in ev_q, so that a list on another stream starts behind it.
+// The device table of n_dirs directions for work on `stream`, which is then behind ev_q: kept per context by n_dirs (cached_table)
 int32_t probe_table(brt_ctx* ctx, DeviceCtx& dc, uint32_t n_dirs, hipStream_t stream) {
-    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    if (dc.probe_dirs_n == n_dirs && dc.d_probe_dirs) return BRT_OK;
-    HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    dc.probe_dirs_n = 0u;
-    dc.h_probe_dirs.resize((size_t)n_dirs * 4u);
-    probe_directions(n_dirs, dc.h_probe_dirs.data(), 4u);
-    const size_t bytes = (size_t)n_dirs * 16u;
-    const int32_t rc = ensure(ctx, &dc.d_probe_dirs, &dc.probe_dirs_cap, bytes);
-    if (rc != BRT_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(dc.d_probe_dirs, dc.h_probe_dirs.data(), bytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    dc.probe_dirs_n = n_dirs;
-    return BRT_OK;
+    return cached_table(ctx, dc, dc.probe_dirs, n_dirs, stream, [&](std::vector<float>& h) {
+        h.resize((size_t)n_dirs * 4u);
+        probe_directions(n_dirs, h.data(), 4u);
+    });
 }
 
 int32_t probe_rays_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_probes, uint32_t n_probes, uint32_t n_dirs,
                            void* d_rays) {
     ProbeRaysArgs a;
     a.probes = static_cast<const uint4*>(d_probes);
-    a.dirs = reinterpret_cast<const float4*>(dc.d_probe_dirs);
+    a.dirs = reinterpret_cast<const float4*>(dc.probe_dirs.d);
     a.rays = static_cast<uint4*>(d_rays);
     a.n_probes = n_probes;
     a.n_dirs = n_dirs;
@@ -76,7 +65,7 @@ int32_t probe_project_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, c
                               uint32_t basis, void* d_out) {
     ProbeProjectArgs a;
     a.results = static_cast<const float4*>(d_results);
-    a.dirs = reinterpret_cast<const float4*>(dc.d_probe_dirs);
+    a.dirs = reinterpret_cast<const float4*>(dc.probe_dirs.d);
     a.out = static_cast<uint32_t*>(d_out);
     a.n_probes = n_probes;
     a.n_dirs = n_dirs;
@@ -124,8 +113,8 @@ int32_t bake_check(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t
     return BRT_OK;
 }
 
-// The bake of device buffers on `stream`: in chunks of whole probes, generate -> the radiance launch -> project, all behind ev_q, which
-// the last step records.  The lists are staged in d_qrays / d_qhits (one user at a time: `staged`).
+// The bake of device buffers on `stream`: in chunks of whole probes (bake_chunks), generate -> the radiance launch -> project, all
+// behind ev_q, which the last step records.  The lists are staged in d_qrays / d_qhits (one user at a time: `staged`).
 int32_t bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void* d_probes, uint32_t n_probes, uint32_t n_dirs,
                      uint32_t bounces, uint32_t basis, void* d_out, bool counted, BakeRun* run) {
     const uint32_t chunk_rays = std::min(std::max(ctx->knobs[K_PROBE_CHUNK_RAYS], 1u), kMaxEntries);
@@ -134,19 +123,12 @@ int32_t bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const void
     int32_t rc = staged(ctx, dc, {{&dc.d_qrays, &dc.qrays_cap, bytes}, {&dc.d_qhits, &dc.qhits_cap, bytes}});
     if (rc == BRT_OK) rc = probe_table(ctx, dc, n_dirs, stream);
     if (rc != BRT_OK) return rc;
-    run->chunks = (n_probes + per_chunk - 1u) / per_chunk;
-    if (counted) run->counts.assign((size_t)run->chunks * 3u, 0u);
-    for (uint32_t c = 0; c < run->chunks; c++) {
-        const uint32_t first = c * per_chunk, n = std::min(per_chunk, n_probes - first);
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-        rc = probe_rays_enqueue(ctx, dc, stream, static_cast<const char*>(d_probes) + (size_t)first * 16u, n, n_dirs, dc.d_qrays);
-        if (rc == BRT_OK) rc = radiance_enqueue(ctx, dc, stream, dc.d_qrays, n * n_dirs, 1u, bounces, dc.d_qhits, counted, &run->rl);
-        if (rc == BRT_OK) rc = probe_project_enqueue(ctx, dc, stream, dc.d_qhits, n, n_dirs, basis, static_cast<char*>(d_out) + (size_t)first * 128u);
-        if (rc != BRT_OK) return rc;
-        if (counted) HIP_TRY(ctx, hipMemcpyAsync(&run->counts[(size_t)c * 3u], dc.d_radctl, 24u, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    }
-    return BRT_OK;
+    return bake_chunks(ctx, dc, stream, n_probes, per_chunk, counted, run, [&](uint32_t first, uint32_t n) {
+        int32_t r = probe_rays_enqueue(ctx, dc, stream, static_cast<const char*>(d_probes) + (size_t)first * 16u, n, n_dirs, dc.d_qrays);
+        if (r == BRT_OK) r = radiance_enqueue(ctx, dc, stream, dc.d_qrays, n * n_dirs, 1u, bounces, dc.d_qhits, counted, &run->rl);
+        if (r == BRT_OK) r = probe_project_enqueue(ctx, dc, stream, dc.d_qhits, n, n_dirs, basis, static_cast<char*>(d_out) + (size_t)first * 128u);
+        return r;
+    });
 }
 
 void bake_stats(const brt_ctx* ctx, const BakeRun& run, uint32_t rebuilt, uint64_t* out8) {
@@ -207,8 +189,7 @@ int32_t brt_host_probe_irradiance(const void* record128, const float* normal3, f
 
 int32_t brt_probe_rays_device(brt_ctx* ctx, const void* d_probes, uint32_t n_probes, uint32_t n_dirs, void* d_rays, void* hip_stream,
                               uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     const int32_t rc = step_check(ctx, d_probes, 16u, d_rays, (size_t)n_dirs * 32u, n_probes, n_dirs, PROBE_SH9, flags);
     if (rc != BRT_OK || n_probes == 0u) return rc;
     return step_run(ctx, n_dirs, hip_stream, flags, [&](DeviceCtx& dc, hipStream_t stream) {
@@ -219,8 +200,7 @@ int32_t brt_probe_rays_device(brt_ctx* ctx, const void* d_probes, uint32_t n_pro
 
 int32_t brt_probe_project_device(brt_ctx* ctx, const void* d_results, uint32_t n_probes, uint32_t n_dirs, uint32_t basis, void* d_out,
                                  void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     const int32_t rc = step_check(ctx, d_results, (size_t)n_dirs * 32u, d_out, 128u, n_probes, n_dirs, basis, flags);
     if (rc != BRT_OK || n_probes == 0u) return rc;
     return step_run(ctx, n_dirs, hip_stream, flags, [&](DeviceCtx& dc, hipStream_t stream) {
@@ -231,50 +211,31 @@ int32_t brt_probe_project_device(brt_ctx* ctx, const void* d_results, uint32_t n
 
 int32_t brt_bake_probes_device(brt_ctx* ctx, const void* d_probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
                                float origin_bound, void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = bake_check(ctx, d_probes, n_probes, n_dirs, bounces, basis, origin_bound, d_out);
     if (rc != BRT_OK) return rc;
-    BakeRun run;
-    uint32_t rebuilt = 0u;
-    if (n_probes == 0u) { bake_stats(ctx, run, 0u, out_stats8); return BRT_OK; }
-    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        const int32_t r = bake_enqueue(ctx, dc, sc.stream, d_probes, n_probes, n_dirs, bounces, basis, d_out, sc.own, &run);
-        if (r != BRT_OK || !sc.own) return r;
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
+    if (n_probes == 0u) { bake_stats(ctx, BakeRun(), 0u, out_stats8); return BRT_OK; }
+    return bake_call(ctx, origin_bound, hip_stream, flags, out_stats8, [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
+        return bake_enqueue(ctx, dc, stream, d_probes, n_probes, n_dirs, bounces, basis, d_out, counted, run);
     });
-    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
-    return rc;
     });
 }
 
 int32_t brt_bake_probes(brt_ctx* ctx, const void* probes, uint32_t n_probes, uint32_t n_dirs, uint32_t bounces, uint32_t basis,
                         float origin_bound, void* out, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = bake_check(ctx, probes, n_probes, n_dirs, bounces, basis, origin_bound, out);
     if (rc != BRT_OK) return rc;
-    BakeRun run;
-    uint32_t rebuilt = 0u;
-    if (n_probes == 0u) { bake_stats(ctx, run, 0u, out_stats8); return BRT_OK; }
-    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        // the probes and the records on the device: one buffer, 16 + 128 bytes per probe
-        const size_t in_bytes = align256((size_t)n_probes * 16u), bytes = in_bytes + (size_t)n_probes * 128u;
-        int32_t r = staged(ctx, dc, {{&dc.d_probe_io, &dc.probe_io_cap, bytes}});
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_probe_io, probes, (size_t)n_probes * 16u, hipMemcpyHostToDevice, dc.stream));
-        r = bake_enqueue(ctx, dc, dc.stream, dc.d_probe_io, n_probes, n_dirs, bounces, basis, dc.d_probe_io + in_bytes, true, &run);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_probe_io + in_bytes, (size_t)n_probes * 128u, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
+    if (n_probes == 0u) { bake_stats(ctx, BakeRun(), 0u, out_stats8); return BRT_OK; }
+    // the probes and the records on the device: one buffer, 16 + 128 bytes per probe
+    const size_t in_bytes = align256((size_t)n_probes * 16u), out_bytes_ = (size_t)n_probes * 128u;
+    return bake_call_host(ctx, origin_bound, in_bytes + out_bytes_, {in_bytes, out, out_bytes_}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) -> int32_t {
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, probes, (size_t)n_probes * 16u, hipMemcpyHostToDevice, stream));
+        return bake_enqueue(ctx, dc, stream, dc.d_list_io, n_probes, n_dirs, bounces, basis, dc.d_list_io + in_bytes, counted, run);
     });
-    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
-    return rc;
     });
 }
 

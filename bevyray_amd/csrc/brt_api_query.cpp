@@ -212,8 +212,7 @@ extern "C" {
 
 int32_t brt_query_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* d_hits,
                               void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = query_check(ctx, d_rays, n_rays, mode, origin_bound, d_hits);
     if (rc != BRT_OK) return rc;
@@ -233,8 +232,7 @@ int32_t brt_query_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays,
 }
 
 int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* hits, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = query_check(ctx, rays, n_rays, mode, origin_bound, hits);
     if (rc != BRT_OK) return rc;
     QueryLaunch ql{};
@@ -260,8 +258,7 @@ int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t
 }
 
 int32_t brt_query_origin_bound(brt_ctx* ctx, float* out_bound) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!out_bound) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_bound is null");
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     *out_bound = query_bound_of(ctx);

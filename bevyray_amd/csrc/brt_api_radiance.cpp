@@ -78,8 +78,7 @@ extern "C" {
 
 int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound,
                                  void* d_out, void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = radiance_check(ctx, d_rays, n_rays, samples, bounces, origin_bound, d_out);
     if (rc != BRT_OK) return rc;
@@ -101,8 +100,7 @@ int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_ra
 
 int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound, void* out,
                           uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     int32_t rc = radiance_check(ctx, rays, n_rays, samples, bounces, origin_bound, out);
     if (rc != BRT_OK) return rc;
     RadianceLaunch rl{};

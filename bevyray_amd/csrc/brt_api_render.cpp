@@ -397,8 +397,7 @@ extern "C" {
 
 int32_t brt_render(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t width, uint32_t height,
                    const float* raster_rgba, const float* raster_depth, float* out_rgba, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!out_rgba) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_rgba is null");
     if (const int32_t bad = post_flags_check(ctx, level, flags)) return bad;
     if (const int32_t bad = scene_ready(ctx, level)) return bad;
@@ -413,8 +412,7 @@ int32_t brt_render_part_device(brt_ctx* ctx, const void* camera80, const void* w
                                uint32_t height, uint32_t part, uint32_t n_parts, const float* d_raster_rgba,
                                const float* d_raster_depth, float* d_out_tile, void* hip_stream, uint32_t flags,
                                brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL | BRT_FLAG_BLEND_POST))
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "a rank's strips have no neighbours: denoise / accumulate the assembled frame (brt_denoise_device, brt_blend_post_device)");
     if (!d_out_tile) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out_tile is null");
@@ -430,8 +428,7 @@ int32_t brt_render_part_device(brt_ctx* ctx, const void* camera80, const void* w
 int32_t brt_render_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t level, uint32_t width, uint32_t height,
                           const float* d_raster_rgba, const float* d_raster_depth, void* d_frame, void* hip_stream, uint32_t flags,
                           brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
     if (const int32_t bad = post_flags_check(ctx, level, flags)) return bad;
     if (const int32_t bad = scene_ready(ctx, level)) return bad;
@@ -444,8 +441,7 @@ int32_t brt_render_device(brt_ctx* ctx, const void* camera80, const void* window
 
 int32_t brt_deinterleave_device(brt_ctx* ctx, const float* d_tiles, uint32_t n_parts, uint32_t width, uint32_t height,
                                 void* d_frame, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL | BRT_FLAG_BLEND_POST))
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the de-interleave does not denoise or accumulate: brt_denoise_device on the assembled frame");
     if (!d_tiles || !d_frame || n_parts == 0) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null buffer / n_parts == 0");

@@ -279,8 +279,7 @@ int32_t brt_render_upscaled_refined_device(brt_ctx* ctx, const void* camera80, c
 int32_t brt_upscale_refine_mask_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                                        const float* d_low_rgba, uint32_t width, uint32_t height, void* d_mask_u8, void* hip_stream,
                                        uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_low_rgba || !d_mask_u8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_low_rgba / d_mask_u8 is null");
     if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
     if (const int32_t bad = refine_check(ctx, camera80, window16, low_width, low_height, width, height, BRT_REFINE_EDGES | BRT_REFINE_SPECULAR))

@@ -1,20 +1,14 @@
 // brt_api_volume.cpp -- irradiance volumes (brt_volume.h, brt_volume.hip; DESIGN.md "Irradiance volumes") on the first device: a regular
 // lattice of light probes baked in one call, and lists of {position, normal} shaded from the baked records.  The bake is the light
-// probes' (brt_api_probe.cpp bake_enqueue) over probes that k_volume_probes writes; streams, ordering behind ev_q and the staging rule
-// are those of every list call (brt_frame.h: with_reach, with_list_call, staged, list_step_run).
+// probes' (brt_api_probe.cpp bake_enqueue) over probes that k_volume_probes writes; the skeleton of a bake export, streams, ordering
+// behind ev_q and the staging rule are those of every list call (brt_frame.h: bake_call, bake_call_host, with_list_call, staged,
+// list_step_run, device_aligned).  Here: the descriptor's checks, the argument packing and the host twins.
 #include "brt_frame.h"
 #include "brt_volume.h"
 
 using namespace brt;
 
 namespace {
-
-// the kernels read and write whole 16-byte words: a DEVICE buffer of the caller's must be 16-byte aligned (hipMalloc's are)
-int32_t device_aligned(brt_ctx* ctx, std::initializer_list<const void*> ptrs) {
-    for (const void* p : ptrs)
-        if (reinterpret_cast<uintptr_t>(p) & 15u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "device buffers must be 16-byte aligned");
-    return BRT_OK;
-}
 
 // the caller's 48 bytes -> *v and the number of probes, or the refusal of a descriptor (ctx may be null: the host exports)
 int32_t volume_check(brt_ctx* ctx, const void* volume48, VolumeDesc* v, uint32_t* n_probes) {
@@ -78,8 +72,10 @@ int32_t volume_sample_enqueue(brt_ctx* ctx, hipStream_t stream, const VolumeDesc
     return BRT_OK;
 }
 
-// the lattice's probes in the context's buffer (`staged`) for work on `stream`, behind ev_q and recorded in it
-int32_t volume_probes_staged(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const VolumeDesc& v, uint32_t n_probes) {
+// The bake into the DEVICE buffer d_records on `stream`: the lattice's probes in the context's buffer (`staged`), behind ev_q and
+// recorded in it, then the light probes' bake over them
+int32_t volume_bake_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const VolumeDesc& v, uint32_t n_probes, uint32_t n_dirs,
+                            uint32_t bounces, void* d_records, bool counted, BakeRun* run) {
     const size_t bytes = (size_t)n_probes * 16u;
     int32_t rc = staged(ctx, dc, {{&dc.d_volume_probes, &dc.volume_probes_cap, bytes}});
     if (rc != BRT_OK) return rc;
@@ -87,7 +83,7 @@ int32_t volume_probes_staged(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, co
     rc = volume_probes_enqueue(ctx, stream, v, n_probes, dc.d_volume_probes);
     if (rc != BRT_OK) return rc;
     HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    return BRT_OK;
+    return bake_enqueue(ctx, dc, stream, dc.d_volume_probes, n_probes, n_dirs, bounces, v.basis, d_records, counted, run);
 }
 
 // what both bakes check before anything is enqueued
@@ -138,8 +134,7 @@ int32_t brt_host_volume_sample(const void* volume48, const void* records, const 
 }
 
 int32_t brt_volume_probes_device(brt_ctx* ctx, const void* volume48, void* d_probes, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     VolumeDesc v;
     uint32_t n_probes = 0u;
     int32_t rc = caller_stream_flags_check(ctx, flags);
@@ -154,56 +149,37 @@ int32_t brt_volume_probes_device(brt_ctx* ctx, const void* volume48, void* d_pro
 
 int32_t brt_bake_volume_device(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uint32_t bounces, float origin_bound, void* d_records,
                                void* hip_stream, uint32_t flags, uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     VolumeDesc v;
-    uint32_t n_probes = 0u, rebuilt = 0u;
+    uint32_t n_probes = 0u;
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = volume_bake_check(ctx, volume48, n_dirs, bounces, origin_bound, d_records, &v, &n_probes);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_records});
     if (rc != BRT_OK) return rc;
-    BakeRun run;
-    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = volume_probes_staged(ctx, dc, sc.stream, v, n_probes);
-        if (r == BRT_OK) r = bake_enqueue(ctx, dc, sc.stream, dc.d_volume_probes, n_probes, n_dirs, bounces, v.basis, d_records, sc.own, &run);
-        if (r != BRT_OK || !sc.own) return r;
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
+    return bake_call(ctx, origin_bound, hip_stream, flags, out_stats8, [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
+        return volume_bake_enqueue(ctx, dc, stream, v, n_probes, n_dirs, bounces, d_records, counted, run);
     });
-    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
-    return rc;
     });
 }
 
 int32_t brt_bake_volume(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uint32_t bounces, float origin_bound, void* records,
                         uint64_t* out_stats8) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     VolumeDesc v;
-    uint32_t n_probes = 0u, rebuilt = 0u;
-    int32_t rc = volume_bake_check(ctx, volume48, n_dirs, bounces, origin_bound, records, &v, &n_probes);
+    uint32_t n_probes = 0u;
+    const int32_t rc = volume_bake_check(ctx, volume48, n_dirs, bounces, origin_bound, records, &v, &n_probes);
     if (rc != BRT_OK) return rc;
-    BakeRun run;
-    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        const size_t bytes = (size_t)n_probes * 128u;
-        int32_t r = staged(ctx, dc, {{&dc.d_volume_io, &dc.volume_io_cap, bytes}});
-        if (r == BRT_OK) r = volume_probes_staged(ctx, dc, dc.stream, v, n_probes);
-        if (r == BRT_OK) r = bake_enqueue(ctx, dc, dc.stream, dc.d_volume_probes, n_probes, n_dirs, bounces, v.basis, dc.d_volume_io, true, &run);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(records, dc.d_volume_io, bytes, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
+    const size_t bytes = (size_t)n_probes * 128u;
+    return bake_call_host(ctx, origin_bound, bytes, {0u, records, bytes}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
+        return volume_bake_enqueue(ctx, dc, stream, v, n_probes, n_dirs, bounces, dc.d_list_io, counted, run);
     });
-    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
-    return rc;
     });
 }
 
 int32_t brt_sample_volume_device(brt_ctx* ctx, const void* volume48, const void* d_records, const void* d_points, uint32_t n_points,
                                  void* d_out, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     VolumeDesc v;
     uint32_t n_probes = 0u;
     int32_t rc = caller_stream_flags_check(ctx, flags);
@@ -218,8 +194,7 @@ int32_t brt_sample_volume_device(brt_ctx* ctx, const void* volume48, const void*
 }
 
 int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* records, const void* points, uint32_t n_points, void* out) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     VolumeDesc v;
     uint32_t n_probes = 0u;
     int32_t rc = volume_check(ctx, volume48, &v, &n_probes);
@@ -229,14 +204,14 @@ int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* record
         // the records, the points and the samples on the device: one buffer
         const size_t rec_bytes = (size_t)n_probes * 128u, pt_bytes = (size_t)n_points * 32u, out_bytes_ = (size_t)n_points * 16u;
         const size_t pt_off = align256(rec_bytes), out_off = pt_off + align256(pt_bytes), bytes = out_off + out_bytes_;
-        int32_t r = staged(ctx, dc, {{&dc.d_volume_io, &dc.volume_io_cap, bytes}});
+        int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, bytes}});
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_volume_io, records, rec_bytes, hipMemcpyHostToDevice, dc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_volume_io + pt_off, points, pt_bytes, hipMemcpyHostToDevice, dc.stream));
-        r = volume_sample_enqueue(ctx, dc.stream, v, dc.d_volume_io, dc.d_volume_io + pt_off, n_points, dc.d_volume_io + out_off);
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, records, rec_bytes, hipMemcpyHostToDevice, dc.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io + pt_off, points, pt_bytes, hipMemcpyHostToDevice, dc.stream));
+        r = volume_sample_enqueue(ctx, dc.stream, v, dc.d_list_io, dc.d_list_io + pt_off, n_points, dc.d_list_io + out_off);
         if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_volume_io + out_off, out_bytes_, hipMemcpyDeviceToHost, dc.stream));
+        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_list_io + out_off, out_bytes_, hipMemcpyDeviceToHost, dc.stream));
         HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;

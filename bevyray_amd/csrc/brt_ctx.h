@@ -21,6 +21,14 @@
 
 namespace brt {
 
+// A table computed on the host and kept on the device by a key (0: none), with the host copy its upload reads (brt_frame.h cached_table)
+struct DeviceTable {
+    float* d = nullptr;
+    size_t cap = 0;
+    uint64_t key = 0;
+    std::vector<float> h;
+};
+
 struct DeviceCtx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -149,32 +157,24 @@ struct DeviceCtx {
     // d_qrays / d_qhits, which therefore have one user at a time
     uint32_t* d_radctl = nullptr;
     size_t radctl_cap = 0;
-    // light probes (brt_probe.h), first device only: the direction table {x, y, z, 0} of probe_dirs_n directions (0: none) and the host
-    // copy its upload reads; the probes and records of brt_bake_probes.  A bake stages its lists in d_qrays / d_qhits and is ordered by
-    // ev_q like the radiance lists it launches; the table is rewritten only once every list of the context has ended
-    float* d_probe_dirs = nullptr;
-    size_t probe_dirs_cap = 0;
-    uint32_t probe_dirs_n = 0;
-    std::vector<float> h_probe_dirs;
-    char* d_probe_io = nullptr;
-    size_t probe_io_cap = 0;
-    // irradiance volumes (brt_volume.h), first device only: the probes k_volume_probes generates for a bake, and the records, points and
-    // samples of the host entry points.  Ordered by ev_q like the probe buffers: each grows only once every list of the context has ended
+    // light probes (brt_probe.h), first device only: the direction table {x, y, z, 0}, kept by n_dirs.  A bake stages its lists in
+    // d_qrays / d_qhits and is ordered by ev_q like the radiance lists it launches; the table is rewritten only once every list of the
+    // context has ended (brt_frame.h cached_table)
+    DeviceTable probe_dirs;
+    // the device side of the host forms brt_bake_probes (probes and records), brt_bake_volume (records), brt_sample_volume (records,
+    // points and samples) and brt_bake_envmap (the chain).  Every user is synchronous on `stream` and reaches the buffer through `staged`
+    // (brt_frame.h): it grows only once every list of the context has ended, and a call has returned before the next one takes it over
+    char* d_list_io = nullptr;
+    size_t list_io_cap = 0;
+    // irradiance volumes (brt_volume.h), first device only: the probes k_volume_probes generates for a bake.  Ordered by ev_q like the
+    // staging buffers: it grows only once every list of the context has ended
     char* d_volume_probes = nullptr;
     size_t volume_probes_cap = 0;
-    char* d_volume_io = nullptr;
-    size_t volume_io_cap = 0;
-    // reflection probes (brt_envmap.h), first device only: the box levels of a bake (and the f32 level 0 of an RGBA16F one), the chain
-    // of brt_bake_envmap, and the tap tables of the levels 1 .. envmap_taps_levels - 1 (envmap_taps_n taps each; 0: none) with the host
-    // copy their upload reads.  Ordered by ev_q like the probe buffers: each grows only once every list of the context has ended
+    // reflection probes (brt_envmap.h), first device only: the box levels of a bake (and the f32 level 0 of an RGBA16F one), and the tap
+    // tables of the levels 1 .. levels - 1 (n_taps taps each), kept by (levels, n_taps).  Ordered by ev_q like the probe buffers
     char* d_envmap = nullptr;
     size_t envmap_cap = 0;
-    char* d_envmap_io = nullptr;
-    size_t envmap_io_cap = 0;
-    float* d_envmap_taps = nullptr;
-    size_t envmap_taps_cap = 0;
-    uint32_t envmap_taps_levels = 0, envmap_taps_n = 0;
-    std::vector<float> h_envmap_taps;
+    DeviceTable envmap_taps;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;
@@ -283,7 +283,16 @@ inline int32_t ctx_fail(brt_ctx* ctx, int32_t code, const std::string& msg) {
     return code;
 }
 
-#define HIP_TRY(ctx, expr)                                                                              \
+// guard() (brt_host.h) for an export that owns a context: an exception's text is left in the context too, and a null context is refused
+template <class F>
+inline int32_t ctx_guard(brt_ctx* ctx, F&& body) noexcept {
+    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+        if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+        return body();
+    });
+}
+
+#define HIP_TRY(ctx, expr)                                                                             \
     do {                                                                                                \
         hipError_t _e = (expr);                                                                         \
         if (_e != hipSuccess)                                                                           \

@@ -18,7 +18,8 @@
 namespace brt {
 
 constexpr uint32_t kPolicyMask = BRT_POLICY_OR_SHORT_CIRCUIT | BRT_POLICY_MINMAX_SELECT | BRT_POLICY_POW_EXP2_LOG2;
-constexpr uint32_t kLptAfterUpload = 4;      // frames after a scene upload within which the tile costs are measured again (brt_api_order.cpp)
+constexpr double kTwoPi = 6.283185307179586;   // of the host-computed tables (probe directions, envmap taps)
+constexpr uint32_t kLptAfterUpload = 4;     // frames after a scene upload within which the tile costs are measured again (brt_api_order.cpp)
 
 inline double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -136,7 +137,7 @@ int32_t radiance_enqueue(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const 
 // ---- brt_api_probe.cpp ----
 // What the bakes of light probes share with the bake of an irradiance volume (brt_api_volume.cpp).  bake_check: the arguments of a bake
 // (with n_probes = 0 the two pointers are not looked at).  bake_enqueue: the bake of DEVICE buffers on `stream`, in chunks of whole
-// probes, all behind ev_q, which the last step records.  bake_stats: the call's out_stats8.
+// probes (bake_chunks), all behind ev_q, which the last step records.  bake_stats: the out_stats8 of every bake (bake_call).
 struct BakeRun {
     RadianceLaunch rl{};
     uint32_t chunks = 0u;
@@ -178,13 +179,20 @@ int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const De
 bool blend_post_on(uint32_t level, uint32_t flags);
 int32_t post_flags_check(brt_ctx* ctx, uint32_t level, uint32_t flags);
 
-// ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp, brt_api_pixels.cpp) ----
+// ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp,
+// brt_api_envmap.cpp, brt_api_pixels.cpp) ----
 inline int32_t caller_stream_flags_check(brt_ctx* ctx, uint32_t flags) {
     if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
     return BRT_OK;
 }
 inline int32_t origin_bound_check(brt_ctx* ctx, float origin_bound) {
     if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
+    return BRT_OK;
+}
+// the kernels read and write whole 16-byte words: a DEVICE buffer of the caller's must be 16-byte aligned (hipMalloc's are)
+inline int32_t device_aligned(brt_ctx* ctx, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) & 15u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "device buffers must be 16-byte aligned");
     return BRT_OK;
 }
 
@@ -198,6 +206,25 @@ inline int32_t staged(brt_ctx* ctx, DeviceCtx& dc, std::initializer_list<StagedB
         const int32_t rc = ensure(ctx, b.ptr, b.cap, b.bytes);
         if (rc != BRT_OK) return rc;
     }
+    return BRT_OK;
+}
+
+// The device table `t` of `key` (not 0) for work on `stream`, which is then behind ev_q.  Another key rewrites the host copy (fill(t.h)
+// resizes and fills it) and the device copy only once every list of the context has ended (the upload of the old table among them),
+// and the upload is recorded in ev_q, so that a list on another stream starts behind it.
+template <class Fill>
+int32_t cached_table(brt_ctx* ctx, DeviceCtx& dc, DeviceTable& t, uint64_t key, hipStream_t stream, Fill&& fill) {
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    if (t.key == key && t.d) return BRT_OK;
+    HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
+    t.key = 0u;
+    fill(t.h);
+    const size_t bytes = t.h.size() * sizeof(float);
+    const int32_t rc = ensure(ctx, &t.d, &t.cap, bytes);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(t.d, t.h.data(), bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+    t.key = key;
     return BRT_OK;
 }
 
@@ -237,6 +264,58 @@ int32_t list_step_run(brt_ctx* ctx, void* hip_stream, uint32_t flags, Enqueue&& 
         HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
         return BRT_OK;
     }, enqueue);
+}
+
+// The chunks of a bake on `stream`: n_units units (probes, texels), per_chunk at a time.  body(first, n) enqueues generate ->
+// radiance_enqueue -> reduce of one chunk, which runs behind ev_q and records it (the chunks share d_qrays / d_qhits); a counted run
+// copies the chunk's three counts out of d_radctl before the next chunk zeroes them.
+template <class Body>
+int32_t bake_chunks(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, uint32_t n_units, uint32_t per_chunk, bool counted, BakeRun* run,
+                    Body&& body) {
+    run->chunks = (n_units + per_chunk - 1u) / per_chunk;
+    if (counted) run->counts.assign((size_t)run->chunks * 3u, 0u);
+    for (uint32_t c = 0; c < run->chunks; c++) {
+        const uint32_t first = c * per_chunk;
+        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+        const int32_t rc = body(first, std::min(per_chunk, n_units - first));
+        if (rc != BRT_OK) return rc;
+        if (counted) HIP_TRY(ctx, hipMemcpyAsync(&run->counts[(size_t)c * 3u], dc.d_radctl, 24u, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+    }
+    return BRT_OK;
+}
+
+// A bake export behind its argument checks: the tree's reach (with_reach), then enqueue(dc, stream, counted, &run) on the call's stream;
+// the own stream synchronises and is counted; a successful call reports its stats (bake_stats).
+template <class Enqueue>
+int32_t bake_call(brt_ctx* ctx, float origin_bound, void* hip_stream, uint32_t flags, uint64_t* out_stats8, Enqueue&& enqueue) {
+    BakeRun run;
+    uint32_t rebuilt = 0u;
+    const int32_t rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        const int32_t r = enqueue(dc, sc.stream, sc.own, &run);
+        if (r != BRT_OK || !sc.own) return r;
+        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+        return BRT_OK;
+    });
+    if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
+    return rc;
+}
+// The host form: the bake on the context's own stream into d_list_io (io_bytes of it: `staged`), whose `bytes` at `offset` are then
+// copied to `host`; the copy reads the buffer, so ev_q is recorded behind it.  reached(): what the call checks once the tree is
+// settled, before anything is staged.
+struct BakeCopyOut { size_t offset; void* host; size_t bytes; };
+template <class Enqueue, class Reached = int32_t (*)()>
+int32_t bake_call_host(brt_ctx* ctx, float origin_bound, size_t io_bytes, const BakeCopyOut& out, uint64_t* out_stats8, Enqueue&& enqueue,
+                       Reached reached = [] { return (int32_t)BRT_OK; }) {
+    return bake_call(ctx, origin_bound, nullptr, 0u, out_stats8, [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) -> int32_t {
+        int32_t r = reached();
+        if (r == BRT_OK) r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, io_bytes}});
+        if (r == BRT_OK) r = enqueue(dc, stream, counted, run);
+        if (r != BRT_OK) return r;
+        HIP_TRY(ctx, hipMemcpyAsync(out.host, dc.d_list_io + out.offset, out.bytes, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+        return BRT_OK;
+    });
 }
 
 // The out_stats8 of a list call: three counts (nullptr: not gathered), tree rebuilt, the callee-built tree's reach (bits), the form, and

@@ -180,8 +180,7 @@ int32_t brt_rccl_comm_destroy(brt_ctx* ctx, void* comm) {
 
 int32_t brt_gather_rccl(brt_ctx* ctx, void* nccl_comm, int32_t rank, int32_t world, const float* d_tile, float* d_tiles_on_root,
                         uint32_t width, uint32_t height, void* d_frame_on_root, void* hip_stream, uint32_t flags) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL | BRT_FLAG_BLEND_POST))
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the gather does not denoise or accumulate: brt_denoise_device on the root's assembled frame");
     if (!nccl_comm || !d_tile) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null communicator / tile");
@@ -275,8 +274,7 @@ int32_t brt_import_frame_fd(brt_ctx* ctx, int32_t fd, uint64_t bytes, uint32_t h
 }
 
 int32_t brt_release_frame(brt_ctx* ctx, void* d_frame) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     for (size_t i = 0; i < ctx->external.size(); i++)
         if (ctx->external[i].ptr == d_frame) {
             HIP_TRY(ctx, hipSetDevice(ctx->devs[0].device));

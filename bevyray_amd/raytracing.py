@@ -142,6 +142,15 @@ def _stats8(words, names) -> dict:
             "form": int(words[5]), names[1]: int(words[6])}
 
 
+def _bake_call(node, export, *args) -> dict:
+    """One brt_bake_* export of `node`: export(ctx, *args, out_stats8), checked -> the call's stats, kept in node.last_probe_stats."""
+    p = node._p
+    words = (C.c_uint64 * 8)()
+    _lib.check(export(p._ctx, *args, words), p._ctx)
+    node.last_probe_stats = _stats8(words, ("walks", "chunks"))
+    return node.last_probe_stats
+
+
 class CameraExtract:
     """extract.rs:83-158"""
 
@@ -1031,19 +1040,15 @@ class RayTracingNode:
         of PROBE_DTYPE records in host memory -> PROBE_RECORD_DTYPE records (synchronous).  device=True: `probes` is (d_probes,
         n_probes, d_out), device pointers on the first device -> the call's stats; stream rule as for radiance_rays.
         last_probe_stats holds the call's stats."""
-        p = self._p
-        words = (C.c_uint64 * 8)()
+        lib = self._p._lib
         if device:
             d_probes, n_probes, d_out = probes
-            _lib.check(p._lib.brt_bake_probes_device(p._ctx, d_probes or None, int(n_probes), int(n_dirs), int(bounces), int(basis),
-                                                     float(origin_bound), d_out or None, *_stream_args(stream), words), p._ctx)
-            self.last_probe_stats = _stats8(words, ("walks", "chunks"))
-            return self.last_probe_stats
+            return _bake_call(self, lib.brt_bake_probes_device, d_probes or None, int(n_probes), int(n_dirs), int(bounces), int(basis),
+                              float(origin_bound), d_out or None, *_stream_args(stream))
         probes = np.ascontiguousarray(probes, PROBE_DTYPE)
         out = np.empty(probes.shape, PROBE_RECORD_DTYPE)
-        _lib.check(p._lib.brt_bake_probes(p._ctx, probes.ctypes.data if probes.size else None, probes.size, int(n_dirs), int(bounces),
-                                          int(basis), float(origin_bound), out.ctypes.data if probes.size else None, words), p._ctx)
-        self.last_probe_stats = _stats8(words, ("walks", "chunks"))
+        _bake_call(self, lib.brt_bake_probes, probes.ctypes.data if probes.size else None, probes.size, int(n_dirs), int(bounces),
+                   int(basis), float(origin_bound), out.ctypes.data if probes.size else None)
         return out
 
     def probe_rays_device(self, d_probes: int, n_probes: int, n_dirs: int, d_rays: int, stream: Optional[int] = None):
@@ -1072,17 +1077,13 @@ class RayTracingNode:
         """brt_bake_volume*: the records of the lattice `volume` (VOLUME_DTYPE), baked as bake_probes bakes the lattice's probes.
         d_records=None: -> PROBE_RECORD_DTYPE records in host memory (synchronous).  d_records=<device pointer>: the records are written
         there -> the call's stats; stream rule as for bake_probes.  last_probe_stats holds the call's stats."""
-        p = self._p
+        lib = self._p._lib
         v = np.ascontiguousarray(volume, VOLUME_DTYPE).reshape(1)
-        words = (C.c_uint64 * 8)()
         if d_records is not None:
-            _lib.check(p._lib.brt_bake_volume_device(p._ctx, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), d_records or None,
-                                                     *_stream_args(stream), words), p._ctx)
-            self.last_probe_stats = _stats8(words, ("walks", "chunks"))
-            return self.last_probe_stats
+            return _bake_call(self, lib.brt_bake_volume_device, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound),
+                              d_records or None, *_stream_args(stream))
         out = np.empty(max(_volume_probe_count(v), 1), PROBE_RECORD_DTYPE)
-        _lib.check(p._lib.brt_bake_volume(p._ctx, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), out.ctypes.data, words), p._ctx)
-        self.last_probe_stats = _stats8(words, ("walks", "chunks"))
+        _bake_call(self, lib.brt_bake_volume, v.ctypes.data, int(n_dirs), int(bounces), float(origin_bound), out.ctypes.data)
         return out
 
     def sample_volume(self, volume, records, points, device: bool = False, stream: Optional[int] = None):
@@ -1112,20 +1113,13 @@ class RayTracingNode:
         levels concatenated (envmap_level_offsets).  d_out=None: -> the chain's texels in host memory, (n, 4) f32 or, with
         out_format=FLAG_OUT_RGBA16F, f16 (synchronous).  d_out=<device pointer>: the chain is written there -> the call's stats; stream
         rule as for bake_probes.  last_probe_stats holds the call's stats."""
-        p = self._p
-        words = (C.c_uint64 * 8)()
-        pos = _f3(position)
+        lib = self._p._lib
+        args = (_f3(position), int(seed), int(size), int(levels), int(samples), int(bounces), int(n_taps), float(origin_bound))
         if d_out is not None:
-            hs, flags = _stream_args(stream, int(out_format))
-            _lib.check(p._lib.brt_bake_envmap_device(p._ctx, pos, int(seed), int(size), int(levels), int(samples), int(bounces), int(n_taps),
-                                                     float(origin_bound), d_out or None, hs, flags, words), p._ctx)
-            self.last_probe_stats = _stats8(words, ("walks", "chunks"))
-            return self.last_probe_stats
+            return _bake_call(self, lib.brt_bake_envmap_device, *args, d_out or None, *_stream_args(stream, int(out_format)))
         n = envmap_level_offsets(size, levels)[-1] if 0 < int(size) <= 1024 and 0 < int(levels) <= 11 else 1
         out = np.zeros((max(n, 1), 4), np.float16 if out_format == FLAG_OUT_RGBA16F else np.float32)
-        _lib.check(p._lib.brt_bake_envmap(p._ctx, pos, int(seed), int(size), int(levels), int(samples), int(bounces), int(n_taps),
-                                          float(origin_bound), out.ctypes.data, int(out_format), words), p._ctx)
-        self.last_probe_stats = _stats8(words, ("walks", "chunks"))
+        _bake_call(self, lib.brt_bake_envmap, *args, out.ctypes.data, int(out_format))
         return out
 
     def envmap_rays_device(self, position, seed: int, size: int, d_rays: int, stream: Optional[int] = None):

@@ -1,7 +1,8 @@
 """Shared test helpers: hand-made BVHs (single leaf, median split, caterpillar chain, a composer that grafts one onto another),
 a seeded scene large enough for 32-bit tree descriptors with its camera, the upload of a scene whose tree the callee builds,
 uniform builders, the generator of randomized scenes (materials, sizes, cameras, topologies) and a numpy-f32 restatement of the
-camera/sky arithmetic for analytic checks."""
+camera/sky arithmetic for analytic checks; for the GPU tests of the bakes, device buffers and the upload of the cover scene."""
+import functools
 import os
 
 import numpy as np
@@ -165,6 +166,36 @@ def resident_callee_tree(plugin, b, lvl, cam, win, w, h, seeds=()):
         plugin.node.run(lvl, cam, win, w, h)
     st = dict(plugin.node.last_stats)
     return brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models, st["tree_reach"])), win, st
+
+
+def dev(a):
+    """The bytes of a host array in a device tensor of uint8."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+
+def guarded(n_bytes, guard, fill):
+    """A device buffer of n_bytes with `guard` bytes behind it, all of them `fill`."""
+    import torch
+    return torch.full((n_bytes + guard,), fill, dtype=torch.uint8, device="cuda")
+
+
+@functools.lru_cache(maxsize=None)
+def cover():
+    return brt.generate_scene(brt.SCENE_COVER, 1)
+
+
+def upload_cover(plugin, tree):
+    """The cover scene under the caller's PLOC tree, or under the callee's SAH tree with its reach raised by a bake's origin_bound."""
+    b = cover()
+    if tree == "caller":
+        plugin.node.write_buffers(b)
+        return
+    plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
+    one = np.zeros(1, brt.PROBE_DTYPE)
+    one["position"] = (0.0, 30.0, 0.0)
+    plugin.node.bake_probes(one, 1, 0, brt.PROBE_SH9, origin_bound=40.0)
+    assert 40.0 <= plugin.node.query_origin_bound() < np.inf
 
 
 def make_buffers(data, bvh_fn=None):

@@ -16,7 +16,7 @@ import bevyray_amd as brt
 import envmap_ref as er
 import radiance_ref as rr
 from bevyray_amd import _lib
-from helpers import big_scene, big_view, make_buffers
+from helpers import big_scene, big_view, cover as _cover, dev as _dev, guarded as _guarded, make_buffers, upload_cover as _upload_cover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("brt_host_envmap_directions", "brt_host_envmap_taps", "brt_host_envmap_downsample", "brt_host_envmap_filter",
@@ -335,16 +335,6 @@ def test_the_stand_alone_twin_under_sanitizers(tmp_path):
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def _guarded(n_bytes, guard, fill):
-    import torch
-    return torch.full((n_bytes + guard,), fill, dtype=torch.uint8, device="cuda")
-
-
 def _read(d_buf, n_bytes, fill, what):
     import torch
     torch.cuda.synchronize()
@@ -421,23 +411,6 @@ def test_the_downsample_kernel_is_the_host_twin_and_the_restatement(plugin, size
         got = _downsample_device(plugin, _cube(kind, size))
         assert_texels_equal(got, er.downsample(_cube(kind, size)), f"{kind} {size}")
         assert_texels_equal(got, brt.envmap_downsample_host(_cube(kind, size)), f"{kind} {size}, twin")
-
-
-@functools.lru_cache(maxsize=None)
-def _cover():
-    return brt.generate_scene(brt.SCENE_COVER, 1)
-
-
-def _upload_cover(plugin, tree):
-    b = _cover()
-    if tree == "caller":
-        plugin.node.write_buffers(b)
-        return
-    plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
-    one = np.zeros(1, brt.PROBE_DTYPE)
-    one["position"] = (0.0, 30.0, 0.0)
-    plugin.node.bake_probes(one, 1, 0, brt.PROBE_SH9, origin_bound=40.0)
-    assert 40.0 <= plugin.node.query_origin_bound() < np.inf
 
 
 POSITION, SEED, SIZE, LEVELS, TAPS, BOUNCES = (2.5, 1.5, 3.5), 0xFFFFFFC0, 8, 4, 64, 8
@@ -566,6 +539,51 @@ def test_a_scene_with_32_bit_descriptors(plugin):
     with plugin.tuning(BRT_RADIANCE_FORM=STREAM):
         assert_texels_equal(plugin.node.bake_envmap(centre, SIZE, LEVELS, 1, 4, TAPS, 77), want, "streaming")
         assert plugin.node.last_probe_stats["form"] == 1
+
+
+@pytest.mark.gpu
+def test_host_bakes_behind_a_held_bake_rewrite_the_table_and_share_the_io_buffer(plugin):
+    """The tap table and the host forms' io buffer change under a bake in flight.  A device bake of an 8 x 8 cube with 3 levels and 16
+    taps in chunks of 128 texels (384 texels: three chunks) is held on a caller's stream of a new context; with no host synchronisation
+    the host bake of another (levels, n_taps) pair then rewrites the tap table behind it and allocates the io buffer, the host bake of
+    27 probes x 64 directions uploads the direction table for the first time and takes the io buffer over, and the host bake of a
+    2 x 2 x 2 lattice takes it over again.  The smallest shapes at which the bake chunks, the table's key changes and the io buffer
+    changes owner.  Expectations: the same four calls one at a time on the module's context."""
+    import torch
+    _upload_cover(plugin, "caller")
+    held = (POSITION, SEED, 8, 3, 1, 4, 16)
+    g = [np.linspace(lo, hi, 3) for lo, hi in ((-5.0, 5.0), (0.1, 3.0), (-5.0, 5.0))]
+    probes = np.zeros(27, brt.PROBE_DTYPE)
+    probes["position"] = np.stack(np.meshgrid(*g, indexing="ij"), axis=-1).reshape(-1, 3).astype(F32)
+    probes["seed"] = np.arange(27, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(1)
+    vol = brt.make_volume((-3.0, 0.5, -3.0), (6.0, 2.0, 6.0), (2, 2, 2), brt.PROBE_SH9, 0xFFFFFFF0, 0)
+
+    def host_calls(p):
+        return (p.node.bake_envmap(POSITION, 8, 4, 1, 4, 8, SEED).copy(), p.node.bake_probes(probes, 64, 4, brt.PROBE_SH9).copy(),
+                p.node.bake_volume(vol, 64, 4).copy())
+
+    want_held, st = _bake_device(plugin, *held, BRT_PROBE_CHUNK_RAYS=128)
+    assert st["chunks"] == 3
+    want_env, want_probes, want_vol = host_calls(plugin)
+    assert want_held[:, 3].any() and want_env[:, 3].any() and want_probes["hits"].any() and want_vol["hits"].any() and len(want_vol) == 8
+    n = er.level_offsets(8, 3)[-1] * 16
+    d_out = _guarded(n, 32, 0xCD)
+    sa = torch.cuda.Stream()
+    fresh = brt.RaytracePlugin([0])
+    try:
+        fresh.node.write_buffers(_cover())
+        torch.cuda.synchronize()
+        with torch.cuda.stream(sa):
+            torch.cuda._sleep(20_000_000)                       # (a few ms: the held bake starts after the later calls have been made)
+        with fresh.tuning(BRT_PROBE_CHUNK_RAYS=128):
+            st = fresh.node.bake_envmap(POSITION, 8, 3, 1, 4, 16, SEED, d_out=d_out.data_ptr(), stream=sa.cuda_stream)
+        assert st["chunks"] == 3
+        got_env, got_probes, got_vol = host_calls(fresh)
+        assert_texels_equal(got_env, want_env, "the host bake of another pair")
+        assert got_probes.tobytes() == want_probes.tobytes() and got_vol.tobytes() == want_vol.tobytes()
+        assert_texels_equal(_read(d_out, n, 0xCD, "the held bake").view(F32).reshape(-1, 4), want_held, "the held bake")
+    finally:
+        fresh.close()
 
 
 @pytest.mark.gpu

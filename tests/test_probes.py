@@ -14,7 +14,7 @@ import bevyray_amd as brt
 import probe_ref as pr
 import radiance_ref as rr
 from bevyray_amd import _lib
-from helpers import big_scene, big_view, l1_norm, make_buffers
+from helpers import big_scene, big_view, cover as _cover, dev as _dev, l1_norm, make_buffers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("brt_host_probe_directions", "brt_host_probe_irradiance", "brt_probe_rays_device", "brt_probe_project_device",
@@ -178,11 +178,6 @@ def test_rejections_that_need_no_device():
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda()
-
-
 def _host(t, dtype):
     return t.cpu().numpy().view(dtype)
 
@@ -245,11 +240,6 @@ def _steps(plugin, probes, n_dirs, bounces, basis):
     plugin.node.probe_project_device(d_res.data_ptr(), len(probes), n_dirs, basis, d_out.data_ptr())
     torch.cuda.synchronize()
     return _host(d_out, brt.PROBE_RECORD_DTYPE), rad
-
-
-@functools.lru_cache(maxsize=None)
-def _cover():
-    return brt.generate_scene(brt.SCENE_COVER, 1)
 
 
 @functools.lru_cache(maxsize=None)

@@ -14,7 +14,7 @@ import bevyray_amd as brt
 import probe_ref as pr
 import volume_ref as vr
 from bevyray_amd import _lib
-from helpers import make_buffers
+from helpers import cover as _cover, dev as _dev, guarded as _guarded, make_buffers, upload_cover as _upload_cover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("brt_host_volume_probes", "brt_host_volume_sample", "brt_volume_probes_device", "brt_bake_volume_device", "brt_bake_volume",
@@ -366,16 +366,6 @@ def test_eight_identical_records_give_that_records_own_evaluation(basis, flags):
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
 
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
-
-
-def _guarded(n_bytes, guard, fill):
-    import torch
-    return torch.full((n_bytes + guard,), fill, dtype=torch.uint8, device="cuda")
-
-
 def _sample_device(plugin, vol, d_records, pts, stream=None):
     """brt_sample_volume_device on a host list; the sample behind the output is a guard."""
     import torch
@@ -431,23 +421,6 @@ def test_the_kernel_is_the_host_twin_and_the_restatement(plugin, basis, flags, c
             vr.assert_samples_equal(got, want[tail: tail + n], f"list of {n}")
             if n <= 257:
                 assert plugin.node.sample_volume(vol, rec, pts[tail: tail + n]).tobytes() == got.tobytes(), n
-
-
-@functools.lru_cache(maxsize=None)
-def _cover():
-    return brt.generate_scene(brt.SCENE_COVER, 1)
-
-
-def _upload_cover(plugin, tree):
-    b = _cover()
-    if tree == "caller":
-        plugin.node.write_buffers(b)
-        return
-    plugin.node.write_buffers(brt.Buffers(b.models, b.materials, None))
-    one = np.zeros(1, brt.PROBE_DTYPE)
-    one["position"] = (0.0, 30.0, 0.0)
-    plugin.node.bake_probes(one, 1, 0, SH9, origin_bound=40.0)
-    assert 40.0 <= plugin.node.query_origin_bound() < np.inf
 
 
 COVER_COUNT = (4, 3, 4)
