@@ -134,6 +134,13 @@ _PROTOTYPES = {
     "brt_host_blend_covered": (_I32, [_VP, _U32, _F, _F, C.POINTER(_U32)]),
     "brt_render_pixels_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_pixels": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_lens_device": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_lens": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_lens_pixels_device": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_lens_pixels": (_I32, [_VP, _VP, _VP, _VP, _U32, _U32, _VP, _U32, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_host_lens_seed": (_I32, [_VP, _U32, _U32, _U32, _U32, C.POINTER(_U32)]),
+    "brt_host_lens_ray": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.POINTER(_U32), _VP, _VP]),
+    "brt_host_lens_origin_bound": (_I32, [_VP, _VP, C.POINTER(_F)]),
     "brt_upscale_refine_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_refined_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _U32,
                                                   C.POINTER(BrtStats)]),

@@ -147,7 +147,7 @@ struct DeviceCtx {
     // Its users run one behind the other, ordered by ev_q like the queries (so uploads and renumberings wait for them too)
     uint32_t* d_pxbuf = nullptr;
     size_t pxbuf_cap = 0;
-    char* d_pxlist = nullptr;       // brt_render_pixels: the host list on the device, and its results
+    char* d_pxlist = nullptr;       // brt_render_pixels, brt_render_lens*: the host list on the device, and its results
     size_t pxlist_cap = 0;
     char* d_pxout = nullptr;
     size_t pxout_cap = 0;

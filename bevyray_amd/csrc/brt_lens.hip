@@ -1,17 +1,13 @@
-// brt_pixels.hip -- the sparse pixel tracer (brt_render_pixels*, and the refinement of brt_upscale_refine*; DESIGN.md "Refined
-// upsampling").  A list entry names a pixel of the width x height Pure frame; its value is that frame's: the seed of a pixel depends on
-// its frame coordinates alone (pixel_seed), and per pixel the draws and operations are k_trace_simple's (pixel_begin / camera_ray_dir /
-// walk / shade_segment), whichever form runs it.
+// brt_lens.hip -- Pure frames and pixel lists under the lens rule (brt_render_lens*; DESIGN.md "Lens frames"): the two forms of the
+// sparse pixel tracer (brt_pixels.hip) with one change -- a sample starts with lens_sample (THE LENS RULE, brt_lens.h: a pinhole, a thin
+// lens or an orthographic ray; the kernels are compiled per mode) where those call camera_ray_dir and take the camera's position.
+// Everything else is theirs: pixels_begin's seed, walk / shade_segment, the value and its store, the counter claim of a round, the
+// launch (launch_stream, brt_stream.h).  The lens terms are kernel arguments (scalar registers); a lane's origin is the `o` a path
+// carries anyway.
 //
-// k_trace_pixels_plain<D16>                one thread per entry: k_trace_simple's loop over a list, the scene in global memory, a private
-//                                          stack.  Every scene representation and tree.
-// k_trace_pixels_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in
-//                                          LDS (stream_stage, brt_stream.h), the stacks in LDS, so the hand-written walk loops serve it.
-//                                          A lane carries one path.  A round: the wave takes entries from the batch counter (one
-//                                          fetch-add) for the lanes whose pixel has ended, walk_run for all lanes, and the lanes whose
-//                                          walk has ended shade their segment and begin the next one, end the sample or end the pixel.
-// Both forms write the same bytes: an entry's result depends on its pixel alone.  No atomic touches a result.
-// What the streaming form shares with k_query_stream and k_radiance_stream, its launch included: brt_stream.h.
+// k_lens_plain<LENS, D16>                 one thread per entry, the scene in global memory, a private stack.
+// k_lens_stream<LENS, MODE, D16, SIMPLE>  persistent workgroups, a lane carries one path (k_trace_pixels_stream).
+// A null list: entry i is pixel i, in raster order.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -20,14 +16,30 @@
 
 namespace brt {
 
+namespace {
+
+// one sample's primary ray on the RNG state of its pixel
+template <uint32_t LENS>
+BRT_DEV void lens_sample(const FrameParams& fp, const LensView& lv, const PixelState& ps, uint32_t& rng, f3& o, f3& d) {
+    float oo[3], w[3];
+    const bool raw = lens_ray_raw(fp, lv, LENS, ps.ndc0x, ps.ndc0y, rng, oo, w);
+    o = mk3(oo[0], oo[1], oo[2]);
+    d = mk3(w[0], w[1], w[2]);
+    if (raw) d = normalize3(d);
+}
+
+BRT_DEV uint32_t lens_pixel_of(const PixelsArgs& pa, uint32_t i) { return pa.pixels ? pa.pixels[i] : i; }
+
+}  // namespace
+
 // ---- plain form ----------------------------------------------------------------------------------------------------------------------
 
-template <bool D16>
-__global__ __launch_bounds__(256) void k_trace_pixels_plain(DeviceSceneView sv, FrameParams fp, PixelsArgs pa) {
+template <uint32_t LENS, bool D16>
+__global__ __launch_bounds__(256) void k_lens_plain(DeviceSceneView sv, FrameParams fp, PixelsArgs pa, LensView lv) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     uint32_t n_rays = 0u, refused = 0u;
     if (i < pixels_n(pa)) {
-        const uint32_t p = pa.pixels[i];
+        const uint32_t p = lens_pixel_of(pa, i);
         if (p >= fp.width * fp.height) {
             pixels_refuse(pa, i);
             refused = 1u;
@@ -38,8 +50,8 @@ __global__ __launch_bounds__(256) void k_trace_pixels_plain(DeviceSceneView sv, 
             pixels_begin(fp, p, ps);
             uint32_t stack[34];   // DONE sentinel + 32 entries + one spare
             for (uint32_t s = 0; s < fp.sample_count; s++) {          // raytrace.wgsl:161
-                f3 d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);
-                f3 o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
+                f3 o, d;
+                lens_sample<LENS>(fp, lv, ps, ps.rng, o, d);
                 f3 tput = mk3(1.0f, 1.0f, 1.0f);
                 float first_depth = kInf;
                 uint32_t bounce = 0;
@@ -61,8 +73,8 @@ __global__ __launch_bounds__(256) void k_trace_pixels_plain(DeviceSceneView sv, 
 
 // ---- streaming form ------------------------------------------------------------------------------------------------------------------
 
-template <int MODE, bool D16, bool SIMPLE>
-__global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneView sv, FrameParams fp, PixelsArgs pa) {
+template <uint32_t LENS, int MODE, bool D16, bool SIMPLE>
+__global__ __launch_bounds__(BRT_BLOCK) void k_lens_stream(DeviceSceneView sv, FrameParams fp, PixelsArgs pa, LensView lv) {
     static_assert(MODE == SCENE_GLOBAL || D16, "a scene staged in LDS always uses 16-bit descriptors");
     using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
     using DS = Desc<D16>;
@@ -94,7 +106,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneVi
             exhausted = base >= n || n - base <= cnt;
             const uint32_t mine = base + mbcnt64(idle);
             if (!in_flight && base < n && mine < n) {
-                const uint32_t p = pa.pixels[mine];
+                const uint32_t p = lens_pixel_of(pa, mine);
                 if (p >= frame_px) {
                     pixels_refuse(pa, mine);
                     refused++;
@@ -105,8 +117,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneVi
                     if (fp.sample_count == 0u) {                       // (no sample: the average of nothing)
                         pixels_store(pa, entry, pixel, pixels_value(fp, ps));
                     } else {
-                        d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);          // raytrace.wgsl:162, :175-186
-                        o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
+                        lens_sample<LENS>(fp, lv, ps, ps.rng, o, d);
                         tput = mk3(1.0f, 1.0f, 1.0f);
                         first_depth = kInf;
                         bounce = 0u;
@@ -124,8 +135,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneVi
                 ps.sum = ps.sum + color;                                // :165
                 ps.sample++;
                 if (ps.sample < fp.sample_count) {
-                    d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);
-                    o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
+                    lens_sample<LENS>(fp, lv, ps, ps.rng, o, d);
                     tput = mk3(1.0f, 1.0f, 1.0f);
                     first_depth = kInf;
                     bounce = 0u;
@@ -144,21 +154,32 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneVi
 
 // ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
 
-struct PixelsStream {
+template <uint32_t LENS>
+struct LensStream {
     template <int MODE, bool D16, bool SIMPLE>
-    static auto kernel() { return k_trace_pixels_stream<MODE, D16, SIMPLE>; }
+    static auto kernel() { return k_lens_stream<LENS, MODE, D16, SIMPLE>; }
 };
 
-hipError_t launch_trace_pixels(const PixelsLaunch& pl) {
-    if (pl.args.n_pixels == 0u) return hipSuccess;
-    if (!pl.args.pixels || !pl.args.out || pl.frame.policy_flags != 0u) return hipErrorInvalidValue;
-    if (pl.form == LIST_PLAIN) {
-        const dim3 grid((pl.args.n_pixels + 255u) / 256u);
-        if (pl.scene.desc16) hipLaunchKernelGGL(k_trace_pixels_plain<true>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
-        else hipLaunchKernelGGL(k_trace_pixels_plain<false>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
+template <uint32_t LENS>
+static hipError_t launch_lens_mode(const LensLaunch& ll) {
+    if (ll.form == LIST_PLAIN) {
+        const dim3 grid((ll.args.n_pixels + 255u) / 256u);
+        if (ll.scene.desc16) hipLaunchKernelGGL((k_lens_plain<LENS, true>), grid, dim3(256), 0, ll.stream, ll.scene, ll.frame, ll.args, ll.lens);
+        else hipLaunchKernelGGL((k_lens_plain<LENS, false>), grid, dim3(256), 0, ll.stream, ll.scene, ll.frame, ll.args, ll.lens);
         return hipGetLastError();
     }
-    return launch_stream<PixelsStream>(pl, pl.args.counter, pl.frame, pl.args);
+    return launch_stream<LensStream<LENS>>(ll, ll.args.counter, ll.frame, ll.args, ll.lens);
+}
+
+hipError_t launch_trace_lens(const LensLaunch& ll) {
+    if (ll.args.n_pixels == 0u) return hipSuccess;
+    if (!ll.args.out || ll.frame.policy_flags != 0u) return hipErrorInvalidValue;
+    switch (ll.lens.mode) {
+        case LENS_PINHOLE: return launch_lens_mode<LENS_PINHOLE>(ll);
+        case LENS_THIN: return launch_lens_mode<LENS_THIN>(ll);
+        case LENS_ORTHO: return launch_lens_mode<LENS_ORTHO>(ll);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace brt

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "brt_kernels.h"
+#include "brt_lens.h"
 
 namespace brt {
 
@@ -28,5 +29,12 @@ struct PixelsLaunch : StreamLaunch {
     PixelsArgs args;
 };
 hipError_t launch_trace_pixels(const PixelsLaunch& pl);
+
+// The same list under the lens rule (brt_lens.h, brt_lens.hip): a sample's primary ray is lens_ray_raw's instead of the pinhole's.
+// args.pixels may be null: entry i is pixel i (a whole frame, n_pixels = width * height).
+struct LensLaunch : PixelsLaunch {
+    LensView lens;
+};
+hipError_t launch_trace_lens(const LensLaunch& ll);
 
 }  // namespace brt

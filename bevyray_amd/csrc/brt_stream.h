@@ -1,7 +1,7 @@
-// brt_stream.h -- what the streaming list kernels share (k_query_stream, k_radiance_stream, k_trace_pixels_stream): the scene in
-// global memory or staged in LDS, a lane's stack and idle walk, and the launch of the streaming form.  Included by brt_query.hip,
-// brt_radiance.hip and brt_pixels.hip only.  The counter claim of a round stays written out in each kernel: as a function it changes
-// their instructions.
+// brt_stream.h -- what the streaming list kernels share (k_query_stream, k_radiance_stream, k_trace_pixels_stream, k_lens_stream): the
+// scene in global memory or staged in LDS, a lane's stack and idle walk, and the launch of the streaming form.  Included by
+// brt_query.hip, brt_radiance.hip and (through brt_pixels_dev.h) brt_pixels.hip and brt_lens.hip only.  The counter claim of a round
+// stays written out in each kernel: as a function it changes their instructions.
 #pragma once
 #include "brt_trace.h"
 

@@ -230,6 +230,27 @@ public:
                               brt_stats* stats = nullptr) {
         check(brt_render_pixels_device(ctx_, &camera, &window, width, height, d_pixels, n_pixels, d_out_rgba, hip_stream, flags, stats), ctx_);
     }
+    // Lens frames (include/bevyray_amd.h "lens frames"): the Pure frame, or a list of its pixels, with a thin lens (depth of field) or an
+    // orthographic camera (camera.projection_type = 1) in place of the pinhole.  flags: BRT_FLAG_KERNEL_SIMPLE, and for the device forms
+    // BRT_FLAG_CALLER_STREAM and (frames) BRT_FLAG_OUT_*.
+    void render_lens(const CameraExtract& camera, const WindowExtract& window, const brt_lens& lens, uint32_t width, uint32_t height,
+                     float* out_rgba, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_lens(ctx_, &camera, &window, &lens, width, height, out_rgba, flags, stats), ctx_);
+    }
+    void render_lens_device(const CameraExtract& camera, const WindowExtract& window, const brt_lens& lens, uint32_t width, uint32_t height,
+                            void* d_frame, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_lens_device(ctx_, &camera, &window, &lens, width, height, d_frame, hip_stream, flags, stats), ctx_);
+    }
+    void render_lens_pixels(const CameraExtract& camera, const WindowExtract& window, const brt_lens& lens, uint32_t width, uint32_t height,
+                            const uint32_t* pixels, uint32_t n_pixels, float* out_rgba, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_lens_pixels(ctx_, &camera, &window, &lens, width, height, pixels, n_pixels, out_rgba, flags, stats), ctx_);
+    }
+    void render_lens_pixels_device(const CameraExtract& camera, const WindowExtract& window, const brt_lens& lens, uint32_t width,
+                                   uint32_t height, const uint32_t* d_pixels, uint32_t n_pixels, float* d_out_rgba, void* hip_stream = nullptr,
+                                   uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_lens_pixels_device(ctx_, &camera, &window, &lens, width, height, d_pixels, n_pixels, d_out_rgba, hip_stream, flags,
+                                            stats), ctx_);
+    }
     // Refined upsampling (include/bevyray_amd.h "refined upsampling"): upscale_device / render_upscaled_device with the output pixels of
     // `classes` (BRT_REFINE_EDGES | BRT_REFINE_SPECULAR) traced at full size.  `window` is the FULL-SIZE window.  d_refined_count: a device
     // word that receives the number of refined pixels (or nullptr).  upscale_refine_mask_device: the class bits per pixel, nothing traced.

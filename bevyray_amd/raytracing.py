@@ -494,6 +494,46 @@ def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.n
     return ray
 
 
+# brt_lens (include/bevyray_amd.h "lens frames"): the descriptor of brt_render_lens*
+LENS_DTYPE = np.dtype([("aperture_radius", np.float32), ("focus_distance", np.float32), ("ortho_height", np.float32),
+                       ("reserved", np.uint32, 5)])
+assert LENS_DTYPE.itemsize == 32
+
+
+def lens(aperture_radius: float = 0.0, focus_distance: float = 1.0, ortho_height: float = 0.0) -> np.ndarray:
+    """One LENS_DTYPE record.  aperture_radius 0: a pinhole; > 0: a thin lens focused on the plane at focus_distance along the camera's
+    direction.  ortho_height: the height of the view volume of an orthographic camera (camera["projection_type"] = 1)."""
+    d = np.zeros(1, LENS_DTYPE)
+    d["aperture_radius"] = aperture_radius
+    d["focus_distance"] = focus_distance
+    d["ortho_height"] = ortho_height
+    return d
+
+
+def lens_seed(window, width: int, height: int, px: int, py: int) -> int:
+    """brt_host_lens_seed: the RNG seed of pixel (px, py) of a width x height frame (raytrace.wgsl:95)."""
+    seed = C.c_uint32()
+    _lib.check(_lib.load().brt_host_lens_seed(window.ctypes.data, int(width), int(height), int(px), int(py), C.byref(seed)))
+    return seed.value
+
+
+def lens_ray(camera, window, lens_desc, width: int, height: int, px: int, py: int, state: int):
+    """brt_host_lens_ray: the lens rule for one sample of pixel (px, py) on the RNG state `state` -> (origin (3,) f32, direction (3,)
+    f32, the state behind the rule's draws).  The compiled twin of the kernels behind RayTracingNode.render_lens*."""
+    st = C.c_uint32(int(state))
+    o, d = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    _lib.check(_lib.load().brt_host_lens_ray(camera.ctypes.data, window.ctypes.data, lens_desc.ctypes.data, int(width), int(height),
+                                             int(px), int(py), C.byref(st), o.ctypes.data, d.ctypes.data))
+    return o, d, st.value
+
+
+def lens_origin_bound(camera, lens_desc) -> float:
+    """brt_host_lens_origin_bound: a 1-norm no origin of the lens rule exceeds for this camera and lens (inf: none)."""
+    out = C.c_float()
+    _lib.check(_lib.load().brt_host_lens_origin_bound(camera.ctypes.data, lens_desc.ctypes.data, C.byref(out)))
+    return out.value
+
+
 class RaytracePlugin:
     """mod.rs:24-84.  build()/finish() create the GPU context (the reference queues the
     render pipeline in RaytracingPipeline::from_world, pipeline.rs:233-331)."""
@@ -907,6 +947,53 @@ class RayTracingNode:
         stats = BrtStats()
         _lib.check(p._lib.brt_render_pixels_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_pixels or None,
                                                    int(n_pixels), d_out or None, *_stream_args(stream, flags), C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    # -- lens frames: depth of field and orthographic projection (include/bevyray_amd.h) ------------
+
+    def render_lens(self, camera, window, lens_desc, width: int, height: int, flags: int = 0) -> np.ndarray:
+        """brt_render_lens: the Pure width x height frame under the lens rule (LENS_DTYPE, lens()) -> (height, width, 4) f32.  flags:
+        FLAG_KERNEL_SIMPLE (the one-thread-per-pixel form; same bytes)."""
+        p = self._p
+        out = np.zeros((height, width, 4) if 0 < width <= 32768 and 0 < height <= 32768 else (1, 1, 4), np.float32)
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_lens(p._ctx, camera.ctypes.data, window.ctypes.data, lens_desc.ctypes.data, width, height,
+                                          out.ctypes.data, flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return out
+
+    def render_lens_device(self, camera, window, lens_desc, width: int, height: int, d_frame: int, stream: Optional[int] = None,
+                           out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_lens_device: the same frame into d_frame (a device pointer on the first device) in `out_format` (FLAG_OUT_*).
+        Stream rule as for render_part_device; the counts of last_stats only on the own stream."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_lens_device(p._ctx, camera.ctypes.data, window.ctypes.data, lens_desc.ctypes.data, width, height,
+                                                 d_frame or None, *_stream_args(stream, out_format | flags), C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def render_lens_pixels(self, camera, window, lens_desc, width: int, height: int, pixels: np.ndarray, flags: int = 0) -> np.ndarray:
+        """brt_render_lens_pixels: render_pixels under the lens rule: entry i is the value render_lens holds at pixels[i]."""
+        p = self._p
+        pixels = np.ascontiguousarray(pixels, np.uint32)
+        out = np.zeros((pixels.size, 4), np.float32)
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_lens_pixels(p._ctx, camera.ctypes.data, window.ctypes.data, lens_desc.ctypes.data, width, height,
+                                                 pixels.ctypes.data if pixels.size else None, pixels.size,
+                                                 out.ctypes.data if pixels.size else None, flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return out
+
+    def render_lens_pixels_device(self, camera, window, lens_desc, width: int, height: int, d_pixels: int, n_pixels: int, d_out: int,
+                                  stream: Optional[int] = None, flags: int = 0) -> dict:
+        """brt_render_lens_pixels_device: render_pixels_device under the lens rule."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_lens_pixels_device(p._ctx, camera.ctypes.data, window.ctypes.data, lens_desc.ctypes.data, width,
+                                                        height, d_pixels or None, int(n_pixels), d_out or None,
+                                                        *_stream_args(stream, flags), C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
 

@@ -158,7 +158,7 @@ typedef struct brt_stats {
     uint32_t hot_records;      /* a scene walked from an LDS tile + L2 (scene_in_lds == 2): the tree's records are numbered by how often this
                                   view visits them (measured by the pre-pass of a first frame), so that the tile holds the ones the walk
                                   uses; this many of them were visited at all.  0: breadth-first numbering (no pre-pass yet / another mode) */
-    uint32_t reserved;         /* brt_render_pixels*: list entries refused (they name no pixel of the frame); else 0 */
+    uint32_t reserved;         /* brt_render_pixels*, brt_render_lens_pixels*: list entries refused (they name no pixel of the frame); else 0 */
 } brt_stats;
 
 uint32_t brt_abi_version(void);
@@ -469,8 +469,8 @@ int32_t brt_host_pixel_ray(const void* camera80, const void* window16, uint32_t 
 
 /* ---- radiance queries ----------------------------------------------------------------------------------------------------------------
  * Path-traced colour for batches of the caller's rays (reflection rays from a G-buffer, light probes, cube maps, fisheye or orthographic
- * views, a host integrator): what a ray SEES, where a ray query answers what it hits.  On the context's first device.  Rule, kernels and
- * costs: DESIGN.md "Radiance queries".  Deterministic; the default policy only (brt_set_policy: else BRT_ERR_UNSUPPORTED).
+ * views -- whole orthographic frames: brt_render_lens* --, a host integrator): what a ray SEES, where a ray query answers what it
+ * hits.  On the context's first device.  Rule, kernels and costs: DESIGN.md "Radiance queries".  Deterministic; the default policy only (brt_set_policy: else BRT_ERR_UNSUPPORTED).
  *   ray, 32 bytes    { origin.xyz, seed, direction.xyz, user }: f32 x 3, u32, f32 x 3, u32 -- the query ray with `seed` where t_max is.
  *                    The direction is used as given, as in ray queries; raytrace normalises where the shader does.
  *   result, 32 bytes { t, r, g, b, sphere, material, status, user }: f32 x 4 and u32 x 4 -- the query hit with the colour where the
@@ -803,6 +803,71 @@ int32_t brt_render_pixels_device(brt_ctx* ctx, const void* camera80, const void*
                                  brt_stats* stats_or_null);
 int32_t brt_render_pixels(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const uint32_t* pixels,
                           uint32_t n_pixels, float* out_rgba32f, uint32_t flags, brt_stats* stats_or_null);
+
+/* ---- lens frames: depth of field and orthographic projection ----------------------------------------------------------------------------
+ * Pure (level 3) frames and pixel lists whose primary rays come from a thin lens or an orthographic camera instead of the pinhole.  Only
+ * ray generation differs: the seed of a pixel (raytrace.wgsl:95), the RNG state its samples share, raytrace() at level 3 and the average
+ * (raytrace.wgsl:161-171, alpha 1) are the Pure frame's.  On the context's first device, by the kernels of the sparse pixel tracer with
+ * another sample start.  Rule (csrc/brt_lens.h holds the operation order), kernels and costs: DESIGN.md "Lens frames".
+ *   brt_lens, 32 bytes   { aperture_radius, focus_distance, ortho_height, reserved[5] }; the reserved words must be 0.  The entry
+ *                        points take it as lens32, 32 bytes at any address, like the camera and the window.
+ *   the rule, per sample 1. the two jitter draws and ndc_x, ndc_y as in the Pure frame; v = (direction + sx * right) + sy * up as there.
+ *                        2. perspective (camera.projection_type 0), aperture_radius == 0: origin = position, direction = normalize(v); no
+ *                           further draw: the frame is the Pure frame of brt_render_device bit for bit.
+ *                        3. perspective, aperture_radius r > 0: a point (x, y) of the unit disk by rejection (x = 2 u1 - 1, y = 2 u2 - 1,
+ *                           draws in that order, accepted when x * x + y * y <= 1.0); l = (r * x) * right + (r * y) * up; origin =
+ *                           position + l, direction = normalize(focus_distance * v - l).  All rays of one jitter draw meet in one point
+ *                           of the plane at focus_distance along camera.direction; what lies there is sharp.
+ *                        4. orthographic (camera.projection_type 1): half = 0.5 * ortho_height; origin = (position + ((ndc_x * aspect) *
+ *                           half) * right) + (ndc_y * half) * up, direction = normalize(camera.direction).  ortho_height is the height
+ *                           of the view volume in units of |up| (aspect * ortho_height its width in units of |right|); fov, near and far
+ *                           are not read; aperture_radius must be 0.
+ *   brt_render_lens_device   the whole width x height frame into d_frame (DEVICE) in the store format of BRT_FLAG_OUT_*.  flags:
+ *                            BRT_FLAG_OUT_*, BRT_FLAG_CALLER_STREAM, BRT_FLAG_KERNEL_SIMPLE (the one-thread-per-pixel form; the bytes are the
+ *                            same).  Stream rule as for brt_render_device; lens calls run one behind the other with the context's pixel
+ *                            lists and queries, on whatever streams they come.
+ *   brt_render_lens          the same into a HOST buffer of RGBA f32, synchronous.  flags: BRT_FLAG_KERNEL_SIMPLE only.
+ *   brt_render_lens_pixels_device / brt_render_lens_pixels   the list form, with the conventions of brt_render_pixels*: entry i is pixel
+ *                            p = py * width + px, its value goes to out[i] (RGBA f32); an entry >= width * height is not traced, stores
+ *                            four zeros and is counted in stats.reserved; n_pixels = 0 is BRT_OK.
+ *   stats_or_null            as for brt_render_pixels* (kernel_variant 34: the persistent form, 35: the plain form).
+ *   tree reach               the call first settles the tree for the camera, as every render call does; with aperture_radius > 0 or an
+ *                            orthographic camera it then raises a callee-built tree's reach, if needed, to what origins within
+ *                            brt_host_lens_origin_bound need -- as brt_query_rays does for its origin_bound, and with the same side
+ *                            effect: later frames are traced on that tree until the next upload (stats.tree_rebuilt reports a rebuild).
+ *   brt_host_lens_seed       host arithmetic, no context: the seed of pixel (px, py) of a width x height frame.
+ *   brt_host_lens_ray        host arithmetic, no context: the rule for ONE sample of that pixel on the RNG state *state_inout, which it
+ *                            advances as the kernel does (start from brt_host_lens_seed; the state after a sample's raytrace() is the next
+ *                            sample's).  o3 / d3 receive origin and direction.
+ *   brt_host_lens_origin_bound  host arithmetic: *out = a 1-norm that no origin of the rule exceeds for this camera and lens, whatever the
+ *                            window (of at least one row) and the frame size, rounding included (+INF: there is none).
+ * Refusals: BRT_ERR_INVALID_ARGUMENT for a null pointer, non-zero reserved words, an aperture_radius that is NaN, negative or infinite, a
+ * focus_distance that is not finite and > 0 while the radius is > 0, an ortho_height that is not finite and > 0 or a window height of 0
+ * for an orthographic camera, a radius > 0 on an orthographic camera, projection_type > 1, sizes outside [1, 32768], any other flag --
+ * the post-passes BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL / BRT_FLAG_BLEND_POST included: their guide buffers assume pinhole rays.
+ * BRT_ERR_UNSUPPORTED for a non-default policy (brt_set_policy) and for an origin bound that is not finite or that the callee's tree
+ * cannot be raised to cover.  BRT_ERR_NO_SCENE before an upload.  brt_last_error names the field.  A refused call leaves the context
+ * usable.  Every other entry point keeps answering BRT_ERR_UNSUPPORTED for an orthographic camera. */
+typedef struct brt_lens {
+    float aperture_radius;     /* radius of the lens disk in units of |right| / |up|; 0: a pinhole */
+    float focus_distance;      /* distance of the focus plane along camera.direction, in units of |direction| (read when the radius is > 0) */
+    float ortho_height;        /* orthographic cameras: height of the view volume in units of |up| */
+    uint32_t reserved[5];      /* must be 0 */
+} brt_lens;
+int32_t brt_render_lens_device(brt_ctx* ctx, const void* camera80, const void* window16, const void* lens32, uint32_t width,
+                               uint32_t height, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_render_lens(brt_ctx* ctx, const void* camera80, const void* window16, const void* lens32, uint32_t width, uint32_t height,
+                        float* out_rgba32f, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_render_lens_pixels_device(brt_ctx* ctx, const void* camera80, const void* window16, const void* lens32, uint32_t width,
+                                      uint32_t height, const uint32_t* d_pixels, uint32_t n_pixels, float* d_out_rgba32f, void* hip_stream,
+                                      uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_render_lens_pixels(brt_ctx* ctx, const void* camera80, const void* window16, const void* lens32, uint32_t width,
+                               uint32_t height, const uint32_t* pixels, uint32_t n_pixels, float* out_rgba32f, uint32_t flags,
+                               brt_stats* stats_or_null);
+int32_t brt_host_lens_seed(const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py, uint32_t* out_seed);
+int32_t brt_host_lens_ray(const void* camera80, const void* window16, const void* lens32, uint32_t width, uint32_t height, uint32_t px,
+                          uint32_t py, uint32_t* state_inout, float* o3, float* d3);
+int32_t brt_host_lens_origin_bound(const void* camera80, const void* lens32, float* out_bound);
 
 /* ---- refined upsampling ---------------------------------------------------------------------------------------------------------------
  * The guide-buffer upsampling with the pixels it cannot reconstruct traced at FULL size by the sparse pixel tracer.  An output pixel p
