@@ -38,7 +38,7 @@ namespace brt {
 #ifndef BRT_ASM_COUNT
 #define BRT_ASM_COUNT 0
 #endif
-struct AsmCounts { uint32_t int_exec, int_lanes, leaf_exec, leaf_lanes, ball_exec, ball_lanes, fix_int_lanes, fix_leaf_lanes, rows_int_exec, rows_calls, rows_cycles, wide_cycles; };
+struct AsmCounts { uint32_t int_exec, int_lanes, leaf_exec, leaf_lanes, ball_exec, ball_lanes, fix_int_lanes, fix_leaf_lanes, rows_int_exec, rows_calls, rows_cycles, wide_cycles, leaf_slow; };
 // (a call's counts are wave-uniform scalars; they are booked by the first lane that is active at the call, like prof_section, and
 //  summed over the lanes at the end of the kernel)
 __device__ __forceinline__ bool first_active_lane() {
@@ -85,7 +85,8 @@ BRT_DEV float max_sel(float a, float b) { return a < b ? b : a; }
 #ifndef BRT_SHARED_RCP
 #define BRT_SHARED_RCP 3   // bit 0: normalize(), bit 1: 1 / direction.  (A/B on one MI355X, headline frame: 13.33 ms without,
                            // 13.18 with bit 0, 13.08 with both; the sphere test's `/ a` with a per-ray reciprocal did NOT pay --
-                           // its range guard and wave vote cost the leaf step what the shorter quotient saves: 13.16 ms)
+                           // its range guard and wave vote cost the leaf step what the shorter quotient saves: 13.16 ms.
+                           // That was the COMPILER's leaf step; in the hand-written one it pays: BRT_LEAF_TAIL)
 #endif
 constexpr float kPlainLo = 0x1p-40f, kPlainHi = 0x1p40f;
 struct RcpRef { float d, r1; };
@@ -139,13 +140,46 @@ BRT_DEV float sqrt_plain(float x) {
     return r;
 }
 
+// The compiler's OTHER correctly rounded lowering (the one it uses when f32 denormals are flushed): Newton on v_rsq_f32 (1 ulp),
+//     r = rsq(x), s = x r, h = r / 2, e = 1/2 - h s;  h += h e, s += s e;  s += (x - s s) h
+// -- 8 instructions, one of them quarter rate, no compare and no select (sqrt_plain: 9, four of them 4-cycle compares / selects).
+// Every intermediate scales by an exact power of two with x, so for STRICTLY POSITIVE x in [2^-80, 2^80], where x, r and the
+// residual x - s s stay normal numbers, the denormal mode plays no part and the result is the correctly rounded root
+// (BRT_DBG_SQRT_SWEEP with a non-zero third input: every float of that range, bit for bit against __builtin_sqrtf).  NOT for 0
+// (rsq(0) = inf, 0 inf = NaN); a negative or NaN argument gives NaN, as sqrt does.
+// BRT_EXACT_FORMS selects where the form is used -- bit 0: the compiler-built shading (normalize3, sqrt3), bit 1: the sqrt of the
+// hand-written leaf step, bit 2: the leaf step's divide in the plain form with the reciprocal of `a` refined once per call
+// (BRT_LEAF_TAIL below).  A/B of the arms on one MI355X, headline frame, five alternated bench runs each (profiles/exact_forms/ab.txt,
+// medians): 8.926 ms without, 8.811 with bit 1, 8.811 with bit 2, 8.716 with both -- and 8.959 with bit 0 alone, 8.706 with all three,
+// which does not separate from bits 1 + 2: in the compiler-built shading the form does NOT pay (a measured negative; where its ten
+// cycles per call go was not taken apart), so bit 0 stays off.
+#ifndef BRT_EXACT_FORMS
+#define BRT_EXACT_FORMS 6
+#endif
+BRT_DEV float sqrt_rsq(float x) {
+    const float r = __builtin_amdgcn_rsqf(x);
+    float s = x * r, h = 0.5f * r;
+    const float e = __builtin_fmaf(-h, s, 0.5f);
+    h = __builtin_fmaf(h, e, h);
+    s = __builtin_fmaf(s, e, s);
+    const float d = __builtin_fmaf(-s, s, x);
+    return __builtin_fmaf(d, h, s);
+}
+
 // sqrt of three values at once (the sample colour, raytrace.wgsl:223): the short form when every active lane's
 // components are zero (sqrt_plain returns +-0 for +-0: v_sqrt_f32 does, and both residual tests are false) or in the plain range
 BRT_DEV f3 sqrt3(f3 c) {
     const float ax = __builtin_fabsf(c.x), ay = __builtin_fabsf(c.y), az = __builtin_fabsf(c.z);
     const float mx = max_f(max_f(ax, ay), az);
-    const bool plain = (min_f(min_f(ax, ay), az) >= 0x1p-80f && mx <= 0x1p80f) || mx == 0.0f;
+    const bool zero = mx == 0.0f;
+    const bool plain = (min_f(min_f(ax, ay), az) >= 0x1p-80f && mx <= 0x1p80f) || zero;
+#if BRT_EXACT_FORMS & 1
+    // (a lane is plain with all three components in the range or all three zero -- absorbed paths, bounce-limit ends: the zeros,
+    //  which the rsq form does not survive, are their own roots and pass through on the compare the guard has already made)
+    if (wave_all(plain)) return mk3(zero ? c.x : sqrt_rsq(c.x), zero ? c.y : sqrt_rsq(c.y), zero ? c.z : sqrt_rsq(c.z));
+#else
     if (wave_all(plain)) return mk3(sqrt_plain(c.x), sqrt_plain(c.y), sqrt_plain(c.z));
+#endif
     return mk3(__builtin_sqrtf(c.x), __builtin_sqrtf(c.y), __builtin_sqrtf(c.z));
 }
 
@@ -154,7 +188,11 @@ BRT_DEV f3 normalize3(f3 v) {
     // components in [2^-40, 2^39]  =>  dot in [2^-80, 2^80) and len in [max |v_i|, 2 max |v_i|): both plain
     // (products and sums of positive terms are monotone, sqrt is monotone, the sum has 3 terms)
     if (wave_all(all_within(v, kPlainLo, 0x1p39f))) {
+#if BRT_EXACT_FORMS & 1
+        const RcpRef R = rcp_refined(sqrt_rsq(dot3(v, v)));
+#else
         const RcpRef R = rcp_refined(sqrt_plain(dot3(v, v)));
+#endif
         return mk3(div_plain(v.x, R), div_plain(v.y, R), div_plain(v.z, R));
     }
 #endif
@@ -635,15 +673,157 @@ BRT_DEV void walk_loop_wave(const ScenePtrs& sc, f3 o, f3 d, float a, f3 inv, ui
 // operand, and the arithmetic works on them in place.
 // Interior step: raytrace.wgsl:327-342 + 387-398 (see walk_interior_step for the forms used: near / far planes by granule,
 // the three compares of the push rule as one).  Leaf step: raytrace.wgsl:348-362 + 371-383 -- the discriminant, then
-// hipcc's own correctly rounded sqrt and divide expansions, instruction for instruction as it emits them for sphere_test
-// (2^32 pre-scale below 2^-96, v_sqrt_f32 + two residual corrections, class fix-up; v_div_scale x2, v_rcp_f32 + one Newton step,
-// three fma steps, v_div_fmas, v_div_fixup), with the wait states its hazard recogniser would insert; the accept rule
-// t > 0.001 && t < closest moves t and the sphere id under EXEC.
+// BRT_LEAF_TAIL (below): the correctly rounded sqrt and divide in their short forms where every active lane is in their range,
+// hipcc's own expansions out of line otherwise -- the same bits either way; the accept rule t > 0.001 && t < closest moves t and
+// the sphere id under EXEC.
+// ---- the tail of the leaf step: t = (h - sqrt(discriminant)) / a, with the discriminant in v104 and h in v107; t ends up in v104 ----
+// BRT_LEAF_SQRT_FULL / BRT_LEAF_DIV_FULL are hipcc's own expansions, instruction for instruction as it emits them for sphere_test (2^32
+// pre-scale below 2^-96, v_sqrt_f32 + two residual corrections, class fix-up; v_div_scale x2, v_rcp_f32 + one Newton step, three fma
+// steps, v_div_fmas, v_div_fixup), in an order in which every wait state its hazard recogniser fills with s_nop (VALU -> vcc / SGPR ->
+// v_cndmask: 2, v_sqrt / v_rcp -> use: 1) holds an instruction that is needed anyway; FILL is the one such slot an unrelated
+// instruction can take (the pop's pointer move).  A negative discriminant gives NaN, rejected by the accept rule like the shader's -1.
+// By the price list above the two blocks are ~60 + ~36 of the step's ~162 cycles, most of it scaffolding for arguments a sphere test
+// practically never has.  BRT_EXACT_FORMS (bits 1, 2) replaces them, for a wave whose lanes are all in range, by
+//   sqrt    sqrt_rsq (8 instructions, 22 cycles), for discriminants in [2^-80, 2^80] -- and for negative or NaN ones, which give NaN
+//           in either form;
+//   divide  div_plain with the refined reciprocal of `a` made ONCE PER CALL (rcp_refined depends on the ray alone): 5 instructions,
+//           10 cycles, for |n| <= 2^40.  walk_run keeps rays whose `a` is outside [kLeafALo, kPlainHi] out of these loops (they walk in
+//           the compiler's loop first, like the rays that fail ray_is_safe).  |n| has NO lower limit: n = h - sqrt(disc) is 0 or tiny
+//           for every ray that starts on a sphere and points into it (refraction, reflection inside glass); with a >= 2^-29 and
+//           |n| < 2^-40 the correctly rounded quotient is at most 2^-11 < 0.001 in magnitude, so the reference rejects such a lane by
+//           t > 0.001, and div_plain -- |n r1| <= 2^-11 (1 + 2^-22), two corrections of relative size 2^-22 -- rejects it too; where
+//           2^-40 <= |n| the pair (n, a) is in the range where div_plain IS the compiler's expansion (BRT_DBG_DIV_SWEEP).
+// The guard is three compares (|disc| < 2^-80 also catches +-0, whose rsq is inf; a NaN passes every test and stays a NaN) and ONE
+// scalar branch, untaken unless some active lane fails: then the whole wave runs the full forms out of line, from the preserved
+// discriminant and h, and rejoins at the accept rule -- for the lanes that were in range the two forms give the same bits.
+constexpr float kLeafALo = 0x1p-29f;
+#define BRT_LEAF_SQRT_FULL(FILL)                                                                                                       \
+        "v_cmp_gt_f32_e32 vcc, %[c_tiny], v104\n"               /* below 2^-96: scale by 2^32 (vcc stays until the result is scaled back) */ \
+        "v_mul_f32_e32 v105, 0x4f800000, v104\n"                                                                                       \
+        FILL                                                                                                                           \
+        "v_cndmask_b32_e32 v104, v104, v105, vcc\n"                                                                                    \
+        "v_sqrt_f32_e32 v105, v104\n"                           /* s */                                                                \
+        "v_cmp_class_f32_e64 %[s_both], v104, %[c_cls]\n"       /* +-0 and +inf are their own roots */                                 \
+        "v_add_u32_e32 v106, -1, v105\n"                        /* s - 1 ulp */                                                        \
+        "v_add_u32_e32 v109, 1, v105\n"                         /* s + 1 ulp */                                                        \
+        "v_fma_f32 v108, -v106, v105, v104\n"                   /* x - (s - 1 ulp) s */                                                \
+        "v_fma_f32 v110, -v109, v105, v104\n"                   /* x - (s + 1 ulp) s */                                                \
+        "v_cmp_ge_f32_e64 %[s_p2], 0, v108\n"                                                                                          \
+        "v_cmp_lt_f32_e64 %[s_any], 0, v110\n"                                                                                         \
+        "s_nop 0\n"                                             /* (the one wait state left over) */                                   \
+        "v_cndmask_b32_e64 v106, v105, v106, %[s_p2]\n"                                                                                \
+        "v_cndmask_b32_e64 v105, v106, v109, %[s_any]\n"                                                                               \
+        "v_mul_f32_e32 v106, 0x37800000, v105\n"                                                                                       \
+        "v_cndmask_b32_e32 v105, v105, v106, vcc\n"                                                                                    \
+        "v_cndmask_b32_e64 v104, v105, v104, %[s_both]\n"       /* sqrt(discriminant) */
+#define BRT_LEAF_DIV_FULL                                                                                                              \
+        "v_div_scale_f32 v105, %[s_p2], %[a], %[a], v104\n"     /* v104 = n -> v104 = n / a */                                         \
+        "v_rcp_f32_e32 v106, v105\n"                                                                                                   \
+        "v_div_scale_f32 v107, vcc, v104, %[a], v104\n"                                                                                \
+        "v_fma_f32 v109, -v105, v106, 1.0\n"                                                                                           \
+        "v_fmac_f32_e32 v106, v109, v106\n"                                                                                            \
+        "v_mul_f32_e32 v108, v107, v106\n"                                                                                             \
+        "v_fma_f32 v109, -v105, v108, v107\n"                                                                                          \
+        "v_fmac_f32_e32 v108, v109, v106\n"                                                                                            \
+        "v_fma_f32 v105, -v105, v108, v107\n"                                                                                          \
+        "v_div_fmas_f32 v105, v105, v106, v108\n"                                                                                      \
+        "v_div_fixup_f32 v104, v105, %[a], v104\n"              /* t */
+#define BRT_LEAF_POP_MOVE "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"   /* (the pop's pointer move) */
+// sqrt_rsq of v104 into v106 (v104 stays); GUARDS go into the wait state between v_rsq_f32 and its first use
+#define BRT_LEAF_SQRT_RSQ(GUARDS)                                                                                                      \
+        "v_rsq_f32_e32 v105, v104\n"                            /* r */                                                                \
+        GUARDS                                                                                                                         \
+        BRT_LEAF_POP_MOVE                                                                                                              \
+        "v_mul_f32_e32 v106, v104, v105\n"                      /* s = x r */                                                          \
+        "v_mul_f32_e32 v108, 0.5, v105\n"                       /* h = r / 2 */                                                        \
+        "v_fma_f32 v109, -v108, v106, 0.5\n"                    /* e = 1/2 - h s */                                                    \
+        "v_fmac_f32_e32 v108, v108, v109\n"                     /* h += h e */                                                         \
+        "v_fmac_f32_e32 v106, v106, v109\n"                     /* s += s e */                                                         \
+        "v_fma_f32 v109, -v106, v106, v104\n"                   /* d = x - s s */                                                      \
+        "v_fmac_f32_e32 v106, v109, v108\n"                     /* s += d h */
+#define BRT_LEAF_GUARD_DISC                                                                                                            \
+        "v_cmp_gt_f32_e64 %[s_p2], %[c_lo2], |v104|\n"          /* |disc| < 2^-80 (with +-0) */                                        \
+        "v_cmp_lt_f32_e64 %[s_any], %[c_hi2], v104\n"           /* disc > 2^80 (with +inf) */
+// rcp_refined(a), once per call
+#define BRT_LEAF_RCP_A                                                                                                                 \
+        "v_rcp_f32_e32 %[r1], %[a]\n"                                                                                                  \
+        "s_nop 0\n"                                                                                                                    \
+        "v_fma_f32 %[t0], -%[a], %[r1], 1.0\n"                                                                                         \
+        "v_fmac_f32_e32 %[r1], %[t0], %[r1]\n"
+#if BRT_ASM_COUNT
+#define BRT_COUNT_LEAF_SLOW "s_add_u32 %[c_ls], %[c_ls], 1\n"
+#else
+#define BRT_COUNT_LEAF_SLOW
+#endif
+#if (BRT_EXACT_FORMS & 6) == 6
+#define BRT_LEAF_ENTRY BRT_LEAF_RCP_A
+#define BRT_LEAF_TAIL                                                                                                                  \
+        BRT_LEAF_SQRT_RSQ(BRT_LEAF_GUARD_DISC)                                                                                         \
+        "v_sub_f32_e32 v105, v107, v106\n"                      /* n = h - sqrt(discriminant) */                                       \
+        "v_cmp_lt_f32_e64 %[s_both], %[c_hi], |v105|\n"         /* |n| > 2^40 */                                                       \
+        "v_mul_f32_e32 v106, v105, %[r1]\n"                     /* div_plain: q = n r1 */                                              \
+        "s_or_b64 %[s_p2], %[s_p2], %[s_any]\n"                                                                                        \
+        "v_fma_f32 v108, -%[a], v106, v105\n"                   /* e = n - a q */                                                      \
+        "s_or_b64 %[s_p2], %[s_p2], %[s_both]\n"                                                                                       \
+        "s_cbranch_scc1 20f\n"                                  /* some lane out of range: the full forms, out of line */              \
+        "v_fmac_f32_e32 v106, v108, %[r1]\n"                    /* q += e r1 */                                                        \
+        "v_fma_f32 v108, -%[a], v106, v105\n"                   /* e = n - a q */                                                      \
+        "v_fma_f32 v104, v108, %[r1], v106\n"                   /* t = q + e r1 */                                                     \
+        "21:\n"
+#define BRT_LEAF_TAIL_SLOW                                                                                                             \
+        "20:\n"                                                                                                                        \
+        BRT_COUNT_LEAF_SLOW                                                                                                            \
+        BRT_LEAF_SQRT_FULL("s_nop 0\n")                                                                                                \
+        "v_sub_f32_e32 v104, v107, v104\n"                                                                                             \
+        BRT_LEAF_DIV_FULL                                                                                                              \
+        "s_branch 21b\n"
+#elif BRT_EXACT_FORMS & 2
+#define BRT_LEAF_ENTRY
+#define BRT_LEAF_TAIL                                                                                                                  \
+        BRT_LEAF_SQRT_RSQ(BRT_LEAF_GUARD_DISC)                                                                                         \
+        "s_or_b64 %[s_p2], %[s_p2], %[s_any]\n"                                                                                        \
+        "s_cbranch_scc1 20f\n"                                                                                                         \
+        "v_mov_b32_e32 v104, v106\n"                                                                                                   \
+        "21:\n"                                                                                                                        \
+        "v_sub_f32_e32 v104, v107, v104\n"                      /* h - sqrt(discriminant) */                                           \
+        BRT_LEAF_DIV_FULL
+#define BRT_LEAF_TAIL_SLOW                                                                                                             \
+        "20:\n"                                                                                                                        \
+        BRT_COUNT_LEAF_SLOW                                                                                                            \
+        BRT_LEAF_SQRT_FULL("s_nop 0\n")                                                                                                \
+        "s_branch 21b\n"
+#elif BRT_EXACT_FORMS & 4
+#define BRT_LEAF_ENTRY BRT_LEAF_RCP_A
+#define BRT_LEAF_TAIL                                                                                                                  \
+        BRT_LEAF_SQRT_FULL(BRT_LEAF_POP_MOVE)                                                                                          \
+        "v_sub_f32_e32 v104, v107, v104\n"                      /* n = h - sqrt(discriminant) */                                       \
+        "v_cmp_lt_f32_e64 %[s_both], %[c_hi], |v104|\n"         /* |n| > 2^40 */                                                       \
+        "v_mul_f32_e32 v106, v104, %[r1]\n"                                                                                            \
+        "v_fma_f32 v108, -%[a], v106, v104\n"                                                                                          \
+        "s_and_b64 %[s_both], %[s_both], exec\n"                                                                                       \
+        "s_cbranch_scc1 20f\n"                                                                                                         \
+        "v_fmac_f32_e32 v106, v108, %[r1]\n"                                                                                           \
+        "v_fma_f32 v108, -%[a], v106, v104\n"                                                                                          \
+        "v_fma_f32 v104, v108, %[r1], v106\n"                                                                                          \
+        "21:\n"
+#define BRT_LEAF_TAIL_SLOW                                                                                                             \
+        "20:\n"                                                                                                                        \
+        BRT_COUNT_LEAF_SLOW                                                                                                            \
+        BRT_LEAF_DIV_FULL                                                                                                              \
+        "s_branch 21b\n"
+#else
+#define BRT_LEAF_ENTRY
+#define BRT_LEAF_TAIL                                                                                                                  \
+        BRT_LEAF_SQRT_FULL(BRT_LEAF_POP_MOVE)                                                                                          \
+        "v_sub_f32_e32 v104, v107, v104\n"                      /* h - sqrt(discriminant) */                                           \
+        BRT_LEAF_DIV_FULL
+#define BRT_LEAF_TAIL_SLOW
+#endif
 BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uint32_t& closest_idx, uint32_t gofs_x, uint32_t gofs_y,
                                uint32_t gofs_z, f3 o, f3 inv, f3 d, float a, uint32_t sph, uint32_t exit_at, uint32_t vote, AsmCounts* ac = nullptr) {
 #if BRT_HAND_ASM
 #if BRT_ASM_COUNT
-    uint32_t c_ie, c_il, c_le, c_ll, c_tmp;
+    uint32_t c_ie, c_il, c_le, c_ll, c_ls, c_tmp;
 #define BRT_COUNT_INT "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_il], %[c_il], %[c_tmp]\n s_add_u32 %[c_ie], %[c_ie], 1\n"
 #define BRT_COUNT_LEAF "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_ll], %[c_ll], %[c_tmp]\n s_add_u32 %[c_le], %[c_le], 1\n"
 #else
@@ -654,13 +834,20 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
     float below;
     uint64_t s_all, s_take, s_p2, s_any, s_both;
     const uint32_t rec_bytes = PAIR_BYTES, c_tiny = 0x0f800000u /* 2^-96 */, c_eps = 0x3a83126fu /* 0.001f */, c_cls = 0x260u /* +-0, +inf */;
+#if BRT_EXACT_FORMS & 6
+    const uint32_t c_lo2 = 0x17800000u /* 2^-80 */, c_hi2 = 0x67800000u /* 2^80 */, c_hi = 0x53800000u /* 2^40 */;
+#endif
+#if BRT_EXACT_FORMS & 4
+    float r1;                                                   // rcp_refined(a).r1
+#endif
     asm volatile(
 #if BRT_ASM_COUNT
-        "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n"
+        "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n s_mov_b32 %[c_ls], 0\n"
 #endif
         "s_waitcnt lgkmcnt(0)\n"                                // nothing of the compiler's in flight: the counted waits below are exact
         "s_mov_b64 %[s_all], exec\n"
         "v_add_u32_e32 %[below], -1, %[closest]\n"              // the largest float below closest (closest is FLT_MAX or an accepted t > 0)
+        BRT_LEAF_ENTRY
         // ---- outer loop: leave when at most exit_at lanes still walk -------------------------------------------------------
         "3:\n"
         "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n"
@@ -751,41 +938,7 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "v_mul_f32_e32 v105, v107, v107\n"                      // h h
         "v_mul_f32_e32 v104, %[a], v104\n"                      // a c
         "v_sub_f32_e32 v104, v105, v104\n"                      // discriminant
-        // sqrt(discriminant), correctly rounded: hipcc's expansion (a negative argument gives NaN, rejected below like the
-        // shader's -1).  Same operations on the same values as the compiler emits; the order is chosen so that every wait
-        // state its hazard recogniser fills with s_nop (VALU -> vcc / SGPR -> v_cndmask: 2, v_sqrt / v_rcp -> use: 1) holds
-        // an instruction that is needed anyway.
-        "v_cmp_gt_f32_e32 vcc, %[c_tiny], v104\n"               // below 2^-96: scale by 2^32 (vcc stays until the result is scaled back)
-        "v_mul_f32_e32 v105, 0x4f800000, v104\n"
-        "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"            // (the pop's pointer move)
-        "v_cndmask_b32_e32 v104, v104, v105, vcc\n"
-        "v_sqrt_f32_e32 v105, v104\n"                           // s
-        "v_cmp_class_f32_e64 %[s_both], v104, %[c_cls]\n"       // +-0 and +inf are their own roots
-        "v_add_u32_e32 v106, -1, v105\n"                        // s - 1 ulp
-        "v_add_u32_e32 v109, 1, v105\n"                         // s + 1 ulp
-        "v_fma_f32 v108, -v106, v105, v104\n"                   // x - (s - 1 ulp) s
-        "v_fma_f32 v110, -v109, v105, v104\n"                   // x - (s + 1 ulp) s
-        "v_cmp_ge_f32_e64 %[s_p2], 0, v108\n"
-        "v_cmp_lt_f32_e64 %[s_any], 0, v110\n"
-        "s_nop 0\n"                                             // (the one wait state left over)
-        "v_cndmask_b32_e64 v106, v105, v106, %[s_p2]\n"
-        "v_cndmask_b32_e64 v105, v106, v109, %[s_any]\n"
-        "v_mul_f32_e32 v106, 0x37800000, v105\n"
-        "v_cndmask_b32_e32 v105, v105, v106, vcc\n"
-        "v_cndmask_b32_e64 v104, v105, v104, %[s_both]\n"
-        "v_sub_f32_e32 v104, v107, v104\n"                      // h - sqrt(discriminant)
-        // ... / a, correctly rounded: hipcc's expansion
-        "v_div_scale_f32 v105, %[s_p2], %[a], %[a], v104\n"
-        "v_rcp_f32_e32 v106, v105\n"
-        "v_div_scale_f32 v107, vcc, v104, %[a], v104\n"
-        "v_fma_f32 v109, -v105, v106, 1.0\n"
-        "v_fmac_f32_e32 v106, v109, v106\n"
-        "v_mul_f32_e32 v108, v107, v106\n"
-        "v_fma_f32 v109, -v105, v108, v107\n"
-        "v_fmac_f32_e32 v108, v109, v106\n"
-        "v_fma_f32 v105, -v105, v108, v107\n"
-        "v_div_fmas_f32 v105, v105, v106, v108\n"
-        "v_div_fixup_f32 v104, v105, %[a], v104\n"              // t
+        BRT_LEAF_TAIL                                           // t = (h - sqrt(discriminant)) / a, see above
         // accepted iff t > 0.001 && t < closest (raytrace.wgsl:353-354; strict: the first sphere reached wins ties)
         "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"
         "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"
@@ -796,21 +949,28 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "s_mov_b64 exec, %[s_all]\n"
         "s_waitcnt lgkmcnt(0)\n"                                // the pop has long arrived; the next test reads it
         "s_branch 3b\n"
+        BRT_LEAF_TAIL_SLOW
         "9:\n"
         "s_waitcnt lgkmcnt(0)\n"
         : [cur] "+v"(cur), [spa] "+v"(spa), [closest] "+v"(closest), [cidx] "+v"(closest_idx), [below] "=&v"(below), [t0] "=&v"(t0),
           [tx] "=&v"(tx), [ty] "=&v"(ty), [tz] "=&v"(tz), [pop] "=&v"(pop), [cnt] "=&s"(cnt), [nw] "=&s"(nw), [thr] "=&s"(thr),
           [s_all] "=&s"(s_all), [s_take] "=&s"(s_take), [s_p2] "=&s"(s_p2), [s_any] "=&s"(s_any), [s_both] "=&s"(s_both)
 #if BRT_ASM_COUNT
-          , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_tmp] "=&s"(c_tmp)
+          , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_ls] "=&s"(c_ls), [c_tmp] "=&s"(c_tmp)
+#endif
+#if BRT_EXACT_FORMS & 4
+          , [r1] "=&v"(r1)
 #endif
         : [gofs_x] "v"(gofs_x), [gofs_y] "v"(gofs_y), [gofs_z] "v"(gofs_z), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(inv.x),
           [iy] "v"(inv.y), [iz] "v"(inv.z), [dx] "v"(d.x), [dy] "v"(d.y), [dz] "v"(d.z), [a] "v"(a), [sph] "s"(sph), [exit_at] "s"(exit_at),
           [vote] "s"(vote), [rec_bytes] "s"(rec_bytes), [c_tiny] "s"(c_tiny), [c_eps] "s"(c_eps), [c_cls] "s"(c_cls)
+#if BRT_EXACT_FORMS & 6
+          , [c_lo2] "s"(c_lo2), [c_hi2] "s"(c_hi2), [c_hi] "s"(c_hi)
+#endif
         : "vcc", "scc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112",
           "v113");
 #if BRT_ASM_COUNT
-    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; }
+    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; ac->leaf_slow += c_ls; }
 #endif
 #undef BRT_COUNT_INT
 #undef BRT_COUNT_LEAF
@@ -827,7 +987,7 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
                                uint32_t exit_at, uint32_t vote, AsmCounts* ac = nullptr) {
 #if BRT_HAND_ASM
 #if BRT_ASM_COUNT
-    uint32_t c_ie, c_il, c_le, c_ll, c_tmp;
+    uint32_t c_ie, c_il, c_le, c_ll, c_ls, c_tmp;
 #define BRT_COUNT_INT "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_il], %[c_il], %[c_tmp]\n s_add_u32 %[c_ie], %[c_ie], 1\n"
 #define BRT_COUNT_LEAF "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_ll], %[c_ll], %[c_tmp]\n s_add_u32 %[c_le], %[c_le], 1\n"
 #else
@@ -838,13 +998,20 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
     float below;
     uint64_t s_all, s_take, s_p2, s_any, s_both;
     const uint32_t rec_bytes = PAIR_BYTES, c_tiny = 0x0f800000u /* 2^-96 */, c_eps = 0x3a83126fu /* 0.001f */, c_cls = 0x260u /* +-0, +inf */;
+#if BRT_EXACT_FORMS & 6
+    const uint32_t c_lo2 = 0x17800000u /* 2^-80 */, c_hi2 = 0x67800000u /* 2^80 */, c_hi = 0x53800000u /* 2^40 */;
+#endif
+#if BRT_EXACT_FORMS & 4
+    float r1;                                                   // rcp_refined(a).r1
+#endif
     asm volatile(
 #if BRT_ASM_COUNT
-        "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n"
+        "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n s_mov_b32 %[c_ls], 0\n"
 #endif
         "s_waitcnt lgkmcnt(0)\n"                                // nothing of the compiler's in flight: the counted waits below are exact
         "s_mov_b64 %[s_all], exec\n"
         "v_add_u32_e32 %[below], -1, %[closest]\n"              // the largest float below closest (closest is FLT_MAX or an accepted t > 0)
+        BRT_LEAF_ENTRY
         // ---- outer loop: leave when at most exit_at lanes still walk -------------------------------------------------------
         "3:\n"
         "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n"
@@ -940,41 +1107,7 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "v_mul_f32_e32 v105, v107, v107\n"                      // h h
         "v_mul_f32_e32 v104, %[a], v104\n"                      // a c
         "v_sub_f32_e32 v104, v105, v104\n"                      // discriminant
-        // sqrt(discriminant), correctly rounded: hipcc's expansion (a negative argument gives NaN, rejected below like the
-        // shader's -1).  Same operations on the same values as the compiler emits; the order is chosen so that every wait
-        // state its hazard recogniser fills with s_nop (VALU -> vcc / SGPR -> v_cndmask: 2, v_sqrt / v_rcp -> use: 1) holds
-        // an instruction that is needed anyway.
-        "v_cmp_gt_f32_e32 vcc, %[c_tiny], v104\n"               // below 2^-96: scale by 2^32 (vcc stays until the result is scaled back)
-        "v_mul_f32_e32 v105, 0x4f800000, v104\n"
-        "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"            // (the pop's pointer move)
-        "v_cndmask_b32_e32 v104, v104, v105, vcc\n"
-        "v_sqrt_f32_e32 v105, v104\n"                           // s
-        "v_cmp_class_f32_e64 %[s_both], v104, %[c_cls]\n"       // +-0 and +inf are their own roots
-        "v_add_u32_e32 v106, -1, v105\n"                        // s - 1 ulp
-        "v_add_u32_e32 v109, 1, v105\n"                         // s + 1 ulp
-        "v_fma_f32 v108, -v106, v105, v104\n"                   // x - (s - 1 ulp) s
-        "v_fma_f32 v110, -v109, v105, v104\n"                   // x - (s + 1 ulp) s
-        "v_cmp_ge_f32_e64 %[s_p2], 0, v108\n"
-        "v_cmp_lt_f32_e64 %[s_any], 0, v110\n"
-        "s_nop 0\n"                                             // (the one wait state left over)
-        "v_cndmask_b32_e64 v106, v105, v106, %[s_p2]\n"
-        "v_cndmask_b32_e64 v105, v106, v109, %[s_any]\n"
-        "v_mul_f32_e32 v106, 0x37800000, v105\n"
-        "v_cndmask_b32_e32 v105, v105, v106, vcc\n"
-        "v_cndmask_b32_e64 v104, v105, v104, %[s_both]\n"
-        "v_sub_f32_e32 v104, v107, v104\n"                      // h - sqrt(discriminant)
-        // ... / a, correctly rounded: hipcc's expansion
-        "v_div_scale_f32 v105, %[s_p2], %[a], %[a], v104\n"
-        "v_rcp_f32_e32 v106, v105\n"
-        "v_div_scale_f32 v107, vcc, v104, %[a], v104\n"
-        "v_fma_f32 v109, -v105, v106, 1.0\n"
-        "v_fmac_f32_e32 v106, v109, v106\n"
-        "v_mul_f32_e32 v108, v107, v106\n"
-        "v_fma_f32 v109, -v105, v108, v107\n"
-        "v_fmac_f32_e32 v108, v109, v106\n"
-        "v_fma_f32 v105, -v105, v108, v107\n"
-        "v_div_fmas_f32 v105, v105, v106, v108\n"
-        "v_div_fixup_f32 v104, v105, %[a], v104\n"              // t
+        BRT_LEAF_TAIL                                           // t = (h - sqrt(discriminant)) / a, see above
         // accepted iff t > 0.001 && t < closest (raytrace.wgsl:353-354; strict: the first sphere reached wins ties)
         "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"
         "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"
@@ -985,6 +1118,7 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "s_mov_b64 exec, %[s_all]\n"
         "s_waitcnt lgkmcnt(0)\n"                                // the pop has long arrived; the next test reads it
         "s_branch 3b\n"
+        BRT_LEAF_TAIL_SLOW
         // ---- out of line: an interior step with lanes on both sides (two EXEC masks, one destination) ---------------------------
         "8:\n"
         "v_add_u32_e32 %[ty], %[t0], %[gofs_y]\n"
@@ -1009,15 +1143,21 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
           [tx] "=&v"(tx), [ty] "=&v"(ty), [tz] "=&v"(tz), [pop] "=&v"(pop), [cnt] "=&s"(cnt), [nw] "=&s"(nw), [thr] "=&s"(thr),
           [s_all] "=&s"(s_all), [s_take] "=&s"(s_take), [s_p2] "=&s"(s_p2), [s_any] "=&s"(s_any), [s_both] "=&s"(s_both)
 #if BRT_ASM_COUNT
-          , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_tmp] "=&s"(c_tmp)
+          , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_ls] "=&s"(c_ls), [c_tmp] "=&s"(c_tmp)
+#endif
+#if BRT_EXACT_FORMS & 4
+          , [r1] "=&v"(r1)
 #endif
         : [gofs_x] "v"(gofs_x), [gofs_y] "v"(gofs_y), [gofs_z] "v"(gofs_z), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(inv.x),
           [iy] "v"(inv.y), [iz] "v"(inv.z), [dx] "v"(d.x), [dy] "v"(d.y), [dz] "v"(d.z), [a] "v"(a), [near_bytes] "s"(near_bytes), [far] "s"(far), [sphg] "s"(sphg), [exit_at] "s"(exit_at),
           [vote] "s"(vote), [rec_bytes] "s"(rec_bytes), [c_tiny] "s"(c_tiny), [c_eps] "s"(c_eps), [c_cls] "s"(c_cls)
+#if BRT_EXACT_FORMS & 6
+          , [c_lo2] "s"(c_lo2), [c_hi2] "s"(c_hi2), [c_hi] "s"(c_hi)
+#endif
         : "vcc", "scc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112",
           "v113");
 #if BRT_ASM_COUNT
-    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; }
+    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; ac->leaf_slow += c_ls; }
 #endif
 #undef BRT_COUNT_INT
 #undef BRT_COUNT_LEAF
@@ -1038,7 +1178,8 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
 // any association gives the same bits; rays that can produce a NaN never come here), four row broadcasts bring them to every lane
 // and each lane makes the reference's decision (raytrace.wgsl:331, :338-341) for itself: ~38 instructions per step instead of ~66.
 // The leaf step forms the two dot products of hit_sphere (raytrace.wgsl:371-383) across three lanes in the shader's order,
-// (x x' + y y') + z z', and then runs hipcc's sqrt and divide expansions exactly as walk_wave_lds_asm does.  Same nodes in the same
+// (x x' + y y') + z z', and then runs hipcc's full sqrt and divide expansions (the instructions of BRT_LEAF_SQRT_FULL / BRT_LEAF_DIV_FULL; the short
+// forms of BRT_LEAF_TAIL were not taken over: a row's step is a dependent chain, not an issue budget).  Same nodes in the same
 // order, same ties, same t: pixels and counters do not change.  The rays' stacks stay where they are (the row reads and writes its
 // source lane's column of the wave's stack array), so a walk that was suspended by the wide loop is finished here as it stands.
 // Rays travel through 80 bytes of LDS scratch per row: { o, a | 1/d, closest | d, closest id | granule offsets, cur | stack top }.
@@ -1416,7 +1557,10 @@ BRT_DEV void walk_run(const ScenePtrs& sc, WalkState<StackT>& w, StackT* stk, f3
     uint32_t n = w.n;
     const uint32_t ox = w.ox, oy = w.oy, oz = w.oz;
     const bool pending = cur != DS::DONE && (SIMPLE_TREE || n < 31u);
-    const bool unsafe = !sc.boxes_ordered || (pending && !ray_is_safe(o, inv));
+    // (the hand-written loops divide by `a` in the plain form, BRT_LEAF_TAIL: a ray whose `a` is outside that form's range -- or a NaN --
+    //  is walked by the compiler's loop like one that fails ray_is_safe)
+    constexpr bool kPlainA = (BRT_EXACT_FORMS & 4) != 0 && BRT_WALK_FAST && STRIDE == 64 && !COUNTERS && SIMPLE_TREE && D16;
+    const bool unsafe = !sc.boxes_ordered || (pending && !ray_is_safe(o, inv)) || (kPlainA && pending && !(a >= kLeafALo && a <= kPlainHi));
     if (STRIDE == 64) {
         // Wave-level loop.  The kernel is bound by instruction issue, the two bodies cost the wave ~60-70
         // instructions each however few lanes take part, and a ray needs ~6 interior steps per leaf step:

@@ -211,16 +211,19 @@ __global__ void k_debug_eval(uint32_t op, const float* __restrict__ in, float* _
             r[0] = (float)bad; r[1] = __uint_as_float(bad_n); r[2] = __uint_as_float(bad_d);
             break;
         }
-        case BRT_DBG_SQRT_SWEEP: {   // first bits, count -> mismatches of sqrt_plain against __builtin_sqrtf over `count` consecutive floats
+        case BRT_DBG_SQRT_SWEEP: {   // first bits, count, form -> mismatches against __builtin_sqrtf over `count` consecutive floats: of sqrt_plain
+            // (form 0) or of sqrt_rsq (form != 0: strictly positive arguments only, no +-0)
             const uint32_t first = __float_as_uint(a[0]) + i * (uint32_t)a[1];
             const uint32_t count = (uint32_t)a[1];
+            const bool rsq = a[2] != 0.0f;
             uint32_t bad = 0, bad_x = 0;
             for (uint32_t k = 0; k < count; k++) {
                 const float x = __uint_as_float(first + k);
                 if (!(x >= 0x1p-80f && x <= 0x1p80f)) continue;
-                if (__float_as_uint(sqrt_plain(x)) != __float_as_uint(__builtin_sqrtf(x))) { if (!bad) bad_x = first + k; bad++; }
+                const float s = rsq ? sqrt_rsq(x) : sqrt_plain(x);
+                if (__float_as_uint(s) != __float_as_uint(__builtin_sqrtf(x))) { if (!bad) bad_x = first + k; bad++; }
             }
-            if (i == 0) {   // and +-0, which sqrt3 (brt_device.h) also sends through the short form
+            if (i == 0 && !rsq) {   // and +-0, which sqrt3 (brt_device.h) also sends through sqrt_plain
                 for (uint32_t z = 0u; z < 2u; z++) {
                     const float x = __uint_as_float(z << 31);
                     if (__float_as_uint(sqrt_plain(x)) != __float_as_uint(__builtin_sqrtf(x))) { if (!bad) bad_x = z << 31; bad++; }

@@ -903,6 +903,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_persistent(DeviceSceneView 
         const AsmCounts& c = hc.asm_counts;
         const uint32_t v[12] = {wave_sum(c.int_exec), wave_sum(c.int_lanes), wave_sum(c.leaf_exec), wave_sum(c.leaf_lanes), wave_sum(c.ball_exec), wave_sum(c.ball_lanes),
                                 wave_sum(c.fix_int_lanes), wave_sum(c.fix_leaf_lanes), wave_sum(c.rows_int_exec), wave_sum(c.rows_calls), wave_sum(c.rows_cycles), wave_sum(c.wide_cycles)};
+        const uint32_t wave_sum_slow = wave_sum(c.leaf_slow);
         if (lane == 0) {            // (word 32 is the tile queue's counter)
             for (int k = 0; k < 6; k++) atomicAdd(&counters[33 + k], (unsigned long long)v[k]);
             atomicAdd(&counters[39], (unsigned long long)v[6]);
@@ -911,6 +912,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_persistent(DeviceSceneView 
             atomicAdd(&counters[5], (unsigned long long)v[9]);        // calls of that walk  (words 44 and 5 .. 7 are phase times in the COUNTERS build)
             atomicAdd(&counters[6], (unsigned long long)v[10]);       // shader clocks in the row-mode walk ...
             atomicAdd(&counters[7], (unsigned long long)v[11]);       // ... and in the wide hand-written walk (first active lane's view, summed over the waves)
+            atomicAdd(&counters[4], (unsigned long long)wave_sum_slow);   // of the leaf executions: through the full sqrt / divide forms (BRT_LEAF_TAIL_SLOW; word 4 is the hit count of the COUNTERS build)
         }
     }
 #endif

@@ -353,7 +353,7 @@ enum {
     BRT_DBG_DIV = 6,       /* in: n, d            out: n / d, shared-reciprocal short form, 1 / d, its short form (brt_device.h) */
     BRT_DBG_DIV_SWEEP = 7, /* in: seed (bits), count          out: mismatches of the short forms over `count` random plain-range pairs,
                               bits of the first mismatching n and d */
-    BRT_DBG_SQRT_SWEEP = 8,/* in: first (bits), count         out: mismatches of the short sqrt over `count` consecutive floats per element
+    BRT_DBG_SQRT_SWEEP = 8,/* in: first (bits), count, form   out: mismatches of the short sqrt (form 0; form != 0: of the rsq form, positive arguments only) over `count` consecutive floats per element
                               (element i starts at first + i * count; element 0 also checks +0 and -0), bits of the first mismatching argument */
     BRT_DBG_ENCODE = 9     /* in: c               out (as floats holding integers): the 8-bit sRGB code, the 8-bit unorm code, the f16 bits of c
                               (the store conversions of BRT_FLAG_OUT_*) */

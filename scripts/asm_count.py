@@ -43,6 +43,9 @@ def main():
         #  those few steps are counted there)
         fix_i, fix_l = asm["repairing_loop_lanes"]
         rec["production_frame"]["of_which_in_the_repairing_loop"] = {"interior_lanes": fix_i, "leaf_lanes": fix_l}
+        # leaf steps of the hand-written loops that left the short sqrt / divide forms for the full ones (BRT_LEAF_TAIL_SLOW)
+        rec["production_frame"]["leaf_slow_exec"] = asm["leaf_slow_exec"]
+        rec["production_frame"]["leaf_slow_share"] = round(asm["leaf_slow_exec"] / max(1, asm["leaf"][0]), 6)
         lanes_equal = (asm["interior"][1] + fix_i == cs["interior_visits"] == prof["interior"][1] and
                        asm["leaf"][1] + fix_l == cs["sphere_tests"] == prof["leaf"][1] and
                        asm["ball"][1] == prof["ball"][1] and st["rays"] == cs["rays"])
