@@ -1,9 +1,9 @@
 // brt_api_lens.cpp -- Pure frames and pixel lists under the lens rule (brt_lens.h, brt_lens.hip; DESIGN.md "Lens frames") on the first
 // device: a thin lens (depth of field) or an orthographic projection where every other entry point has a pinhole.  The call is the
-// sparse pixel tracer's (brt_api_pixels.cpp): the launch plan of every list kernel (plan_list), the control words and the staging
-// buffers of the pixel lists.  The tree follows the call's camera (with_tree_reach) and then, for origins off the camera's position,
-// the rule's origin bound (ensure_query_reach), which persists in query_level as after a ray query.  The host twin of the rule
-// (brt_host_lens_ray, brt_host_lens_seed, brt_host_lens_origin_bound) needs no context.
+// sparse pixel tracer's (pixels_call, brt_api_pixels.cpp) with the lens attached: the launch plan of every list kernel (plan_list), the
+// control words and the staging buffers of the pixel lists.  The tree follows the call's camera (with_tree_reach) and then, for origins
+// off the camera's position, the rule's origin bound (ensure_query_reach), which persists in query_level as after a ray query.  The
+// host twin of the rule (brt_host_lens_ray, brt_host_lens_seed, brt_host_lens_origin_bound) needs no context.
 #include "brt_frame.h"
 
 using namespace brt;
@@ -59,12 +59,6 @@ int32_t lens_check(brt_ctx* ctx, const void* camera80, const void* window16, con
     return BRT_OK;
 }
 
-int32_t size_check(brt_ctx* ctx, uint32_t width, uint32_t height) {
-    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
-    return BRT_OK;
-}
-
 // what every render entry point checks before it touches the device
 int32_t lens_call_check(brt_ctx* ctx, const void* camera80, const void* window16, const void* lens, uint32_t width, uint32_t height,
                         uint32_t flags, uint32_t allowed, LensCall* lc) {
@@ -101,116 +95,15 @@ int32_t with_lens_reach(brt_ctx* ctx, const void* camera80, const LensCall& lc, 
     return rc;
 }
 
-// One list (d_pixels null: entry i is pixel i) on `stream`, behind whatever wrote it there.  ctl: pixels_enqueue's.
-int32_t lens_enqueue(brt_ctx* ctx, DeviceCtx& dc, const LensCall& lc, const void* window16, uint32_t width, uint32_t height,
-                     const uint32_t* d_pixels, uint32_t n_pixels, const PixelsTarget& target, uint32_t* d_ctl, hipStream_t stream,
-                     bool force_plain, LensLaunch* ll) {
+// A list (pixels null: entry i is pixel i), or a frame, behind its checks: the sparse pixel tracer's call (pixels_call) with the lens
+// attached.  out_host: the host form, of host buffers; else `target` of DEVICE buffers on the call's stream.
+int32_t lens_call(brt_ctx* ctx, const void* camera80, const void* window16, const LensCall& lc, uint32_t width, uint32_t height,
+                  const uint32_t* pixels, uint32_t n_pixels, const PixelsTarget& target, float* out_host, void* hip_stream, uint32_t flags,
+                  brt_stats* stats) {
     Camera pinhole = lc.cam;
     pinhole.projection_type = 0u;       // (the frame terms of an orthographic camera are the perspective ones; the rule ignores fov)
-    int32_t rc = make_frame_params(ctx, &pinhole, window16, BRT_LEVEL_PURE, width, height, 0u, 1u, &ll->frame);
-    if (rc != BRT_OK) return rc;
-    if (ll->frame.policy_flags != 0u) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "lens frames implement the default policy only (brt_set_policy)");
-    const uint32_t form = ctx->knobs[K_PIXELS_FORM];
-    // waves per SIMD where nothing is staged (make usage-lens): 114 VGPRs with the hand-written loop (4), 80-94 without (5)
-    plan_list(ctx, dc, n_pixels, !(form == 1u || (force_plain && form != 2u)), 4u, 5u, false, ll);
-    PixelsArgs& pa = ll->args;
-    pa.pixels = d_pixels;
-    pa.n_pixels = n_pixels;
-    pa.count = nullptr;
-    pa.out = target.d_out;
-    pa.scatter = target.scatter ? 1u : 0u;
-    pa.out_format = target.out_format;
-    pa.stat = reinterpret_cast<unsigned long long*>(d_ctl);
-    pa.counter = d_ctl + 4;
-    ll->lens = lc.lv;
-    ll->stream = stream;
-    HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 20, stream));
-    HIP_TRY(ctx, launch_trace_lens(*ll));
-    return BRT_OK;
-}
-
-int32_t lens_ctl(brt_ctx* ctx, DeviceCtx& dc) {
-    if (dc.d_pxbuf) return BRT_OK;
-    return ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, 32u);
-}
-
-void lens_stats(const LensLaunch& ll, const unsigned long long* counts2, uint32_t n_entries, double total_ms, brt_stats* stats) {
-    if (!stats) return;
-    // (the tree fields are with_lens_reach's)
-    stats->rays = counts2 ? counts2[0] : 0u;
-    stats->reserved = counts2 ? (uint32_t)std::min<unsigned long long>(counts2[1], 0xffffffffull) : 0u;      // entries refused
-    stats->paths = counts2 ? ((uint64_t)n_entries - counts2[1]) * ll.frame.sample_count : 0u;
-    stats->n_workgroups = list_groups(ll, n_entries);
-    stats->threads_per_workgroup = ll.form == LIST_STREAM ? ll.block : 256u;
-    stats->lds_bytes = (uint32_t)ll.lds_bytes;
-    stats->scene_in_lds = ll.form != LIST_STREAM ? 0u : ll.scene_mode == SCENE_LDS ? 1u : (ll.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
-    stats->kernel_variant = ll.form == LIST_STREAM ? 34u : 35u;      // (the pixel tracer's are 32 / 33)
-    stats->total_ms = total_ms;
-}
-
-// A list, or a frame, of DEVICE buffers on the call's stream (brt_render_pixels_device's skeleton)
-int32_t lens_device_call(brt_ctx* ctx, const void* camera80, const void* window16, const LensCall& lc, uint32_t width, uint32_t height,
-                         const uint32_t* d_pixels, uint32_t n_pixels, const PixelsTarget& target, void* hip_stream, uint32_t flags,
-                         brt_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    DeviceCtx& dc = ctx->devs[0];
-    LensLaunch ll{};
-    unsigned long long counts[2] = {0u, 0u};
-    bool own = false;
-    const int32_t rc = with_lens_reach(ctx, camera80, lc, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        own = sc.own;
-        int32_t r = lens_ctl(ctx, dc);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_q, 0));
-        r = lens_enqueue(ctx, dc, lc, window16, width, height, d_pixels, n_pixels, target, dc.d_pxbuf, sc.stream,
-                         (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u, &ll);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));
-        if (!sc.own) return BRT_OK;
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_pxbuf, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
-    });
-    if (rc == BRT_OK) lens_stats(ll, own ? counts : nullptr, n_pixels, ms_since(t0), stats);
-    return rc;
-}
-
-// ... and of HOST buffers, synchronous on the context's own stream (brt_render_pixels' skeleton; pixels null: entry i is pixel i)
-int32_t lens_host_call(brt_ctx* ctx, const void* camera80, const void* window16, const LensCall& lc, uint32_t width, uint32_t height,
-                       const uint32_t* pixels, uint32_t n_pixels, float* out_rgba32f, uint32_t flags, brt_stats* stats) {
-    const auto t0 = std::chrono::steady_clock::now();
-    DeviceCtx& dc = ctx->devs[0];
-    LensLaunch ll{};
-    unsigned long long counts[2] = {0u, 0u};
-    const int32_t rc = with_lens_reach(ctx, camera80, lc, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const size_t list_bytes = pixels ? (size_t)n_pixels * 4u : 0u, out_bytes = (size_t)n_pixels * 16u;
-        if (dc.pxlist_cap < list_bytes || dc.pxout_cap < out_bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-        int32_t r = lens_ctl(ctx, dc);
-        if (r == BRT_OK && pixels) r = ensure(ctx, &dc.d_pxlist, &dc.pxlist_cap, list_bytes);
-        if (r == BRT_OK) r = ensure(ctx, &dc.d_pxout, &dc.pxout_cap, out_bytes);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-        if (pixels) HIP_TRY(ctx, hipMemcpyAsync(dc.d_pxlist, pixels, list_bytes, hipMemcpyHostToDevice, dc.stream));
-        r = lens_enqueue(ctx, dc, lc, window16, width, height, pixels ? reinterpret_cast<const uint32_t*>(dc.d_pxlist) : nullptr, n_pixels,
-                         {dc.d_pxout, false, 0u}, dc.d_pxbuf, dc.stream, (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u, &ll);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out_rgba32f, dc.d_pxout, out_bytes, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_pxbuf, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
-    });
-    if (rc == BRT_OK) lens_stats(ll, counts, n_pixels, ms_since(t0), stats);
-    return rc;
-}
-
-int32_t list_check(brt_ctx* ctx, const void* pixels, uint32_t n_pixels, const void* out) {
-    if (n_pixels > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_pixels too large");
-    if (n_pixels != 0u && (!pixels || !out)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "pixels / out is null");
-    return BRT_OK;
+    const PixelsCall pc = {&pinhole, window16, width, height, pixels, n_pixels, &lc.lv, flags, target, hip_stream, out_host};
+    return pixels_call(ctx, pc, stats, [&](auto&& body) { return with_lens_reach(ctx, camera80, lc, stats, body); });
 }
 
 // raytrace.wgsl:95 and :146-147 for pixel (px, py): pixel_begin's expressions (brt_trace.h)
@@ -237,8 +130,8 @@ int32_t brt_render_lens_device(brt_ctx* ctx, const void* camera80, const void* w
                                             BRT_FLAG_CALLER_STREAM | BRT_FLAG_KERNEL_SIMPLE | BRT_FLAG_OUT_MASK, &lc))
         return bad;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    return lens_device_call(ctx, camera80, window16, lc, width, height, nullptr, width * height, {d_frame, true, flags & BRT_FLAG_OUT_MASK},
-                            hip_stream, flags, stats);
+    return lens_call(ctx, camera80, window16, lc, width, height, nullptr, width * height, {d_frame, true, flags & BRT_FLAG_OUT_MASK}, nullptr,
+                     hip_stream, flags, stats);
     });
 }
 
@@ -249,7 +142,7 @@ int32_t brt_render_lens(brt_ctx* ctx, const void* camera80, const void* window16
     if (!out_rgba32f) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out_rgba32f is null");
     if (const int32_t bad = lens_call_check(ctx, camera80, window16, lens32, width, height, flags, BRT_FLAG_KERNEL_SIMPLE, &lc)) return bad;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    return lens_host_call(ctx, camera80, window16, lc, width, height, nullptr, width * height, out_rgba32f, flags, stats);
+    return lens_call(ctx, camera80, window16, lc, width, height, nullptr, width * height, {}, out_rgba32f, nullptr, flags, stats);
     });
 }
 
@@ -263,7 +156,7 @@ int32_t brt_render_lens_pixels_device(brt_ctx* ctx, const void* camera80, const 
         return bad;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_pixels == 0u) return BRT_OK;
-    return lens_device_call(ctx, camera80, window16, lc, width, height, d_pixels, n_pixels, {d_out_rgba32f, false, 0u}, hip_stream, flags, stats);
+    return lens_call(ctx, camera80, window16, lc, width, height, d_pixels, n_pixels, {d_out_rgba32f, false, 0u}, nullptr, hip_stream, flags, stats);
     });
 }
 
@@ -275,7 +168,7 @@ int32_t brt_render_lens_pixels(brt_ctx* ctx, const void* camera80, const void* w
     if (const int32_t bad = lens_call_check(ctx, camera80, window16, lens32, width, height, flags, BRT_FLAG_KERNEL_SIMPLE, &lc)) return bad;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_pixels == 0u) return BRT_OK;
-    return lens_host_call(ctx, camera80, window16, lc, width, height, pixels, n_pixels, out_rgba32f, flags, stats);
+    return lens_call(ctx, camera80, window16, lc, width, height, pixels, n_pixels, {}, out_rgba32f, nullptr, flags, stats);
     });
 }
 

@@ -158,10 +158,45 @@ struct PixelsTarget {
 };
 // Behind whatever wrote the list on `stream`: the list traced as pixels of the width x height Pure frame of camera80 / window16 on the
 // first device.  d_count: a device word holding the number of entries (nullptr: n_pixels, which is else the list's capacity).  ctl: 8
-// words of the caller's {u64 rays, u64 refused, u32 batch counter, ...}, zeroed here.  Refuses a non-default policy.
+// words of the caller's {u64 rays, u64 refused, u32 batch counter, ...}, zeroed here.  Refuses a non-default policy.  lens: the list
+// under the lens rule (brt_lens.hip), where a null d_pixels means that entry i is pixel i; camera80 is then the pinhole camera of the
+// frame terms.
 int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                        const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
-                       hipStream_t stream, bool force_plain, PixelsLaunch* pl);
+                       hipStream_t stream, bool force_plain, PixelsLaunch* pl, const LensView* lens = nullptr);
+// What brt_render_pixels* and brt_render_lens* (brt_api_lens.cpp) share.  The two checks of a frame size and of a list with its output;
+// a call behind its checks, of n_pixels > 0 entries; its two bodies, which run once the tree is settled; and the launch fields of its
+// stats (counts2 null: not counted; kernel_variant 32 / 33, under a lens 34 / 35).
+int32_t size_check(brt_ctx* ctx, uint32_t width, uint32_t height);
+int32_t list_check(brt_ctx* ctx, const void* pixels, uint32_t n_pixels, const void* out);
+struct PixelsCall {
+    const void *camera80, *window16;     // as pixels_enqueue takes them
+    uint32_t width, height;
+    const uint32_t* pixels;              // the device form's DEVICE list, the host form's host list
+    uint32_t n_pixels;
+    const LensView* lens;
+    uint32_t flags;
+    PixelsTarget target;                 // the device form's
+    void* hip_stream;
+    float* out_rgba32f;                  // the host form's (null: the device form)
+};
+struct PixelsRun {
+    PixelsLaunch pl{};
+    unsigned long long counts[2] = {0u, 0u};
+    bool counted = false;
+};
+int32_t pixels_run_device(brt_ctx* ctx, const PixelsCall& pc, PixelsRun* run);      // DEVICE buffers on the call's stream
+int32_t pixels_run_host(brt_ctx* ctx, const PixelsCall& pc, PixelsRun* run);        // host buffers, synchronous on the context's own stream
+void pixels_stats(const PixelsCall& pc, const PixelsRun& run, double total_ms, brt_stats* stats);
+// reach(body): the tree for the call, then body() -- with_tree_reach, or brt_api_lens.cpp's with_lens_reach
+template <class Reach>
+int32_t pixels_call(brt_ctx* ctx, const PixelsCall& pc, brt_stats* stats, Reach&& reach) {
+    const auto t0 = std::chrono::steady_clock::now();
+    PixelsRun run;
+    const int32_t rc = reach([&]() -> int32_t { return pc.out_rgba32f ? pixels_run_host(ctx, pc, &run) : pixels_run_device(ctx, pc, &run); });
+    if (rc == BRT_OK && stats) pixels_stats(pc, run, ms_since(t0), stats);
+    return rc;
+}
 
 // ---- brt_api_upscale.cpp ----
 bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes);

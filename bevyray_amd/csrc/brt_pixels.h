@@ -1,4 +1,5 @@
-// brt_pixels.h -- host-callable launcher of the sparse pixel tracer (brt_pixels.hip).  The rules: DESIGN.md "Refined upsampling".
+// brt_pixels.h -- host-callable launchers of the sparse pixel tracer (brt_pixels.hip, brt_lens.hip; the kernels: brt_pixels_dev.h).  The
+// rules: DESIGN.md "Refined upsampling" and "Lens frames".
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,9 +33,6 @@ hipError_t launch_trace_pixels(const PixelsLaunch& pl);
 
 // The same list under the lens rule (brt_lens.h, brt_lens.hip): a sample's primary ray is lens_ray_raw's instead of the pinhole's.
 // args.pixels may be null: entry i is pixel i (a whole frame, n_pixels = width * height).
-struct LensLaunch : PixelsLaunch {
-    LensView lens;
-};
-hipError_t launch_trace_lens(const LensLaunch& ll);
+hipError_t launch_trace_lens(const PixelsLaunch& pl, const LensView& lens);
 
 }  // namespace brt

@@ -1,164 +1,23 @@
 // brt_pixels.hip -- the sparse pixel tracer (brt_render_pixels*, and the refinement of brt_upscale_refine*; DESIGN.md "Refined
 // upsampling").  A list entry names a pixel of the width x height Pure frame; its value is that frame's: the seed of a pixel depends on
 // its frame coordinates alone (pixel_seed), and per pixel the draws and operations are k_trace_simple's (pixel_begin / camera_ray_dir /
-// walk / shade_segment), whichever form runs it.
-//
-// k_trace_pixels_plain<D16>                one thread per entry: k_trace_simple's loop over a list, the scene in global memory, a private
-//                                          stack.  Every scene representation and tree.
-// k_trace_pixels_stream<MODE, D16, SIMPLE> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged in
-//                                          LDS (stream_stage, brt_stream.h), the stacks in LDS, so the hand-written walk loops serve it.
-//                                          A lane carries one path.  A round: the wave takes entries from the batch counter (one
-//                                          fetch-add) for the lanes whose pixel has ended, walk_run for all lanes, and the lanes whose
-//                                          walk has ended shade their segment and begin the next one, end the sample or end the pixel.
-// Both forms write the same bytes: an entry's result depends on its pixel alone.  No atomic touches a result.
-// What the streaming form shares with k_query_stream and k_radiance_stream, its launch included: brt_stream.h.
+// walk / shade_segment), whichever form runs it.  The kernels are k_list_plain and k_list_stream (brt_pixels_dev.h) under the pinhole
+// start rule; brt_lens.hip instantiates them under the lens rule.
 #include <hip/hip_runtime.h>
-
-#include <type_traits>
 
 #include "brt_pixels_dev.h"
 
 namespace brt {
 
-// ---- plain form ----------------------------------------------------------------------------------------------------------------------
-
-template <bool D16>
-__global__ __launch_bounds__(256) void k_trace_pixels_plain(DeviceSceneView sv, FrameParams fp, PixelsArgs pa) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    uint32_t n_rays = 0u, refused = 0u;
-    if (i < pixels_n(pa)) {
-        const uint32_t p = pa.pixels[i];
-        if (p >= fp.width * fp.height) {
-            pixels_refuse(pa, i);
-            refused = 1u;
-        } else {
-            const ScenePtrs sc = scene_global(sv);
-            HitCounters hc = {};
-            PixelState ps;
-            pixels_begin(fp, p, ps);
-            uint32_t stack[34];   // DONE sentinel + 32 entries + one spare
-            for (uint32_t s = 0; s < fp.sample_count; s++) {          // raytrace.wgsl:161
-                f3 d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);
-                f3 o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
-                f3 tput = mk3(1.0f, 1.0f, 1.0f);
-                float first_depth = kInf;
-                uint32_t bounce = 0;
-                f3 color;
-                for (;;) {
-                    float t;
-                    uint32_t idx;
-                    raycast<1, false, D16, false>(sc, sv.root_desc, stack, o, d, t, idx, hc);
-                    n_rays++;
-                    if (shade_segment<false>(sc, fp, o, d, tput, bounce, first_depth, t, idx, ps.rng, color, hc)) break;
-                }
-                ps.sum = ps.sum + color;
-            }
-            pixels_store(pa, i, p, pixels_value(fp, ps));
-        }
+// a sample starts as k_trace_simple's does (raytrace.wgsl:162, :175-186); every entry names its pixel
+struct PinholeStart {
+    static BRT_DEV uint32_t pixel_of(const PixelsArgs& pa, uint32_t i) { return pa.pixels[i]; }
+    static BRT_DEV void sample(const FrameParams& fp, const PixelState& ps, uint32_t& rng, f3& o, f3& d) {
+        d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, rng);
+        o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
     }
-    pixels_count(pa, n_rays, refused);
-}
-
-// ---- streaming form ------------------------------------------------------------------------------------------------------------------
-
-template <int MODE, bool D16, bool SIMPLE>
-__global__ __launch_bounds__(BRT_BLOCK) void k_trace_pixels_stream(DeviceSceneView sv, FrameParams fp, PixelsArgs pa) {
-    static_assert(MODE == SCENE_GLOBAL || D16, "a scene staged in LDS always uses 16-bit descriptors");
-    using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
-    using DS = Desc<D16>;
-    extern __shared__ uint4 smem[];
-    ScenePtrs sc = scene_global(sv);
-    StackT* stacks = stream_stage<MODE, StackT>(sv, smem, sc);
-    const uint32_t lane = lane_id();
-    StackT* stk = stream_stack<D16>(sv, stacks, lane);
-    const uint32_t n = pixels_n(pa), frame_px = fp.width * fp.height;
-
-    WalkState<StackT> walk = walk_idle<D16>(stk);
-    PixelState ps = {};
-    f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f), tput = mk3(1.0f, 1.0f, 1.0f);
-    uint32_t bounce = 0u;
-    float first_depth = kInf;
-    uint32_t entry = 0u, pixel = 0u;
-    bool in_flight = false;          // this lane holds a pixel whose samples have not ended
-    bool exhausted = false;          // wave-uniform: the batch counter has passed the last entry
-    uint32_t n_rays = 0u, refused = 0u;
-    HitCounters hc = {};
-    for (;;) {
-        if (!exhausted) {
-            // entries for the idle lanes: one fetch-add of the wave
-            const uint64_t idle = __ballot(!in_flight);
-            const uint32_t cnt = (uint32_t)__popcll(idle);
-            uint32_t base = 0u;
-            if (lane == 0u) base = atomicAdd(pa.counter, cnt);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            exhausted = base >= n || n - base <= cnt;
-            const uint32_t mine = base + mbcnt64(idle);
-            if (!in_flight && base < n && mine < n) {
-                const uint32_t p = pa.pixels[mine];
-                if (p >= frame_px) {
-                    pixels_refuse(pa, mine);
-                    refused++;
-                } else {
-                    entry = mine;
-                    pixel = p;
-                    pixels_begin(fp, p, ps);
-                    if (fp.sample_count == 0u) {                       // (no sample: the average of nothing)
-                        pixels_store(pa, entry, pixel, pixels_value(fp, ps));
-                    } else {
-                        d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);          // raytrace.wgsl:162, :175-186
-                        o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
-                        tput = mk3(1.0f, 1.0f, 1.0f);
-                        first_depth = kInf;
-                        bounce = 0u;
-                        walk_begin<D16>(walk, sc, sv.root_desc, stk, d);
-                        in_flight = true;
-                    }
-                }
-            }
-        }
-        walk_run<64, false, D16, SIMPLE, MODE, StackT>(sc, walk, stk, o, d, kWalkExitLanes, kLeafVote, hc);
-        if (in_flight && !walk_pending<D16, SIMPLE>(walk)) {
-            n_rays++;
-            f3 color;
-            if (shade_segment<false>(sc, fp, o, d, tput, bounce, first_depth, walk.closest, walk.closest_idx, ps.rng, color, hc)) {
-                ps.sum = ps.sum + color;                                // :165
-                ps.sample++;
-                if (ps.sample < fp.sample_count) {
-                    d = camera_ray_dir(fp, ps.ndc0x, ps.ndc0y, ps.rng);
-                    o = mk3(fp.cam_pos[0], fp.cam_pos[1], fp.cam_pos[2]);
-                    tput = mk3(1.0f, 1.0f, 1.0f);
-                    first_depth = kInf;
-                    bounce = 0u;
-                } else {
-                    pixels_store(pa, entry, pixel, pixels_value(fp, ps));
-                    in_flight = false;
-                }
-            }
-            if (in_flight) walk_begin<D16>(walk, sc, sv.root_desc, stk, d);
-            else walk.cur = DS::DONE;
-        }
-        if (exhausted && __ballot(in_flight) == 0ull) break;
-    }
-    pixels_count(pa, n_rays, refused);
-}
-
-// ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
-
-struct PixelsStream {
-    template <int MODE, bool D16, bool SIMPLE>
-    static auto kernel() { return k_trace_pixels_stream<MODE, D16, SIMPLE>; }
 };
 
-hipError_t launch_trace_pixels(const PixelsLaunch& pl) {
-    if (pl.args.n_pixels == 0u) return hipSuccess;
-    if (!pl.args.pixels || !pl.args.out || pl.frame.policy_flags != 0u) return hipErrorInvalidValue;
-    if (pl.form == LIST_PLAIN) {
-        const dim3 grid((pl.args.n_pixels + 255u) / 256u);
-        if (pl.scene.desc16) hipLaunchKernelGGL(k_trace_pixels_plain<true>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
-        else hipLaunchKernelGGL(k_trace_pixels_plain<false>, grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args);
-        return hipGetLastError();
-    }
-    return launch_stream<PixelsStream>(pl, pl.args.counter, pl.frame, pl.args);
-}
+hipError_t launch_trace_pixels(const PixelsLaunch& pl) { return launch_list<PinholeStart>(pl, false); }
 
 }  // namespace brt

@@ -11,7 +11,7 @@
 //                                   are still under way (walk_run's early exit and WalkState), instead of waiting for its longest walk.
 //                                   ANY mode ends a lane's walk at the first return of walk_run at which closest < t_max.
 // Both forms write the same bytes: a lane's result depends on its own ray alone.  No atomics touch a result.
-// What the streaming form shares with k_radiance_stream and k_trace_pixels_stream, its launch included: brt_stream.h.
+// What the streaming form shares with k_radiance_stream and k_list_stream (brt_pixels_dev.h), its launch included: brt_stream.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>

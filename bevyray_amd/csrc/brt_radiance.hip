@@ -17,7 +17,7 @@
 //                                      walk has ended shade their segment and begin the next one, end the sample or end the entry.
 // Both forms write the same bytes: an entry's result depends on its own record alone.  No atomic touches a result; a result goes out as
 // two float4 stores.
-// What the streaming form shares with k_query_stream and k_trace_pixels_stream, its launch included: brt_stream.h.
+// What the streaming form shares with k_query_stream and k_list_stream (brt_pixels_dev.h), its launch included: brt_stream.h.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>

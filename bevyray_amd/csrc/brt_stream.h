@@ -1,4 +1,4 @@
-// brt_stream.h -- what the streaming list kernels share (k_query_stream, k_radiance_stream, k_trace_pixels_stream, k_lens_stream): the
+// brt_stream.h -- what the streaming list kernels share (k_query_stream, k_radiance_stream, and k_list_stream of the pixel lists): the
 // scene in global memory or staged in LDS, a lane's stack and idle walk, and the launch of the streaming form.  Included by
 // brt_query.hip, brt_radiance.hip and (through brt_pixels_dev.h) brt_pixels.hip and brt_lens.hip only.  The counter claim of a round
 // stays written out in each kernel: as a function it changes their instructions.

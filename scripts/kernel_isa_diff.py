@@ -7,7 +7,9 @@ register, and the same "Kernel info" block behind the kernel (the figures -Rpass
 scratch, LDS, occupancy): the register allocator named the same values differently.  Comments,
 directives and the numbering of local labels are ignored; an empty template parameter pack in a mangled name counts as no pack (the
 instantiation of a kernel template that gained an optional trailing argument), and a seventh argument `false` of k_trace_persistent
-counts as no argument (the template lost that parameter; its `true` instantiation has no namesake and is reported missing).  Exit
+counts as no argument (the template lost that parameter; its `true` instantiation has no namesake and is reported missing), and
+k_trace_pixels_{plain,stream}<...> and k_lens_{plain,stream}<LENS, ...> count as their namesakes k_list_*<PinholeStart, ...> and
+k_list_*<LensStart<LENS>, ..., LensView> (the two families became one pair of templates under a start rule).  Exit
 status 1 if a kernel is DIFF or missing."""
 import re
 import sys
@@ -30,8 +32,10 @@ def kernels(path, info=None):
             block = None
         m = re.match(r"^(_Z\w+):", ln)
         if m:
-            cur = m.group(1).replace("EJEEEv", "EEEv").replace("DpT1_", "")
+            cur = re.sub(r"DpT\d_", "", m.group(1).replace("EJEEEv", "EEEv"))
             cur = re.sub(r"(k_trace_persistentI(?:L[ib]\dE){6})Lb0E(EEv)", r"\1\2", cur)
+            cur = re.sub(r"\d\dk_trace_pixels_(plain|stream)I", lambda g: f"{len(g.group(1)) + 7}k_list_{g.group(1)}INS_12PinholeStartE", cur)
+            cur = re.sub(r"k_lens_(plain|stream)I(Lj\dE)((?:L[ib]\dE)+)EEv(\w+)NS_8LensViewE$", r"k_list_\1INS_9LensStartI\2EE\3JNS_8LensViewEEEEv\4", cur)
             out[cur] = []
             last = cur
         elif cur is not None:

@@ -579,6 +579,42 @@ def test_out_of_frame_entries_are_zero_and_counted(plugin, thin_cover):
 
 
 @pytest.mark.gpu
+def test_radius_zero_lists_are_the_pixel_tracers(plugin):
+    """Where the two families of the one kernel pair meet: a shuffled list of all pixels of the 97 x 3 cover frame (2 spp, 1 bounce) with
+    two out-of-frame entries, by brt_render_lens_pixels* at aperture radius 0 and by brt_render_pixels*, in both forms through the host and
+    the device entry point: the same bits (four zeros at the refused entries), the same refused, path and ray counts, and each family's
+    own kernel_variant."""
+    import torch
+    w, h = 97, 3
+    plugin.node.write_buffers(_cover())
+    _, cam, win = brt.cover_camera(w, h, 2, 1)
+    lens = brt.lens(0.0, 3.0, 5.0)
+    px = np.concatenate([np.arange(w * h), [w * h, 0xFFFFFFFF]]).astype(np.uint32)
+    px = px[np.random.default_rng(97).permutation(px.size)]
+    bad = px >= w * h
+    assert px.size == w * h + 2 and bad.sum() == 2 and 0 < np.flatnonzero(bad)[0] and np.flatnonzero(bad)[1] < px.size - 1
+
+    def pinhole_dev(flags):
+        d_px = _dev(px)
+        out = torch.full((px.size, 4), 7.5, dtype=torch.float32, device="cuda")
+        plugin.node.render_pixels_device(cam, win, w, h, d_px.data_ptr(), px.size, out.data_ptr(), flags=flags)
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    for flags, form in ((0, 0), (brt.FLAG_KERNEL_SIMPLE, 1)):
+        for entry in ("device", "host"):
+            got = _pixels_dev(plugin, cam, win, lens, w, h, px, flags) if entry == "device" else plugin.node.render_lens_pixels(cam, win, lens, w, h, px, flags)
+            ls = dict(plugin.node.last_stats)
+            want = pinhole_dev(flags) if entry == "device" else plugin.node.render_pixels(cam, win, w, h, px, flags)
+            ps = dict(plugin.node.last_stats)
+            print(f"{entry} flags {flags}: rays {ls['rays']} / {ps['rays']}, paths {ls['paths']} / {ps['paths']}, reserved {ls['reserved']} / {ps['reserved']}")
+            assert _same_bits(got, want) and not _bits(got[bad]).any() and (got[~bad, 3] == 1.0).all(), (flags, entry)
+            assert ls["reserved"] == ps["reserved"] == 2 and ls["paths"] == ps["paths"] == w * h * 2, (flags, entry, ls, ps)
+            assert ls["rays"] == ps["rays"], (flags, entry, ls["rays"], ps["rays"])
+            assert ls["kernel_variant"] == STREAM_FORM + form and ps["kernel_variant"] == 32 + form, (flags, entry, ls, ps)
+
+
+@pytest.mark.gpu
 def test_sample_count_zero(plugin, thin_cover):
     b, cam, win, lens, _, _ = thin_cover
     plugin.node.write_buffers(b)

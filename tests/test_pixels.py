@@ -224,7 +224,7 @@ def _both_forms(plugin, oracle, b, lvl, cam, win, w, h, order, tag):
 
 @pytest.mark.gpu
 def test_lists_around_the_launch_lane_count(plugin, oracle):
-    """k_trace_pixels_stream's exit test (`base >= n || n - base <= cnt`) at lists of L - 1, L, L + 1, 2 L and 2 L + 63 entries, L the
+    """k_list_stream's exit test (`base >= n || n - base <= cnt`) at lists of L - 1, L, L + 1, 2 L and 2 L + 63 entries, L the
     lanes of the launch, at 1 spp with the longest pixels of the frame in a run at the end, so that the last fetch happens while lanes are
     busy.  L is read twice: from a list of 1000 entries (the launch is as wide as the list needs: one workgroup) and from one that is
     longer than the widest launch (every CU's workgroups).  The second L is above 70 000 on an MI355X and no knob plan_stream honours
