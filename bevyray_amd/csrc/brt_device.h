@@ -819,6 +819,139 @@ constexpr float kLeafALo = 0x1p-29f;
         BRT_LEAF_DIV_FULL
 #define BRT_LEAF_TAIL_SLOW
 #endif
+// The interior step of the two wide loops below, in the parts that only move masks, addresses and waits.  A wave issues one instruction per
+// ~5.3 cycles whatever the instruction is (tests/tools/issue_bench.hip), so beside the vector-pipe cycles the step is priced in instructions:
+// 66 as first written (44 vector, 6 LDS, 16 scalar).  BRT_INT_STEP selects cheaper forms of the scalar part; per lane nothing changes -- the
+// same sub / mul / min / max on the same operands in the same order, the same push rule, the same stack contents:
+//   bit 0: the test for interior lanes writes EXEC itself (v_cmpx; at the loop head, at the back edge and for the leaf lanes): no copy of
+//          the mask at the head, and with bits 1 and 2 no restore at the back edge
+//   bit 1: the next node by two selects, cur = p2 ? R : (p1 ? L : pop), instead of three moves under three EXEC masks
+//   bit 2: the stack pointer by arithmetic, spa += ((p1 + p2) - 1) * 128 (a select, an add with carry-in, a shift-add), instead of two adds
+//          under two EXEC masks; with bit 1 the decision writes EXEC nowhere
+//   bit 3: three counted waits (x and y | z | descriptors and pop) instead of four;  bit 4: two (x, y and z | descriptors and pop)
+// (gfx950 wait states: a VALU write of an SGPR or VCC needs two instructions before a VALU reads it as a mask -- the ds_write between the
+//  compares and the selects is one of them.)  Shipped: 7, a step of 57 instructions (44 vector, 6 LDS, 7 scalar).  Headline frame, five
+// alternated bench runs per arm, medians of two sessions (parent 8.747 resp. 8.722 ms): bit 0 8.657, bit 1 8.639, bits 0 + 1 8.573, all
+// three 8.546 in the first; bit 2 alone 8.746, bits 0 + 2 8.666, all three 8.523 in the second.  Fewer waits are SLOWER: bit 3 alone 8.790,
+// bit 4 alone 8.884 in the second session, 8.624 / 8.700 on top of 7 in the first.
+// tests/tools/int_step_bench.hip times the forms in isolation; docs/experiments.md ("Interior step in the instruction currency") and
+// profiles/interior_step/ have every arm.
+#ifndef BRT_INT_STEP
+#define BRT_INT_STEP 7
+#endif
+#if BRT_INT_STEP & 1
+#define BRT_INT_TEST "v_cmpx_lt_i32_e32 vcc, -1, %[cur]\n"       /* interior descriptors are >= 0; EXEC = VCC = the lanes at one */
+#define BRT_INT_HEAD
+#define BRT_INT_TAKE "exec"
+#define BRT_INT_SAVE_TAKE "s_mov_b64 %[s_take], exec\n"          /* (walk_wave_top_asm's out-of-line step narrows EXEC twice) */
+#define BRT_INT_LEAF_LANES                                       /* (the interior steps leave EXEC narrowed) */                        \
+        "s_mov_b64 exec, %[s_all]\n"                                                                                                   \
+        "v_cmpx_gt_i32_e32 vcc, -1, %[cur]\n"
+#else
+#define BRT_INT_TEST "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n"        /* interior descriptors are >= 0 */
+#define BRT_INT_HEAD                                                                                                                   \
+        "s_mov_b64 %[s_take], vcc\n"                                                                                                   \
+        "s_mov_b64 exec, vcc\n"
+#define BRT_INT_TAKE "%[s_take]"
+#define BRT_INT_LEAF_LANES                                                                                                             \
+        "v_cmp_gt_i32_e32 vcc, -1, %[cur]\n"                                                                                           \
+        "s_and_b64 exec, %[s_all], vcc\n"
+#define BRT_INT_SAVE_TAKE
+#endif
+// (with bit 0 the step may leave EXEC at the lanes that took it: the lanes at an interior node afterwards are among them, and the leaf step
+//  and the exit set EXEC from s_all)
+#if (BRT_INT_STEP & 7) == 7
+#define BRT_INT_RESTORE
+#else
+#define BRT_INT_RESTORE "s_mov_b64 exec, %[s_all]\n"
+#endif
+#define BRT_INT_X                                                                                                                      \
+        "v_sub_f32_e32 v100, v100, %[ox]\n v_sub_f32_e32 v101, v101, %[ox]\n v_sub_f32_e32 v102, v102, %[ox]\n v_sub_f32_e32 v103, v103, %[ox]\n" \
+        "v_mul_f32_e32 v100, v100, %[ix]\n v_mul_f32_e32 v101, v101, %[ix]\n v_mul_f32_e32 v102, v102, %[ix]\n v_mul_f32_e32 v103, v103, %[ix]\n"
+#define BRT_INT_Y                                                                                                                      \
+        "v_sub_f32_e32 v104, v104, %[oy]\n v_sub_f32_e32 v105, v105, %[oy]\n v_sub_f32_e32 v106, v106, %[oy]\n v_sub_f32_e32 v107, v107, %[oy]\n" \
+        "v_mul_f32_e32 v104, v104, %[iy]\n v_mul_f32_e32 v105, v105, %[iy]\n v_mul_f32_e32 v106, v106, %[iy]\n v_mul_f32_e32 v107, v107, %[iy]\n"
+#define BRT_INT_Z                                                                                                                      \
+        "v_sub_f32_e32 v108, v108, %[oz]\n v_sub_f32_e32 v109, v109, %[oz]\n v_sub_f32_e32 v110, v110, %[oz]\n v_sub_f32_e32 v111, v111, %[oz]\n" \
+        "v_mul_f32_e32 v108, v108, %[iz]\n v_mul_f32_e32 v109, v109, %[iz]\n v_mul_f32_e32 v110, v110, %[iz]\n v_mul_f32_e32 v111, v111, %[iz]\n"
+// the slab arithmetic behind its waits: W3 / W2 / W1 / W0 wait until at most 3 / 2 / 1 / 0 of { pop, x, y, z, descriptors } are outstanding
+#if BRT_INT_STEP & 16
+#define BRT_INT_SLABS(W3, W2, W1) W1 BRT_INT_X BRT_INT_Y BRT_INT_Z
+#elif BRT_INT_STEP & 8
+#define BRT_INT_SLABS(W3, W2, W1) W2 BRT_INT_X BRT_INT_Y W1 BRT_INT_Z
+#else
+#define BRT_INT_SLABS(W3, W2, W1) W3 BRT_INT_X W2 BRT_INT_Y W1 BRT_INT_Z
+#endif
+#if BRT_INT_STEP & 2
+#define BRT_INT_CUR_SEL                                                                                                                \
+        "v_cndmask_b32_e32 %[cur], %[pop], v112, vcc\n"         /* L if it is pushed, else the pop */                                  \
+        "v_cndmask_b32_e64 %[cur], %[cur], v113, %[s_p2]\n"     /* R if it is pushed (pushed last, popped first) */
+#define BRT_INT_CUR_POP
+#define BRT_INT_CUR_LR
+#else
+#define BRT_INT_CUR_SEL
+#define BRT_INT_CUR_POP "v_mov_b32_e32 %[cur], %[pop]\n"
+#define BRT_INT_CUR_LR                                                                                                                 \
+        "s_andn2_b64 exec, vcc, %[s_p2]\n"                      /* only L */                                                           \
+        "v_mov_b32_e32 %[cur], v112\n"                                                                                                 \
+        "s_mov_b64 exec, %[s_p2]\n"                             /* R (pushed last, popped first) */                                    \
+        "v_mov_b32_e32 %[cur], v113\n"
+#endif
+#if BRT_INT_STEP & 4
+#define BRT_INT_SPA_MASKS
+#define BRT_INT_SPA_SEL                                                                                                                \
+        "v_cndmask_b32_e64 %[t0], -1, 0, %[s_p2]\n"             /* p2 - 1 */                                                           \
+        "v_addc_co_u32_e64 %[t0], %[s_both], 0, %[t0], vcc\n"   /* + p1: -1 pops, 0 stays, +1 leaves L on the stack (carry out unused) */ \
+        "v_lshl_add_u32 %[spa], %[t0], 7, %[spa]\n"
+#define BRT_INT_SPA_POP
+#define BRT_INT_SPA_BOTH
+#else
+#define BRT_INT_SPA_MASKS                                                                                                              \
+        "s_or_b64 %[s_any], vcc, %[s_p2]\n"                                                                                            \
+        "s_and_b64 %[s_both], vcc, %[s_p2]\n"
+#define BRT_INT_SPA_SEL
+#define BRT_INT_SPA_POP "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"
+#define BRT_INT_SPA_BOTH                                                                                                               \
+        "s_mov_b64 exec, %[s_both]\n"                           /* both: L stays on the stack */                                       \
+        "v_add_u32_e32 %[spa], 0x80, %[spa]\n"
+#endif
+#if (BRT_INT_STEP & 6) == 6
+#define BRT_INT_NONE
+#else
+#define BRT_INT_NONE "s_andn2_b64 exec, " BRT_INT_TAKE ", %[s_any]\n"   /* no child pushed: pop */
+#endif
+#if (BRT_INT_STEP & 6) == 4
+#undef BRT_INT_SPA_MASKS
+#define BRT_INT_SPA_MASKS "s_or_b64 %[s_any], vcc, %[s_p2]\n"
+#endif
+#define BRT_INT_PUSH "ds_write_b16 %[spa], v112 offset:128\n"    /* child L above the top: dead unless both are pushed */
+#if BRT_INT_STEP & 6
+#define BRT_INT_PUSH_EARLY
+#define BRT_INT_PUSH_LATE BRT_INT_PUSH                           /* (one of the two instructions between the compares and the selects) */
+#else
+#define BRT_INT_PUSH_EARLY BRT_INT_PUSH
+#define BRT_INT_PUSH_LATE
+#endif
+// the decision (W0: descriptors and the pop, which went out first, are here) and the back edge
+#define BRT_INT_DECIDE(W0)                                                                                                            \
+        W0                                                                                                                             \
+        BRT_INT_PUSH_EARLY                                                                                                             \
+        "v_cmp_le_f32_e32 vcc, v100, v102\n"                    /* p1: child L is pushed (raytrace.wgsl:331) */                        \
+        "v_cmp_le_f32_e64 %[s_p2], v101, v103\n"                /* p2: child R is pushed (raytrace.wgsl:338) */                        \
+        BRT_INT_PUSH_LATE                                                                                                              \
+        BRT_INT_SPA_MASKS                                                                                                              \
+        BRT_INT_CUR_SEL                                                                                                                \
+        BRT_INT_SPA_SEL                                                                                                                \
+        BRT_INT_NONE                                                                                                                   \
+        BRT_INT_CUR_POP                                                                                                                \
+        BRT_INT_SPA_POP                                                                                                                \
+        BRT_INT_CUR_LR                                                                                                                 \
+        BRT_INT_SPA_BOTH                                                                                                               \
+        BRT_INT_RESTORE                                                                                                                \
+        BRT_INT_TEST                                                                                                                   \
+        "s_bcnt1_i32_b64 %[cnt], vcc\n"                                                                                                \
+        "s_cmp_gt_u32 %[cnt], %[thr]\n"                                                                                                \
+        "s_cbranch_scc1 1b\n"
 BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uint32_t& closest_idx, uint32_t gofs_x, uint32_t gofs_y,
                                uint32_t gofs_z, f3 o, f3 inv, f3 d, float a, uint32_t sph, uint32_t exit_at, uint32_t vote, AsmCounts* ac = nullptr) {
 #if BRT_HAND_ASM
@@ -856,14 +989,13 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "s_cbranch_scc1 9f\n"
         "s_max_u32 %[thr], %[nw], %[vote]\n"                    // interior steps while more than max(walking, vote) - vote lanes are at one
         "s_sub_u32 %[thr], %[thr], %[vote]\n"
-        "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n"                    // interior descriptors are >= 0
+        BRT_INT_TEST
         "s_bcnt1_i32_b64 %[cnt], vcc\n"
         "s_cmp_le_u32 %[cnt], %[thr]\n"
         "s_cbranch_scc1 5f\n"
-        // ---- interior steps ----------------------------------------------------------------------------------------------------
+        // ---- interior steps (BRT_INT_STEP, above) -------------------------------------------------------------------------------
         "1:\n"
-        "s_mov_b64 %[s_take], vcc\n"
-        "s_mov_b64 exec, vcc\n"
+        BRT_INT_HEAD
         BRT_COUNT_INT
         "ds_read_i16 %[pop], %[spa]\n"                          // the would-be pop: needs no address arithmetic, goes out first
         "v_mul_lo_u32 %[t0], %[cur], %[rec_bytes]\n"
@@ -874,15 +1006,7 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "v_add_u32_e32 %[tz], %[t0], %[gofs_z]\n"
         "ds_read_b128 v[108:111], %[tz]\n"
         "ds_read_b64 v[112:113], %[t0] offset:96\n"             // descriptors of L and R
-        "s_waitcnt lgkmcnt(3)\n"
-        "v_sub_f32_e32 v100, v100, %[ox]\n v_sub_f32_e32 v101, v101, %[ox]\n v_sub_f32_e32 v102, v102, %[ox]\n v_sub_f32_e32 v103, v103, %[ox]\n"
-        "v_mul_f32_e32 v100, v100, %[ix]\n v_mul_f32_e32 v101, v101, %[ix]\n v_mul_f32_e32 v102, v102, %[ix]\n v_mul_f32_e32 v103, v103, %[ix]\n"
-        "s_waitcnt lgkmcnt(2)\n"
-        "v_sub_f32_e32 v104, v104, %[oy]\n v_sub_f32_e32 v105, v105, %[oy]\n v_sub_f32_e32 v106, v106, %[oy]\n v_sub_f32_e32 v107, v107, %[oy]\n"
-        "v_mul_f32_e32 v104, v104, %[iy]\n v_mul_f32_e32 v105, v105, %[iy]\n v_mul_f32_e32 v106, v106, %[iy]\n v_mul_f32_e32 v107, v107, %[iy]\n"
-        "s_waitcnt lgkmcnt(1)\n"
-        "v_sub_f32_e32 v108, v108, %[oz]\n v_sub_f32_e32 v109, v109, %[oz]\n v_sub_f32_e32 v110, v110, %[oz]\n v_sub_f32_e32 v111, v111, %[oz]\n"
-        "v_mul_f32_e32 v108, v108, %[iz]\n v_mul_f32_e32 v109, v109, %[iz]\n v_mul_f32_e32 v110, v110, %[iz]\n v_mul_f32_e32 v111, v111, %[iz]\n"
+        BRT_INT_SLABS("s_waitcnt lgkmcnt(3)\n", "s_waitcnt lgkmcnt(2)\n", "s_waitcnt lgkmcnt(1)\n")
         "v_max_f32_e32 v100, v100, v104\n"
         "v_max_f32_e32 v101, v101, v105\n"
         "v_min_f32_e32 v102, v102, v106\n"
@@ -891,30 +1015,10 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "v_max3_f32 v101, v101, v109, 1\n"
         "v_min3_f32 v102, v102, v110, %[below]\n"               // t_far = min(.., below(closest))
         "v_min3_f32 v103, v103, v111, %[below]\n"
-        "s_waitcnt lgkmcnt(0)\n"                                // descriptors (and the pop, which went out first) are here
-        "ds_write_b16 %[spa], v112 offset:128\n"                // child L above the top: dead unless both are pushed
-        "v_cmp_le_f32_e32 vcc, v100, v102\n"                    // p1: child L is pushed (raytrace.wgsl:331)
-        "v_cmp_le_f32_e64 %[s_p2], v101, v103\n"                // p2: child R is pushed (raytrace.wgsl:338)
-        "s_or_b64 %[s_any], vcc, %[s_p2]\n"
-        "s_and_b64 %[s_both], vcc, %[s_p2]\n"
-        "s_andn2_b64 exec, %[s_take], %[s_any]\n"               // no child pushed: pop
-        "v_mov_b32_e32 %[cur], %[pop]\n"
-        "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"
-        "s_andn2_b64 exec, vcc, %[s_p2]\n"                      // only L
-        "v_mov_b32_e32 %[cur], v112\n"
-        "s_mov_b64 exec, %[s_p2]\n"                             // R (pushed last, popped first)
-        "v_mov_b32_e32 %[cur], v113\n"
-        "s_mov_b64 exec, %[s_both]\n"                           // both: L stays on the stack
-        "v_add_u32_e32 %[spa], 0x80, %[spa]\n"
-        "s_mov_b64 exec, %[s_all]\n"
-        "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n"
-        "s_bcnt1_i32_b64 %[cnt], vcc\n"
-        "s_cmp_gt_u32 %[cnt], %[thr]\n"
-        "s_cbranch_scc1 1b\n"
+        BRT_INT_DECIDE("s_waitcnt lgkmcnt(0)\n")
         // ---- one leaf step for every lane that waits at a leaf --------------------------------------------------------------
         "5:\n"
-        "v_cmp_gt_i32_e32 vcc, -1, %[cur]\n"                    // leaf descriptors are < -1
-        "s_and_b64 exec, %[s_all], vcc\n"
+        BRT_INT_LEAF_LANES                                      // leaf descriptors are < -1
         BRT_COUNT_LEAF
         "v_and_b32_e32 v112, 0x3fff, %[cur]\n"                  // the leaf's sphere
         "v_lshl_add_u32 %[t0], v112, 4, %[sph]\n"
@@ -1020,14 +1124,13 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "s_cbranch_scc1 9f\n"
         "s_max_u32 %[thr], %[nw], %[vote]\n"                    // interior steps while more than max(walking, vote) - vote lanes are at one
         "s_sub_u32 %[thr], %[thr], %[vote]\n"
-        "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n"                    // interior descriptors are >= 0
+        BRT_INT_TEST
         "s_bcnt1_i32_b64 %[cnt], vcc\n"
         "s_cmp_le_u32 %[cnt], %[thr]\n"
         "s_cbranch_scc1 5f\n"
-        // ---- interior steps ----------------------------------------------------------------------------------------------------
+        // ---- interior steps (BRT_INT_STEP, above) -------------------------------------------------------------------------------
         "1:\n"
-        "s_mov_b64 %[s_take], vcc\n"
-        "s_mov_b64 exec, vcc\n"
+        BRT_INT_HEAD
         BRT_COUNT_INT
         "ds_read_i16 %[pop], %[spa]\n"                          // the would-be pop: needs no address arithmetic, goes out first
         "v_mul_lo_u32 %[t0], %[cur], %[rec_bytes]\n"
@@ -1043,15 +1146,7 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "6:\n"
         // (counted waits that hold for every mix: the LDS queue is {pop, x, y, z, descriptors} or just {pop}, the vector-memory queue {x, y, z,
         //  descriptors} or empty -- a lane's x granule has arrived when at most 3 are outstanding in BOTH)
-        "s_waitcnt vmcnt(3) lgkmcnt(3)\n"
-        "v_sub_f32_e32 v100, v100, %[ox]\n v_sub_f32_e32 v101, v101, %[ox]\n v_sub_f32_e32 v102, v102, %[ox]\n v_sub_f32_e32 v103, v103, %[ox]\n"
-        "v_mul_f32_e32 v100, v100, %[ix]\n v_mul_f32_e32 v101, v101, %[ix]\n v_mul_f32_e32 v102, v102, %[ix]\n v_mul_f32_e32 v103, v103, %[ix]\n"
-        "s_waitcnt vmcnt(2) lgkmcnt(2)\n"
-        "v_sub_f32_e32 v104, v104, %[oy]\n v_sub_f32_e32 v105, v105, %[oy]\n v_sub_f32_e32 v106, v106, %[oy]\n v_sub_f32_e32 v107, v107, %[oy]\n"
-        "v_mul_f32_e32 v104, v104, %[iy]\n v_mul_f32_e32 v105, v105, %[iy]\n v_mul_f32_e32 v106, v106, %[iy]\n v_mul_f32_e32 v107, v107, %[iy]\n"
-        "s_waitcnt vmcnt(1) lgkmcnt(1)\n"
-        "v_sub_f32_e32 v108, v108, %[oz]\n v_sub_f32_e32 v109, v109, %[oz]\n v_sub_f32_e32 v110, v110, %[oz]\n v_sub_f32_e32 v111, v111, %[oz]\n"
-        "v_mul_f32_e32 v108, v108, %[iz]\n v_mul_f32_e32 v109, v109, %[iz]\n v_mul_f32_e32 v110, v110, %[iz]\n v_mul_f32_e32 v111, v111, %[iz]\n"
+        BRT_INT_SLABS("s_waitcnt vmcnt(3) lgkmcnt(3)\n", "s_waitcnt vmcnt(2) lgkmcnt(2)\n", "s_waitcnt vmcnt(1) lgkmcnt(1)\n")
         "v_max_f32_e32 v100, v100, v104\n"
         "v_max_f32_e32 v101, v101, v105\n"
         "v_min_f32_e32 v102, v102, v106\n"
@@ -1060,30 +1155,10 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "v_max3_f32 v101, v101, v109, 1\n"
         "v_min3_f32 v102, v102, v110, %[below]\n"               // t_far = min(.., below(closest))
         "v_min3_f32 v103, v103, v111, %[below]\n"
-        "s_waitcnt vmcnt(0) lgkmcnt(0)\n"                       // descriptors (and the pop, which went out first) are here
-        "ds_write_b16 %[spa], v112 offset:128\n"                // child L above the top: dead unless both are pushed
-        "v_cmp_le_f32_e32 vcc, v100, v102\n"                    // p1: child L is pushed (raytrace.wgsl:331)
-        "v_cmp_le_f32_e64 %[s_p2], v101, v103\n"                // p2: child R is pushed (raytrace.wgsl:338)
-        "s_or_b64 %[s_any], vcc, %[s_p2]\n"
-        "s_and_b64 %[s_both], vcc, %[s_p2]\n"
-        "s_andn2_b64 exec, %[s_take], %[s_any]\n"               // no child pushed: pop
-        "v_mov_b32_e32 %[cur], %[pop]\n"
-        "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"
-        "s_andn2_b64 exec, vcc, %[s_p2]\n"                      // only L
-        "v_mov_b32_e32 %[cur], v112\n"
-        "s_mov_b64 exec, %[s_p2]\n"                             // R (pushed last, popped first)
-        "v_mov_b32_e32 %[cur], v113\n"
-        "s_mov_b64 exec, %[s_both]\n"                           // both: L stays on the stack
-        "v_add_u32_e32 %[spa], 0x80, %[spa]\n"
-        "s_mov_b64 exec, %[s_all]\n"
-        "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n"
-        "s_bcnt1_i32_b64 %[cnt], vcc\n"
-        "s_cmp_gt_u32 %[cnt], %[thr]\n"
-        "s_cbranch_scc1 1b\n"
+        BRT_INT_DECIDE("s_waitcnt vmcnt(0) lgkmcnt(0)\n")
         // ---- one leaf step for every lane that waits at a leaf --------------------------------------------------------------
         "5:\n"
-        "v_cmp_gt_i32_e32 vcc, -1, %[cur]\n"                    // leaf descriptors are < -1
-        "s_and_b64 exec, %[s_all], vcc\n"
+        BRT_INT_LEAF_LANES                                      // leaf descriptors are < -1
         BRT_COUNT_LEAF
         "v_and_b32_e32 v112, 0x3fff, %[cur]\n"                  // the leaf's sphere
         "v_lshlrev_b32_e32 %[t0], 4, v112\n"
@@ -1121,6 +1196,7 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         BRT_LEAF_TAIL_SLOW
         // ---- out of line: an interior step with lanes on both sides (two EXEC masks, one destination) ---------------------------
         "8:\n"
+        BRT_INT_SAVE_TAKE
         "v_add_u32_e32 %[ty], %[t0], %[gofs_y]\n"
         "v_add_u32_e32 %[tz], %[t0], %[gofs_z]\n"
         "s_and_b64 exec, %[s_take], vcc\n"                      // the global loads go out first ...
