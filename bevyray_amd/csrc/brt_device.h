@@ -21,6 +21,12 @@ namespace brt {
 
 #define BRT_DEV __device__ __forceinline__
 
+// Four compile-time switches were retired at their shipped values once their measurements were done (docs/experiments.md).  A build that
+// still passes one would silently be the product, and an A/B against it would compare a library with itself.
+#if defined(BRT_INT_STEP) || defined(BRT_EXACT_FORMS) || defined(BRT_SHARED_RCP) || defined(BRT_WALK_FAST_TOP)
+#error "BRT_INT_STEP, BRT_EXACT_FORMS, BRT_SHARED_RCP and BRT_WALK_FAST_TOP are retired (fixed at 7, 6, 3 and 1); their arms build from commit 6041ad3"
+#endif
+
 // The hand-written loops (walk_wave_lds_asm, ball_loop_asm) name gfx950 registers and count its wait states and its lgkmcnt by
 // hand: a device pass for any other target (the Makefile's ARCH can be overridden) compiles them out and takes the
 // compiler-built loops (walk_loop_wave, the `while (need)` sampler of shade_landed) instead.
@@ -82,12 +88,9 @@ BRT_DEV float max_sel(float a, float b) { return a < b ? b : a; }
 // normalize() or the sphere tests of one ray share it.  Outside the plain range the callers use `/`.  Whether a
 // WAVE takes the short form is decided by ballot (all its active lanes plain), so there is one straight-line body
 // either way.  tests: BRT_DBG_DIV / BRT_DBG_DIV_SWEEP compare both forms bit for bit (2^-40 .. 2^40 x all mantissas).
-#ifndef BRT_SHARED_RCP
-#define BRT_SHARED_RCP 3   // bit 0: normalize(), bit 1: 1 / direction.  (A/B on one MI355X, headline frame: 13.33 ms without,
-                           // 13.18 with bit 0, 13.08 with both; the sphere test's `/ a` with a per-ray reciprocal did NOT pay --
-                           // its range guard and wave vote cost the leaf step what the shorter quotient saves: 13.16 ms.
-                           // That was the COMPILER's leaf step; in the hand-written one it pays: BRT_LEAF_TAIL)
-#endif
+// Used by normalize3 and by walk_begin's 1 / direction (A/B on one MI355X, headline frame: 13.33 ms without, 13.18 with the first,
+// 13.08 with both; in the COMPILER's leaf step a per-ray reciprocal for `/ a` did not pay, 13.16 ms; in the hand-written one it does:
+// BRT_LEAF_TAIL).  This was the switch BRT_SHARED_RCP, retired at 3; the arms build from commit 6041ad3.
 constexpr float kPlainLo = 0x1p-40f, kPlainHi = 0x1p40f;
 struct RcpRef { float d, r1; };
 BRT_DEV RcpRef rcp_refined(float d) {
@@ -147,15 +150,10 @@ BRT_DEV float sqrt_plain(float x) {
 // residual x - s s stay normal numbers, the denormal mode plays no part and the result is the correctly rounded root
 // (BRT_DBG_SQRT_SWEEP with a non-zero third input: every float of that range, bit for bit against __builtin_sqrtf).  NOT for 0
 // (rsq(0) = inf, 0 inf = NaN); a negative or NaN argument gives NaN, as sqrt does.
-// BRT_EXACT_FORMS selects where the form is used -- bit 0: the compiler-built shading (normalize3, sqrt3), bit 1: the sqrt of the
-// hand-written leaf step, bit 2: the leaf step's divide in the plain form with the reciprocal of `a` refined once per call
-// (BRT_LEAF_TAIL below).  A/B of the arms on one MI355X, headline frame, five alternated bench runs each (profiles/exact_forms/ab.txt,
-// medians): 8.926 ms without, 8.811 with bit 1, 8.811 with bit 2, 8.716 with both -- and 8.959 with bit 0 alone, 8.706 with all three,
-// which does not separate from bits 1 + 2: in the compiler-built shading the form does NOT pay (a measured negative; where its ten
-// cycles per call go was not taken apart), so bit 0 stays off.
-#ifndef BRT_EXACT_FORMS
-#define BRT_EXACT_FORMS 6
-#endif
+// The hand-written leaf step uses this form (BRT_LEAF_TAIL below, with the plain divide by `a`): headline frame 8.926 -> 8.716 ms.  In the
+// compiler-built shading (normalize3, sqrt3) it does NOT pay -- 8.959 ms alone, a measured negative -- so those keep sqrt_plain.  This was
+// the switch BRT_EXACT_FORMS, retired at 6: docs/experiments.md ("Short exact forms in the leaf step"), profiles/exact_forms/ab.txt; the arms build from
+// commit 6041ad3.  (The function itself serves BRT_DBG_SQRT_SWEEP.)
 BRT_DEV float sqrt_rsq(float x) {
     const float r = __builtin_amdgcn_rsqf(x);
     float s = x * r, h = 0.5f * r;
@@ -173,29 +171,17 @@ BRT_DEV f3 sqrt3(f3 c) {
     const float mx = max_f(max_f(ax, ay), az);
     const bool zero = mx == 0.0f;
     const bool plain = (min_f(min_f(ax, ay), az) >= 0x1p-80f && mx <= 0x1p80f) || zero;
-#if BRT_EXACT_FORMS & 1
-    // (a lane is plain with all three components in the range or all three zero -- absorbed paths, bounce-limit ends: the zeros,
-    //  which the rsq form does not survive, are their own roots and pass through on the compare the guard has already made)
-    if (wave_all(plain)) return mk3(zero ? c.x : sqrt_rsq(c.x), zero ? c.y : sqrt_rsq(c.y), zero ? c.z : sqrt_rsq(c.z));
-#else
     if (wave_all(plain)) return mk3(sqrt_plain(c.x), sqrt_plain(c.y), sqrt_plain(c.z));
-#endif
     return mk3(__builtin_sqrtf(c.x), __builtin_sqrtf(c.y), __builtin_sqrtf(c.z));
 }
 
 BRT_DEV f3 normalize3(f3 v) {
-#if BRT_SHARED_RCP & 1
     // components in [2^-40, 2^39]  =>  dot in [2^-80, 2^80) and len in [max |v_i|, 2 max |v_i|): both plain
     // (products and sums of positive terms are monotone, sqrt is monotone, the sum has 3 terms)
     if (wave_all(all_within(v, kPlainLo, 0x1p39f))) {
-#if BRT_EXACT_FORMS & 1
-        const RcpRef R = rcp_refined(sqrt_rsq(dot3(v, v)));
-#else
         const RcpRef R = rcp_refined(sqrt_plain(dot3(v, v)));
-#endif
         return mk3(div_plain(v.x, R), div_plain(v.y, R), div_plain(v.z, R));
     }
-#endif
     const float len = __builtin_sqrtf(dot3(v, v));
     return mk3(v.x / len, v.y / len, v.z / len);
 }
@@ -456,11 +442,8 @@ struct WalkState {
 template <bool D16, typename StackT>
 BRT_DEV void walk_begin(WalkState<StackT>& w, const ScenePtrs& sc, uint32_t root_desc, StackT* stk, f3 d) {
     w.a = dot3(d, d);
-#if BRT_SHARED_RCP & 2
     if (wave_all(all_within(d, kPlainLo, kPlainHi))) w.inv = mk3(recip_plain(d.x), recip_plain(d.y), recip_plain(d.z));
-    else
-#endif
-        w.inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    else w.inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     // (under the compare-select policy the walk applies min / max itself, to {t_min, t_max} in the shader's operand order: granule G0)
     w.ox = PAIR_X + ((w.inv.x < 0.0f && !sc.minmax_select) ? 16u : 0u);
     w.oy = PAIR_Y + ((w.inv.y < 0.0f && !sc.minmax_select) ? 16u : 0u);
@@ -653,14 +636,14 @@ BRT_DEV void walk_loop_wave(const ScenePtrs& sc, f3 o, f3 d, float a, f3 inv, ui
 // v_lshl_add that move the results into `cur` and the stack pointer, 14 on the record address, 8 on two compares for the
 // loop control and ~27 on four branch instructions (one taken): ~160.  Here the selects become v_mov / v_add_u32 under
 // EXEC masks built on the scalar unit (11 cycles instead of 24), the loop has ONE branch per iteration (the taken
-// back edge) and one compare: ~134.  Same per-lane steps in the same order as walk_loop_wave: pixels and counters do
+// back edge) and one compare: ~134.  (That was the step as first written; it has since been re-priced in instructions and the moves under
+// masks are selects again: BRT_WIDE_INT_STEP below.)  Same per-lane steps in the same order as walk_loop_wave: pixels and counters do
 // not change.  (Only for SIMPLE trees, without COUNTERS, for waves without unsafe rays; everything else takes walk_loop_wave.)
 #ifndef BRT_WALK_FAST
 #define BRT_WALK_FAST BRT_HAND_ASM
 #endif
-#ifndef BRT_WALK_FAST_TOP
-#define BRT_WALK_FAST_TOP 1   // the hand-written loop also for scenes walked from the LDS tile + global memory (walk_wave_top_asm)
-#endif
+// (BRT_WALK_FAST covers both wide loops: scenes walked from the LDS tile + global memory take walk_wave_top_asm.  Its own switch,
+//  BRT_WALK_FAST_TOP, was retired at 1 -- profiles/r04/ab_walk_top.txt: config 5 16.7 -> 14.8 ms; the other arm builds from commit 6041ad3.)
 // The whole wave-level walk loop (walk_loop_wave's nest: interior steps until `vote` lanes wait at a leaf, one leaf step,
 // until at most exit_at lanes still walk) as ONE block of hand-scheduled code.
 //   cur / spa     descriptor of the lane's current node (sign-extended 16-bit form: interior >= 0, leaf < -1, DONE = -1) and
@@ -681,9 +664,10 @@ BRT_DEV void walk_loop_wave(const ScenePtrs& sc, f3 o, f3 d, float a, f3 inv, ui
 // pre-scale below 2^-96, v_sqrt_f32 + two residual corrections, class fix-up; v_div_scale x2, v_rcp_f32 + one Newton step, three fma
 // steps, v_div_fmas, v_div_fixup), in an order in which every wait state its hazard recogniser fills with s_nop (VALU -> vcc / SGPR ->
 // v_cndmask: 2, v_sqrt / v_rcp -> use: 1) holds an instruction that is needed anyway; FILL is the one such slot an unrelated
-// instruction can take (the pop's pointer move).  A negative discriminant gives NaN, rejected by the accept rule like the shader's -1.
+// instruction can take (both users have none: s_nop 0); A names the operand that holds `a`.  A negative discriminant gives NaN, rejected
+// by the accept rule like the shader's -1.
 // By the price list above the two blocks are ~60 + ~36 of the step's ~162 cycles, most of it scaffolding for arguments a sphere test
-// practically never has.  BRT_EXACT_FORMS (bits 1, 2) replaces them, for a wave whose lanes are all in range, by
+// practically never has.  BRT_LEAF_TAIL replaces them, for a wave whose lanes are all in range, by
 //   sqrt    sqrt_rsq (8 instructions, 22 cycles), for discriminants in [2^-80, 2^80] -- and for negative or NaN ones, which give NaN
 //           in either form;
 //   divide  div_plain with the refined reciprocal of `a` made ONCE PER CALL (rcp_refined depends on the ray alone): 5 instructions,
@@ -696,6 +680,9 @@ BRT_DEV void walk_loop_wave(const ScenePtrs& sc, f3 o, f3 d, float a, f3 inv, ui
 // The guard is three compares (|disc| < 2^-80 also catches +-0, whose rsq is inf; a NaN passes every test and stays a NaN) and ONE
 // scalar branch, untaken unless some active lane fails: then the whole wave runs the full forms out of line, from the preserved
 // discriminant and h, and rejoins at the accept rule -- for the lanes that were in range the two forms give the same bits.
+// Measured (headline frame, five alternated bench runs per arm): 8.926 ms with the full forms in line, 8.811 with either short form alone,
+// 8.716 with both -- docs/experiments.md ("Short exact forms in the leaf step"), profiles/exact_forms/.  This was bits 1 and 2 of the switch
+// BRT_EXACT_FORMS, retired at 6; the three other tails build from commit 6041ad3.
 constexpr float kLeafALo = 0x1p-29f;
 #define BRT_LEAF_SQRT_FULL(FILL)                                                                                                       \
         "v_cmp_gt_f32_e32 vcc, %[c_tiny], v104\n"               /* below 2^-96: scale by 2^32 (vcc stays until the result is scaled back) */ \
@@ -716,10 +703,10 @@ constexpr float kLeafALo = 0x1p-29f;
         "v_mul_f32_e32 v106, 0x37800000, v105\n"                                                                                       \
         "v_cndmask_b32_e32 v105, v105, v106, vcc\n"                                                                                    \
         "v_cndmask_b32_e64 v104, v105, v104, %[s_both]\n"       /* sqrt(discriminant) */
-#define BRT_LEAF_DIV_FULL                                                                                                              \
-        "v_div_scale_f32 v105, %[s_p2], %[a], %[a], v104\n"     /* v104 = n -> v104 = n / a */                                         \
+#define BRT_LEAF_DIV_FULL(A)                                                                                                           \
+        "v_div_scale_f32 v105, %[s_p2], " A ", " A ", v104\n"   /* v104 = n -> v104 = n / a */                                         \
         "v_rcp_f32_e32 v106, v105\n"                                                                                                   \
-        "v_div_scale_f32 v107, vcc, v104, %[a], v104\n"                                                                                \
+        "v_div_scale_f32 v107, vcc, v104, " A ", v104\n"                                                                               \
         "v_fma_f32 v109, -v105, v106, 1.0\n"                                                                                           \
         "v_fmac_f32_e32 v106, v109, v106\n"                                                                                            \
         "v_mul_f32_e32 v108, v107, v106\n"                                                                                             \
@@ -727,7 +714,7 @@ constexpr float kLeafALo = 0x1p-29f;
         "v_fmac_f32_e32 v108, v109, v106\n"                                                                                            \
         "v_fma_f32 v105, -v105, v108, v107\n"                                                                                          \
         "v_div_fmas_f32 v105, v105, v106, v108\n"                                                                                      \
-        "v_div_fixup_f32 v104, v105, %[a], v104\n"              /* t */
+        "v_div_fixup_f32 v104, v105, " A ", v104\n"             /* t */
 #define BRT_LEAF_POP_MOVE "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"   /* (the pop's pointer move) */
 // sqrt_rsq of v104 into v106 (v104 stays); GUARDS go into the wait state between v_rsq_f32 and its first use
 #define BRT_LEAF_SQRT_RSQ(GUARDS)                                                                                                      \
@@ -750,13 +737,25 @@ constexpr float kLeafALo = 0x1p-29f;
         "s_nop 0\n"                                                                                                                    \
         "v_fma_f32 %[t0], -%[a], %[r1], 1.0\n"                                                                                         \
         "v_fmac_f32_e32 %[r1], %[t0], %[r1]\n"
+// the wide loops' own counts of the diagnostic build: interior steps, leaf steps, the lanes of each (EXEC), leaf steps through the full forms
 #if BRT_ASM_COUNT
-#define BRT_COUNT_LEAF_SLOW "s_add_u32 %[c_ls], %[c_ls], 1\n"
+#define BRT_WIDE_COUNT_LOCALS uint32_t c_ie, c_il, c_le, c_ll, c_ls, c_tmp;
+#define BRT_WIDE_COUNT_INIT "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n s_mov_b32 %[c_ls], 0\n"
+#define BRT_WIDE_COUNT_INT "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_il], %[c_il], %[c_tmp]\n s_add_u32 %[c_ie], %[c_ie], 1\n"
+#define BRT_WIDE_COUNT_LEAF "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_ll], %[c_ll], %[c_tmp]\n s_add_u32 %[c_le], %[c_le], 1\n"
+#define BRT_WIDE_COUNT_LEAF_SLOW "s_add_u32 %[c_ls], %[c_ls], 1\n"
+#define BRT_WIDE_COUNT_OUTPUTS , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_ls] "=&s"(c_ls), [c_tmp] "=&s"(c_tmp)
+#define BRT_WIDE_COUNT_BOOK                                                                                                            \
+    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; ac->leaf_slow += c_ls; }
 #else
-#define BRT_COUNT_LEAF_SLOW
+#define BRT_WIDE_COUNT_LOCALS
+#define BRT_WIDE_COUNT_INIT
+#define BRT_WIDE_COUNT_INT
+#define BRT_WIDE_COUNT_LEAF
+#define BRT_WIDE_COUNT_LEAF_SLOW
+#define BRT_WIDE_COUNT_OUTPUTS
+#define BRT_WIDE_COUNT_BOOK
 #endif
-#if (BRT_EXACT_FORMS & 6) == 6
-#define BRT_LEAF_ENTRY BRT_LEAF_RCP_A
 #define BRT_LEAF_TAIL                                                                                                                  \
         BRT_LEAF_SQRT_RSQ(BRT_LEAF_GUARD_DISC)                                                                                         \
         "v_sub_f32_e32 v105, v107, v106\n"                      /* n = h - sqrt(discriminant) */                                       \
@@ -772,231 +771,153 @@ constexpr float kLeafALo = 0x1p-29f;
         "21:\n"
 #define BRT_LEAF_TAIL_SLOW                                                                                                             \
         "20:\n"                                                                                                                        \
-        BRT_COUNT_LEAF_SLOW                                                                                                            \
+        BRT_WIDE_COUNT_LEAF_SLOW                                                                                                       \
         BRT_LEAF_SQRT_FULL("s_nop 0\n")                                                                                                \
         "v_sub_f32_e32 v104, v107, v104\n"                                                                                             \
-        BRT_LEAF_DIV_FULL                                                                                                              \
+        BRT_LEAF_DIV_FULL("%[a]")                                                                                                      \
         "s_branch 21b\n"
-#elif BRT_EXACT_FORMS & 2
-#define BRT_LEAF_ENTRY
-#define BRT_LEAF_TAIL                                                                                                                  \
-        BRT_LEAF_SQRT_RSQ(BRT_LEAF_GUARD_DISC)                                                                                         \
-        "s_or_b64 %[s_p2], %[s_p2], %[s_any]\n"                                                                                        \
-        "s_cbranch_scc1 20f\n"                                                                                                         \
-        "v_mov_b32_e32 v104, v106\n"                                                                                                   \
-        "21:\n"                                                                                                                        \
-        "v_sub_f32_e32 v104, v107, v104\n"                      /* h - sqrt(discriminant) */                                           \
-        BRT_LEAF_DIV_FULL
-#define BRT_LEAF_TAIL_SLOW                                                                                                             \
-        "20:\n"                                                                                                                        \
-        BRT_COUNT_LEAF_SLOW                                                                                                            \
-        BRT_LEAF_SQRT_FULL("s_nop 0\n")                                                                                                \
-        "s_branch 21b\n"
-#elif BRT_EXACT_FORMS & 4
-#define BRT_LEAF_ENTRY BRT_LEAF_RCP_A
-#define BRT_LEAF_TAIL                                                                                                                  \
-        BRT_LEAF_SQRT_FULL(BRT_LEAF_POP_MOVE)                                                                                          \
-        "v_sub_f32_e32 v104, v107, v104\n"                      /* n = h - sqrt(discriminant) */                                       \
-        "v_cmp_lt_f32_e64 %[s_both], %[c_hi], |v104|\n"         /* |n| > 2^40 */                                                       \
-        "v_mul_f32_e32 v106, v104, %[r1]\n"                                                                                            \
-        "v_fma_f32 v108, -%[a], v106, v104\n"                                                                                          \
-        "s_and_b64 %[s_both], %[s_both], exec\n"                                                                                       \
-        "s_cbranch_scc1 20f\n"                                                                                                         \
-        "v_fmac_f32_e32 v106, v108, %[r1]\n"                                                                                           \
-        "v_fma_f32 v108, -%[a], v106, v104\n"                                                                                          \
-        "v_fma_f32 v104, v108, %[r1], v106\n"                                                                                          \
-        "21:\n"
-#define BRT_LEAF_TAIL_SLOW                                                                                                             \
-        "20:\n"                                                                                                                        \
-        BRT_COUNT_LEAF_SLOW                                                                                                            \
-        BRT_LEAF_DIV_FULL                                                                                                              \
-        "s_branch 21b\n"
-#else
-#define BRT_LEAF_ENTRY
-#define BRT_LEAF_TAIL                                                                                                                  \
-        BRT_LEAF_SQRT_FULL(BRT_LEAF_POP_MOVE)                                                                                          \
-        "v_sub_f32_e32 v104, v107, v104\n"                      /* h - sqrt(discriminant) */                                           \
-        BRT_LEAF_DIV_FULL
-#define BRT_LEAF_TAIL_SLOW
-#endif
-// The interior step of the two wide loops below, in the parts that only move masks, addresses and waits.  A wave issues one instruction per
-// ~5.3 cycles whatever the instruction is (tests/tools/issue_bench.hip), so beside the vector-pipe cycles the step is priced in instructions:
-// 66 as first written (44 vector, 6 LDS, 16 scalar).  BRT_INT_STEP selects cheaper forms of the scalar part; per lane nothing changes -- the
-// same sub / mul / min / max on the same operands in the same order, the same push rule, the same stack contents:
-//   bit 0: the test for interior lanes writes EXEC itself (v_cmpx; at the loop head, at the back edge and for the leaf lanes): no copy of
-//          the mask at the head, and with bits 1 and 2 no restore at the back edge
-//   bit 1: the next node by two selects, cur = p2 ? R : (p1 ? L : pop), instead of three moves under three EXEC masks
-//   bit 2: the stack pointer by arithmetic, spa += ((p1 + p2) - 1) * 128 (a select, an add with carry-in, a shift-add), instead of two adds
-//          under two EXEC masks; with bit 1 the decision writes EXEC nowhere
-//   bit 3: three counted waits (x and y | z | descriptors and pop) instead of four;  bit 4: two (x, y and z | descriptors and pop)
-// (gfx950 wait states: a VALU write of an SGPR or VCC needs two instructions before a VALU reads it as a mask -- the ds_write between the
-//  compares and the selects is one of them.)  Shipped: 7, a step of 57 instructions (44 vector, 6 LDS, 7 scalar).  Headline frame, five
-// alternated bench runs per arm, medians of two sessions (parent 8.747 resp. 8.722 ms): bit 0 8.657, bit 1 8.639, bits 0 + 1 8.573, all
-// three 8.546 in the first; bit 2 alone 8.746, bits 0 + 2 8.666, all three 8.523 in the second.  Fewer waits are SLOWER: bit 3 alone 8.790,
-// bit 4 alone 8.884 in the second session, 8.624 / 8.700 on top of 7 in the first.
-// tests/tools/int_step_bench.hip times the forms in isolation; docs/experiments.md ("Interior step in the instruction currency") and
-// profiles/interior_step/ have every arm.
-#ifndef BRT_INT_STEP
-#define BRT_INT_STEP 7
-#endif
-#if BRT_INT_STEP & 1
-#define BRT_INT_TEST "v_cmpx_lt_i32_e32 vcc, -1, %[cur]\n"       /* interior descriptors are >= 0; EXEC = VCC = the lanes at one */
-#define BRT_INT_HEAD
-#define BRT_INT_TAKE "exec"
-#define BRT_INT_SAVE_TAKE "s_mov_b64 %[s_take], exec\n"          /* (walk_wave_top_asm's out-of-line step narrows EXEC twice) */
-#define BRT_INT_LEAF_LANES                                       /* (the interior steps leave EXEC narrowed) */                        \
-        "s_mov_b64 exec, %[s_all]\n"                                                                                                   \
-        "v_cmpx_gt_i32_e32 vcc, -1, %[cur]\n"
-#else
-#define BRT_INT_TEST "v_cmp_lt_i32_e32 vcc, -1, %[cur]\n"        /* interior descriptors are >= 0 */
-#define BRT_INT_HEAD                                                                                                                   \
-        "s_mov_b64 %[s_take], vcc\n"                                                                                                   \
-        "s_mov_b64 exec, vcc\n"
-#define BRT_INT_TAKE "%[s_take]"
-#define BRT_INT_LEAF_LANES                                                                                                             \
-        "v_cmp_gt_i32_e32 vcc, -1, %[cur]\n"                                                                                           \
-        "s_and_b64 exec, %[s_all], vcc\n"
-#define BRT_INT_SAVE_TAKE
-#endif
-// (with bit 0 the step may leave EXEC at the lanes that took it: the lanes at an interior node afterwards are among them, and the leaf step
-//  and the exit set EXEC from s_all)
-#if (BRT_INT_STEP & 7) == 7
-#define BRT_INT_RESTORE
-#else
-#define BRT_INT_RESTORE "s_mov_b64 exec, %[s_all]\n"
-#endif
-#define BRT_INT_X                                                                                                                      \
+
+// ---- the two wide loops (walk_wave_lds_asm, walk_wave_top_asm below) are ONE text: the pieces here, each written once ---------------
+// A loop differs from the other only in where a record and a sphere come from -- how the four loads of an interior step are issued, how the
+// sphere is fetched and waited for, the waits' counters and the inputs that name the memory; that is what the function bodies hold.
+//
+// The interior step.  A wave issues one instruction per ~5.3 cycles whatever the instruction is (tests/tools/issue_bench.hip), so beside the
+// vector-pipe cycles the step is priced in instructions: 57 (44 vector, 6 LDS, 7 scalar) -- the record's loads, 24 sub / mul and 8 min / max
+// of the slab test behind four counted waits, and a decision of 12 that writes EXEC nowhere but in the test at its end:
+//   the test for interior lanes writes EXEC itself (v_cmpx, here and at the loop's entry): the step leaves EXEC at the lanes that took it --
+//     the lanes at an interior node afterwards are among them --, and the leaf step and the exit set EXEC from s_all;
+//   the next node by two selects, cur = p2 ? R : (p1 ? L : pop);
+//   the stack pointer by arithmetic, spa += ((p1 + p2) - 1) * 128 (a select, an add with carry-in, a shift-add).
+// Per lane this is walk_interior_step: the same sub / mul / min / max on the same operands in the same order, the same push rule, the same
+// stack contents.  (gfx950 wait states: a VALU write of an SGPR or VCC needs two instructions before a VALU reads it as a mask -- the
+// ds_write between the compares and the selects is one of them.)
+// Measured: as first written the step was 66 instructions (moves and adds under EXEC masks built on the scalar unit, 16 scalar); headline
+// frame 8.747 resp. 8.722 ms with that step, 8.546 resp. 8.523 with this one, every combination of the three changes in between; fewer
+// counted waits (three or two instead of four) are SLOWER, 8.624 / 8.700 ms.  docs/experiments.md ("Interior step in the instruction
+// currency") and profiles/interior_step/ have every arm; they were the switch BRT_INT_STEP, retired at 7, and build from commit 6041ad3.
+// tests/tools/int_step_bench.hip times this text in isolation.
+// W3 / W2 / W1 / W0 wait until at most 3 / 2 / 1 / 0 of { pop, x, y, z, descriptors } are outstanding: x | y | z | descriptors and the pop,
+// which went out first.
+#define BRT_WIDE_INT_STEP(W3, W2, W1, W0)                                                                                              \
+        W3                                                                                                                             \
         "v_sub_f32_e32 v100, v100, %[ox]\n v_sub_f32_e32 v101, v101, %[ox]\n v_sub_f32_e32 v102, v102, %[ox]\n v_sub_f32_e32 v103, v103, %[ox]\n" \
-        "v_mul_f32_e32 v100, v100, %[ix]\n v_mul_f32_e32 v101, v101, %[ix]\n v_mul_f32_e32 v102, v102, %[ix]\n v_mul_f32_e32 v103, v103, %[ix]\n"
-#define BRT_INT_Y                                                                                                                      \
+        "v_mul_f32_e32 v100, v100, %[ix]\n v_mul_f32_e32 v101, v101, %[ix]\n v_mul_f32_e32 v102, v102, %[ix]\n v_mul_f32_e32 v103, v103, %[ix]\n" \
+        W2                                                                                                                             \
         "v_sub_f32_e32 v104, v104, %[oy]\n v_sub_f32_e32 v105, v105, %[oy]\n v_sub_f32_e32 v106, v106, %[oy]\n v_sub_f32_e32 v107, v107, %[oy]\n" \
-        "v_mul_f32_e32 v104, v104, %[iy]\n v_mul_f32_e32 v105, v105, %[iy]\n v_mul_f32_e32 v106, v106, %[iy]\n v_mul_f32_e32 v107, v107, %[iy]\n"
-#define BRT_INT_Z                                                                                                                      \
+        "v_mul_f32_e32 v104, v104, %[iy]\n v_mul_f32_e32 v105, v105, %[iy]\n v_mul_f32_e32 v106, v106, %[iy]\n v_mul_f32_e32 v107, v107, %[iy]\n" \
+        W1                                                                                                                             \
         "v_sub_f32_e32 v108, v108, %[oz]\n v_sub_f32_e32 v109, v109, %[oz]\n v_sub_f32_e32 v110, v110, %[oz]\n v_sub_f32_e32 v111, v111, %[oz]\n" \
-        "v_mul_f32_e32 v108, v108, %[iz]\n v_mul_f32_e32 v109, v109, %[iz]\n v_mul_f32_e32 v110, v110, %[iz]\n v_mul_f32_e32 v111, v111, %[iz]\n"
-// the slab arithmetic behind its waits: W3 / W2 / W1 / W0 wait until at most 3 / 2 / 1 / 0 of { pop, x, y, z, descriptors } are outstanding
-#if BRT_INT_STEP & 16
-#define BRT_INT_SLABS(W3, W2, W1) W1 BRT_INT_X BRT_INT_Y BRT_INT_Z
-#elif BRT_INT_STEP & 8
-#define BRT_INT_SLABS(W3, W2, W1) W2 BRT_INT_X BRT_INT_Y W1 BRT_INT_Z
-#else
-#define BRT_INT_SLABS(W3, W2, W1) W3 BRT_INT_X W2 BRT_INT_Y W1 BRT_INT_Z
-#endif
-#if BRT_INT_STEP & 2
-#define BRT_INT_CUR_SEL                                                                                                                \
-        "v_cndmask_b32_e32 %[cur], %[pop], v112, vcc\n"         /* L if it is pushed, else the pop */                                  \
-        "v_cndmask_b32_e64 %[cur], %[cur], v113, %[s_p2]\n"     /* R if it is pushed (pushed last, popped first) */
-#define BRT_INT_CUR_POP
-#define BRT_INT_CUR_LR
-#else
-#define BRT_INT_CUR_SEL
-#define BRT_INT_CUR_POP "v_mov_b32_e32 %[cur], %[pop]\n"
-#define BRT_INT_CUR_LR                                                                                                                 \
-        "s_andn2_b64 exec, vcc, %[s_p2]\n"                      /* only L */                                                           \
-        "v_mov_b32_e32 %[cur], v112\n"                                                                                                 \
-        "s_mov_b64 exec, %[s_p2]\n"                             /* R (pushed last, popped first) */                                    \
-        "v_mov_b32_e32 %[cur], v113\n"
-#endif
-#if BRT_INT_STEP & 4
-#define BRT_INT_SPA_MASKS
-#define BRT_INT_SPA_SEL                                                                                                                \
-        "v_cndmask_b32_e64 %[t0], -1, 0, %[s_p2]\n"             /* p2 - 1 */                                                           \
-        "v_addc_co_u32_e64 %[t0], %[s_both], 0, %[t0], vcc\n"   /* + p1: -1 pops, 0 stays, +1 leaves L on the stack (carry out unused) */ \
-        "v_lshl_add_u32 %[spa], %[t0], 7, %[spa]\n"
-#define BRT_INT_SPA_POP
-#define BRT_INT_SPA_BOTH
-#else
-#define BRT_INT_SPA_MASKS                                                                                                              \
-        "s_or_b64 %[s_any], vcc, %[s_p2]\n"                                                                                            \
-        "s_and_b64 %[s_both], vcc, %[s_p2]\n"
-#define BRT_INT_SPA_SEL
-#define BRT_INT_SPA_POP "v_add_u32_e32 %[spa], 0xffffff80, %[spa]\n"
-#define BRT_INT_SPA_BOTH                                                                                                               \
-        "s_mov_b64 exec, %[s_both]\n"                           /* both: L stays on the stack */                                       \
-        "v_add_u32_e32 %[spa], 0x80, %[spa]\n"
-#endif
-#if (BRT_INT_STEP & 6) == 6
-#define BRT_INT_NONE
-#else
-#define BRT_INT_NONE "s_andn2_b64 exec, " BRT_INT_TAKE ", %[s_any]\n"   /* no child pushed: pop */
-#endif
-#if (BRT_INT_STEP & 6) == 4
-#undef BRT_INT_SPA_MASKS
-#define BRT_INT_SPA_MASKS "s_or_b64 %[s_any], vcc, %[s_p2]\n"
-#endif
-#define BRT_INT_PUSH "ds_write_b16 %[spa], v112 offset:128\n"    /* child L above the top: dead unless both are pushed */
-#if BRT_INT_STEP & 6
-#define BRT_INT_PUSH_EARLY
-#define BRT_INT_PUSH_LATE BRT_INT_PUSH                           /* (one of the two instructions between the compares and the selects) */
-#else
-#define BRT_INT_PUSH_EARLY BRT_INT_PUSH
-#define BRT_INT_PUSH_LATE
-#endif
-// the decision (W0: descriptors and the pop, which went out first, are here) and the back edge
-#define BRT_INT_DECIDE(W0)                                                                                                            \
+        "v_mul_f32_e32 v108, v108, %[iz]\n v_mul_f32_e32 v109, v109, %[iz]\n v_mul_f32_e32 v110, v110, %[iz]\n v_mul_f32_e32 v111, v111, %[iz]\n" \
+        "v_max_f32_e32 v100, v100, v104\n"                                                                                             \
+        "v_max_f32_e32 v101, v101, v105\n"                                                                                             \
+        "v_min_f32_e32 v102, v102, v106\n"                                                                                             \
+        "v_min_f32_e32 v103, v103, v107\n"                                                                                             \
+        "v_max3_f32 v100, v100, v108, 1\n"                      /* t_near = max(.., denorm_min) */                                     \
+        "v_max3_f32 v101, v101, v109, 1\n"                                                                                             \
+        "v_min3_f32 v102, v102, v110, %[below]\n"               /* t_far = min(.., below(closest)) */                                  \
+        "v_min3_f32 v103, v103, v111, %[below]\n"                                                                                      \
         W0                                                                                                                             \
-        BRT_INT_PUSH_EARLY                                                                                                             \
         "v_cmp_le_f32_e32 vcc, v100, v102\n"                    /* p1: child L is pushed (raytrace.wgsl:331) */                        \
         "v_cmp_le_f32_e64 %[s_p2], v101, v103\n"                /* p2: child R is pushed (raytrace.wgsl:338) */                        \
-        BRT_INT_PUSH_LATE                                                                                                              \
-        BRT_INT_SPA_MASKS                                                                                                              \
-        BRT_INT_CUR_SEL                                                                                                                \
-        BRT_INT_SPA_SEL                                                                                                                \
-        BRT_INT_NONE                                                                                                                   \
-        BRT_INT_CUR_POP                                                                                                                \
-        BRT_INT_SPA_POP                                                                                                                \
-        BRT_INT_CUR_LR                                                                                                                 \
-        BRT_INT_SPA_BOTH                                                                                                               \
-        BRT_INT_RESTORE                                                                                                                \
-        BRT_INT_TEST                                                                                                                   \
+        "ds_write_b16 %[spa], v112 offset:128\n"                /* child L above the top: dead unless both are pushed */               \
+        "v_cndmask_b32_e32 %[cur], %[pop], v112, vcc\n"         /* L if it is pushed, else the pop */                                  \
+        "v_cndmask_b32_e64 %[cur], %[cur], v113, %[s_p2]\n"     /* R if it is pushed (pushed last, popped first) */                    \
+        "v_cndmask_b32_e64 %[t0], -1, 0, %[s_p2]\n"             /* p2 - 1 */                                                           \
+        "v_addc_co_u32_e64 %[t0], %[s_both], 0, %[t0], vcc\n"   /* + p1: -1 pops, 0 stays, +1 leaves L on the stack (carry out unused) */ \
+        "v_lshl_add_u32 %[spa], %[t0], 7, %[spa]\n"                                                                                    \
+        "v_cmpx_lt_i32_e32 vcc, -1, %[cur]\n"                   /* interior descriptors are >= 0; EXEC = VCC = the lanes at one */     \
         "s_bcnt1_i32_b64 %[cnt], vcc\n"                                                                                                \
         "s_cmp_gt_u32 %[cnt], %[thr]\n"                                                                                                \
         "s_cbranch_scc1 1b\n"
+// the locals of a loop's function ...
+#define BRT_WIDE_LOCALS                                                                                                                \
+    uint32_t t0, tx, ty, tz, pop, cnt, nw, thr;                                                                                        \
+    float below, r1;                                            /* r1: rcp_refined(a).r1 */                                            \
+    uint64_t s_all, s_take, s_p2, s_any, s_both;                                                                                       \
+    const uint32_t rec_bytes = PAIR_BYTES, c_tiny = 0x0f800000u /* 2^-96 */, c_eps = 0x3a83126fu /* 0.001f */, c_cls = 0x260u /* +-0, +inf */; \
+    const uint32_t c_lo2 = 0x17800000u /* 2^-80 */, c_hi2 = 0x67800000u /* 2^80 */, c_hi = 0x53800000u /* 2^40 */;                     \
+    BRT_WIDE_COUNT_LOCALS
+// ... and its operand lists; MORE: the inputs that name the loop's memory, in their place among the scalar inputs.  (s_take is only used by
+// walk_wave_top_asm's out-of-line step; the other loop carries it so that the list is one.)
+#define BRT_WIDE_OUTPUTS                                                                                                               \
+          [cur] "+v"(cur), [spa] "+v"(spa), [closest] "+v"(closest), [cidx] "+v"(closest_idx), [below] "=&v"(below), [t0] "=&v"(t0),   \
+          [tx] "=&v"(tx), [ty] "=&v"(ty), [tz] "=&v"(tz), [pop] "=&v"(pop), [cnt] "=&s"(cnt), [nw] "=&s"(nw), [thr] "=&s"(thr),        \
+          [s_all] "=&s"(s_all), [s_take] "=&s"(s_take), [s_p2] "=&s"(s_p2), [s_any] "=&s"(s_any), [s_both] "=&s"(s_both)               \
+          BRT_WIDE_COUNT_OUTPUTS, [r1] "=&v"(r1)
+#define BRT_WIDE_INPUTS(...)                                                                                                           \
+          [gofs_x] "v"(gofs_x), [gofs_y] "v"(gofs_y), [gofs_z] "v"(gofs_z), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(inv.x), \
+          [iy] "v"(inv.y), [iz] "v"(inv.z), [dx] "v"(d.x), [dy] "v"(d.y), [dz] "v"(d.z), [a] "v"(a), __VA_ARGS__, [exit_at] "s"(exit_at), \
+          [vote] "s"(vote), [rec_bytes] "s"(rec_bytes), [c_tiny] "s"(c_tiny), [c_eps] "s"(c_eps), [c_cls] "s"(c_cls),                  \
+          [c_lo2] "s"(c_lo2), [c_hi2] "s"(c_hi2), [c_hi] "s"(c_hi)
+#define BRT_WIDE_CLOBBERS                                                                                                              \
+          "vcc", "scc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113"
+#define BRT_WIDE_PROLOGUE                                                                                                              \
+        BRT_WIDE_COUNT_INIT                                                                                                            \
+        "s_waitcnt lgkmcnt(0)\n"                                /* nothing of the compiler's in flight: the counted waits below are exact */ \
+        "s_mov_b64 %[s_all], exec\n"                                                                                                   \
+        "v_add_u32_e32 %[below], -1, %[closest]\n"              /* the largest float below closest (closest is FLT_MAX or an accepted t > 0) */ \
+        BRT_LEAF_RCP_A
+// the outer loop's head, label 3: leave (to 9) when at most exit_at lanes still walk, go to the leaf step (5) or fall into the interior steps
+#define BRT_WIDE_OUTER_HEAD                                                                                                            \
+        "3:\n"                                                                                                                         \
+        "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n"                                                                                           \
+        "s_bcnt1_i32_b64 %[nw], vcc\n"                                                                                                 \
+        "s_cmp_le_u32 %[nw], %[exit_at]\n"                                                                                             \
+        "s_cbranch_scc1 9f\n"                                                                                                          \
+        "s_max_u32 %[thr], %[nw], %[vote]\n"                    /* interior steps while more than max(walking, vote) - vote lanes are at one */ \
+        "s_sub_u32 %[thr], %[thr], %[vote]\n"                                                                                          \
+        "v_cmpx_lt_i32_e32 vcc, -1, %[cur]\n"                   /* interior descriptors are >= 0; EXEC = VCC = the lanes at one */     \
+        "s_bcnt1_i32_b64 %[cnt], vcc\n"                                                                                                \
+        "s_cmp_le_u32 %[cnt], %[thr]\n"                                                                                                \
+        "s_cbranch_scc1 5f\n"
+// one leaf step for every lane that waits at a leaf, label 5: its lanes and their sphere's index ...
+#define BRT_WIDE_LEAF_HEAD                                                                                                             \
+        "5:\n"                                                                                                                         \
+        "s_mov_b64 exec, %[s_all]\n"                            /* (the interior steps leave EXEC narrowed) */                         \
+        "v_cmpx_gt_i32_e32 vcc, -1, %[cur]\n"                   /* leaf descriptors are < -1 */                                        \
+        BRT_WIDE_COUNT_LEAF                                                                                                            \
+        "v_and_b32_e32 v112, 0x3fff, %[cur]\n"                  /* the leaf's sphere */
+// ... and, with the sphere { centre, r^2 } in v[100:103] and the pop under way, its test, the accept rule and the way back to 3
+#define BRT_WIDE_LEAF_TEST                                                                                                             \
+        "v_sub_f32_e32 v104, v100, %[ox]\n"                     /* oc = centre - origin */                                             \
+        "v_sub_f32_e32 v105, v101, %[oy]\n"                                                                                            \
+        "v_sub_f32_e32 v106, v102, %[oz]\n"                                                                                            \
+        "v_mul_f32_e32 v107, %[dx], v104\n"                     /* h = dot(d, oc) = (dx ocx + dy ocy) + dz ocz */                      \
+        "v_mul_f32_e32 v108, %[dy], v105\n"                                                                                            \
+        "v_mul_f32_e32 v104, v104, v104\n"                      /* dot(oc, oc) */                                                      \
+        "v_mul_f32_e32 v105, v105, v105\n"                                                                                             \
+        "v_add_f32_e32 v104, v104, v105\n"                                                                                             \
+        "v_mul_f32_e32 v105, v106, v106\n"                                                                                             \
+        "v_mul_f32_e32 v109, %[dz], v106\n"                                                                                            \
+        "v_add_f32_e32 v107, v107, v108\n"                                                                                             \
+        "v_add_f32_e32 v104, v105, v104\n"                                                                                             \
+        "v_add_f32_e32 v107, v109, v107\n"                      /* h */                                                                \
+        "v_sub_f32_e32 v104, v104, v103\n"                      /* c = dot(oc, oc) - r^2 */                                            \
+        "v_mul_f32_e32 v105, v107, v107\n"                      /* h h */                                                              \
+        "v_mul_f32_e32 v104, %[a], v104\n"                      /* a c */                                                              \
+        "v_sub_f32_e32 v104, v105, v104\n"                      /* discriminant */                                                     \
+        BRT_LEAF_TAIL                                           /* t = (h - sqrt(discriminant)) / a, see above */                      \
+        /* accepted iff t > 0.001 && t < closest (raytrace.wgsl:353-354; strict: the first sphere reached wins ties) */                \
+        "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"                                                                                       \
+        "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"                                                                                 \
+        "s_and_b64 exec, vcc, %[s_p2]\n"                                                                                               \
+        "v_mov_b32_e32 %[closest], v104\n"                                                                                             \
+        "v_mov_b32_e32 %[cidx], v112\n"                                                                                                \
+        "v_add_u32_e32 %[below], -1, v104\n"                                                                                           \
+        "s_mov_b64 exec, %[s_all]\n"                                                                                                   \
+        "s_waitcnt lgkmcnt(0)\n"                                /* the pop has long arrived; the next test reads it */                 \
+        "s_branch 3b\n"                                                                                                                \
+        BRT_LEAF_TAIL_SLOW
+
 BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uint32_t& closest_idx, uint32_t gofs_x, uint32_t gofs_y,
                                uint32_t gofs_z, f3 o, f3 inv, f3 d, float a, uint32_t sph, uint32_t exit_at, uint32_t vote, AsmCounts* ac = nullptr) {
 #if BRT_HAND_ASM
-#if BRT_ASM_COUNT
-    uint32_t c_ie, c_il, c_le, c_ll, c_ls, c_tmp;
-#define BRT_COUNT_INT "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_il], %[c_il], %[c_tmp]\n s_add_u32 %[c_ie], %[c_ie], 1\n"
-#define BRT_COUNT_LEAF "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_ll], %[c_ll], %[c_tmp]\n s_add_u32 %[c_le], %[c_le], 1\n"
-#else
-#define BRT_COUNT_INT
-#define BRT_COUNT_LEAF
-#endif
-    uint32_t t0, tx, ty, tz, pop, cnt, nw, thr;
-    float below;
-    uint64_t s_all, s_take, s_p2, s_any, s_both;
-    const uint32_t rec_bytes = PAIR_BYTES, c_tiny = 0x0f800000u /* 2^-96 */, c_eps = 0x3a83126fu /* 0.001f */, c_cls = 0x260u /* +-0, +inf */;
-#if BRT_EXACT_FORMS & 6
-    const uint32_t c_lo2 = 0x17800000u /* 2^-80 */, c_hi2 = 0x67800000u /* 2^80 */, c_hi = 0x53800000u /* 2^40 */;
-#endif
-#if BRT_EXACT_FORMS & 4
-    float r1;                                                   // rcp_refined(a).r1
-#endif
+    BRT_WIDE_LOCALS
     asm volatile(
-#if BRT_ASM_COUNT
-        "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n s_mov_b32 %[c_ls], 0\n"
-#endif
-        "s_waitcnt lgkmcnt(0)\n"                                // nothing of the compiler's in flight: the counted waits below are exact
-        "s_mov_b64 %[s_all], exec\n"
-        "v_add_u32_e32 %[below], -1, %[closest]\n"              // the largest float below closest (closest is FLT_MAX or an accepted t > 0)
-        BRT_LEAF_ENTRY
-        // ---- outer loop: leave when at most exit_at lanes still walk -------------------------------------------------------
-        "3:\n"
-        "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n"
-        "s_bcnt1_i32_b64 %[nw], vcc\n"
-        "s_cmp_le_u32 %[nw], %[exit_at]\n"
-        "s_cbranch_scc1 9f\n"
-        "s_max_u32 %[thr], %[nw], %[vote]\n"                    // interior steps while more than max(walking, vote) - vote lanes are at one
-        "s_sub_u32 %[thr], %[thr], %[vote]\n"
-        BRT_INT_TEST
-        "s_bcnt1_i32_b64 %[cnt], vcc\n"
-        "s_cmp_le_u32 %[cnt], %[thr]\n"
-        "s_cbranch_scc1 5f\n"
-        // ---- interior steps (BRT_INT_STEP, above) -------------------------------------------------------------------------------
-        "1:\n"
-        BRT_INT_HEAD
-        BRT_COUNT_INT
+        BRT_WIDE_PROLOGUE
+        BRT_WIDE_OUTER_HEAD
+        "1:\n"                                                  // ---- interior steps: the record from the LDS
+        BRT_WIDE_COUNT_INT
         "ds_read_i16 %[pop], %[spa]\n"                          // the would-be pop: needs no address arithmetic, goes out first
         "v_mul_lo_u32 %[t0], %[cur], %[rec_bytes]\n"
         "v_add_u32_e32 %[tx], %[t0], %[gofs_x]\n"
@@ -1006,78 +927,19 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "v_add_u32_e32 %[tz], %[t0], %[gofs_z]\n"
         "ds_read_b128 v[108:111], %[tz]\n"
         "ds_read_b64 v[112:113], %[t0] offset:96\n"             // descriptors of L and R
-        BRT_INT_SLABS("s_waitcnt lgkmcnt(3)\n", "s_waitcnt lgkmcnt(2)\n", "s_waitcnt lgkmcnt(1)\n")
-        "v_max_f32_e32 v100, v100, v104\n"
-        "v_max_f32_e32 v101, v101, v105\n"
-        "v_min_f32_e32 v102, v102, v106\n"
-        "v_min_f32_e32 v103, v103, v107\n"
-        "v_max3_f32 v100, v100, v108, 1\n"                      // t_near = max(.., denorm_min)
-        "v_max3_f32 v101, v101, v109, 1\n"
-        "v_min3_f32 v102, v102, v110, %[below]\n"               // t_far = min(.., below(closest))
-        "v_min3_f32 v103, v103, v111, %[below]\n"
-        BRT_INT_DECIDE("s_waitcnt lgkmcnt(0)\n")
-        // ---- one leaf step for every lane that waits at a leaf --------------------------------------------------------------
-        "5:\n"
-        BRT_INT_LEAF_LANES                                      // leaf descriptors are < -1
-        BRT_COUNT_LEAF
-        "v_and_b32_e32 v112, 0x3fff, %[cur]\n"                  // the leaf's sphere
+        BRT_WIDE_INT_STEP("s_waitcnt lgkmcnt(3)\n", "s_waitcnt lgkmcnt(2)\n", "s_waitcnt lgkmcnt(1)\n", "s_waitcnt lgkmcnt(0)\n")
+        BRT_WIDE_LEAF_HEAD                                      // ---- the leaf step: the sphere from the LDS
         "v_lshl_add_u32 %[t0], v112, 4, %[sph]\n"
         "ds_read_b128 v[100:103], %[t0]\n"                      // { centre, r^2 }
         "ds_read_i16 %[cur], %[spa]\n"                          // pop
         "s_waitcnt lgkmcnt(1)\n"
-        "v_sub_f32_e32 v104, v100, %[ox]\n"                     // oc = centre - origin
-        "v_sub_f32_e32 v105, v101, %[oy]\n"
-        "v_sub_f32_e32 v106, v102, %[oz]\n"
-        "v_mul_f32_e32 v107, %[dx], v104\n"                     // h = dot(d, oc) = (dx ocx + dy ocy) + dz ocz
-        "v_mul_f32_e32 v108, %[dy], v105\n"
-        "v_mul_f32_e32 v104, v104, v104\n"                      // dot(oc, oc)
-        "v_mul_f32_e32 v105, v105, v105\n"
-        "v_add_f32_e32 v104, v104, v105\n"
-        "v_mul_f32_e32 v105, v106, v106\n"
-        "v_mul_f32_e32 v109, %[dz], v106\n"
-        "v_add_f32_e32 v107, v107, v108\n"
-        "v_add_f32_e32 v104, v105, v104\n"
-        "v_add_f32_e32 v107, v109, v107\n"                      // h
-        "v_sub_f32_e32 v104, v104, v103\n"                      // c = dot(oc, oc) - r^2
-        "v_mul_f32_e32 v105, v107, v107\n"                      // h h
-        "v_mul_f32_e32 v104, %[a], v104\n"                      // a c
-        "v_sub_f32_e32 v104, v105, v104\n"                      // discriminant
-        BRT_LEAF_TAIL                                           // t = (h - sqrt(discriminant)) / a, see above
-        // accepted iff t > 0.001 && t < closest (raytrace.wgsl:353-354; strict: the first sphere reached wins ties)
-        "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"
-        "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"
-        "s_and_b64 exec, vcc, %[s_p2]\n"
-        "v_mov_b32_e32 %[closest], v104\n"
-        "v_mov_b32_e32 %[cidx], v112\n"
-        "v_add_u32_e32 %[below], -1, v104\n"
-        "s_mov_b64 exec, %[s_all]\n"
-        "s_waitcnt lgkmcnt(0)\n"                                // the pop has long arrived; the next test reads it
-        "s_branch 3b\n"
-        BRT_LEAF_TAIL_SLOW
+        BRT_WIDE_LEAF_TEST
         "9:\n"
         "s_waitcnt lgkmcnt(0)\n"
-        : [cur] "+v"(cur), [spa] "+v"(spa), [closest] "+v"(closest), [cidx] "+v"(closest_idx), [below] "=&v"(below), [t0] "=&v"(t0),
-          [tx] "=&v"(tx), [ty] "=&v"(ty), [tz] "=&v"(tz), [pop] "=&v"(pop), [cnt] "=&s"(cnt), [nw] "=&s"(nw), [thr] "=&s"(thr),
-          [s_all] "=&s"(s_all), [s_take] "=&s"(s_take), [s_p2] "=&s"(s_p2), [s_any] "=&s"(s_any), [s_both] "=&s"(s_both)
-#if BRT_ASM_COUNT
-          , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_ls] "=&s"(c_ls), [c_tmp] "=&s"(c_tmp)
-#endif
-#if BRT_EXACT_FORMS & 4
-          , [r1] "=&v"(r1)
-#endif
-        : [gofs_x] "v"(gofs_x), [gofs_y] "v"(gofs_y), [gofs_z] "v"(gofs_z), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(inv.x),
-          [iy] "v"(inv.y), [iz] "v"(inv.z), [dx] "v"(d.x), [dy] "v"(d.y), [dz] "v"(d.z), [a] "v"(a), [sph] "s"(sph), [exit_at] "s"(exit_at),
-          [vote] "s"(vote), [rec_bytes] "s"(rec_bytes), [c_tiny] "s"(c_tiny), [c_eps] "s"(c_eps), [c_cls] "s"(c_cls)
-#if BRT_EXACT_FORMS & 6
-          , [c_lo2] "s"(c_lo2), [c_hi2] "s"(c_hi2), [c_hi] "s"(c_hi)
-#endif
-        : "vcc", "scc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112",
-          "v113");
-#if BRT_ASM_COUNT
-    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; ac->leaf_slow += c_ls; }
-#endif
-#undef BRT_COUNT_INT
-#undef BRT_COUNT_LEAF
+        : BRT_WIDE_OUTPUTS
+        : BRT_WIDE_INPUTS([sph] "s"(sph))
+        : BRT_WIDE_CLOBBERS);
+    BRT_WIDE_COUNT_BOOK
 #endif
 }
 
@@ -1090,48 +952,12 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
                                uint32_t gofs_z, f3 o, f3 inv, f3 d, float a, uint32_t near_bytes, uint64_t far, uint64_t sphg,
                                uint32_t exit_at, uint32_t vote, AsmCounts* ac = nullptr) {
 #if BRT_HAND_ASM
-#if BRT_ASM_COUNT
-    uint32_t c_ie, c_il, c_le, c_ll, c_ls, c_tmp;
-#define BRT_COUNT_INT "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_il], %[c_il], %[c_tmp]\n s_add_u32 %[c_ie], %[c_ie], 1\n"
-#define BRT_COUNT_LEAF "s_bcnt1_i32_b64 %[c_tmp], exec\n s_add_u32 %[c_ll], %[c_ll], %[c_tmp]\n s_add_u32 %[c_le], %[c_le], 1\n"
-#else
-#define BRT_COUNT_INT
-#define BRT_COUNT_LEAF
-#endif
-    uint32_t t0, tx, ty, tz, pop, cnt, nw, thr;
-    float below;
-    uint64_t s_all, s_take, s_p2, s_any, s_both;
-    const uint32_t rec_bytes = PAIR_BYTES, c_tiny = 0x0f800000u /* 2^-96 */, c_eps = 0x3a83126fu /* 0.001f */, c_cls = 0x260u /* +-0, +inf */;
-#if BRT_EXACT_FORMS & 6
-    const uint32_t c_lo2 = 0x17800000u /* 2^-80 */, c_hi2 = 0x67800000u /* 2^80 */, c_hi = 0x53800000u /* 2^40 */;
-#endif
-#if BRT_EXACT_FORMS & 4
-    float r1;                                                   // rcp_refined(a).r1
-#endif
+    BRT_WIDE_LOCALS
     asm volatile(
-#if BRT_ASM_COUNT
-        "s_mov_b32 %[c_ie], 0\n s_mov_b32 %[c_il], 0\n s_mov_b32 %[c_le], 0\n s_mov_b32 %[c_ll], 0\n s_mov_b32 %[c_ls], 0\n"
-#endif
-        "s_waitcnt lgkmcnt(0)\n"                                // nothing of the compiler's in flight: the counted waits below are exact
-        "s_mov_b64 %[s_all], exec\n"
-        "v_add_u32_e32 %[below], -1, %[closest]\n"              // the largest float below closest (closest is FLT_MAX or an accepted t > 0)
-        BRT_LEAF_ENTRY
-        // ---- outer loop: leave when at most exit_at lanes still walk -------------------------------------------------------
-        "3:\n"
-        "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n"
-        "s_bcnt1_i32_b64 %[nw], vcc\n"
-        "s_cmp_le_u32 %[nw], %[exit_at]\n"
-        "s_cbranch_scc1 9f\n"
-        "s_max_u32 %[thr], %[nw], %[vote]\n"                    // interior steps while more than max(walking, vote) - vote lanes are at one
-        "s_sub_u32 %[thr], %[thr], %[vote]\n"
-        BRT_INT_TEST
-        "s_bcnt1_i32_b64 %[cnt], vcc\n"
-        "s_cmp_le_u32 %[cnt], %[thr]\n"
-        "s_cbranch_scc1 5f\n"
-        // ---- interior steps (BRT_INT_STEP, above) -------------------------------------------------------------------------------
-        "1:\n"
-        BRT_INT_HEAD
-        BRT_COUNT_INT
+        BRT_WIDE_PROLOGUE
+        BRT_WIDE_OUTER_HEAD
+        "1:\n"                                                  // ---- interior steps: the record from the tile, or out of line (8)
+        BRT_WIDE_COUNT_INT
         "ds_read_i16 %[pop], %[spa]\n"                          // the would-be pop: needs no address arithmetic, goes out first
         "v_mul_lo_u32 %[t0], %[cur], %[rec_bytes]\n"
         "v_cmp_le_u32_e32 vcc, %[near_bytes], %[t0]\n"          // lanes whose record is only in the global array (L2)
@@ -1146,57 +972,17 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "6:\n"
         // (counted waits that hold for every mix: the LDS queue is {pop, x, y, z, descriptors} or just {pop}, the vector-memory queue {x, y, z,
         //  descriptors} or empty -- a lane's x granule has arrived when at most 3 are outstanding in BOTH)
-        BRT_INT_SLABS("s_waitcnt vmcnt(3) lgkmcnt(3)\n", "s_waitcnt vmcnt(2) lgkmcnt(2)\n", "s_waitcnt vmcnt(1) lgkmcnt(1)\n")
-        "v_max_f32_e32 v100, v100, v104\n"
-        "v_max_f32_e32 v101, v101, v105\n"
-        "v_min_f32_e32 v102, v102, v106\n"
-        "v_min_f32_e32 v103, v103, v107\n"
-        "v_max3_f32 v100, v100, v108, 1\n"                      // t_near = max(.., denorm_min)
-        "v_max3_f32 v101, v101, v109, 1\n"
-        "v_min3_f32 v102, v102, v110, %[below]\n"               // t_far = min(.., below(closest))
-        "v_min3_f32 v103, v103, v111, %[below]\n"
-        BRT_INT_DECIDE("s_waitcnt vmcnt(0) lgkmcnt(0)\n")
-        // ---- one leaf step for every lane that waits at a leaf --------------------------------------------------------------
-        "5:\n"
-        BRT_INT_LEAF_LANES                                      // leaf descriptors are < -1
-        BRT_COUNT_LEAF
-        "v_and_b32_e32 v112, 0x3fff, %[cur]\n"                  // the leaf's sphere
+        BRT_WIDE_INT_STEP("s_waitcnt vmcnt(3) lgkmcnt(3)\n", "s_waitcnt vmcnt(2) lgkmcnt(2)\n", "s_waitcnt vmcnt(1) lgkmcnt(1)\n",
+                          "s_waitcnt vmcnt(0) lgkmcnt(0)\n")
+        BRT_WIDE_LEAF_HEAD                                      // ---- the leaf step: the sphere from global memory
         "v_lshlrev_b32_e32 %[t0], 4, v112\n"
         "global_load_dwordx4 v[100:103], %[t0], %[sphg]\n"      // { centre, r^2 }
         "ds_read_i16 %[cur], %[spa]\n"                          // pop
         "s_waitcnt vmcnt(0)\n"
-        "v_sub_f32_e32 v104, v100, %[ox]\n"                     // oc = centre - origin
-        "v_sub_f32_e32 v105, v101, %[oy]\n"
-        "v_sub_f32_e32 v106, v102, %[oz]\n"
-        "v_mul_f32_e32 v107, %[dx], v104\n"                     // h = dot(d, oc) = (dx ocx + dy ocy) + dz ocz
-        "v_mul_f32_e32 v108, %[dy], v105\n"
-        "v_mul_f32_e32 v104, v104, v104\n"                      // dot(oc, oc)
-        "v_mul_f32_e32 v105, v105, v105\n"
-        "v_add_f32_e32 v104, v104, v105\n"
-        "v_mul_f32_e32 v105, v106, v106\n"
-        "v_mul_f32_e32 v109, %[dz], v106\n"
-        "v_add_f32_e32 v107, v107, v108\n"
-        "v_add_f32_e32 v104, v105, v104\n"
-        "v_add_f32_e32 v107, v109, v107\n"                      // h
-        "v_sub_f32_e32 v104, v104, v103\n"                      // c = dot(oc, oc) - r^2
-        "v_mul_f32_e32 v105, v107, v107\n"                      // h h
-        "v_mul_f32_e32 v104, %[a], v104\n"                      // a c
-        "v_sub_f32_e32 v104, v105, v104\n"                      // discriminant
-        BRT_LEAF_TAIL                                           // t = (h - sqrt(discriminant)) / a, see above
-        // accepted iff t > 0.001 && t < closest (raytrace.wgsl:353-354; strict: the first sphere reached wins ties)
-        "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"
-        "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"
-        "s_and_b64 exec, vcc, %[s_p2]\n"
-        "v_mov_b32_e32 %[closest], v104\n"
-        "v_mov_b32_e32 %[cidx], v112\n"
-        "v_add_u32_e32 %[below], -1, v104\n"
-        "s_mov_b64 exec, %[s_all]\n"
-        "s_waitcnt lgkmcnt(0)\n"                                // the pop has long arrived; the next test reads it
-        "s_branch 3b\n"
-        BRT_LEAF_TAIL_SLOW
+        BRT_WIDE_LEAF_TEST
         // ---- out of line: an interior step with lanes on both sides (two EXEC masks, one destination) ---------------------------
         "8:\n"
-        BRT_INT_SAVE_TAKE
+        "s_mov_b64 %[s_take], exec\n"                           // (the lanes of the step: EXEC is narrowed twice below)
         "v_add_u32_e32 %[ty], %[t0], %[gofs_y]\n"
         "v_add_u32_e32 %[tz], %[t0], %[gofs_z]\n"
         "s_and_b64 exec, %[s_take], vcc\n"                      // the global loads go out first ...
@@ -1215,28 +1001,10 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "s_branch 6b\n"
         "9:\n"
         "s_waitcnt lgkmcnt(0)\n"
-        : [cur] "+v"(cur), [spa] "+v"(spa), [closest] "+v"(closest), [cidx] "+v"(closest_idx), [below] "=&v"(below), [t0] "=&v"(t0),
-          [tx] "=&v"(tx), [ty] "=&v"(ty), [tz] "=&v"(tz), [pop] "=&v"(pop), [cnt] "=&s"(cnt), [nw] "=&s"(nw), [thr] "=&s"(thr),
-          [s_all] "=&s"(s_all), [s_take] "=&s"(s_take), [s_p2] "=&s"(s_p2), [s_any] "=&s"(s_any), [s_both] "=&s"(s_both)
-#if BRT_ASM_COUNT
-          , [c_ie] "=&s"(c_ie), [c_il] "=&s"(c_il), [c_le] "=&s"(c_le), [c_ll] "=&s"(c_ll), [c_ls] "=&s"(c_ls), [c_tmp] "=&s"(c_tmp)
-#endif
-#if BRT_EXACT_FORMS & 4
-          , [r1] "=&v"(r1)
-#endif
-        : [gofs_x] "v"(gofs_x), [gofs_y] "v"(gofs_y), [gofs_z] "v"(gofs_z), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(inv.x),
-          [iy] "v"(inv.y), [iz] "v"(inv.z), [dx] "v"(d.x), [dy] "v"(d.y), [dz] "v"(d.z), [a] "v"(a), [near_bytes] "s"(near_bytes), [far] "s"(far), [sphg] "s"(sphg), [exit_at] "s"(exit_at),
-          [vote] "s"(vote), [rec_bytes] "s"(rec_bytes), [c_tiny] "s"(c_tiny), [c_eps] "s"(c_eps), [c_cls] "s"(c_cls)
-#if BRT_EXACT_FORMS & 6
-          , [c_lo2] "s"(c_lo2), [c_hi2] "s"(c_hi2), [c_hi] "s"(c_hi)
-#endif
-        : "vcc", "scc", "memory", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112",
-          "v113");
-#if BRT_ASM_COUNT
-    if (first_active_lane()) { ac->int_exec += c_ie; ac->int_lanes += c_il; ac->leaf_exec += c_le; ac->leaf_lanes += c_ll; ac->leaf_slow += c_ls; }
-#endif
-#undef BRT_COUNT_INT
-#undef BRT_COUNT_LEAF
+        : BRT_WIDE_OUTPUTS
+        : BRT_WIDE_INPUTS([near_bytes] "s"(near_bytes), [far] "s"(far), [sphg] "s"(sphg))
+        : BRT_WIDE_CLOBBERS);
+    BRT_WIDE_COUNT_BOOK
 #endif
 }
 
@@ -1254,7 +1022,7 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
 // any association gives the same bits; rays that can produce a NaN never come here), four row broadcasts bring them to every lane
 // and each lane makes the reference's decision (raytrace.wgsl:331, :338-341) for itself: ~38 instructions per step instead of ~66.
 // The leaf step forms the two dot products of hit_sphere (raytrace.wgsl:371-383) across three lanes in the shader's order,
-// (x x' + y y') + z z', and then runs hipcc's full sqrt and divide expansions (the instructions of BRT_LEAF_SQRT_FULL / BRT_LEAF_DIV_FULL; the short
+// (x x' + y y') + z z', and then runs hipcc's full sqrt and divide expansions (BRT_LEAF_SQRT_FULL / BRT_LEAF_DIV_FULL; the short
 // forms of BRT_LEAF_TAIL were not taken over: a row's step is a dependent chain, not an issue budget).  Same nodes in the same
 // order, same ties, same t: pixels and counters do not change.  The rays' stacks stay where they are (the row reads and writes its
 // source lane's column of the wave's stack array), so a walk that was suspended by the wide loop is finished here as it stands.
@@ -1309,36 +1077,9 @@ BRT_DEV void walk_rows_asm(uint32_t& cur, uint32_t spa, float& closest, uint32_t
         "v_mul_f32_e32 v105, v107, v107\n" \
         "v_mul_f32_e32 v104, %[ra], v104\n" \
         "v_sub_f32_e32 v104, v105, v104\n" \
-        "v_cmp_gt_f32_e32 vcc, %[c_tiny], v104\n" \
-        "v_mul_f32_e32 v105, 0x4f800000, v104\n" \
-        "s_nop 0\n" \
-        "v_cndmask_b32_e32 v104, v104, v105, vcc\n" \
-        "v_sqrt_f32_e32 v105, v104\n" \
-        "v_cmp_class_f32_e64 %[s_both], v104, %[c_cls]\n" \
-        "v_add_u32_e32 v106, -1, v105\n" \
-        "v_add_u32_e32 v109, 1, v105\n" \
-        "v_fma_f32 v108, -v106, v105, v104\n" \
-        "v_fma_f32 v110, -v109, v105, v104\n" \
-        "v_cmp_ge_f32_e64 %[s_p2], 0, v108\n" \
-        "v_cmp_lt_f32_e64 %[s_any], 0, v110\n" \
-        "s_nop 0\n" \
-        "v_cndmask_b32_e64 v106, v105, v106, %[s_p2]\n" \
-        "v_cndmask_b32_e64 v105, v106, v109, %[s_any]\n" \
-        "v_mul_f32_e32 v106, 0x37800000, v105\n" \
-        "v_cndmask_b32_e32 v105, v105, v106, vcc\n" \
-        "v_cndmask_b32_e64 v104, v105, v104, %[s_both]\n" \
+        BRT_LEAF_SQRT_FULL("s_nop 0\n") \
         "v_sub_f32_e32 v104, v107, v104\n" \
-        "v_div_scale_f32 v105, %[s_p2], %[ra], %[ra], v104\n" \
-        "v_rcp_f32_e32 v106, v105\n" \
-        "v_div_scale_f32 v107, vcc, v104, %[ra], v104\n" \
-        "v_fma_f32 v109, -v105, v106, 1.0\n" \
-        "v_fmac_f32_e32 v106, v109, v106\n" \
-        "v_mul_f32_e32 v108, v107, v106\n" \
-        "v_fma_f32 v109, -v105, v108, v107\n" \
-        "v_fmac_f32_e32 v108, v109, v106\n" \
-        "v_fma_f32 v105, -v105, v108, v107\n" \
-        "v_div_fmas_f32 v105, v105, v106, v108\n" \
-        "v_div_fixup_f32 v104, v105, %[ra], v104\n" \
+        BRT_LEAF_DIV_FULL("%[ra]") \
         "s_nop 1\n" \
         "v_mov_b32_dpp v105, v104 row_newbcast:0 row_mask:0xf bank_mask:0xf\n" \
         "v_cmp_lt_f32_e32 vcc, %[c_eps], v105\n" \
@@ -1635,7 +1376,7 @@ BRT_DEV void walk_run(const ScenePtrs& sc, WalkState<StackT>& w, StackT* stk, f3
     const bool pending = cur != DS::DONE && (SIMPLE_TREE || n < 31u);
     // (the hand-written loops divide by `a` in the plain form, BRT_LEAF_TAIL: a ray whose `a` is outside that form's range -- or a NaN --
     //  is walked by the compiler's loop like one that fails ray_is_safe)
-    constexpr bool kPlainA = (BRT_EXACT_FORMS & 4) != 0 && BRT_WALK_FAST && STRIDE == 64 && !COUNTERS && SIMPLE_TREE && D16;
+    constexpr bool kPlainA = BRT_WALK_FAST && STRIDE == 64 && !COUNTERS && SIMPLE_TREE && D16;
     const bool unsafe = !sc.boxes_ordered || (pending && !ray_is_safe(o, inv)) || (kPlainA && pending && !(a >= kLeafALo && a <= kPlainHi));
     if (STRIDE == 64) {
         // Wave-level loop.  The kernel is bound by instruction issue, the two bodies cost the wave ~60-70
@@ -1675,7 +1416,7 @@ BRT_DEV void walk_run(const ScenePtrs& sc, WalkState<StackT>& w, StackT* stk, f3
             else if (any_unsafe)
                 walk_loop_wave<COUNTERS, D16, SIMPLE_TREE, true, MODE>(sc, o, d, a, inv, ox, oy, oz, closest, closest_idx, cur, sp,
                                                                        n, exit_at, vote, hc);
-            constexpr bool kByHandTop = BRT_WALK_FAST && BRT_WALK_FAST_TOP && MODE != SCENE_LDS && !COUNTERS && SIMPLE_TREE && D16;
+            constexpr bool kByHandTop = BRT_WALK_FAST && MODE != SCENE_LDS && !COUNTERS && SIMPLE_TREE && D16;
             // a thin wave (the tail of a pixel chain): a ray to a row of 16 lanes, every walk to its end (walk_rows_asm)
             constexpr bool kRows = kByHand && BRT_WALK_ROWS && ROWS;
             bool rows = false;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds ab/lib<NAME>.so from the current sources with extra compiler flags, for scripts/ab_libs.py / scripts/ab.sh:
-#   scripts/build_variant.sh NAME "-DBRT_SHARED_RCP=0"      (objects under bevyray_amd/csrc/build_<NAME>/, removed afterwards)
+#   scripts/build_variant.sh NAME "-DBRT_ASM_COUNT=1"       (objects under bevyray_amd/csrc/build_<NAME>/, removed afterwards)
 set -e
 name="$1"; flags="$2"
 root="$(cd "$(dirname "$0")/.." && pwd)"

@@ -1,4 +1,4 @@
-"""The short correctly rounded forms of the leaf step and the shading (BRT_EXACT_FORMS, brt_device.h): sqrt_rsq -- Newton on v_rsq_f32 --
+"""The short correctly rounded forms of the leaf step and the shading (sqrt_rsq, BRT_LEAF_TAIL, brt_device.h): sqrt_rsq -- Newton on v_rsq_f32 --
 on every float of its range, the guarded tail of the hand-written leaf step on the rays at and beyond the edges of its guards (through
 the streaming ray query, which walks in walk_wave_lds_asm / walk_wave_top_asm), and small frames, all bit for bit against the compiler's
 forms resp. the CPU oracle."""

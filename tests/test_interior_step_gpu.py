@@ -1,4 +1,4 @@
-"""The interior step of the hand-written walk loops (BRT_INT_STEP, brt_device.h: walk_wave_lds_asm, walk_wave_top_asm) on the shipped
+"""The interior step of the hand-written walk loops (BRT_WIDE_INT_STEP, brt_device.h: walk_wave_lds_asm, walk_wave_top_asm) on the shipped
 build: small frames at which a slip in the push / pop rule, the stack pointer or a record address shows, as `uint32` and with their
 ray counts against the C oracle, in the production instantiations (LEAN 1, LEAN 2) and in the knobs-live one.  The oracle frame of a
 case is computed once and shared by the instantiations."""

@@ -1,10 +1,9 @@
 // int_step_bench.hip -- the interior step of the wide walk loops in the instruction currency.  (development aid, not part of the product)
 //
-//   hipcc --offload-arch=gfx950 -O3 -Ibevyray_amd/csrc -DBRT_INT_STEP=N -o ab/int_step_bench_N tests/tools/int_step_bench.hip && ab/int_step_bench_N
-//   (scripts/int_step_bench.sh builds and runs every arm)
+//   hipcc --offload-arch=gfx950 -O3 -Ibevyray_amd/csrc -o ab/int_step_bench tests/tools/int_step_bench.hip && ab/int_step_bench
 //
-// Sibling of pair_step_bench.hip.  The step is NOT copied here: the kernel is put together from the macros walk_wave_lds_asm is put together
-// from (brt_device.h, BRT_INT_*), so an arm of BRT_INT_STEP is timed exactly as the product would run it.  Every lane walks a chain of pair
+// Sibling of pair_step_bench.hip.  The step is NOT copied here: the slab test and the decision are the piece the two wide loops share (brt_device.h,
+// BRT_WIDE_INT_STEP) behind walk_wave_lds_asm's loads, so the step is timed exactly as the product runs it.  Every lane walks a chain of pair
 // records in LDS (child L always pushed, child R never) that ends in a leaf after up to 256 steps; the host starts the chain over until the
 // requested number of steps is reached.  Four settings on ONE CU:
 //     alone, 1 wave per SIMD   (4 waves)            alone, 4 waves per SIMD   (16 waves)
@@ -33,7 +32,6 @@ static_assert(REC == brt::PAIR_BYTES, "the chain below is laid out for 112-byte 
 // one execution of the interior loop as walk_wave_lds_asm runs it: from the test at the loop's entry to the fall-through at its end
 #define STEP_TEXT                                                                                                                      \
         "1:\n"                                                                                                                         \
-        BRT_INT_HEAD                                                                                                                   \
         "ds_read_i16 %[pop], %[spa]\n"                                                                                                 \
         "v_mul_lo_u32 %[t0], %[cur], %[rec_bytes]\n"                                                                                   \
         "v_add_u32_e32 %[tx], %[t0], %[gofs_x]\n"                                                                                      \
@@ -43,16 +41,7 @@ static_assert(REC == brt::PAIR_BYTES, "the chain below is laid out for 112-byte 
         "v_add_u32_e32 %[tz], %[t0], %[gofs_z]\n"                                                                                      \
         "ds_read_b128 v[108:111], %[tz]\n"                                                                                             \
         "ds_read_b64 v[112:113], %[t0] offset:96\n"                                                                                    \
-        BRT_INT_SLABS("s_waitcnt lgkmcnt(3)\n", "s_waitcnt lgkmcnt(2)\n", "s_waitcnt lgkmcnt(1)\n")                                    \
-        "v_max_f32_e32 v100, v100, v104\n"                                                                                             \
-        "v_max_f32_e32 v101, v101, v105\n"                                                                                             \
-        "v_min_f32_e32 v102, v102, v106\n"                                                                                             \
-        "v_min_f32_e32 v103, v103, v107\n"                                                                                             \
-        "v_max3_f32 v100, v100, v108, 1\n"                                                                                             \
-        "v_max3_f32 v101, v101, v109, 1\n"                                                                                             \
-        "v_min3_f32 v102, v102, v110, %[below]\n"                                                                                      \
-        "v_min3_f32 v103, v103, v111, %[below]\n"                                                                                      \
-        BRT_INT_DECIDE("s_waitcnt lgkmcnt(0)\n")
+        BRT_WIDE_INT_STEP("s_waitcnt lgkmcnt(3)\n", "s_waitcnt lgkmcnt(2)\n", "s_waitcnt lgkmcnt(1)\n", "s_waitcnt lgkmcnt(0)\n")
 
 struct Mix { int vector, lds, scalar, all; };
 constexpr Mix count_step() {
@@ -121,7 +110,7 @@ __global__ void __launch_bounds__(1024) k_step(unsigned rounds, unsigned fillers
             "s_waitcnt lgkmcnt(0)\n"
             "s_mov_b64 %[s_all], exec\n"
             "v_add_u32_e32 %[below], -1, %[closest]\n"
-            BRT_INT_TEST
+            "v_cmpx_lt_i32_e32 vcc, -1, %[cur]\n"          // the loop's entry: EXEC = the lanes at an interior node
             STEP_TEXT
             "s_waitcnt lgkmcnt(0)\n"
             "s_mov_b64 exec, %[s_all]\n"
@@ -150,8 +139,7 @@ int main() {
     CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
     constexpr Mix mix = count_step();
     const unsigned rounds = 4000;              // x 256 steps of the longest lane's chain
-    std::printf("BRT_INT_STEP=%d: %d instructions per interior step (%d vector, %d LDS, %d scalar)\n", BRT_INT_STEP, mix.all, mix.vector, mix.lds,
-                mix.scalar);
+    std::printf("%d instructions per interior step (%d vector, %d LDS, %d scalar)\n", mix.all, mix.vector, mix.lds, mix.scalar);
     struct Case { const char* name; int threads; unsigned fillers; };
     const Case cases[] = {
         {"alone, 1 wave per SIMD", 256, 0u},
