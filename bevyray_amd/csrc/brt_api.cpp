@@ -183,6 +183,7 @@ int32_t upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const 
         v.desc16 = e.desc16 ? 1u : 0u;
         v.simple_tree = e.simple_tree ? 1u : 0u;
         v.boxes_ordered = e.boxes_ordered ? 1u : 0u;
+        v.spheres_bounded = e.spheres_bounded ? 1u : 0u;
         dc.view = v;
         dc.hot_records = kept_hot;
         if (reuse) dc.hot_tree = ctx->tree_epoch;

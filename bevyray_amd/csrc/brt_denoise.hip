@@ -72,6 +72,7 @@ BRT_DEV void denoise_guides_pixel(const DeviceSceneView& sv, const FrameParams& 
     sc.hits = nullptr;
     sc.minmax_select = false;
     sc.boxes_ordered = sv.boxes_ordered != 0u;
+    sc.spheres_bounded = sv.spheres_bounded != 0u;
     sc.spheres = reinterpret_cast<const float4*>(sv.spheres);
     sc.sphere_material = sv.sphere_material;
     sc.materials = reinterpret_cast<const float4*>(sv.materials);

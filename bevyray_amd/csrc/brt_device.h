@@ -27,6 +27,18 @@ namespace brt {
 #error "BRT_INT_STEP, BRT_EXACT_FORMS, BRT_SHARED_RCP and BRT_WALK_FAST_TOP are retired (fixed at 7, 6, 3 and 1); their arms build from commit 6041ad3"
 #endif
 
+// The leaf step, the outer head and the sampler's bookkeeping in the instruction currency (docs/experiments.md, "Leaf step in the instruction
+// currency"; profiles/leaf_issue/): a bit mask of arms, each of which leaves every lane's operations, operands and order as they are.
+//   bit 0 (1)  A  the leaf tail's guards for disc > 2^80 and |n| > 2^40 hold by precondition (walk_run, BRT_LEAF_TAIL): -4 per leaf step
+//   bit 1 (2)  B  the accept rule narrows EXEC by two v_cmpx in a row instead of two compares and an s_and: -1 per leaf step
+//   bit 2 (4)  C  a leaf step entered from the outer head takes its lanes from the head's masks (walking & ~interior): -1 there
+//   bit 3 (8)  E  the sampler's masks by s_xor / s_andn2 with the move's mask written to EXEC directly: -2 per iteration
+// (a planned arm D, the sphere's address straight from the descriptor, has no bit: the step needs the descriptor after its pop has
+//  overwritten `cur`, so a copy takes the place of the mask and nothing is saved -- docs/experiments.md)
+#ifndef BRT_LEAF_ISSUE
+#define BRT_LEAF_ISSUE 15
+#endif
+
 // The hand-written loops (walk_wave_lds_asm, ball_loop_asm) name gfx950 registers and count its wait states and its lgkmcnt by
 // hand: a device pass for any other target (the Makefile's ARCH can be overridden) compiles them out and takes the
 // compiler-built loops (walk_loop_wave, the `while (need)` sampler of shade_landed) instead.
@@ -262,6 +274,23 @@ BRT_DEV void ball_loop_asm(uint32_t& rng, f3& acc, float rough, uint64_t m2, uin
     "v_xor_b32_e32 %[rng], %[t], %[rng]\n"                                                                                  \
     "v_cvt_f32_u32_e32 " dst ", %[rng]\n"                                                                                  \
     "v_fma_f32 " dst ", " dst ", %[c_2m31], -1.0\n"       /* rng_ball_coord: 2 * (state * 2^-32) - 1, rounded once */
+// who needs how many, after the accept test: EXEC ends up at the lanes that go from two to one (they move their point aside).  The accepted
+// lanes (VCC) are a subset of m1 | m2 -- the loop's EXEC -- and m1 and m2 are disjoint, so "one -> none, two -> one" is m1 ^= vcc and the
+// mask of the move can go to EXEC directly: four scalar instructions per iteration with the s_or at the end (BRT_LEAF_ISSUE bit 3; as
+// first written six: the mask in a pair of its own, m1 cleared and or-ed).
+#if BRT_LEAF_ISSUE & 8
+#define BRT_BALL_BOOK                                                                                                       \
+        "s_and_b64 exec, %[m2], vcc\n"                      /* two needed -> one */                                        \
+        "s_xor_b64 %[m1], %[m1], vcc\n"                     /* one needed -> none, and those of m2 */                      \
+        "s_andn2_b64 %[m2], %[m2], vcc\n"
+#else
+#define BRT_BALL_BOOK                                                                                                       \
+        "s_and_b64 %[s_up], %[m2], vcc\n"                   /* two needed -> one */                                        \
+        "s_andn2_b64 %[m1], %[m1], vcc\n"                   /* one needed -> none */                                       \
+        "s_andn2_b64 %[m2], %[m2], vcc\n"                                                                                   \
+        "s_or_b64 %[m1], %[m1], %[s_up]\n"                                                                                  \
+        "s_mov_b64 exec, %[s_up]\n"
+#endif
 #define BRT_BALL_ITERATION                                                                                                  \
         BRT_RNG_DRAW("%[x]")                                                                                                \
         BRT_RNG_DRAW("%[y]")                                                                                                \
@@ -272,11 +301,7 @@ BRT_DEV void ball_loop_asm(uint32_t& rng, f3& acc, float rough, uint64_t m2, uin
         "v_mul_f32_e32 %[r], %[z], %[z]\n"                                                                                  \
         "v_add_f32_e32 %[q], %[q], %[r]\n"                                                                                  \
         "v_cmp_ge_f32_e32 vcc, 1.0, %[q]\n"                 /* accepted (inactive lanes: 0) */                             \
-        "s_and_b64 %[s_up], %[m2], vcc\n"                   /* two needed -> one */                                        \
-        "s_andn2_b64 %[m1], %[m1], vcc\n"                   /* one needed -> none */                                       \
-        "s_andn2_b64 %[m2], %[m2], vcc\n"                                                                                   \
-        "s_or_b64 %[m1], %[m1], %[s_up]\n"                                                                                  \
-        "s_mov_b64 exec, %[s_up]\n"                                                                                         \
+        BRT_BALL_BOOK                                                                                                       \
         "v_mov_b32_e32 %[x1], %[x]\n"                       /* the first of two points */                                  \
         "v_mov_b32_e32 %[y1], %[y]\n"                                                                                       \
         "v_mov_b32_e32 %[z1], %[z]\n"                                                                                       \
@@ -320,6 +345,7 @@ BRT_DEV void ball_loop_asm(uint32_t& rng, f3& acc, float rough, uint64_t m2, uin
 #endif
 #undef BRT_COUNT_BALL
 #undef BRT_BALL_ITERATION
+#undef BRT_BALL_BOOK
 #undef BRT_RNG_DRAW
 #endif
 }
@@ -370,6 +396,7 @@ struct ScenePtrs {
     uint32_t sph_base;       // SCENE_LDS: LDS byte address of the spheres
     uint32_t rows_scratch;   // SCENE_LDS: LDS byte address of THIS WAVE's scratch for the row-mode walk (walk_rows_asm), 0: none
     bool boxes_ordered;      // every child box finite with min <= max (decided at upload)
+    bool spheres_bounded;    // every |centre_i| <= kLeafCentreMax and r^2 <= kLeafR2Max (decided at upload; BRT_LEAF_TAIL's precondition)
     const float4* spheres;
     const uint32_t* sphere_material;
     const float4* materials;
@@ -496,11 +523,15 @@ BRT_DEV void walk_leaf_step(const ScenePtrs& sc, f3 o, f3 d, float a, float& clo
 // (b - o) * inv is monotone in b and never NaN, so the value read as "near" IS min(t_min, t_max) and
 // the value read as "far" IS max(t_min, t_max) of raytrace.wgsl:391-392 (up to the sign of a zero,
 // which no comparison below can see).
+// BOUNDED (the instantiations that walk in the hand-written loops, walk_run): the origin's components are not just finite but at most
+// kLeafOriginMax in magnitude -- a compare each instead of a class test, and a NaN fails it; BRT_LEAF_TAIL's precondition on the ray.
+template <bool BOUNDED = false>
 BRT_DEV bool ray_is_safe(f3 o, f3 inv) {
     constexpr int kFinite = 0x1F8;          // -normal, -denormal, -0, +0, +denormal, +normal
     constexpr int kFiniteNonZero = 0x198;   // -normal, -denormal, +denormal, +normal
-    return __builtin_amdgcn_classf(o.x, kFinite) && __builtin_amdgcn_classf(o.y, kFinite) &&
-           __builtin_amdgcn_classf(o.z, kFinite) && __builtin_amdgcn_classf(inv.x, kFiniteNonZero) &&
+    const bool origin = BOUNDED ? (__builtin_fabsf(o.x) <= kLeafOriginMax && __builtin_fabsf(o.y) <= kLeafOriginMax && __builtin_fabsf(o.z) <= kLeafOriginMax)
+                                : (__builtin_amdgcn_classf(o.x, kFinite) && __builtin_amdgcn_classf(o.y, kFinite) && __builtin_amdgcn_classf(o.z, kFinite));
+    return origin && __builtin_amdgcn_classf(inv.x, kFiniteNonZero) &&
            __builtin_amdgcn_classf(inv.y, kFiniteNonZero) && __builtin_amdgcn_classf(inv.z, kFiniteNonZero);
 }
 
@@ -677,7 +708,8 @@ BRT_DEV void walk_loop_wave(const ScenePtrs& sc, f3 o, f3 d, float a, f3 inv, ui
 //           |n| < 2^-40 the correctly rounded quotient is at most 2^-11 < 0.001 in magnitude, so the reference rejects such a lane by
 //           t > 0.001, and div_plain -- |n r1| <= 2^-11 (1 + 2^-22), two corrections of relative size 2^-22 -- rejects it too; where
 //           2^-40 <= |n| the pair (n, a) is in the range where div_plain IS the compiler's expansion (BRT_DBG_DIV_SWEEP).
-// The guard is three compares (|disc| < 2^-80 also catches +-0, whose rsq is inf; a NaN passes every test and stays a NaN) and ONE
+// The guard was three compares (|disc| < 2^-80 also catches +-0, whose rsq is inf; a NaN passes every test and stays a NaN; since
+// BRT_LEAF_ISSUE bit 0 only that first one is left, see above BRT_LEAF_TAIL) and ONE
 // scalar branch, untaken unless some active lane fails: then the whole wave runs the full forms out of line, from the preserved
 // discriminant and h, and rejoins at the accept rule -- for the lanes that were in range the two forms give the same bits.
 // Measured (headline frame, five alternated bench runs per arm): 8.926 ms with the full forms in line, 8.811 with either short form alone,
@@ -756,6 +788,30 @@ constexpr float kLeafALo = 0x1p-29f;
 #define BRT_WIDE_COUNT_OUTPUTS
 #define BRT_WIDE_COUNT_BOOK
 #endif
+// BRT_LEAF_ISSUE bit 0: the two UPPER guards hold by precondition, and the step keeps the lower one and a branch on VCC -- 17 instructions
+// instead of 21 (two 4-cycle compares and two s_or gone).  walk_run admits a ray to these loops only with |o_i| <= B_o = 2^24 and
+// a = dot(d, d) in [2^-29, 2^8], and only in a scene with |centre_i| <= B_c = 2^24 and r^2 <= B_r = 2^50 (brt_layout.h; decided at upload,
+// ScenePtrs::spheres_bounded).  Then, every f32 result within a factor (1 + 2^-23) of its exact value and u = 2^-23:
+//   |oc_i| = |centre_i - o_i| <= 2^25 exactly (the sum of two floats <= 2^24 is representable or rounds to at most 2^25);
+//   dot(oc, oc) <= 3 * 2^50 (1 + u)^3 < 2^52;   |c| = |dot(oc, oc) - r^2| <= (2^52 + 2^50)(1 + u) < 2^53;
+//   |d_i| <= sqrt(a (1 + u)^3) <= 2^4 (1 + u)^2 (a is the ROUNDED sum of the rounded squares, all non-negative), so
+//   |h| = |dot(d, oc)| <= 3 * 2^4 (1 + u)^2 * 2^25 * (1 + u)^3 < 2^31,   h h < 2^62 (1 + u),   |a c| <= 2^8 * 2^53 (1 + u) = 2^61 (1 + u);
+//   |disc| = |h h - a c| <= (2^62 + 2^61)(1 + u)^2 < 2^63  << 2^80;
+//   |n| = |h - sqrt(disc)| <= (2^31 + 2^31.5)(1 + u)^2 < 2^33  << 2^40   (sqrt is correctly rounded; a negative disc gives NaN either way).
+// (Cauchy-Schwarz, h^2 <= a |oc|^2, gives 2^62 and 2^32; the componentwise bounds above need no such step and leave 17 resp. 7 binades of
+// room.)  tests/test_leaf_issue_gpu.py evaluates the corner in f64 and sends rays at each bound and one float beyond it through the loops.
+#if BRT_LEAF_ISSUE & 1
+#define BRT_LEAF_TAIL                                                                                                                  \
+        BRT_LEAF_SQRT_RSQ("v_cmp_gt_f32_e64 vcc, %[c_lo2], |v104|\n")   /* |disc| < 2^-80 (with +-0): the one guard left */            \
+        "v_sub_f32_e32 v105, v107, v106\n"                      /* n = h - sqrt(discriminant) */                                       \
+        "v_mul_f32_e32 v106, v105, %[r1]\n"                     /* div_plain: q = n r1 */                                              \
+        "v_fma_f32 v108, -%[a], v106, v105\n"                   /* e = n - a q */                                                      \
+        "s_cbranch_vccnz 20f\n"                                 /* some lane's discriminant is tiny or 0: the full forms, out of line */ \
+        "v_fmac_f32_e32 v106, v108, %[r1]\n"                    /* q += e r1 */                                                        \
+        "v_fma_f32 v108, -%[a], v106, v105\n"                   /* e = n - a q */                                                      \
+        "v_fma_f32 v104, v108, %[r1], v106\n"                   /* t = q + e r1 */                                                     \
+        "21:\n"
+#else
 #define BRT_LEAF_TAIL                                                                                                                  \
         BRT_LEAF_SQRT_RSQ(BRT_LEAF_GUARD_DISC)                                                                                         \
         "v_sub_f32_e32 v105, v107, v106\n"                      /* n = h - sqrt(discriminant) */                                       \
@@ -769,7 +825,8 @@ constexpr float kLeafALo = 0x1p-29f;
         "v_fma_f32 v108, -%[a], v106, v105\n"                   /* e = n - a q */                                                      \
         "v_fma_f32 v104, v108, %[r1], v106\n"                   /* t = q + e r1 */                                                     \
         "21:\n"
-#define BRT_LEAF_TAIL_SLOW                                                                                                             \
+#endif
+#define BRT_LEAF_TAIL_SLOW                                                                                                            \
         "20:\n"                                                                                                                        \
         BRT_WIDE_COUNT_LEAF_SLOW                                                                                                       \
         BRT_LEAF_SQRT_FULL("s_nop 0\n")                                                                                                \
@@ -833,7 +890,7 @@ constexpr float kLeafALo = 0x1p-29f;
 #define BRT_WIDE_LOCALS                                                                                                                \
     uint32_t t0, tx, ty, tz, pop, cnt, nw, thr;                                                                                        \
     float below, r1;                                            /* r1: rcp_refined(a).r1 */                                            \
-    uint64_t s_all, s_take, s_p2, s_any, s_both;                                                                                       \
+    uint64_t s_all, s_take, s_p2, s_any, s_both, s_walk;                                                                               \
     const uint32_t rec_bytes = PAIR_BYTES, c_tiny = 0x0f800000u /* 2^-96 */, c_eps = 0x3a83126fu /* 0.001f */, c_cls = 0x260u /* +-0, +inf */; \
     const uint32_t c_lo2 = 0x17800000u /* 2^-80 */, c_hi2 = 0x67800000u /* 2^80 */, c_hi = 0x53800000u /* 2^40 */;                     \
     BRT_WIDE_COUNT_LOCALS
@@ -843,7 +900,7 @@ constexpr float kLeafALo = 0x1p-29f;
           [cur] "+v"(cur), [spa] "+v"(spa), [closest] "+v"(closest), [cidx] "+v"(closest_idx), [below] "=&v"(below), [t0] "=&v"(t0),   \
           [tx] "=&v"(tx), [ty] "=&v"(ty), [tz] "=&v"(tz), [pop] "=&v"(pop), [cnt] "=&s"(cnt), [nw] "=&s"(nw), [thr] "=&s"(thr),        \
           [s_all] "=&s"(s_all), [s_take] "=&s"(s_take), [s_p2] "=&s"(s_p2), [s_any] "=&s"(s_any), [s_both] "=&s"(s_both)               \
-          BRT_WIDE_COUNT_OUTPUTS, [r1] "=&v"(r1)
+          BRT_WIDE_COUNT_OUTPUTS, [r1] "=&v"(r1), [s_walk] "=&s"(s_walk)
 #define BRT_WIDE_INPUTS(...)                                                                                                           \
           [gofs_x] "v"(gofs_x), [gofs_y] "v"(gofs_y), [gofs_z] "v"(gofs_z), [ox] "v"(o.x), [oy] "v"(o.y), [oz] "v"(o.z), [ix] "v"(inv.x), \
           [iy] "v"(inv.y), [iz] "v"(inv.z), [dx] "v"(d.x), [dy] "v"(d.y), [dz] "v"(d.z), [a] "v"(a), __VA_ARGS__, [exit_at] "s"(exit_at), \
@@ -858,10 +915,15 @@ constexpr float kLeafALo = 0x1p-29f;
         "v_add_u32_e32 %[below], -1, %[closest]\n"              /* the largest float below closest (closest is FLT_MAX or an accepted t > 0) */ \
         BRT_LEAF_RCP_A
 // the outer loop's head, label 3: leave (to 9) when at most exit_at lanes still walk, go to the leaf step (5) or fall into the interior steps
+// (BRT_LEAF_ISSUE bit 2: "walking" stays in a scalar pair of its own, for the leaf step that is entered from here)
+#if BRT_LEAF_ISSUE & 4
+#define BRT_WIDE_HEAD_WALKING "v_cmp_ne_u32_e64 %[s_walk], -1, %[cur]\n s_bcnt1_i32_b64 %[nw], %[s_walk]\n"
+#else
+#define BRT_WIDE_HEAD_WALKING "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n s_bcnt1_i32_b64 %[nw], vcc\n"
+#endif
 #define BRT_WIDE_OUTER_HEAD                                                                                                            \
         "3:\n"                                                                                                                         \
-        "v_cmp_ne_u32_e32 vcc, -1, %[cur]\n"                                                                                           \
-        "s_bcnt1_i32_b64 %[nw], vcc\n"                                                                                                 \
+        BRT_WIDE_HEAD_WALKING                                                                                                          \
         "s_cmp_le_u32 %[nw], %[exit_at]\n"                                                                                             \
         "s_cbranch_scc1 9f\n"                                                                                                          \
         "s_max_u32 %[thr], %[nw], %[vote]\n"                    /* interior steps while more than max(walking, vote) - vote lanes are at one */ \
@@ -871,14 +933,45 @@ constexpr float kLeafALo = 0x1p-29f;
         "s_cmp_le_u32 %[cnt], %[thr]\n"                                                                                                \
         "s_cbranch_scc1 5f\n"
 // one leaf step for every lane that waits at a leaf, label 5: its lanes and their sphere's index ...
+// LANES_ALL finds them among all the call's lanes (the interior steps leave EXEC narrowed).  BRT_LEAF_ISSUE bit 2: a step entered from the
+// outer head, label 5, has them in the head's masks -- every walking lane that is not at an interior node (VCC there: the v_cmpx ran under
+// s_all) waits at a leaf -- and sets EXEC by ONE scalar instruction (LANES_HEAD).  The step that the interior run falls into cannot: a
+// lane may have ended its walk inside the run, `walking` is stale for it, and VCC only covers the last step's lanes; it tests all lanes as
+// before.  Two entries with different first instructions and no branch between them means the step's text stands twice in the loop
+// (BRT_WIDE_LEAF_STEPS; the local labels 20 / 21 of the tail resolve to the nearest copy).
+#define BRT_WIDE_LEAF_LANES_ALL                                                                                                        \
+        "s_mov_b64 exec, %[s_all]\n"                                                                                                   \
+        "v_cmpx_gt_i32_e32 vcc, -1, %[cur]\n"                   /* leaf descriptors are < -1 */
+#define BRT_WIDE_LEAF_LANES_HEAD                                                                                                       \
+        "s_andn2_b64 exec, %[s_walk], vcc\n"                    /* walking and not at an interior node */
 #define BRT_WIDE_LEAF_HEAD                                                                                                             \
-        "5:\n"                                                                                                                         \
-        "s_mov_b64 exec, %[s_all]\n"                            /* (the interior steps leave EXEC narrowed) */                         \
-        "v_cmpx_gt_i32_e32 vcc, -1, %[cur]\n"                   /* leaf descriptors are < -1 */                                        \
         BRT_WIDE_COUNT_LEAF                                                                                                            \
         "v_and_b32_e32 v112, 0x3fff, %[cur]\n"                  /* the leaf's sphere */
+// FETCH: the loop's own sphere fetch, pop and wait
+#if BRT_LEAF_ISSUE & 4
+#define BRT_WIDE_LEAF_STEPS(FETCH)                                                                                                     \
+        BRT_WIDE_LEAF_LANES_ALL BRT_WIDE_LEAF_HEAD FETCH BRT_WIDE_LEAF_TEST                                                            \
+        "5:\n"                                                                                                                         \
+        BRT_WIDE_LEAF_LANES_HEAD BRT_WIDE_LEAF_HEAD FETCH BRT_WIDE_LEAF_TEST
+#else
+#define BRT_WIDE_LEAF_STEPS(FETCH)                                                                                                     \
+        "5:\n"                                                                                                                         \
+        BRT_WIDE_LEAF_LANES_ALL BRT_WIDE_LEAF_HEAD FETCH BRT_WIDE_LEAF_TEST
+#endif
+// the accept rule's lanes, from the step's: t > 0.001 && t < closest, both strict (a NaN t fails the first).  BRT_LEAF_ISSUE bit 1: the second
+// v_cmpx only narrows what the first left, so EXEC needs no mask round trip through the scalar unit (two instructions instead of three).
+#if BRT_LEAF_ISSUE & 2
+#define BRT_WIDE_LEAF_ACCEPT                                                                                                           \
+        "v_cmpx_lt_f32_e32 vcc, %[c_eps], v104\n"                                                                                      \
+        "v_cmpx_lt_f32_e32 vcc, v104, %[closest]\n"
+#else
+#define BRT_WIDE_LEAF_ACCEPT                                                                                                           \
+        "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"                                                                                       \
+        "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"                                                                                 \
+        "s_and_b64 exec, vcc, %[s_p2]\n"
+#endif
 // ... and, with the sphere { centre, r^2 } in v[100:103] and the pop under way, its test, the accept rule and the way back to 3
-#define BRT_WIDE_LEAF_TEST                                                                                                             \
+#define BRT_WIDE_LEAF_TEST                                                                                                            \
         "v_sub_f32_e32 v104, v100, %[ox]\n"                     /* oc = centre - origin */                                             \
         "v_sub_f32_e32 v105, v101, %[oy]\n"                                                                                            \
         "v_sub_f32_e32 v106, v102, %[oz]\n"                                                                                            \
@@ -898,11 +991,9 @@ constexpr float kLeafALo = 0x1p-29f;
         "v_sub_f32_e32 v104, v105, v104\n"                      /* discriminant */                                                     \
         BRT_LEAF_TAIL                                           /* t = (h - sqrt(discriminant)) / a, see above */                      \
         /* accepted iff t > 0.001 && t < closest (raytrace.wgsl:353-354; strict: the first sphere reached wins ties) */                \
-        "v_cmp_lt_f32_e32 vcc, %[c_eps], v104\n"                                                                                       \
-        "v_cmp_lt_f32_e64 %[s_p2], v104, %[closest]\n"                                                                                 \
-        "s_and_b64 exec, vcc, %[s_p2]\n"                                                                                               \
+        BRT_WIDE_LEAF_ACCEPT                                                                                                           \
         "v_mov_b32_e32 %[closest], v104\n"                                                                                             \
-        "v_mov_b32_e32 %[cidx], v112\n"                                                                                                \
+        "v_mov_b32_e32 %[cidx], v112\n"                                                                                               \
         "v_add_u32_e32 %[below], -1, v104\n"                                                                                           \
         "s_mov_b64 exec, %[s_all]\n"                                                                                                   \
         "s_waitcnt lgkmcnt(0)\n"                                /* the pop has long arrived; the next test reads it */                 \
@@ -928,12 +1019,11 @@ BRT_DEV void walk_wave_lds_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         "ds_read_b128 v[108:111], %[tz]\n"
         "ds_read_b64 v[112:113], %[t0] offset:96\n"             // descriptors of L and R
         BRT_WIDE_INT_STEP("s_waitcnt lgkmcnt(3)\n", "s_waitcnt lgkmcnt(2)\n", "s_waitcnt lgkmcnt(1)\n", "s_waitcnt lgkmcnt(0)\n")
-        BRT_WIDE_LEAF_HEAD                                      // ---- the leaf step: the sphere from the LDS
-        "v_lshl_add_u32 %[t0], v112, 4, %[sph]\n"
-        "ds_read_b128 v[100:103], %[t0]\n"                      // { centre, r^2 }
-        "ds_read_i16 %[cur], %[spa]\n"                          // pop
-        "s_waitcnt lgkmcnt(1)\n"
-        BRT_WIDE_LEAF_TEST
+        BRT_WIDE_LEAF_STEPS(                                    // ---- the leaf step: the sphere from the LDS
+            "v_lshl_add_u32 %[t0], v112, 4, %[sph]\n"
+            "ds_read_b128 v[100:103], %[t0]\n"                  // { centre, r^2 }
+            "ds_read_i16 %[cur], %[spa]\n"                      // pop
+            "s_waitcnt lgkmcnt(1)\n")
         "9:\n"
         "s_waitcnt lgkmcnt(0)\n"
         : BRT_WIDE_OUTPUTS
@@ -974,12 +1064,11 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
         //  descriptors} or empty -- a lane's x granule has arrived when at most 3 are outstanding in BOTH)
         BRT_WIDE_INT_STEP("s_waitcnt vmcnt(3) lgkmcnt(3)\n", "s_waitcnt vmcnt(2) lgkmcnt(2)\n", "s_waitcnt vmcnt(1) lgkmcnt(1)\n",
                           "s_waitcnt vmcnt(0) lgkmcnt(0)\n")
-        BRT_WIDE_LEAF_HEAD                                      // ---- the leaf step: the sphere from global memory
-        "v_lshlrev_b32_e32 %[t0], 4, v112\n"
-        "global_load_dwordx4 v[100:103], %[t0], %[sphg]\n"      // { centre, r^2 }
-        "ds_read_i16 %[cur], %[spa]\n"                          // pop
-        "s_waitcnt vmcnt(0)\n"
-        BRT_WIDE_LEAF_TEST
+        BRT_WIDE_LEAF_STEPS(                                    // ---- the leaf step: the sphere from global memory
+            "v_lshlrev_b32_e32 %[t0], 4, v112\n"
+            "global_load_dwordx4 v[100:103], %[t0], %[sphg]\n"  // { centre, r^2 }
+            "ds_read_i16 %[cur], %[spa]\n"                      // pop
+            "s_waitcnt vmcnt(0)\n")
         // ---- out of line: an interior step with lanes on both sides (two EXEC masks, one destination) ---------------------------
         "8:\n"
         "s_mov_b64 %[s_take], exec\n"                           // (the lanes of the step: EXEC is narrowed twice below)
@@ -1377,7 +1466,14 @@ BRT_DEV void walk_run(const ScenePtrs& sc, WalkState<StackT>& w, StackT* stk, f3
     // (the hand-written loops divide by `a` in the plain form, BRT_LEAF_TAIL: a ray whose `a` is outside that form's range -- or a NaN --
     //  is walked by the compiler's loop like one that fails ray_is_safe)
     constexpr bool kPlainA = BRT_WALK_FAST && STRIDE == 64 && !COUNTERS && SIMPLE_TREE && D16;
-    const bool unsafe = !sc.boxes_ordered || (pending && !ray_is_safe(o, inv)) || (kPlainA && pending && !(a >= kLeafALo && a <= kPlainHi));
+    // (BRT_LEAF_ISSUE bit 0: that tail has no guard for a discriminant above 2^80 or |n| above 2^40 any more.  They cannot arise for an origin,
+    //  an `a` and a scene inside the bounds of brt_layout.h -- the derivation stands above BRT_LEAF_TAIL --; a ray or a scene outside them is
+    //  "unsafe" in the same sense.  The compiler's loop runs such a wave until at most exit_at lanes walk, so the hand-written one never
+    //  steps for it.)
+    constexpr bool kBounded = kPlainA && (BRT_LEAF_ISSUE & 1);
+    constexpr float kAHi = kBounded ? kLeafAHi : kPlainHi;
+    const bool unsafe = !sc.boxes_ordered || (kBounded && !sc.spheres_bounded) || (pending && !ray_is_safe<kBounded>(o, inv)) ||
+                        (kPlainA && pending && !(a >= kLeafALo && a <= kAHi));
     if (STRIDE == 64) {
         // Wave-level loop.  The kernel is bound by instruction issue, the two bodies cost the wave ~60-70
         // instructions each however few lanes take part, and a ray needs ~6 interior steps per leaf step:

@@ -155,12 +155,17 @@ int32_t validate_and_encode(const Model* models, uint32_t n_models, const Materi
     e.n_models = n_models;
     e.spheres.resize(4 * (size_t)n_models);
     e.sphere_material.resize(n_models);
+    e.spheres_bounded = true;
     for (uint32_t i = 0; i < n_models; i++) {
-        e.spheres[4 * (size_t)i + 0] = models[i].position[0];
-        e.spheres[4 * (size_t)i + 1] = models[i].position[1];
-        e.spheres[4 * (size_t)i + 2] = models[i].position[2];
-        e.spheres[4 * (size_t)i + 3] = models[i].radius * models[i].radius;  // raytrace.wgsl:375
+        float* s = &e.spheres[4 * (size_t)i];
+        s[0] = models[i].position[0];
+        s[1] = models[i].position[1];
+        s[2] = models[i].position[2];
+        s[3] = models[i].radius * models[i].radius;  // raytrace.wgsl:375
         e.sphere_material[i] = models[i].material_id;
+        // the hand-written leaf step's precondition on the scene (brt_layout.h; a NaN fails its comparison)
+        if (!(std::fabs(s[0]) <= kLeafCentreMax && std::fabs(s[1]) <= kLeafCentreMax && std::fabs(s[2]) <= kLeafCentreMax && s[3] <= kLeafR2Max))
+            e.spheres_bounded = false;
     }
     e.n_materials = n_materials;
     e.materials.resize(8 * (size_t)n_materials);

@@ -52,6 +52,7 @@ struct EncodedScene {
     bool desc16 = false;                 // descriptors in the 16-bit form (brt_layout.h)
     bool simple_tree = false;            // single-sphere leaves only, depth below the stack-overflow rule
     bool boxes_ordered = false;          // every child box finite with min <= max
+    bool spheres_bounded = false;        // every |centre_i| <= kLeafCentreMax and r^2 <= kLeafR2Max (brt_layout.h)
 };
 
 int32_t validate_and_encode(const Model* models, uint32_t n_models, const Material* materials, uint32_t n_materials,

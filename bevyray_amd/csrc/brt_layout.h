@@ -138,6 +138,11 @@ enum SceneMode : int {
                          // deeper records, spheres and material ids from global memory
 };
 
+// Bounds under which the hand-written leaf step's short sqrt and divide need no upper range guard (brt_device.h, BRT_LEAF_TAIL, has the
+// derivation): on a ray's origin components and dot(d, d) (walk_run, per ray) and on a scene's sphere centres and r^2 (validate_and_encode,
+// per scene: `spheres_bounded`).  A ray or scene outside them is walked by the compiler's loop and gives the same bits.
+constexpr float kLeafOriginMax = 0x1p24f, kLeafCentreMax = 0x1p24f, kLeafR2Max = 0x1p50f, kLeafAHi = 0x1p8f;
+
 struct DeviceSceneView {
     const float* pairs;      // n_pairs records of PAIR_BYTES
     const float* spheres;    // float4[n_models]
@@ -151,7 +156,8 @@ struct DeviceSceneView {
     uint32_t desc16;         // 1: descriptors are in the 16-bit form
     uint32_t simple_tree;    // 1: every leaf holds one sphere and max leaf depth + 1 < 31
     uint32_t boxes_ordered;  // 1: every child box is finite with min <= max
-    uint32_t lds_pairs;      // SCENE_LDS_TOP: pair records [0, lds_pairs) are staged in LDS (set per launch)
+    uint32_t spheres_bounded;  // 1: every sphere has |centre_i| <= kLeafCentreMax and r^2 <= kLeafR2Max (below)
+    uint32_t lds_pairs;     // SCENE_LDS_TOP: pair records [0, lds_pairs) are staged in LDS (set per launch)
 };
 
 // Defaults of the tuning knobs in FrameParams.  The production kernel (TUNABLE = false) has them folded in as

@@ -12,6 +12,7 @@ BRT_DEV ScenePtrs scene_global(const DeviceSceneView& sv) {      // the scene in
     sc.pairs = reinterpret_cast<const char*>(sv.pairs);
     sc.pairs_far = sc.pairs;
     sc.boxes_ordered = sv.boxes_ordered != 0u;
+    sc.spheres_bounded = sv.spheres_bounded != 0u;
     sc.spheres = reinterpret_cast<const float4*>(sv.spheres);
     sc.sphere_material = sv.sphere_material;
     sc.materials = reinterpret_cast<const float4*>(sv.materials);

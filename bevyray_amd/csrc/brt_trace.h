@@ -494,6 +494,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_persistent(DeviceSceneView 
     sc.materials = reinterpret_cast<const float4*>(sv.materials);
     sc.sphere_mats = reinterpret_cast<const float4*>(sv.sphere_mats);
     sc.boxes_ordered = sv.boxes_ordered != 0u;
+    sc.spheres_bounded = sv.spheres_bounded != 0u;
     sc.pairs_far = reinterpret_cast<const char*>(sv.pairs);
     sc.near_bytes = 0u;
     sc.near_base = 0u;
