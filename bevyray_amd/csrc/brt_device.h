@@ -1118,9 +1118,13 @@ BRT_DEV void walk_wave_top_asm(uint32_t& cur, uint32_t& spa, float& closest, uin
 // Rays travel through 80 bytes of LDS scratch per row: { o, a | 1/d, closest | d, closest id | granule offsets, cur | stack top }.
 // EXEC: unlike the other hand-written loops this one WIDENS the execution mask (to the 16 n lanes of its rows, whatever lanes were active at the
 // call) and restores it at the end.  What it writes there are only its own temporaries -- asm outputs and the clobbered v100 - v113 --, which by
-// the compiler's own liveness hold no value across this statement; the call sits in the round loop of the kernel, where no other side of a
-// divergent branch is pending whose values could live in those registers for the lanes that are inactive here (suite, fuzz and sequence soaks
-// run through it: profiles/r06/fuzz_soak.txt).
+// the compiler's own liveness hold no value across this statement.  That liveness follows the thread-level flow, so it covers only lanes that
+// reach the statement: the kernel therefore calls walk_run with the whole wave where this loop exists (brt_trace.h, kRowsHere), parked lanes
+// with cur == DONE, and no other side of a divergent branch is pending whose values could live in those registers for lanes that are inactive
+// here.  (Called under `if (active)` it overwrote a counter of the parked lanes in one instantiation of the -DBRT_ASM_COUNT build.)
+// tests/test_hand_loops_gpu.py reaches the loop on purpose -- every walk of a frame of at most four pixels, the hand-over from the wide loop,
+// rows that serve lanes 0 and 63 and lane pairs that share a stack dword, an unsafe ray in a thin wave -- and proves the reach by the loop's own
+// counts before it compares the shipped build's frames with the oracle's.
 #ifndef BRT_WALK_ROWS
 #define BRT_WALK_ROWS BRT_HAND_ASM
 #endif

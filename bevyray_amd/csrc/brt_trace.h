@@ -860,7 +860,18 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_trace_persistent(DeviceSceneView 
         if (fresh) walk_begin<D16>(walk, sc, sv.root_desc, stk, d);
         if (COUNTERS) { const unsigned long long now = wall_clock64(); ticks_pre += now - t_mark; t_mark = now; }
         if (kPhasePrio == 1 && !wave_crit) __builtin_amdgcn_s_setprio(1);
-        if (active) walk_run<64, COUNTERS, D16, SIMPLE, MODE, StackT, kHits, TUNABLE, LEAN != 2>(sc, walk, stk, o, d, finish_walks ? 0u : walk_exit_lanes, leaf_vote, hc);
+        // An instantiation that can take the row-mode loop (walk_run's kRows) calls walk_run with the WHOLE wave, not under `if (active)`:
+        // walk_rows_asm widens EXEC to the lanes of its rows, and under a divergent branch the lanes that bypass it may keep live values
+        // in registers the compiler has handed to the loop's temporaries (its liveness follows the thread-level flow).  It did happen: in
+        // the -DBRT_ASM_COUNT build of the knobs-live instantiation the parked lanes' repairing-loop counter shared a register with them
+        // (tests/test_hand_loops_gpu.py).  A parked lane has no walk -- it landed or was handed over --, which is said here whatever it holds.
+        constexpr bool kRowsHere = BRT_WALK_FAST && BRT_WALK_ROWS && MODE == SCENE_LDS && !COUNTERS && SIMPLE && D16 && LEAN != 2;
+        if constexpr (kRowsHere) {
+            if (!active) walk.cur = Desc<D16>::DONE;
+            walk_run<64, COUNTERS, D16, SIMPLE, MODE, StackT, kHits, TUNABLE, true>(sc, walk, stk, o, d, finish_walks ? 0u : walk_exit_lanes, leaf_vote, hc);
+        } else {
+            if (active) walk_run<64, COUNTERS, D16, SIMPLE, MODE, StackT, kHits, TUNABLE, LEAN != 2>(sc, walk, stk, o, d, finish_walks ? 0u : walk_exit_lanes, leaf_vote, hc);
+        }
         in_flight = active && walk_pending<D16, SIMPLE>(walk);
         if (COUNTERS) { const unsigned long long now = wall_clock64(); ticks_walk += now - t_mark; t_mark = now; }
         const bool landed = active && !in_flight;      // walk finished: shade this segment now

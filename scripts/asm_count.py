@@ -8,6 +8,8 @@ hand-written loops count their own executions and active lanes in scalar registe
 5 in that build, production frame and counting frame, and prints both sets side by side.  The LANE counts must be equal (the same
 per-lane steps in the same order: they are the oracle's counters); the EXECUTION counts may differ (who shares a wave differs:
 half-sample jobs, the leaf vote counted on walkers instead of leaf lanes) and the difference is printed.
+The identities are ASSERTED, on small frames, the row-mode loop and three large views, by tests/test_hand_loops_gpu.py (which builds the
+variant itself); this script prints the two full-size frames' figures.
     BRT_LIB_PATH=ab/libasmcount.so python scripts/asm_count.py"""
 import json
 import os

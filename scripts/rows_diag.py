@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """-DBRT_ASM_COUNT build: how much of a thin frame's walk runs in the row-mode loop (walk_rows_asm)?
+(That thin frames reach the loop, and what it computes there, is asserted by tests/test_hand_loops_gpu.py; this prints the shares.)
     BRT_LIB_PATH=ab/libasmcount.so python scripts/rows_diag.py [scene]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

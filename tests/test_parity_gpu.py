@@ -690,6 +690,12 @@ def test_config5_10k_spheres_full_size(plugin, oracle):
     assert cnt3["interior_visits"] < 0.85 * cnt["interior_visits"]
     st = _timed_combination(plugin, b, lvl, cam, win, w, h, want, cnt["rays"])
     assert st["scene_in_lds"] == 2 and st["hot_records"] != 0      # the top of the tree in the LDS tile, records numbered by use
+    # which LEAN instantiation the view settles in, by the launch rule (brt_api_launch.cpp launch_part): LEAN 2 when
+    # spp * (bounces + 1) = 576 is below half the frame's rays per lane of the GPU.  The frame has 318 628 648 rays: 1215 per lane of 256 CUs,
+    # half of that 607 -- the steady-state instantiation, walking in walk_wave_top_asm.
+    import torch
+    lanes = torch.cuda.get_device_properties(0).multi_processor_count * 1024
+    assert st["kernel_variant"] == (2 if spp * (bounces + 1) < (cnt["rays"] // lanes) // 2 else 1) == 2, (st["kernel_variant"], cnt["rays"], lanes)
 
 
 # ---- GPU BVH build --------------------------------------------------------------------
