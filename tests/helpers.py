@@ -1,6 +1,7 @@
 """Shared test helpers: hand-made BVHs (single leaf, median split, caterpillar chain, a composer that grafts one onto another),
 a seeded scene large enough for 32-bit tree descriptors with its camera, the upload of a scene whose tree the callee builds,
-uniform builders, the generator of randomized scenes (materials, sizes, cameras, topologies) and a numpy-f32 restatement of the
+uniform builders, the generator of randomized scenes (materials, sizes, cameras, topologies), the generator of wild scenes that
+scripts/fuzz_parity.py and tests/shade_cases.py share, and a numpy-f32 restatement of the
 camera/sky arithmetic for analytic checks; for the GPU tests of the bakes, device buffers and the upload of the cover scene."""
 import functools
 import os
@@ -239,6 +240,129 @@ def _random_case(rng):
                              seed=float(np.float32(rng.random())), level=brt.Raytracing(int(rng.integers(1, 4))),
                              window_height=int(rng.integers(1, 1200)))
     return b, lvl, cam, win, w, h
+
+
+SPECIAL = [0.0, -0.0, np.nan, np.inf, -np.inf, 3.0e38, -3.0e38, 1e-38, 1e-45, 1.0, -1.0, 1e6, 1e-6]
+
+
+def _special(rng):
+    return float(SPECIAL[int(rng.integers(0, len(SPECIAL)))])
+
+
+def _wild_material(rng, wild):
+    def unit():
+        if wild and rng.random() < 0.15:
+            return _special(rng) if rng.random() < 0.5 else float(rng.uniform(-2, 3))
+        return float(rng.choice([0.0, 1.0, rng.random()]))
+    ior = float(rng.uniform(0.3, 3.0))
+    if wild and rng.random() < 0.2:
+        ior = _special(rng)
+    return brt.StandardMaterial(base_color=tuple(float(x) for x in rng.random(3)), metallic=unit(),
+                                perceptual_roughness=unit(), ior=ior, specular_transmission=unit())
+
+
+def _wild_case(rng, wild=True, max_spheres=None, callee_trees=True):
+    """The generator of scripts/fuzz_parity.py (which draws `wild` itself: half of its cases stay sane but structurally varied): the values
+    the reference never guards against (raytrace.wgsl has no validation) -- zero / negative / huge / NaN / infinite radii and positions,
+    coincident spheres (exact ties, raytrace.wgsl:353 strict `<`), materials outside [0, 1], ior 0 and inf, poisoned boxes, cameras inside
+    spheres, degenerate up vectors, window height 0 (infinite jitter), NaN / huge / negative random_seed, sample_count 0, bounce counts
+    past the stack size, hand-made trees deeper than the 32-entry stack, multi-sphere leaves.
+    max_spheres: larger draws are folded below it (the suite's table: a case stays under a second on the oracle).
+    callee_trees: topology 0 leaves the tree to the callee (buffers.bvh None); False: it is the caller's PLOC tree.
+    -> dict(buffers, level, camera, window, w, h, raster, depth, wild, topo, mode, n_parts, far_cam)."""
+    n = int(rng.choice([1, 2, 3, int(rng.integers(4, 40)), int(rng.integers(40, 400)), int(rng.integers(400, 3000)),
+                        int(rng.integers(8200, 12000)),       # does not fit LDS: top-of-tree tile, 16-bit descriptors
+                        int(rng.integers(16400, 18000))],     # > 16382 spheres: 32-bit descriptors, all from L2
+                       p=[0.05, 0.05, 0.05, 0.45, 0.285, 0.1, 0.01, 0.005]))
+    if max_spheres is not None and n > max_spheres:
+        n = max_spheres - n % 64
+    spread = float(rng.choice([0.5, 4.0, 30.0]))
+    data = []
+    for i in range(n):
+        r = float(rng.uniform(0.05, 1.5)) if rng.random() < 0.9 else float(rng.uniform(20, 2000))
+        pos = [float(x) for x in rng.uniform(-spread, spread, 3)]
+        if r > 10:
+            pos[1] = -r - 1.0
+        data.append((tuple(pos), r, _wild_material(rng, wild)))
+    if n >= 2 and rng.random() < 0.3:    # coincident spheres: exact ties in t
+        for _ in range(int(rng.integers(1, 4))):
+            a, b = rng.integers(0, n, 2)
+            data[int(b)] = (data[int(a)][0], data[int(a)][1], data[int(b)][2])
+
+    topo = int(rng.integers(0, 5))
+    if n > 400 and topo in (1, 3):
+        topo = 0                          # single leaf / chain of 1000s of spheres: too slow for the oracle
+    bvh_fn = [None, single_leaf_bvh, lambda m: median_split_bvh(m, int(rng.integers(1, 9))), chain_bvh,
+              lambda m: chain_bvh(m, far_first=True)][topo]
+    if topo in (3, 4) and n < 2:
+        bvh_fn = single_leaf_bvh
+    if bvh_fn is None and not callee_trees:
+        bvh_fn = brt.build_bvh
+    b = brt.prepare_buffers([(p, brt.RaytracedSphere(r), m) for p, r, m in data])
+    models = b.models.copy()
+    if wild:
+        for _ in range(int(rng.integers(0, 4))):
+            i = int(rng.integers(0, n))
+            if rng.random() < 0.5:
+                models["radius"][i] = _special(rng)
+            else:
+                models["position"][i, int(rng.integers(0, 3))] = _special(rng)
+    bvh = None if bvh_fn is None else bvh_fn(models)
+    if bvh is not None and wild and rng.random() < 0.2:      # a poisoned box
+        k = int(rng.integers(0, len(bvh)))
+        bvh["bounds_min" if rng.random() < 0.5 else "bounds_max"][k, int(rng.integers(0, 3))] = _special(rng)
+    b = brt.Buffers(models, b.materials, bvh)
+
+    big = n > 400
+    w, h = (int(rng.integers(1, 40)), int(rng.integers(1, 30))) if big else (int(rng.integers(1, 90)), int(rng.integers(1, 60)))
+    if rng.random() < 0.1:
+        h = int(rng.integers(60, 200))    # enough 8-row strips for every part of an 8-way split
+    # (32+ samples: the first frame of a view runs a pre-pass, which for a scene walked from an LDS tile + L2 also re-numbers the tree's
+    #  records by their use -- brt_api_order.cpp apply_hot_order)
+    spp = int(rng.choice([0, 1, 2, 3, 5, 9, 33, 64], p=[0.03, 0.29, 0.24, 0.19, 0.11, 0.06, 0.05, 0.03]))
+    bounces = int(rng.choice([0, 1, 3, 8, 20, 70], p=[0.1, 0.15, 0.3, 0.3, 0.1, 0.05]))
+    per_ray = n if topo in (1, 3, 4) else 40          # sphere/box tests per ray, roughly
+    while w * h * max(spp, 1) * (bounces + 1) * per_ray > 2e8 and w * h > 1:   # keep the oracle under about a second
+        w, h = max(1, w // 2), max(1, (h * 2) // 3)
+    pos = tuple(float(x) for x in rng.uniform(-8, 8, 3))
+    far_cam = rng.random() < 0.35
+    if far_cam:                           # a camera far outside the scene: distance log-uniform in [1, 2000] (the callee's tree must follow it:
+        dist = float(np.exp(rng.uniform(0.0, np.log(2000.0))))        # brt_sah.h "leaf boxes", VERDICT r4 #1)
+        v = rng.standard_normal(3)
+        pos = tuple(float(x) for x in dist * v / np.linalg.norm(v))
+    if rng.random() < 0.15:               # camera inside (or on) a sphere
+        i = int(rng.integers(0, n))
+        pos = tuple(float(x) for x in np.nan_to_num(models["position"][i], nan=0.0, posinf=9.0, neginf=-9.0))
+    target = tuple(float(x) for x in rng.uniform(-1, 1, 3))
+    up = (0.0, 1.0, 0.0)
+    if wild and rng.random() < 0.1:
+        up = tuple(float(x) for x in rng.uniform(-1, 1, 3))
+    fov = float(rng.uniform(0.2, 1.5))
+    if far_cam:                           # ... looking at the scene through a field of view as narrow as 1e-3
+        fov = float(np.exp(rng.uniform(np.log(1e-3), np.log(1.5))))
+    if wild and rng.random() < 0.15:
+        fov = float(rng.choice([1e-4, 3.1, 3.14159274, 0.0, 6.0]))
+    seed = float(np.float32(rng.random()))
+    if wild and rng.random() < 0.2:
+        seed = float(rng.choice([0.0, 1.0, -0.5, 1e9, np.nan, np.inf, 1e-30]))
+    window_height = int(rng.integers(1, 2400))
+    if wild and rng.random() < 0.05:
+        window_height = 0
+    near, far = 0.1, 1000.0
+    if wild and rng.random() < 0.1:
+        near, far = float(rng.choice([0.0, 5.0, 1e4])), float(rng.choice([0.0, 1.0, 1e30]))
+    lvl, cam, win = uniforms(w, h, spp=spp, bounces=bounces, pos=pos, target=target, fov=fov, seed=seed,
+                             level=brt.Raytracing(int(rng.integers(0, 4))), near=near, far=far, up=up,
+                             window_height=window_height)
+    raster = depth = None
+    if rng.random() < 0.4:
+        raster = rng.random((h, w, 4), dtype=np.float32)
+        depth = rng.random((h, w), dtype=np.float32) * np.float32(rng.choice([0.05, 1.0]))
+        if wild and rng.random() < 0.3:
+            depth[rng.random((h, w)) < 0.1] = np.float32(_special(rng))
+    mode = str(rng.choice(["run", "multi", "parts", "simple"], p=[0.6, 0.15, 0.15, 0.1]))
+    return dict(buffers=b, level=lvl, camera=cam, window=win, w=w, h=h, raster=raster, depth=depth, wild=wild, topo=topo,
+                mode=mode, n_parts=int(rng.choice([2, 3, 5, 8])), far_cam=far_cam)
 
 
 def fixture_buffers():

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""The child process of tests/test_hand_loops_gpu.py: renders every case of tests/hand_loops_cases.py in the library that BRT_LIB_PATH
-names -- the -DBRT_ASM_COUNT build, in which the hand-written loops count their own executions and active lanes -- and writes what it
-saw to the directory given as its argument:
+"""The child process of tests/test_hand_loops_gpu.py and tests/test_shade_production_gpu.py: renders every case of a case module -- its
+second argument, tests/hand_loops_cases.py by default; a module has SMALL, LARGE, MODES, SMALL_FRAMES, LARGE_FRAMES and large_size -- in
+the library that BRT_LIB_PATH names -- the -DBRT_ASM_COUNT build, in which the hand-written loops count their own executions and active
+lanes -- and writes what it saw to the directory given as its first argument:
     records.json        case / mode / frame -> {stats (last_stats of the production launch), asm and order (last_asm_counts and
                         last_order_meta of that launch),
                         counting (last_stats of the FLAG_COUNTERS frame that follows it), profile (its debug_profile())}
     frames.npz          the production frames of the small cases under the same keys
     <case>.npy          the recorded (third) production frame of a large case
 It asserts nothing: the parent does.  A HIP error raises out of the binding and ends the process with a non-zero status.
-    BRT_LIB_PATH=ab/libasmcount.so python tests/tools/hand_loops_child.py OUT_DIR"""
+    BRT_LIB_PATH=ab/libasmcount.so python tests/tools/hand_loops_child.py OUT_DIR [CASE_MODULE]"""
+import importlib
 import json
 import os
 import sys
@@ -20,7 +22,6 @@ sys.path.insert(0, os.path.dirname(TESTS))
 sys.path.insert(0, TESTS)
 
 import bevyray_amd as brt  # noqa: E402
-import hand_loops_cases as hl  # noqa: E402
 
 
 def _record(p, lvl, cam, win, w, h):
@@ -37,6 +38,7 @@ def _record(p, lvl, cam, win, w, h):
 
 def main():
     out_dir = sys.argv[1]
+    hl = importlib.import_module(sys.argv[2] if len(sys.argv) > 2 else "hand_loops_cases")
     import torch
     n_cus = torch.cuda.get_device_properties(0).multi_processor_count
     records, frames = {"lib": os.environ.get("BRT_LIB_PATH", ""), "n_cus": n_cus}, {}
