@@ -96,20 +96,41 @@ BRT_HD bool sah_finite(double x) { return x - x == 0.0; }   // false for +-inf a
 // accepted by as long as the box is CONSERVATIVE for the float arithmetic of the two tests -- a ray that the f32 sphere test accepts
 // must pass the f32 slab test of the sphere's box.  A caller's tree is honoured as it comes; the tree this library builds itself pads
 // by what that needs instead of by 0.1, because the pad is most of a small sphere's box (r = 0.2: half-width 0.3 -> 0.21, half the
-// surface) and the walk pays for it: interior visits per ray 12.7 -> 11.2 (cover), 19.5 -> 17.1 (10 k grid), sphere tests 2.3 -> 1.8.
-// What it needs: the sphere test's discriminant h*h - a*c carries a rounding error of ~2^-24 of its terms, dist^2 * a, i.e. it can
-// accept a ray whose true distance from the centre exceeds r by up to ~2^-24 * dist^2 / (2 r), dist = the distance the ray has
-// travelled to the sphere; the slab arithmetic's own error, ~2^-22 * dist, is small beside it.  dist is bounded by the REACH of the
-// frame: rays start at the camera or on a sphere, so reach = max(2 S, |camera|_1 + S + L) with S the scene's scale (the largest
-// |c|_1 + r over its ordinary spheres, r <= 100: a ground sphere of radius 1000 is not a distance rays travel between its own
-// points -- it is convex) and L the longest tangent from the camera to such a big sphere (how far a primary ray can land on the ground
-// away from the camera).  pad = clamp(2^-24 * reach^2 / r, 0.01, 0.1): twice the model's bound, the reference's own 0.1 where the
-// model asks for more (there the reference's culling is as marginal as any), never less than 0.01.  The camera is not known at
+// surface) and the walk pays for it: interior visits per ray 12.7 -> 11.2 (cover), 19.5 -> 17.1 (10 k grid), sphere tests 2.3 -> 1.8
+// at the 0.01 floor; at the pads of the rule below 10.42 -> 10.63 (cover camera, r = 0.2: 0.027) and 16.46 -> 17.84 (grid: 0.019 .. 0.095).
+// What it needs, with u = 2^-24, D = |c - o| the distance of the ray's origin from the centre, a unit direction and rho the true
+// distance of the f32 ray's line from the f32 centre: hit_sphere accepts when its discriminant h*h - a*c, c = oc.oc - r*r, rounds to
+// >= 0; exactly it is a (r^2 - rho^2), so a ray is accepted up to rho^2 - r^2 <= E, the sum of what the roundings move (first
+// order in u; every dot is (x*x' + y*y') + z*z', at most three roundings on a term):
+//     oc = c - o, a relative u on each component: the discriminant moves by 2 (h d - oc).(u oc) <= 2 u rho D    (|h d - oc| = rho)
+//     h = d.oc                 3 u D on h (|d.oc| summed over absolute terms <= D), 2 h times that on h*h:        6 u D^2
+//     h*h                      its own rounding:                                                                   1 u D^2
+//     oc.oc                    three roundings on positive terms:                                                  3 u D^2
+//     r*r                                                                                                          1 u r^2
+//     c = oc.oc - r*r          its own rounding, |c| <= D^2:                                                       1 u D^2
+//     a = d.d                  3 u on a, times |c|:                                                                3 u D^2
+//     a*c                      its own rounding:                                                                   1 u D^2
+//     h*h - a*c                its own rounding is relative to the result: it cannot change the sign               0
+// E <= u (15 D^2 + 2 rho D + r^2), and rho - r = (rho^2 - r^2) / (rho + r) <= E / (2 r) = u (7.5 D^2 / r + D + r / 2).  (Measured
+// over 4e7 grazing rays: rho^2 - r^2 reaches 9.45 u t^2, the roundings rarely line up -- docs/experiments.md "Grazing rays against
+// the tight boxes"; the rule's former constant, 2^-24, covered 2 u t^2 and lost hits.)  The slab test adds its own error: a plane of the box
+// c -+ (r + pad) is off by u (|c_k| + 2 (r + pad)) (two roundings), and a plane's crossing t_k = (b_k - o_k) * (1 / d_k) carries three
+// roundings, which move the crossing by 3 u |b_k - o_k| <= 3 u (D + r + pad) along the axis: u (3 D + 5 (r + pad) + |c_k|) in all.
+// dist is bounded by the REACH of the frame: rays start at the camera or on a sphere, so reach R = max(2 S, |camera|_1 + S + L) with S
+// the scene's scale (the largest |c|_1 + r over its ordinary spheres, r <= 100: a ground sphere of radius 1000 is not a distance
+// rays travel between its own points -- it is convex) and L the longest tangent from the camera to such a big sphere (how far a
+// primary ray can land on the ground away from the camera); D + r <= |o|_1 + |c|_1 + r <= R and |c_k| <= R / 2.
+// pad = clamp(8 u R^2 / r, 0.01, 0.1) = clamp(2^-21 R^2 / r, ...): 8 is the smallest power of two above the 7.5 of the sphere
+// test, and the half it leaves pays for the rest, u (D + r / 2) + u (3 D + 5 r + 0.5 + R / 2) <= u (4.625 R + 0.5) where R >= 12 r
+// (4 D + 5.5 r <= 4 R + 1.5 r): there 0.5 u R^2 / r >= 6 u R.  Where R < 12 r <= 1200 the whole need is at most
+// u (7.5 * 12 R + 4.5 R + 1.5 r + 0.5) < 0.007: under the floor.  (Second-order terms are 2^-24 of all this.)
+// Above the ceiling the tree keeps the reference's own 0.1 (there the reference's culling is as marginal as any).  The camera is not known at
 // upload: brt_upload_scene builds for reach = 2 S, and a render call whose camera needs more rebuilds the tree on the GPU first
 // (brt_api.cpp ensure_tree_reach; round 4 ignored the camera and lost pixels from a distance of ~260 on: VERDICT r4).
-// Measured: on the 10 k grid (S = 100, pad 0.012) the first pixel of a 640 x 360 x 16 spp frame differs from the brute-force frame at
+// Measured: on the 10 k grid (S = 100) the first pixel of a 640 x 360 x 16 spp frame differs from the brute-force frame at
 // a pad of 1e-4, none at 1e-3 (docs/experiments.md); the -m gpu suite compares the frames of configs 2 and 5 in this tree with the
-// oracle's frames in the caller's 0.1-padded PLOC tree at full size, and far-camera frames (x 20 ... x 60 the cover distance).
+// oracle's frames in the caller's 0.1-padded PLOC tree at full size, and far-camera frames (x 20 ... x 60 the cover distance); grazing
+// rays from near the reach, in scenes whose pads lie between the clamps, against one leaf of all spheres: tests/test_tree_conservative.py.
 // `reach` enters the builders as a FLOOR on the scale (scale = max(S, reach / 2)), as the max's initial key: still an integer max.
 BRT_HD uint32_t sah_reach_key(float reach) {      // initial value of the scale's key-max (kSahKeyMaxIdentity: no floor)
     const float half = 0.5f * reach;
@@ -122,7 +143,7 @@ BRT_HD float sah_scale_term(const float* position, float radius) {      // |c|_1
 BRT_HD float sah_model_pad(float radius, float scale) {
     if (!(radius > 0.0f) || !(radius <= 100.0f) || !(scale - scale == 0.0f)) return 0.1f;
     const float d = 2.0f * scale;
-    float p = (5.9604645e-8f * (d * d)) / radius;      // 2^-24
+    float p = (4.7683716e-7f * (d * d)) / radius;      // 2^-21 = 8 * 2^-24
     p = p > 0.01f ? p : 0.01f;
     return p < 0.1f ? p : 0.1f;                         // (a NaN stays out by the tests above)
 }

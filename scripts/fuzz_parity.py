@@ -167,7 +167,8 @@ def main():
                 prod_checked += 1
                 split_checked += 1 if "BRT_SPLIT_FORCE" in variant else 0
                 hot_checked += 1 if st2.get("hot_records", 0) else 0
-            # the callee's SAH tree pads its leaf boxes by less than the reference's 0.1 (brt_sah.h sah_model_pad): on well-conditioned scenes
+            # the callee's SAH tree pads its leaf boxes by less than the reference's 0.1 (brt_sah.h sah_model_pad: clamp(2^-21 reach^2 / r,
+            # 0.01, 0.1), held to brute force on grazing rays by tests/test_tree_conservative.py): on well-conditioned scenes
             # without coincident spheres (exact ties are decided by the visiting order) the frame must also be the one of the caller's
             # 0.1-padded PLOC tree -- i.e. the tighter boxes culled nothing a ray is accepted by.  Well-conditioned = no sphere of radius
             # > 10: this generator's giant spheres (radius 20-2000, hundreds of them overlapping at coordinates in the thousands) are

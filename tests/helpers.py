@@ -176,9 +176,13 @@ def dev(a):
 
 
 def guarded(n_bytes, guard, fill):
-    """A device buffer of n_bytes with `guard` bytes behind it, all of them `fill`."""
+    """A device buffer of n_bytes with `guard` bytes behind it, all of them `fill`.  The fill is a kernel on torch's stream and the
+    context's own stream is non-blocking: the buffer is handed out once the fill has landed, so that it cannot overwrite what a call
+    on the context's stream writes (seen once: a buffer of 48 bytes that came back all `fill`)."""
     import torch
-    return torch.full((n_bytes + guard,), fill, dtype=torch.uint8, device="cuda")
+    buf = torch.full((n_bytes + guard,), fill, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    return buf
 
 
 @functools.lru_cache(maxsize=None)

@@ -341,7 +341,7 @@ def test_sah_builder_contract_depth_cap_and_determinism():
         assert np.all(leaves["model_count"] == 1) and sorted(leaves["index"].tolist()) == list(range(n))
         inner = nodes[nodes["model_count"] == 0]
         assert len(inner) == n - 1 and np.all(inner["index"] % 2 == 1)                         # children at odd / even slot pairs
-    # finite scenes: every leaf box is the sphere's bounds padded by the rule of brt_sah.h -- clamp(2^-24 (2 S)^2 / r, 0.01, 0.1), S the
+    # finite scenes: every leaf box is the sphere's bounds padded by the rule of brt_sah.h -- clamp(2^-21 (2 S)^2 / r, 0.01, 0.1), S the
     # largest |c|_1 + r over the spheres of radius <= 100; larger spheres keep Model::aabb's 0.1 (extract.rs:220-227) -- and every
     # parent holds its children
     m = cases[0]
@@ -356,7 +356,7 @@ def test_sah_builder_contract_depth_cap_and_determinism():
             c, r = m[nd["index"]]["position"], f32(m[nd["index"]]["radius"])
             if r <= 100:
                 d = f32(2.0) * f32(scale)
-                p = (f32(5.9604645e-8) * (d * d)) / r
+                p = (f32(4.7683716e-7) * (d * d)) / r
                 p = f32(min(max(p, f32(0.01)), f32(0.1)))
             else:
                 p = f32(0.1)
@@ -391,11 +391,15 @@ def test_tree_reach_rule_and_pads_follow_the_camera():
     _, cam, _ = brt.cover_camera(160, 90, 1, 1)
     S, level, reach = brt.tree_reach(m, cam)
     assert S == S_want
-    # the cover camera: |(13, 2, 3)|_1 + S + the tangent to the ground sphere ~ 105 > 2 S, yet every pad of that reach is still the
-    # 0.01 floor -> the tree of the scene's own extent already is that tree: level 0
-    assert (level, reach) == (0, 0.0)
+    # the cover camera: |(13, 2, 3)|_1 + S + the tangent to the ground sphere ~ 105 > 2 S: level 5, and at that reach the pads of the
+    # r = 0.2 spheres have left the 0.01 floor (2^-21 * 106.5^2 / 0.2 = 0.027): its own tree.  Up to a reach of 64 every pad is still
+    # the floor -> the tree of the scene's own extent already is that tree
+    assert level == 5 and reach == float(f32(2.0 * S * 2.0 ** 1.25))
     base = brt.build_bvh_sah(m)
-    assert np.array_equal(base.view(np.uint8), brt.build_bvh_sah(m, 105.0).view(np.uint8))
+    assert np.array_equal(base.view(np.uint8), brt.build_bvh_sah(m, 64.0).view(np.uint8))
+    assert not np.array_equal(base.view(np.uint8), brt.build_bvh_sah(m, reach).view(np.uint8))
+    near = cam.copy(); near["position"][0] = (2.0, 0.3, 1.0)      # a camera among the spheres, 0.3 above the ground: need ~ 50 > 2 S
+    assert brt.tree_reach(m, near)[1:] == (0, 0.0)                # ... level 1 by the distances, level 0 by the pads
     # moving out along the view axis: the level never falls, the reach covers |cam|_1 + S + tangent, the pads grow up to the reference's 0.1
     last_level, last_pads = 0, _leaf_pads(m, base)
     for k in (2, 5, 10, 20, 30, 60, 1000, 1e6):
@@ -415,7 +419,7 @@ def test_tree_reach_rule_and_pads_follow_the_camera():
         # the rule of brt_sah.h at this reach, in f32, for the r = 0.2 spheres
         small = np.isclose(m["radius"], 0.2)
         d = f32(2.0) * max(f32(S), f32(0.5) * f32(reach))
-        want = min(max((f32(5.9604645e-8) * (d * d)) / f32(0.2), f32(0.01)), f32(0.1))
+        want = min(max((f32(4.7683716e-7) * (d * d)) / f32(0.2), f32(0.01)), f32(0.1))
         assert np.allclose(pads[small], float(want), atol=2e-6)
         last_level, last_pads = level, pads
     assert last_level >= 70 and np.allclose(last_pads, 0.1, atol=1e-4)           # far enough out: the reference's own boxes
@@ -439,7 +443,7 @@ def test_far_camera_frames_in_the_callee_tree_equal_the_reference_tree(oracle):
     for k in (1, 20, 25, 30):
         lvl, cam, win = uniforms(w, h, 4, 4, (13.0 * k, 2.0 * k, 3.0 * k), (0, 0, 0), 0.4 / k, 0.5, far=1e5)
         _, level, reach = brt.tree_reach(b.models, cam)
-        assert (level > 0) == (k > 1)
+        assert level >= 5 and (level > 5) == (k > 1)      # (the cover camera's own level: 5)
         frames = [oracle.render(brt.Buffers(b.models, b.materials, t), lvl, cam, win, w, h)[0]
                   for t in (brt.build_bvh_sah(b.models, reach), b.bvh, brute, brt.build_bvh_sah(b.models))]
         assert np.array_equal(frames[0].view(np.uint32), frames[1].view(np.uint32))

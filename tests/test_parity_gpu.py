@@ -189,10 +189,14 @@ def test_hand_made_bvh_topologies(plugin, oracle):
         assert_frames_equal(got, ref)          # pixels do not depend on the topology
     # callee-built BVH (bvh = None): binned SAH inside brt_upload_scene, or PLOC on the GPU with the quality knob off --
     # same pixels, and exactly the oracle's counters on the tree the library says it builds
-    for quality, tree in ((1, brt.build_bvh_sah(b.models)), (0, brt.build_bvh(b.models))):
+    # (the SAH tree is the one of the cover camera's reach -- level 5, pads above the floor: brt_sah.h -- which the context reports)
+    reach = brt.tree_reach(b.models, cam)[2]
+    assert reach > 0
+    for quality, tree in ((1, brt.build_bvh_sah(b.models, reach)), (0, brt.build_bvh(b.models))):
         with plugin.tuning(BRT_BVH_QUALITY=quality):
             got = plugin.node.run(lvl, cam, win, 64, 36, buffers=brt.Buffers(b.models, b.materials, None), flags=brt.FLAG_COUNTERS)
             stats = dict(plugin.node.last_stats)
+        assert stats["tree_reach"] == (reach if quality else 0.0), stats
         assert_frames_equal(got, ref)
         _, cnt = oracle.render(brt.Buffers(b.models, b.materials, tree), lvl, cam, win, 64, 36)
         assert {k: stats[k] for k in COUNTER_KEYS} == cnt, quality
@@ -600,7 +604,8 @@ def test_config2_full_size_properties(plugin, oracle):
     f3 = plugin.node.run(lvl, cam, win, w, h, buffers=brt.Buffers(b.models, b.materials, None), flags=brt.FLAG_COUNTERS)
     s3 = dict(plugin.node.last_stats)
     assert_frames_equal(f3, want)
-    _, cnt3 = oracle.render(brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models)), lvl, cam, win, w, h)
+    assert s3["tree_reach"] == brt.tree_reach(b.models, cam)[2] > 0       # (the cover camera's own reach: level 5)
+    _, cnt3 = oracle.render(brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models, s3["tree_reach"])), lvl, cam, win, w, h)
     assert {k: s3[k] for k in COUNTER_KEYS} == cnt3
     st = _timed_combination(plugin, b, lvl, cam, win, w, h, want, cnt["rays"])
     assert st["kernel_variant"] == 2 and st["scene_in_lds"] == 1
@@ -943,7 +948,7 @@ def test_far_camera_callee_tree_is_rebuilt_for_the_camera(plugin, oracle, kind):
     w, h, spp, bounces = 160, 90, 4, 4
     plugin.node.write_buffers(brt.generate_scene(brt.SCENE_RTIOW_FINAL, 1))     # (another scene first: the upload below is a real one)
     rebuilt = {}
-    for k in (1, 20, 30, 60, 57, 1):
+    for k in (1, 5, 20, 30, 60, 57, 1):
         lvl, cam, win = _far_camera(k, w, h, spp, bounces)
         got = plugin.node.run(lvl, cam, win, w, h, buffers=nb, flags=brt.FLAG_COUNTERS)
         st = dict(plugin.node.last_stats)
@@ -951,9 +956,9 @@ def test_far_camera_callee_tree_is_rebuilt_for_the_camera(plugin, oracle, kind):
         level, reach = brt.tree_reach(b.models, cam)[1:]
         twin = brt.build_bvh_sah(b.models, st["tree_reach"])
         # never a tree whose pads are below what this camera needs: built for at least its reach -- or, where every pad has already
-        # reached the reference's 0.1 (the grid's pads do at x 30), the very same bytes
+        # reached the reference's 0.1 (both scenes' pads do at x 20), the very same bytes
         assert st["tree_reach"] >= reach or np.array_equal(twin.view(np.uint8), brt.build_bvh_sah(b.models, reach).view(np.uint8))
-        assert st["tree_reach"] == reach or k in (57, 60)
+        assert st["tree_reach"] == reach or k in (30, 57, 60)
         want, cnt = oracle.render(brt.Buffers(b.models, b.materials, twin), lvl, cam, win, w, h)
         assert_frames_equal(got, want)
         assert {q: st[q] for q in COUNTER_KEYS} == cnt
@@ -972,8 +977,10 @@ def test_far_camera_callee_tree_is_rebuilt_for_the_camera(plugin, oracle, kind):
             assert (~ref_ok).sum() > 100                                     # the reference's own tree is past its limit here
             assert (differs & ref_ok).sum() <= 32, (k, int((differs & ref_ok).sum()))
             assert (got.view(np.uint32) != truth.view(np.uint32)).any(axis=2).sum() <= 1.05 * (~ref_ok).sum() + 16
-    assert rebuilt[20] == [1] and rebuilt[30] == [1] and rebuilt[60] == [1 if kind == brt.SCENE_COVER else 0] and rebuilt[57] == [0]
-    assert rebuilt[1] == [0, 1]                  # the upload's tree serves the cover camera; coming back from x 57 rebuilds the tight one
+    assert rebuilt[5] == [1] and rebuilt[20] == [1] and rebuilt[30] == [0] and rebuilt[60] == [0] and rebuilt[57] == [0]
+    # the upload's tree serves the cover camera in the grid (its 2 S covers that camera); the cover scene's camera stands further out
+    # than its 2 S and the r = 0.2 pads of its reach have left the floor: a rebuild.  Coming back from x 57 rebuilds the tight tree
+    assert rebuilt[1] == [1 if kind == brt.SCENE_COVER else 0, 1]
     # the tree of the scene's own extent does lose pixels out there (what round 4 shipped): the case is real
     lvl, cam, win = _far_camera(30, w, h, spp, bounces)
     blind = oracle.render(brt.Buffers(b.models, b.materials, brt.build_bvh_sah(b.models)), lvl, cam, win, w, h)[0]

@@ -145,7 +145,7 @@ def _path(kind, w, h, i):
     if kind == "turn":                       # the cover view, then the view straight back from the same point
         target = (0.0, 0.0, 0.0) if i % 2 == 0 else (26.0, 4.0, 6.0)
         return uniforms(w, h, 4, 8, COVER_POS, target, 0.4, _seed(i))
-    k = (20.0, 30.0, 30.0)[i]                # far: the cover view from 20x and 30x (the callee's tree is rebuilt for its reach)
+    k = (4.0, 8.0, 8.0)[i]                   # far: the cover view from 4x and 8x (the callee's tree is rebuilt for its reach; from 20x on every pad is 0.1)
     return uniforms(w, h, 4, 8, (13.0 * k, 2.0 * k, 3.0 * k), (0.0, 0.0, 0.0), 0.4 / k, _seed(i), far=1.0e5)
 
 
