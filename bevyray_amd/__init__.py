@@ -19,6 +19,8 @@ from .raytracing import (  # noqa: F401
     make_volume, volume_probes, volume_sample_host,
     ENVMAP_TAP_DTYPE, ENVMAP_TAPS_COSINE, ENVMAP_TAPS_GGX, ENVMAP_TEXEL16_DTYPE, ENVMAP_TEXEL_DTYPE, envmap_directions,
     envmap_downsample_host, envmap_filter_host, envmap_level_offsets, envmap_taps,
+    LIGHTMAP_INFO_DTYPE, LIGHTMAP_POINT_DTYPE, LIGHTMAP_STATUS_EMPTY, lightmap_dilate_host, lightmap_directions, lightmap_ray,
+    lightmap_sphere_points,
     LENS_DTYPE, lens, lens_origin_bound, lens_ray, lens_seed,
     blend_covered, prepare_buffers, rtiow_camera, srgb_thresholds, tile_rows, upscale_window, validate_scene,
 )

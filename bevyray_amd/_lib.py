@@ -123,6 +123,15 @@ _PROTOTYPES = {
     "brt_envmap_filter_device": (_I32, [_VP, _VP, _U32, _VP, _U32, _U32, _VP, _VP, _U32]),
     "brt_bake_envmap_device": (_I32, [_VP, C.POINTER(_F), _U32, _U32, _U32, _U32, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
     "brt_bake_envmap": (_I32, [_VP, C.POINTER(_F), _U32, _U32, _U32, _U32, _U32, _U32, _F, _VP, _U32, C.POINTER(C.c_uint64)]),
+    "brt_host_lightmap_directions": (_I32, [_U32, C.POINTER(_F)]),
+    "brt_host_lightmap_ray": (_I32, [_VP, _U32, _U32, _VP]),
+    "brt_host_lightmap_sphere_points": (_I32, [C.POINTER(_F), _F, _U32, _F, _U32, _U32, _VP]),
+    "brt_host_lightmap_dilate": (_I32, [_VP, _U32, _U32, _U32, _U32, _VP]),
+    "brt_lightmap_rays_device": (_I32, [_VP, _VP, _U32, _U32, _VP, _VP, _U32]),
+    "brt_lightmap_resolve_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U32]),
+    "brt_lightmap_dilate_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _U32]),
+    "brt_bake_lightmap_device": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _U32, _U32, _F, _VP, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
+    "brt_bake_lightmap": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _U32, _U32, _F, _VP, _VP, _U32, C.POINTER(C.c_uint64)]),
     "brt_host_pixel_ray": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP]),
     "brt_upscale_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),

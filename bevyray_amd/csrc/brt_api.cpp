@@ -1,5 +1,5 @@
 // brt_api.cpp -- the extern "C" boundary (include/bevyray_amd.h): context lifecycle, knobs, scene upload, tree builds.  Its other
-// units: brt_api_launch.cpp, brt_api_order.cpp, brt_api_render.cpp, brt_api_post.cpp, brt_api_upscale.cpp, brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp, brt_api_envmap.cpp; brt_frame.h is what they share.
+// units: brt_api_launch.cpp, brt_api_order.cpp, brt_api_render.cpp, brt_api_post.cpp, brt_api_upscale.cpp, brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp, brt_api_envmap.cpp, brt_api_lightmap.cpp; brt_frame.h is what they share.
 //
 // What each export replaces in the reference is cited in the header.  This file holds no ray
 // arithmetic: rays are traced only by the HIP kernels (brt_kernels.hip).  Without a usable
@@ -23,7 +23,7 @@ void free_device(DeviceCtx& dc) {
              dc.d_raster_depth, dc.d_bvh_scratch, dc.d_tile_cost, dc.d_tile_order, dc.d_order_meta, dc.d_order_scratch, dc.d_slice_state,
              dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_uplow, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits,
              dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.probe_dirs.d, dc.d_list_io, dc.d_volume_probes,
-             dc.d_envmap, dc.envmap_taps.d})
+             dc.d_envmap, dc.envmap_taps.d, dc.d_lightmap, dc.lightmap_dirs.d})
         if (p) (void)hipFree(p);
     if (dc.h_stage) (void)hipHostFree(dc.h_stage);
     for (hipEvent_t e : {dc.ev_copy, dc.ev_asm, dc.ev_in, dc.ev_g0, dc.ev_g1, dc.ev_pack, dc.ev_strip, dc.ev_strip_read, dc.ev_q, dc.ev_dn,

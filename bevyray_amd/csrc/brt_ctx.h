@@ -175,6 +175,11 @@ struct DeviceCtx {
     char* d_envmap = nullptr;
     size_t envmap_cap = 0;
     DeviceTable envmap_taps;
+    // lightmaps (brt_lightmap.h), first device only: the resolved f32 image of a bake and the second image of the dilation passes, and
+    // the hemisphere's direction table {x, y, z, 0}, kept by n_dirs.  Ordered by ev_q like the probe buffers
+    char* d_lightmap = nullptr;
+    size_t lightmap_cap = 0;
+    DeviceTable lightmap_dirs;
     // GPU BVH build
     char* d_bvh_scratch = nullptr;
     size_t bvh_scratch_cap = 0;

@@ -215,7 +215,7 @@ bool blend_post_on(uint32_t level, uint32_t flags);
 int32_t post_flags_check(brt_ctx* ctx, uint32_t level, uint32_t flags);
 
 // ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp,
-// brt_api_envmap.cpp, brt_api_pixels.cpp) ----
+// brt_api_envmap.cpp, brt_api_lightmap.cpp, brt_api_pixels.cpp) ----
 inline int32_t caller_stream_flags_check(brt_ctx* ctx, uint32_t flags) {
     if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
     return BRT_OK;

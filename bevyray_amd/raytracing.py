@@ -485,6 +485,51 @@ def envmap_filter_host(src, taps, dst_size: int) -> np.ndarray:
     return out
 
 
+# lightmaps: brt_bake_lightmap* / brt_lightmap_*_device (include/bevyray_amd.h): one surface point per texel of a chart, the texels
+# (mean linear radiance over the hemisphere: irradiance = pi * rgb; a = 1 traced, 0.5 dilated, 0 neither) and the optional info records
+LIGHTMAP_STATUS_EMPTY = 16
+LIGHTMAP_POINT_DTYPE = np.dtype([("position", np.float32, 3), ("seed", np.uint32), ("normal", np.float32, 3), ("offset", np.float32)])
+LIGHTMAP_INFO_DTYPE = np.dtype([("hits", np.uint32), ("status", np.uint32)])
+assert LIGHTMAP_POINT_DTYPE.itemsize == 32 and LIGHTMAP_INFO_DTYPE.itemsize == 8
+
+
+def lightmap_directions(n_dirs: int) -> np.ndarray:
+    """brt_host_lightmap_directions: the (n_dirs, 3) f32 cosine-weighted hemisphere directions about +z.  Host arithmetic."""
+    n = int(n_dirs)
+    out = np.zeros((n if 0 < n <= 65536 else 0, 3), np.float32)       # (a count out of range is refused before anything is written)
+    _lib.check(_lib.load().brt_host_lightmap_directions(n, out.ctypes.data_as(C.POINTER(C.c_float))))
+    return out
+
+
+def lightmap_ray(point, n_dirs: int, k: int) -> np.ndarray:
+    """brt_host_lightmap_ray: entry k of one LIGHTMAP_POINT_DTYPE point as one RADIANCE_RAY_DTYPE record.  The compiled twin of the
+    kernel behind RayTracingNode.lightmap_rays_device."""
+    pt = np.ascontiguousarray(point, LIGHTMAP_POINT_DTYPE).reshape(1)
+    ray = np.zeros(1, RADIANCE_RAY_DTYPE)
+    _lib.check(_lib.load().brt_host_lightmap_ray(pt.ctypes.data, int(n_dirs), int(k), ray.ctypes.data))
+    return ray
+
+
+def lightmap_sphere_points(centre, radius: float, width: int, height: int, seed: int = 0, offset: float = 0.0) -> np.ndarray:
+    """brt_host_lightmap_sphere_points: the (height, width) LIGHTMAP_POINT_DTYPE points of the latitude-longitude chart of one sphere
+    (azimuth about +Y along x, polar angle from +Y along y).  One parameterisation: a host with other UVs makes its own points."""
+    w, h = int(width), int(height)
+    out = np.zeros((h, w) if 0 < w <= 16384 and 0 < h <= 16384 else (0, 0), LIGHTMAP_POINT_DTYPE)
+    _lib.check(_lib.load().brt_host_lightmap_sphere_points(_f3(centre), float(radius), int(seed), float(offset), w, h,
+                                                           out.ctypes.data if out.size else None))
+    return out
+
+
+def lightmap_dilate_host(texels, passes: int, wrap_u: bool = False) -> np.ndarray:
+    """brt_host_lightmap_dilate: `passes` dilation passes over an (H, W, 4) f32 image.  The compiled twin of the kernel behind
+    RayTracingNode.lightmap_dilate_device."""
+    src = np.ascontiguousarray(texels, np.float32)
+    h, w = src.shape[:2]
+    out = np.zeros(src.shape, np.float32)
+    _lib.check(_lib.load().brt_host_lightmap_dilate(src.ctypes.data, w, h, int(passes), int(wrap_u), out.ctypes.data))
+    return out
+
+
 def pixel_ray(camera, window, width: int, height: int, px: int, py: int) -> np.ndarray:
     """brt_host_pixel_ray: the pixel-centre ray of pixel (px, py) as one RAY_DTYPE record (t_max = inf, user = py * width + px): the
     ray the guide buffer casts for that pixel.  Host arithmetic; for picking through RayTracingNode.query_rays."""
@@ -1231,6 +1276,50 @@ class RayTracingNode:
         p = self._p
         _lib.check(p._lib.brt_envmap_filter_device(p._ctx, d_src or None, int(src_size), d_taps or None, int(n_taps), int(dst_size),
                                                    d_out or None, *_stream_args(stream)), p._ctx)
+
+    # -- lightmaps (include/bevyray_amd.h "lightmaps") ----------------------------------------------
+
+    def bake_lightmap(self, points, n_dirs: int, bounces: int, passes: int = 0, wrap_u: bool = False, origin_bound: float = 0.0,
+                      device: bool = False, stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F, info: bool = True):
+        """brt_bake_lightmap*: per surface point n_dirs radiance entries of one sample and at most `bounces` bounces over the hemisphere
+        of its normal, made linear and averaged into a texel, then `passes` dilation passes.  device=False: `points` is an (H, W) array of
+        LIGHTMAP_POINT_DTYPE in host memory -> (the (H, W, 4) texels, f32 or with out_format=FLAG_OUT_RGBA16F f16, and the (H, W)
+        LIGHTMAP_INFO_DTYPE records or None) (synchronous).  device=True: `points` is (d_points, width, height, d_out, d_info or 0),
+        device pointers on the first device -> the call's stats; stream rule as for bake_probes.  last_probe_stats holds the stats."""
+        lib = self._p._lib
+        tail = (int(n_dirs), int(bounces), int(passes), int(wrap_u), float(origin_bound))
+        if device:
+            d_points, width, height, d_out, d_info = points
+            return _bake_call(self, lib.brt_bake_lightmap_device, d_points or None, int(width), int(height), *tail, d_out or None,
+                              d_info or None, *_stream_args(stream, int(out_format)))
+        points = np.ascontiguousarray(points, LIGHTMAP_POINT_DTYPE)
+        h, w = points.shape
+        out = np.zeros((h, w, 4), np.float16 if out_format == FLAG_OUT_RGBA16F else np.float32)
+        rec = np.zeros((h, w), LIGHTMAP_INFO_DTYPE) if info else None
+        _bake_call(self, lib.brt_bake_lightmap, points.ctypes.data if points.size else None, w, h, *tail,
+                   out.ctypes.data if out.size else None, rec.ctypes.data if info and rec.size else None, int(out_format))
+        return out, rec
+
+    def lightmap_rays_device(self, d_points: int, n_points: int, n_dirs: int, d_rays: int, stream: Optional[int] = None):
+        """brt_lightmap_rays_device: the generation step alone -> n_points * n_dirs RADIANCE_RAY_DTYPE entries at d_rays, point-major."""
+        p = self._p
+        _lib.check(p._lib.brt_lightmap_rays_device(p._ctx, d_points or None, int(n_points), int(n_dirs), d_rays or None,
+                                                   *_stream_args(stream)), p._ctx)
+
+    def lightmap_resolve_device(self, d_results: int, d_points: int, n_points: int, n_dirs: int, d_out: int, d_info: int = 0,
+                                stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):
+        """brt_lightmap_resolve_device: the resolve step alone, n_points * n_dirs RADIANCE_DTYPE results (point-major) and their points
+        -> n_points texels at d_out and, with d_info, LIGHTMAP_INFO_DTYPE records."""
+        p = self._p
+        _lib.check(p._lib.brt_lightmap_resolve_device(p._ctx, d_results or None, d_points or None, int(n_points), int(n_dirs),
+                                                      d_out or None, d_info or None, *_stream_args(stream, int(out_format))), p._ctx)
+
+    def lightmap_dilate_device(self, d_texels: int, width: int, height: int, passes: int, wrap_u: bool, d_out: int,
+                               stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):
+        """brt_lightmap_dilate_device: `passes` dilation passes over the RGBA32F image at d_texels -> d_out (passes = 0 copies)."""
+        p = self._p
+        _lib.check(p._lib.brt_lightmap_dilate_device(p._ctx, d_texels or None, int(width), int(height), int(passes), int(wrap_u),
+                                                     d_out or None, *_stream_args(stream, int(out_format))), p._ctx)
 
     def deinterleave_device(self, d_tiles: int, n_parts: int, width: int, height: int, d_frame: int,
                             stream: Optional[int] = None, out_format: int = FLAG_OUT_RGBA32F):

@@ -715,6 +715,93 @@ int32_t brt_bake_envmap_device(brt_ctx* ctx, const float* position3, uint32_t se
 int32_t brt_bake_envmap(brt_ctx* ctx, const float* position3, uint32_t seed, uint32_t size, uint32_t levels, uint32_t samples,
                         uint32_t bounces, uint32_t n_taps, float origin_bound, void* out, uint32_t flags, uint64_t* out_stats8_or_null);
 
+/* ---- lightmaps --------------------------------------------------------------------------------------------------------------------------
+ * What light arrives at points ON SURFACES: per point the rays of a fixed direction set over the cosine-weighted hemisphere of its normal
+ * are traced as radiance entries, made linear and averaged into the texel of a chart, and the chart's edge is dilated so that the texture
+ * holds under bilinear filtering -- the image of a level-1 / level-2 host's baked lighting (Bevy's `Lightmap { image, uv_rect }`).  On the
+ * context's first device.  Rule, kernels and costs: DESIGN.md "Lightmaps".  Deterministic: f32, every operation separately rounded,
+ * divide and sqrt correctly rounded, in the order written here; the default policy only.
+ *   point, 32 bytes   { f32 position[3]; u32 seed; f32 normal[3]; f32 offset }, one per texel, row-major, width * height of them.  The
+ *                     host rasterises its own UV charts into points; brt_host_lightmap_sphere_points gives one chart of one sphere.
+ *                     EMPTY: the three normal words are all +0.0 / -0.0 (no chart covers the texel); not an error, and looked at first.
+ *                     INVALID: len2 (below) is 0, INF or NaN; a position word is INF or NaN; offset is INF, NaN or < 0.
+ *   direction table   n_dirs in [1, 65536]; for k = 0 .. n_dirs - 1: u = (k + 0.5) / n_dirs, r = sqrt(u), phi = 2 pi frac(k *
+ *                     0.6180339887498949), l_k = (r cos phi, r sin phi, sqrt(1 - u)): cosine-weighted about +z, equal weights.
+ *                     brt_host_lightmap_directions is the only place that computes it: in float64, rounded once to f32.
+ *   frame             len2 = (nx nx + ny ny) + nz nz; len = sqrt(len2); n = (nx / len, ny / len, nz / len).  s = copysign(1, n.z);
+ *                     a = -1 / (s + n.z); b = (n.x n.y) a; t = (1 + (s (n.x n.x)) a, s b, (-s) n.x); bt = (b, s + (n.y n.y) a, -n.y).
+ *                     |s + n.z| >= 1 for a unit n: the basis is never singular.
+ *   rays              o = position + offset * n per component (one multiply, one add); d_k = (l.x * t + l.y * bt) + l.z * n per
+ *                     component.  Entry k of a point is the radiance entry { o, seed + k * 0x9E3779B9 (mod 2^32), d_k, user = k }, traced
+ *                     with samples = 1 and the call's `bounces` under the rule of "radiance queries".  An EMPTY or INVALID point has the
+ *                     position's words as o and 0x7fc00000 in the three direction words: the radiance kernels refuse such an entry
+ *                     without a walk.  Lists are POINT-MAJOR: entry k of point p is record p * n_dirs + k.
+ *   resolve           L = c * c per channel of an entry's colour (as "light probes").  Lane l of 64 sums its entries k = l, l + 64, ...
+ *                     in order from +0.0; then for off = 32, 16, 8, 4, 2, 1: acc[l] = acc[l] + acc[l + off]; rgb = acc[0] / f32(n_dirs),
+ *                     a = 1.0.  rgb is the MEAN LINEAR RADIANCE over the cosine-weighted hemisphere: the irradiance is pi * rgb.
+ *   texel             RGBA32F (16 bytes), or RGBA16F (8 bytes) under BRT_FLAG_OUT_RGBA16F (round to nearest even, once, at the final
+ *                     store).  a = 1.0 traced, 0.5 filled by dilation, 0.0 neither.
+ *   info, 8 bytes     { u32 hits; u32 status }, an optional buffer.  hits: the point's entries whose own ray hit, so 1 - hits / n_dirs is
+ *                     its openness to the sky.  status: entry 0's BRT_QUERY_STATUS_INVALID / BRT_QUERY_STATUS_OUT_OF_REACH bits (a point
+ *                     beyond the tree's bound, brt_query_origin_bound), or BRT_LIGHTMAP_STATUS_EMPTY alone for an EMPTY point.  A point
+ *                     with a status has rgb = 0, a = 0 and hits = 0.
+ *   dilate            `passes` in [0, 64] passes over the f32 image, each from the image the pass before wrote.  A texel with a > 0 is
+ *                     copied.  Any other visits its eight neighbours, dy = -1, 0, 1 outer and dx = -1, 0, 1 inner, the centre skipped;
+ *                     wrap_u = 1: x wraps modulo width (the seam of a latitude-longitude chart), else a neighbour outside the image is
+ *                     skipped, as one above or below it always is.  The neighbours with a > 0 in the pass's SOURCE add their rgb from
+ *                     +0.0 in that order; count > 0: rgb = sum / f32(count), a = 0.5; else the texel is copied.  A NaN rgb propagates and
+ *                     never changes coverage.
+ *   brt_host_lightmap_directions     host arithmetic, no context: out_xyz[3 k ..] = l_k.
+ *   brt_host_lightmap_ray            host arithmetic, no context: entry k (< n_dirs) of the point at point32 -> the 32-byte radiance entry
+ *                     at out_ray32; the compiled twin of the generation kernel.
+ *   brt_host_lightmap_sphere_points  host arithmetic, no context: the latitude-longitude chart of one sphere as width * height points.
+ *                     Texel (x, y), i = y * width + x: phi = 2 pi (x + 0.5) / width about +Y, theta = pi (y + 0.5) / height from +Y;
+ *                     normal = (sin theta cos phi, cos theta, sin theta sin phi); position = centre + radius * normal; in float64,
+ *                     rounded once to f32; seed + i * 0x9E3779B9; `offset` as given.  A finite centre, radius > 0, offset >= 0.  This is
+ *                     ONE parameterisation, for tests and demos: a host whose meshes carry other UVs supplies its own points.
+ *   brt_host_lightmap_dilate         host arithmetic, no context: the passes over width * height RGBA32F texels -> out_f32; the compiled
+ *                     twin of the dilation kernel.  The buffers need no alignment and must not overlap.
+ *   brt_lightmap_rays_device         the generation kernel alone: n_points points at d_points -> n_points * n_dirs radiance entries at
+ *                     d_rays (DEVICE), n_points * n_dirs <= 0x7fff0000.  Needs no scene.
+ *   brt_lightmap_resolve_device      the resolve kernel alone, on any list of radiance results in that layout and its points -> n_points
+ *                     texels at d_out and, if not null, info records at d_info_or_null.  Needs no scene.  flags: BRT_FLAG_CALLER_STREAM,
+ *                     BRT_FLAG_OUT_RGBA16F.
+ *   brt_lightmap_dilate_device       the passes alone: the RGBA32F image at d_texels_f32 -> d_out; passes = 0 copies (and converts).  The
+ *                     images between the passes are the context's.  Needs no scene.  flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_RGBA16F.
+ *   brt_bake_lightmap_device         everything in one call on DEVICE buffers: in chunks of whole points, generate -> the radiance kernels
+ *                     -> resolve into an f32 image of the context; after the last chunk the passes into d_out.  A chunk is max(1,
+ *                     BRT_PROBE_CHUNK_RAYS / n_dirs) points (the light probes' tuning knob).  The bytes written depend neither on the
+ *                     chunk size nor on BRT_RADIANCE_FORM.  bounces, origin_bound: as for brt_radiance_rays.  flags:
+ *                     BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_RGBA16F.
+ *   brt_bake_lightmap                the same for HOST buffers, synchronous.  flags: BRT_FLAG_OUT_RGBA16F only.
+ *   out_stats8_or_null   as for brt_bake_probes: [0..2] walks, entries whose own ray hit, entries refused, summed over the chunks (only
+ *                     calls that synchronise count), [3] the tree was rebuilt, [4] its reach, [5] the radiance form of the last chunk,
+ *                     [6] chunks, [7] 0.
+ * The rays export's flags: BRT_FLAG_CALLER_STREAM only; stream rule and ordering as for the step exports of "light probes".  Refused with
+ * BRT_ERR_INVALID_ARGUMENT and nothing written: null pointers (but d_info_or_null); a DEVICE buffer that is not 16-byte aligned; buffers
+ * that overlap; n_dirs outside [1, 65536]; k >= n_dirs; bounces above 65535; a bad origin_bound; width or height of 0 or above 16384;
+ * passes above 64; wrap_u above 1; n_points * n_dirs above 0x7fff0000; unknown flags.  The bakes: BRT_ERR_NO_SCENE before an upload,
+ * BRT_ERR_UNSUPPORTED under a set policy.  n_points = 0 is BRT_OK for the rays and resolve exports.  A refused call leaves the context
+ * usable; no call here changes a frame or the dispatch history. */
+#define BRT_LIGHTMAP_STATUS_EMPTY 16u
+int32_t brt_host_lightmap_directions(uint32_t n_dirs, float* out_xyz);
+int32_t brt_host_lightmap_ray(const void* point32, uint32_t n_dirs, uint32_t k, void* out_ray32);
+int32_t brt_host_lightmap_sphere_points(const float* centre3, float radius, uint32_t seed, float offset, uint32_t width, uint32_t height,
+                                        void* out_points);
+int32_t brt_host_lightmap_dilate(const void* texels_f32, uint32_t width, uint32_t height, uint32_t passes, uint32_t wrap_u, void* out_f32);
+int32_t brt_lightmap_rays_device(brt_ctx* ctx, const void* d_points, uint32_t n_points, uint32_t n_dirs, void* d_rays, void* hip_stream,
+                                 uint32_t flags);
+int32_t brt_lightmap_resolve_device(brt_ctx* ctx, const void* d_results, const void* d_points, uint32_t n_points, uint32_t n_dirs,
+                                    void* d_out, void* d_info_or_null, void* hip_stream, uint32_t flags);
+int32_t brt_lightmap_dilate_device(brt_ctx* ctx, const void* d_texels_f32, uint32_t width, uint32_t height, uint32_t passes,
+                                   uint32_t wrap_u, void* d_out, void* hip_stream, uint32_t flags);
+int32_t brt_bake_lightmap_device(brt_ctx* ctx, const void* d_points, uint32_t width, uint32_t height, uint32_t n_dirs, uint32_t bounces,
+                                 uint32_t passes, uint32_t wrap_u, float origin_bound, void* d_out, void* d_info_or_null, void* hip_stream,
+                                 uint32_t flags, uint64_t* out_stats8_or_null);
+int32_t brt_bake_lightmap(brt_ctx* ctx, const void* points, uint32_t width, uint32_t height, uint32_t n_dirs, uint32_t bounces,
+                          uint32_t passes, uint32_t wrap_u, float origin_bound, void* out, void* info_or_null, uint32_t flags,
+                          uint64_t* out_stats8_or_null);
+
 /* ---- guide-buffer upsampling ----------------------------------------------------------------------------------------------------------
  * A frame traced at low_width x low_height is presented at width x height: every OUTPUT pixel casts its own pixel-centre ray (the guide
  * buffer's), so sphere silhouettes, the first bounce's base colour and the sky are at full sharpness, and gathers the demodulated colour
