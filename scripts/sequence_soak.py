@@ -3,6 +3,7 @@
 through one context, every frame against the CPU oracle, bit for bit.
 
     python scripts/sequence_soak.py --sequences 200 --seed 3 [--log gpurun_out/sequence_soak.txt]
+    python scripts/sequence_soak.py --families --sequences 200 --seed 3      (steps drawn from all twelve entry-point families)
 
 scripts/fuzz_parity.py draws independent frames; the state this round added lives ACROSS frames (brt_api.cpp, brt_api_order.cpp):
   * the pair records and spheres re-numbered by a view's visit counts (apply_hot_order), counted again after a camera jump -- the
@@ -28,7 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import bevyray_amd as brt                      # noqa: E402
 import oracle_loader                           # noqa: E402
-from helpers import uniforms                   # noqa: E402
+from helpers import random_scene, random_view   # noqa: E402  (the generators this script shares with tests/sequence_cases.py)
 
 COUNTER_KEYS = ("rays", "node_pops", "interior_visits", "sphere_tests", "hits")
 
@@ -39,44 +40,36 @@ def frames_differ(got, want):
     return int((~(same | (np.isnan(got) & np.isnan(want)))).sum())
 
 
-def random_scene(rng):
-    n = int(np.exp(rng.uniform(np.log(70), np.log(6000))))
-    spread = float(rng.choice([3.0, 12.0, 40.0]))
-    data = []
-    ground = rng.random() < 0.5
-    for i in range(n):
-        if i == 0 and ground:
-            data.append(((0.0, -1000.0, 0.0), 1000.0, brt.StandardMaterial(base_color=(0.5, 0.5, 0.5))))
-            continue
-        r = float(rng.uniform(0.05, 0.6)) * (spread / 12.0) ** 0.5
-        pos = rng.uniform(-spread, spread, 3)
-        if ground:
-            pos[1] = r if rng.random() < 0.7 else float(rng.uniform(r, spread / 3))
-        u = rng.random()
-        mat = brt.StandardMaterial(base_color=tuple(float(x) for x in rng.random(3)), metallic=1.0 if u < 0.2 else 0.0,
-                                   perceptual_roughness=float(rng.random()), ior=float(rng.uniform(1.1, 2.4)),
-                                   specular_transmission=1.0 if 0.2 <= u < 0.35 else 0.0)
-        data.append((tuple(float(x) for x in pos), r, mat))
-    b = brt.prepare_buffers([(p, brt.RaytracedSphere(r), m) for p, r, m in data])
-    return b, spread
-
-
-def random_view(rng, spread, w, h, spp, bounces, far=False, near_to=None):
-    if near_to is not None:                # a small move: a few percent of the distance
-        pos, target, fov, seed = near_to
-        d = float(np.linalg.norm(np.subtract(pos, target)))
-        pos = tuple(float(x) for x in np.add(pos, rng.normal(0.0, 0.01 * d, 3)))
-    else:
-        dist = spread * (float(np.exp(rng.uniform(np.log(5.0), np.log(300.0)))) if far else float(rng.uniform(0.3, 2.5)))
-        v = rng.standard_normal(3)
-        v[1] = abs(v[1]) * 0.5 + 0.05
-        pos = tuple(float(x) for x in dist * v / np.linalg.norm(v))
-        target = tuple(float(x) for x in rng.uniform(-0.3, 0.3, 3) * spread)
-        fov = float(rng.uniform(0.3, 1.2)) if not far else float(min(1.2, rng.uniform(1.0, 3.0) * spread / dist))
-        seed = float(np.float32(rng.random()))
-    lvl, cam, win = uniforms(w, h, spp=spp, bounces=bounces, pos=pos, target=target, fov=fov, seed=seed,
-                             level=brt.Raytracing(int(rng.choice([1, 2, 3], p=[0.15, 0.15, 0.7]))))
-    return (lvl, cam, win), (pos, target, fov, seed)
+def soak_families(args):
+    """Random sequences over all twelve families, stepwise (tests/test_call_sequences.py _run_stepwise) -> the exit code"""
+    import sequence_cases as sc
+    import test_call_sequences as tcs
+    oracle = oracle_loader.load()
+    t0 = time.time()
+    seqs = steps = fails = 0
+    totals, lines = {}, []
+    for i in range(args.sequences):
+        if time.time() - t0 > args.seconds:
+            break
+        seq = sc.generate(sc.random_spec(args.seed + i), oracle)
+        try:
+            _, report = tcs._run_stepwise(seq, oracle)
+            for k, v in report.items():
+                totals[k] = totals.get(k, 0) + (int(v) if isinstance(v, (bool, int)) else float(v))
+            steps += len(seq.steps)
+            seqs += 1
+        except AssertionError as e:
+            fails += 1
+            lines.append(f"sequence {seq.name} FAILED: {e}")
+            print(lines[-1], flush=True)
+    summary = (f"sequence_soak --families seed {args.seed}: {seqs} sequences / {steps} steps held to the CPU model or their control context, "
+               f"{fails} failed; {totals}; {time.time() - t0:.0f} s")
+    print(summary, flush=True)
+    if args.log:
+        os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+        with open(args.log, "a") as f:
+            f.write("\n".join(lines + [summary]) + "\n")
+    return 1 if fails else 0
 
 
 def main():
@@ -85,7 +78,10 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--log", default=None)
     ap.add_argument("--seconds", type=float, default=1e9, help="stop after this much wall time")
+    ap.add_argument("--families", action="store_true", help="draw the steps from all twelve entry-point families (tests/sequence_cases.py)")
     args = ap.parse_args()
+    if args.families:
+        sys.exit(soak_families(args))
     import torch
     oracle = oracle_loader.load()
     rng = np.random.default_rng(args.seed)

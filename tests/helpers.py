@@ -1,7 +1,8 @@
 """Shared test helpers: hand-made BVHs (single leaf, median split, caterpillar chain, a composer that grafts one onto another),
 a seeded scene large enough for 32-bit tree descriptors with its camera, the upload of a scene whose tree the callee builds,
 uniform builders, the generator of randomized scenes (materials, sizes, cameras, topologies), the generator of wild scenes that
-scripts/fuzz_parity.py and tests/shade_cases.py share, and a numpy-f32 restatement of the
+scripts/fuzz_parity.py and tests/shade_cases.py share, the scene and view generators that scripts/sequence_soak.py and
+tests/sequence_cases.py share, and a numpy-f32 restatement of the
 camera/sky arithmetic for analytic checks; for the GPU tests of the bakes, device buffers and the upload of the cover scene."""
 import functools
 import os
@@ -367,6 +368,50 @@ def _wild_case(rng, wild=True, max_spheres=None, callee_trees=True):
     mode = str(rng.choice(["run", "multi", "parts", "simple"], p=[0.6, 0.15, 0.15, 0.1]))
     return dict(buffers=b, level=lvl, camera=cam, window=win, w=w, h=h, raster=raster, depth=depth, wild=wild, topo=topo,
                 mode=mode, n_parts=int(rng.choice([2, 3, 5, 8])), far_cam=far_cam)
+
+
+def random_scene(rng, max_spheres=6000):
+    """The scene generator of scripts/sequence_soak.py and tests/sequence_cases.py: 70 .. max_spheres spheres (log-uniform) in a cube of
+    half-edge `spread`, half the scenes over a ground sphere.  -> (Buffers under the caller's PLOC tree, spread)."""
+    n = int(np.exp(rng.uniform(np.log(70), np.log(max_spheres))))
+    spread = float(rng.choice([3.0, 12.0, 40.0]))
+    data = []
+    ground = rng.random() < 0.5
+    for i in range(n):
+        if i == 0 and ground:
+            data.append(((0.0, -1000.0, 0.0), 1000.0, brt.StandardMaterial(base_color=(0.5, 0.5, 0.5))))
+            continue
+        r = float(rng.uniform(0.05, 0.6)) * (spread / 12.0) ** 0.5
+        pos = rng.uniform(-spread, spread, 3)
+        if ground:
+            pos[1] = r if rng.random() < 0.7 else float(rng.uniform(r, spread / 3))
+        u = rng.random()
+        mat = brt.StandardMaterial(base_color=tuple(float(x) for x in rng.random(3)), metallic=1.0 if u < 0.2 else 0.0,
+                                   perceptual_roughness=float(rng.random()), ior=float(rng.uniform(1.1, 2.4)),
+                                   specular_transmission=1.0 if 0.2 <= u < 0.35 else 0.0)
+        data.append((tuple(float(x) for x in pos), r, mat))
+    b = brt.prepare_buffers([(p, brt.RaytracedSphere(r), m) for p, r, m in data])
+    return b, spread
+
+
+def random_view(rng, spread, w, h, spp, bounces, far=False, near_to=None):
+    """A camera of random_scene's scene: a jump, with `far` x 5 .. x 300 the scene's extent (field of view narrowed to match), or with
+    near_to (the description a former call returned) a small move.  -> ((level, camera, window), (pos, target, fov, seed))."""
+    if near_to is not None:                # a small move: a few percent of the distance
+        pos, target, fov, seed = near_to
+        d = float(np.linalg.norm(np.subtract(pos, target)))
+        pos = tuple(float(x) for x in np.add(pos, rng.normal(0.0, 0.01 * d, 3)))
+    else:
+        dist = spread * (float(np.exp(rng.uniform(np.log(5.0), np.log(300.0)))) if far else float(rng.uniform(0.3, 2.5)))
+        v = rng.standard_normal(3)
+        v[1] = abs(v[1]) * 0.5 + 0.05
+        pos = tuple(float(x) for x in dist * v / np.linalg.norm(v))
+        target = tuple(float(x) for x in rng.uniform(-0.3, 0.3, 3) * spread)
+        fov = float(rng.uniform(0.3, 1.2)) if not far else float(min(1.2, rng.uniform(1.0, 3.0) * spread / dist))
+        seed = float(np.float32(rng.random()))
+    lvl, cam, win = uniforms(w, h, spp=spp, bounces=bounces, pos=pos, target=target, fov=fov, seed=seed,
+                             level=brt.Raytracing(int(rng.choice([1, 2, 3], p=[0.15, 0.15, 0.7]))))
+    return (lvl, cam, win), (pos, target, fov, seed)
 
 
 def fixture_buffers():
