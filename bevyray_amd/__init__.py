@@ -22,6 +22,9 @@ from .raytracing import (  # noqa: F401
     LIGHTMAP_INFO_DTYPE, LIGHTMAP_POINT_DTYPE, LIGHTMAP_STATUS_EMPTY, lightmap_dilate_host, lightmap_directions, lightmap_ray,
     lightmap_sphere_points,
     LENS_DTYPE, lens, lens_origin_bound, lens_ray, lens_seed,
+    GBUFFER_DEPTH_DISTANCE, GBUFFER_DEPTH_SHADER, GBUFFER_DEPTH_VIEW, GBUFFER_DTYPE, GBUFFER_IDS_DTYPE, GBUFFER_MOTION_PIXEL,
+    GBUFFER_MOTION_UV16F, GBUFFER_MOTION_UV32F, GBUFFER_NORMAL_RGB10A2, GBUFFER_NORMAL_RGBA32F, GBUFFER_PIXEL_DTYPE, GBUFFER_PLANES,
+    GBUFFER_STATUS_FRONT_FACE, GBUFFER_STATUS_HIT, GBUFFER_STATUS_MOVED, GBUFFER_STATUS_NO_PREVIOUS, gbuffer, gbuffer_pixel, gbuffer_plane,
     blend_covered, prepare_buffers, rtiow_camera, srgb_thresholds, tile_rows, upscale_window, validate_scene,
 )
 

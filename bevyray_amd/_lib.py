@@ -150,6 +150,10 @@ _PROTOTYPES = {
     "brt_host_lens_seed": (_I32, [_VP, _U32, _U32, _U32, _U32, C.POINTER(_U32)]),
     "brt_host_lens_ray": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, C.POINTER(_U32), _VP, _VP]),
     "brt_host_lens_origin_bound": (_I32, [_VP, _VP, C.POINTER(_F)]),
+    "brt_render_gbuffer_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32,
+                                         C.POINTER(C.c_uint64)]),
+    "brt_render_gbuffer": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64)]),
+    "brt_host_gbuffer_pixel": (_I32, [_VP, _VP, _U32, _U32, _U32, _U32, _VP, _VP, _F, _VP, _VP, _VP]),
     "brt_upscale_refine_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _U32, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_render_upscaled_refined_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _U32, _U32, _VP, _U32, _VP, _VP, _U32,
                                                   C.POINTER(BrtStats)]),

@@ -579,6 +579,68 @@ def lens_origin_bound(camera, lens_desc) -> float:
     return out.value
 
 
+# brt_gbuffer (include/bevyray_amd.h "G-buffer"): the descriptor of brt_render_gbuffer*, its modes and formats, the status bits of the
+# ids plane, and the record brt_host_gbuffer_pixel returns
+GBUFFER_DEPTH_VIEW, GBUFFER_DEPTH_SHADER, GBUFFER_DEPTH_DISTANCE = 0, 1, 2
+GBUFFER_NORMAL_RGBA32F, GBUFFER_NORMAL_RGB10A2 = 0, 1
+GBUFFER_MOTION_UV32F, GBUFFER_MOTION_UV16F, GBUFFER_MOTION_PIXEL = 0, 1, 2
+GBUFFER_STATUS_HIT, GBUFFER_STATUS_FRONT_FACE, GBUFFER_STATUS_MOVED, GBUFFER_STATUS_NO_PREVIOUS = 1, 2, 4, 8
+GBUFFER_DTYPE = np.dtype([("depth_mode", np.uint32), ("normal_format", np.uint32), ("motion_format", np.uint32), ("reserved", np.uint32, 5)])
+GBUFFER_PIXEL_DTYPE = np.dtype([("depth", np.float32), ("status", np.uint32), ("normal_rgb10a2", np.uint32), ("reserved0", np.uint32),
+                                ("normal", np.float32, 4), ("motion", np.uint32, 2), ("xy_prev", np.float32, 2),
+                                ("direction", np.float32, 3), ("reserved1", np.uint32)])
+GBUFFER_IDS_DTYPE = np.dtype([("sphere", np.uint32), ("material", np.uint32), ("status", np.uint32), ("reserved", np.uint32)])
+assert GBUFFER_DTYPE.itemsize == 32 and GBUFFER_PIXEL_DTYPE.itemsize == 64 and GBUFFER_IDS_DTYPE.itemsize == 16
+GBUFFER_PLANES = ("depth", "normal", "motion", "ids", "albedo")
+
+
+def gbuffer(depth_mode: int = GBUFFER_DEPTH_VIEW, normal_format: int = GBUFFER_NORMAL_RGBA32F,
+            motion_format: int = GBUFFER_MOTION_UV32F) -> np.ndarray:
+    """One GBUFFER_DTYPE record: the depth mode (GBUFFER_DEPTH_*) and the normal and motion formats of a G-buffer call."""
+    d = np.zeros(1, GBUFFER_DTYPE)
+    d["depth_mode"] = depth_mode
+    d["normal_format"] = normal_format
+    d["motion_format"] = motion_format
+    return d
+
+
+def gbuffer_plane(desc, plane: str, width: int, height: int) -> np.ndarray:
+    """An empty host array of `plane` (GBUFFER_PLANES) of a width x height frame in the formats of `desc`."""
+    nf, mf = int(desc["normal_format"][0]), int(desc["motion_format"][0])
+    if plane == "depth":
+        return np.zeros((height, width), np.float32)
+    if plane == "normal":
+        return np.zeros((height, width, 4), np.float32) if nf == GBUFFER_NORMAL_RGBA32F else np.zeros((height, width), np.uint32)
+    if plane == "motion":
+        return np.zeros((height, width), np.uint32) if mf == GBUFFER_MOTION_UV16F else np.zeros((height, width, 2), np.float32)
+    if plane == "ids":
+        return np.zeros((height, width), GBUFFER_IDS_DTYPE)
+    if plane == "albedo":
+        return np.zeros((height, width, 4), np.float32)
+    raise ValueError(plane)
+
+
+def gbuffer_pixel(camera, window, width: int, height: int, px: int, py: int, desc, t: float, sphere_new=None, sphere_old=None,
+                  prev_camera=None) -> np.ndarray:
+    """brt_host_gbuffer_pixel: the G-buffer rule for pixel (px, py) whose pixel-centre ray hits at t (inf: a miss) the sphere
+    {centre, radius * radius} = sphere_new, which was sphere_old (None: not moved) in the frame of prev_camera (None: this camera)
+    -> one GBUFFER_PIXEL_DTYPE record.  The compiled twin of the kernel behind RayTracingNode.render_gbuffer*."""
+    out = np.zeros(1, GBUFFER_PIXEL_DTYPE)
+    sn = None if sphere_new is None else np.ascontiguousarray(sphere_new, np.float32)
+    so = None if sphere_old is None else np.ascontiguousarray(sphere_old, np.float32)
+    _lib.check(_lib.load().brt_host_gbuffer_pixel(camera.ctypes.data, window.ctypes.data, int(width), int(height), int(px), int(py),
+                                                  desc.ctypes.data, None if prev_camera is None else prev_camera.ctypes.data,
+                                                  C.c_float(t), None if sn is None else sn.ctypes.data,
+                                                  None if so is None else so.ctypes.data, out.ctypes.data))
+    return out
+
+
+def _gbuffer_stats(words) -> dict:
+    return {"cast": int(words[0]), "hits": int(words[1]), "covered": int(words[2]), "tree_rebuilt": int(words[3]),
+            "tree_reach": float(np.array([words[4]], np.uint64).astype(np.uint32).view(np.float32)[0]),
+            "moved": int(words[5]), "no_previous": int(words[6])}
+
+
 class RaytracePlugin:
     """mod.rs:24-84.  build()/finish() create the GPU context (the reference queues the
     render pipeline in RaytracingPipeline::from_world, pipeline.rs:233-331)."""
@@ -817,6 +879,7 @@ class RayTracingNode:
         self.last_query_stats: Optional[dict] = None
         self.last_radiance_stats: Optional[dict] = None
         self.last_probe_stats: Optional[dict] = None
+        self.last_gbuffer_stats: Optional[dict] = None
 
     def write_buffers(self, buffers: Buffers) -> None:
         """pipeline.rs:136-138"""
@@ -1041,6 +1104,41 @@ class RayTracingNode:
                                                         *_stream_args(stream, flags), C.byref(stats)), p._ctx)
         self.last_stats = stats.as_dict()
         return self.last_stats
+
+    # -- G-buffer: depth, normal, motion, ids, albedo of a frame (include/bevyray_amd.h) ------------
+
+    def render_gbuffer(self, camera, window, width: int, height: int, desc, planes: Sequence[str] = GBUFFER_PLANES, prev_camera=None,
+                       prev_models=None, coverage=None, into: Optional[dict] = None) -> dict:
+        """brt_render_gbuffer: the planes named in `planes` (GBUFFER_PLANES) of the width x height frame -> {name: array} (gbuffer_plane's
+        shapes).  prev_camera / prev_models (MODEL_DTYPE, the caller's order): the previous frame's, for the motion plane; coverage: an
+        (height, width, 4) f32 coverage frame whose covered pixels (alpha +0.0) keep what `into` holds.  last_gbuffer_stats: the counts."""
+        p = self._p
+        ok = 0 < width <= 32768 and 0 < height <= 32768
+        out = {k: (into[k] if into is not None and k in into else gbuffer_plane(desc, k, *((width, height) if ok else (1, 1)))) for k in planes}
+        pm = None if prev_models is None else np.ascontiguousarray(prev_models, MODEL_DTYPE)
+        cov = None if coverage is None else np.ascontiguousarray(coverage, np.float32)
+        words = (C.c_uint64 * 8)()
+        ptr = [out[k].ctypes.data if k in out else None for k in GBUFFER_PLANES]
+        _lib.check(p._lib.brt_render_gbuffer(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, desc.ctypes.data,
+                                             None if prev_camera is None else prev_camera.ctypes.data,
+                                             None if pm is None else pm.ctypes.data, None if cov is None else cov.ctypes.data,
+                                             *ptr, words), p._ctx)
+        self.last_gbuffer_stats = _gbuffer_stats(words)
+        return out
+
+    def render_gbuffer_device(self, camera, window, width: int, height: int, desc, d_depth: int = 0, d_normal: int = 0, d_motion: int = 0,
+                              d_ids: int = 0, d_albedo: int = 0, prev_camera=None, d_prev_models: int = 0, d_coverage: int = 0,
+                              stream: Optional[int] = None, flags: int = 0) -> dict:
+        """brt_render_gbuffer_device: the planes whose device pointer (on the first device) is not 0.  Stream rule as for
+        render_part_device; the counts of the returned stats only on the own stream."""
+        p = self._p
+        words = (C.c_uint64 * 8)()
+        _lib.check(p._lib.brt_render_gbuffer_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, desc.ctypes.data,
+                                                    None if prev_camera is None else prev_camera.ctypes.data, d_prev_models or None,
+                                                    d_coverage or None, d_depth or None, d_normal or None, d_motion or None,
+                                                    d_ids or None, d_albedo or None, *_stream_args(stream, flags), words), p._ctx)
+        self.last_gbuffer_stats = _gbuffer_stats(words)
+        return self.last_gbuffer_stats
 
     def upscale_refine_device(self, camera, window, low_width: int, low_height: int, d_low: int, width: int, height: int, d_out: int,
                               classes: int = REFINE_EDGES | REFINE_SPECULAR, d_refined_count: int = 0, stream: Optional[int] = None,

@@ -956,6 +956,89 @@ int32_t brt_host_lens_ray(const void* camera80, const void* window16, const void
                           uint32_t py, uint32_t* state_inout, float* o3, float* d3);
 int32_t brt_host_lens_origin_bound(const void* camera80, const void* lens32, float* out_bound);
 
+/* ---- G-buffer: depth, normal, motion vectors, ids and albedo of a frame ------------------------------------------------------------------
+ * The attributes of the first hit of every pixel-centre ray of a width x height frame -- the hit the denoiser, the temporal pass and the
+ * upsampling work on -- in the layouts a render node hands on: one kernel, one walk per pixel, every requested plane written from its
+ * registers.  On the context's first device.  Rule (csrc/brt_gbuffer.h holds the operation order), kernel and costs: DESIGN.md "G-buffer".
+ *   the ray      uv = (p + 0.5) / size, direction = the camera's pixel-centre direction, origin = camera.position: brt_host_pixel_ray's.
+ *   the hit      the reference's raycast on the resident scene: t, the sphere, n = normalize(ray_at(t) - centre), not flipped.
+ *   brt_gbuffer, 32 bytes  { depth_mode, normal_format, motion_format, reserved[5] }; the reserved words must be 0.
+ *   depth        one f32.  BRT_GBUFFER_DEPTH_VIEW: near / (t * dot(d, normalize(direction))), a miss +0.0 -- reverse-Z planar depth, what an
+ *                infinite reverse-Z depth prepass holds.  BRT_GBUFFER_DEPTH_SHADER: the reference's own compare value for the centre ray
+ *                (raytrace.wgsl:108-113): t > far ? -1.0 : near / t; a miss: the same test on fallback_far = far - 1 (the level that keeps
+ *                the traced sky; level 1's far + 10 always gives -1.0, which the HIT bit lets a host substitute).
+ *                BRT_GBUFFER_DEPTH_DISTANCE: t, a miss +INF.
+ *   normal       world space.  BRT_GBUFFER_NORMAL_RGBA32F: four f32 {n, 1}.  BRT_GBUFFER_NORMAL_RGB10A2: one u32 in the layout of an
+ *                Rgb10a2Unorm texel: channel = u32(floor(clamp(n * 0.5 + 0.5, 0, 1) * 1023 + 0.5)) (a NaN: 0), R in the low bits, alpha 3.
+ *                A miss: zeros.
+ *   ids          four u32 { sphere, material, status, 0 }: sphere is the index into the models of the last upload; status is
+ *                BRT_GBUFFER_STATUS_* bits.  A miss: sphere = material = BRT_QUERY_NONE.
+ *   albedo       four f32: the first four words of the hit's material (base_color.rgb, metallic), bit for bit.  A miss: zeros.
+ *   motion       the previous pixel position (x', y') of the hit point: carried back through its sphere's motion (d_prev_models: the
+ *                previous frame's models, 32 bytes each, in the caller's order and of the same count; null: nothing moved; a sphere has
+ *                MOVED iff its {centre, radius * radius} differ bitwise) and projected into prev_camera80 (null: the current camera) by
+ *                the temporal pass's expressions.  A miss is carried by the camera's rotation alone.  The previous camera bitwise the
+ *                current one and the sphere not moved: (x', y') = (px, py) exactly.  z <= 0 or a position outside (-1, W) x (-1, H):
+ *                BRT_GBUFFER_STATUS_NO_PREVIOUS.  BRT_GBUFFER_MOTION_UV32F: two f32 uv - uv_prev, uv_prev = ((x' + 0.5) / W,
+ *                (y' + 0.5) / H) -- current minus previous in uv units, y down; (0, 0) under NO_PREVIOUS.  BRT_GBUFFER_MOTION_UV16F: the
+ *                same pair as two f16 (round to nearest even), x in the low half of one u32.  BRT_GBUFFER_MOTION_PIXEL: two f32 (x', y'),
+ *                NaN under NO_PREVIOUS: where a host fetches its history.
+ *   coverage     d_coverage_rgba_or_null: the assembled level-1 / 2 coverage frame brt_blend_post_device takes.  A pixel whose alpha is
+ *                exactly +0.0 casts no ray and NONE of its planes is written.
+ *   brt_render_gbuffer_device  DEVICE buffers (16-byte aligned) of width * height entries; every plane pointer may be null (not produced;
+ *                all null is BRT_OK and launches nothing).  flags: BRT_FLAG_CALLER_STREAM only; stream rule as for brt_query_rays_device,
+ *                and G-buffer calls run one behind the other with the context's queries and lists.  out_stats8_or_null: [0] pixels cast,
+ *                [1] hits, [2] covered, [3] tree rebuilt, [4] the callee-built tree's reach (f32 bits), [5] moved, [6] no-previous, [7] 0;
+ *                the counts are filled only by calls that synchronise (the context's own stream).
+ *   brt_render_gbuffer         the same for HOST buffers, synchronous; with a coverage frame the planes are read as well as written.
+ *   brt_host_gbuffer_pixel     host arithmetic, no context: the rule for pixel (px, py) whose ray hits at t (+INF: a miss) the sphere
+ *                {centre, radius * radius} = sphere_new4, which was sphere_old4_or_null (null: not moved) in the previous frame.
+ *                out_pixel64 receives a brt_gbuffer_pixel: the depth of depth_mode, the normal in both formats, the two motion words of
+ *                motion_format, (x', y'), the status bits (HIT, FRONT_FACE, MOVED, NO_PREVIOUS) and the ray's direction.
+ * The call keeps no state: no frame, dispatch history, temporal history or denoiser scratch changes.
+ * Refusals: BRT_ERR_INVALID_ARGUMENT for a null camera, window or descriptor, non-zero reserved words, an unknown mode or format, sizes
+ * outside [1, 32768], any other flag, a misaligned device buffer, a pixel outside the frame.  BRT_ERR_UNSUPPORTED for projection_type 1
+ * (either camera) and for a non-default policy.  BRT_ERR_NO_SCENE before an upload.  brt_last_error names the field. */
+#define BRT_GBUFFER_DEPTH_VIEW 0u
+#define BRT_GBUFFER_DEPTH_SHADER 1u
+#define BRT_GBUFFER_DEPTH_DISTANCE 2u
+#define BRT_GBUFFER_NORMAL_RGBA32F 0u
+#define BRT_GBUFFER_NORMAL_RGB10A2 1u
+#define BRT_GBUFFER_MOTION_UV32F 0u
+#define BRT_GBUFFER_MOTION_UV16F 1u
+#define BRT_GBUFFER_MOTION_PIXEL 2u
+#define BRT_GBUFFER_STATUS_HIT 1u
+#define BRT_GBUFFER_STATUS_FRONT_FACE 2u
+#define BRT_GBUFFER_STATUS_MOVED 4u
+#define BRT_GBUFFER_STATUS_NO_PREVIOUS 8u
+typedef struct brt_gbuffer {
+    uint32_t depth_mode;       /* BRT_GBUFFER_DEPTH_* */
+    uint32_t normal_format;    /* BRT_GBUFFER_NORMAL_* */
+    uint32_t motion_format;    /* BRT_GBUFFER_MOTION_* */
+    uint32_t reserved[5];      /* must be 0 */
+} brt_gbuffer;
+typedef struct brt_gbuffer_pixel {      /* 64 bytes: what brt_host_gbuffer_pixel returns */
+    float depth;
+    uint32_t status;
+    uint32_t normal_rgb10a2;
+    uint32_t reserved0;
+    float normal[4];
+    uint32_t motion[2];        /* the motion plane's words in motion_format (UV16F: one word, then 0) */
+    float xy_prev[2];
+    float direction[3];
+    uint32_t reserved1;
+} brt_gbuffer_pixel;
+int32_t brt_render_gbuffer_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                  const void* gbuffer32, const void* prev_camera80_or_null, const void* d_prev_models_or_null,
+                                  const float* d_coverage_rgba_or_null, void* d_depth, void* d_normal, void* d_motion, void* d_ids,
+                                  void* d_albedo, void* hip_stream, uint32_t flags, uint64_t* out_stats8_or_null);
+int32_t brt_render_gbuffer(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const void* gbuffer32,
+                           const void* prev_camera80_or_null, const void* prev_models_or_null, const float* coverage_rgba_or_null,
+                           void* depth, void* normal, void* motion, void* ids, void* albedo, uint64_t* out_stats8_or_null);
+int32_t brt_host_gbuffer_pixel(const void* camera80, const void* window16, uint32_t width, uint32_t height, uint32_t px, uint32_t py,
+                               const void* gbuffer32, const void* prev_camera80_or_null, float t, const float* sphere_new4,
+                               const float* sphere_old4_or_null, void* out_pixel64);
+
 /* ---- refined upsampling ---------------------------------------------------------------------------------------------------------------
  * The guide-buffer upsampling with the pixels it cannot reconstruct traced at FULL size by the sparse pixel tracer.  An output pixel p
  * whose own guide is a hit has the classes
