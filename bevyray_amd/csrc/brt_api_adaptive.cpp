@@ -1,5 +1,9 @@
 // brt_api_adaptive.cpp -- adaptive sampling on the first device (brt_adaptive.hip; DESIGN.md "Adaptive sampling"): a base frame at
 // base_spp samples, the pixels the rule of brt_adaptive.h selects traced again at the camera's own sample count by the sparse pixel tracer.
+// The skeleton of an export and its stats rule (frame_call), the base frame the context keeps (context_frame, ordered by ev_dn), the
+// selection list and its re-trace (refine_list, trace_selected, ordered by ev_q) and the flag, size and overlap helpers are those of every
+// call on a whole frame (brt_frame.h); the guides and their scratch are the denoiser's (brt_api_post.cpp denoise_begin).  Here: the checks
+// of each export in their order, the settings, the dispatch history of base frames, and the enqueue of the selecting kernel.
 #include "brt_frame.h"
 
 using namespace brt;
@@ -8,8 +12,7 @@ namespace {
 
 int32_t adaptive_check(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height) {
     if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
-    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    if (const int32_t bad = size_check(ctx, width, height)) return bad;
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     Camera cam;
     std::memcpy(&cam, camera80, sizeof cam);
@@ -50,10 +53,9 @@ struct BaseHistory {
 };
 
 // behind the base frame at d_base on `stream`: the full-size guides, the selection into d_out (mask: into d_mask, nothing else), then the
-// selected pixels traced into d_out with the call's own camera; the count to d_count (or nullptr).  pl: the launch of the re-trace
+// selected pixels traced into d_out with the call's own camera; the count to d_count (or nullptr)
 int32_t adaptive_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
-                         const float* d_base, void* d_out, uint32_t out_format, uint8_t* d_mask, uint32_t* d_count, hipStream_t stream,
-                         PixelsLaunch* pl) {
+                         const float* d_base, void* d_out, uint32_t out_format, uint8_t* d_mask, uint32_t* d_count, hipStream_t stream) {
     FrameParams fp;
     DenoiseScratch ds;
     int32_t rc = denoise_begin(ctx, dc, camera80, window16, width, height, stream, &fp, &ds);
@@ -75,26 +77,15 @@ int32_t adaptive_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, cons
         HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));
         return BRT_OK;
     }
-    rc = refine_list(ctx, dc, width, height, stream);
+    SelectList sl;
+    rc = refine_list(ctx, dc, width, height, stream, &sl);
     if (rc != BRT_OK) return rc;
     as.out = d_out;
-    as.count = dc.d_pxbuf + 5;
-    as.list = dc.d_pxbuf + 8;
+    as.count = sl.count;
+    as.list = sl.list;
     HIP_TRY(ctx, launch_adaptive_select(as, stream));
     HIP_TRY(ctx, hipEventRecord(dc.ev_dn, stream));      // (the guides and a base frame of the context are free again)
-    rc = pixels_enqueue(ctx, dc, camera80, window16, width, height, as.list, width * height, as.count, {d_out, true, out_format}, dc.d_pxbuf,
-                        stream, false, pl);
-    if (rc != BRT_OK) return rc;
-    if (d_count) HIP_TRY(ctx, hipMemcpyAsync(d_count, as.count, 4, hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    return BRT_OK;
-}
-
-// the rays of the re-trace, read behind it on the call's own stream (which the caller then synchronises)
-int32_t retrace_rays(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, unsigned long long* rays) {
-    HIP_TRY(ctx, hipMemcpyAsync(rays, dc.d_pxbuf, sizeof *rays, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    return BRT_OK;
+    return trace_selected(ctx, dc, camera80, window16, width, height, sl, d_out, out_format, d_count, stream);
 }
 
 }  // namespace
@@ -115,38 +106,30 @@ int32_t brt_set_adaptive(brt_ctx* ctx, uint32_t base_spp, float threshold, uint3
 
 int32_t brt_render_adaptive_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* d_frame,
                                    uint32_t* d_selected_count_or_null, void* hip_stream, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only (pixels of two sample counts: no post-pass)");
+    if (const int32_t bad = flags_check(ctx, flags, kOutFlags, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only (pixels of two sample counts: no post-pass)"))
+        return bad;
     if (const int32_t bad = adaptive_check(ctx, camera80, window16, width, height)) return bad;
     const uint32_t fmt = flags & BRT_FLAG_OUT_MASK;
     if (overlaps(d_frame, out_bytes(width, height, fmt), d_selected_count_or_null, 4u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame overlaps d_selected_count");
-    DeviceCtx& dc = ctx->devs[0];
     const bool plain = ctx->adaptive.base_spp >= sample_count_of(camera80);
     Camera base_cam;
     std::memcpy(&base_cam, camera80, sizeof base_cam);
     base_cam.sample_count = ctx->adaptive.base_spp;
-    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
+    // the stats are the traced frame's, with the rays of the re-trace added where there is one
+    return frame_call(ctx, camera80, hip_stream, flags, stats, plain ? FRAME_STATS_KEEP : FRAME_STATS_ADD_RETRACE,
+                      [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         if (plain) {      // the base frame would have the camera's samples or more: the plain frame, nothing selected
-            int32_t r = render_frame_device(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, nullptr, nullptr, d_frame, hip_stream, flags, stats);
+            const int32_t r = render_frame_device(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, nullptr, nullptr, d_frame, hip_stream, flags, stats);
             if (r != BRT_OK) return r;
             HIP_TRY(ctx, hipSetDevice(dc.device));
             if (d_selected_count_or_null) HIP_TRY(ctx, hipMemsetAsync(d_selected_count_or_null, 0, 4, sc.stream));
-            if (sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
             return BRT_OK;
         }
-        // the base frame lives in the context, as the low frame of brt_render_upscaled_device does
-        const size_t bytes = (size_t)width * height * 16u;
-        if (dc.uplow_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
-        int32_t r = ensure(ctx, &dc.d_uplow, &dc.uplow_cap, bytes);
+        int32_t r = context_frame(ctx, dc, (size_t)width * height * 16u, sc.stream);
         if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_dn, 0));
         {
             BaseHistory slot(ctx);
             r = render_frame_device(ctx, &base_cam, window16, BRT_LEVEL_PURE, width, height, nullptr, nullptr, dc.d_uplow, hip_stream,
@@ -154,51 +137,28 @@ int32_t brt_render_adaptive_device(brt_ctx* ctx, const void* camera80, const voi
         }
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipSetDevice(dc.device));
-        PixelsLaunch pl{};
-        r = adaptive_enqueue(ctx, dc, camera80, window16, width, height, dc.d_uplow, d_frame, fmt, nullptr, d_selected_count_or_null, sc.stream, &pl);
-        if (r != BRT_OK || !sc.own) return r;
-        unsigned long long rays = 0u;
-        r = retrace_rays(ctx, dc, sc.stream, &rays);
-        if (r == BRT_OK && stats) stats->rays += rays;
-        return r;
+        return adaptive_enqueue(ctx, dc, camera80, window16, width, height, dc.d_uplow, d_frame, fmt, nullptr, d_selected_count_or_null, sc.stream);
     });
-    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
-    return rc;
     });
 }
 
 int32_t brt_adaptive_refine_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                                    const float* d_base_rgba, void* d_out, uint32_t* d_selected_count_or_null, void* hip_stream,
                                    uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_base_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_base_rgba / d_out is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only");
+    if (const int32_t bad = flags_check(ctx, flags, kOutFlags, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only")) return bad;
     if (const int32_t bad = adaptive_check(ctx, camera80, window16, width, height)) return bad;
     const uint32_t fmt = flags & BRT_FLAG_OUT_MASK;
     if (overlaps(d_out, out_bytes(width, height, fmt), d_base_rgba, (size_t)width * height * 16u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out overlaps d_base_rgba");
     if (overlaps(d_out, out_bytes(width, height, fmt), d_selected_count_or_null, 4u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out overlaps d_selected_count");
-    DeviceCtx& dc = ctx->devs[0];
-    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        PixelsLaunch pl{};
-        int32_t r = adaptive_enqueue(ctx, dc, camera80, window16, width, height, d_base_rgba, d_out, fmt, nullptr, d_selected_count_or_null,
-                                     sc.stream, &pl);
-        if (r != BRT_OK) return r;
-        if (stats) std::memset(stats, 0, sizeof *stats);      // (the re-trace's rays, total_ms, and the tree)
-        if (!sc.own) return BRT_OK;
-        unsigned long long rays = 0u;
-        r = retrace_rays(ctx, dc, sc.stream, &rays);
-        if (r == BRT_OK && stats) stats->rays = rays;
-        return r;
+    // the stats: the rays of the re-trace, total_ms, and the tree
+    return frame_call(ctx, camera80, hip_stream, flags, stats, FRAME_STATS_CLEAR | FRAME_STATS_ADD_RETRACE,
+                      [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        return adaptive_enqueue(ctx, dc, camera80, window16, width, height, d_base_rgba, d_out, fmt, nullptr, d_selected_count_or_null, sc.stream);
     });
-    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
-    return rc;
     });
 }
 
@@ -206,18 +166,13 @@ int32_t brt_adaptive_mask_device(brt_ctx* ctx, const void* camera80, const void*
                                  const float* d_base_rgba, void* d_mask_u8, void* hip_stream, uint32_t flags) {
     return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_base_rgba || !d_mask_u8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_base_rgba / d_mask_u8 is null");
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
+    if (const int32_t bad = caller_stream_flags_check(ctx, flags)) return bad;
     if (const int32_t bad = adaptive_check(ctx, camera80, window16, width, height)) return bad;
     if (overlaps(d_mask_u8, (size_t)width * height, d_base_rgba, (size_t)width * height * 16u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_mask_u8 overlaps d_base_rgba");
-    DeviceCtx& dc = ctx->devs[0];
-    return with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, nullptr, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        const int32_t r = adaptive_enqueue(ctx, dc, camera80, window16, width, height, d_base_rgba, nullptr, BRT_FLAG_OUT_RGBA32F,
-                                           static_cast<uint8_t*>(d_mask_u8), nullptr, sc.stream, nullptr);
-        if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return r;
+    return frame_call(ctx, camera80, hip_stream, flags, nullptr, FRAME_STATS_KEEP, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        return adaptive_enqueue(ctx, dc, camera80, window16, width, height, d_base_rgba, nullptr, BRT_FLAG_OUT_RGBA32F,
+                                static_cast<uint8_t*>(d_mask_u8), nullptr, sc.stream);
     });
     });
 }

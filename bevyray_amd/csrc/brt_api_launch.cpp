@@ -8,8 +8,7 @@ int32_t make_frame_params(brt_ctx* ctx, const void* camera80, const void* window
                           uint32_t height, uint32_t part, uint32_t n_parts, FrameParams* out) {
     if (const uint32_t k = ctx->knobs[K_TEST_THROW]) { ctx->knobs.v[K_TEST_THROW] = 0u; throw_for_test(k); }   // (tests: the exception barrier; every brt_render* comes through here)
     if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
-    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    if (const int32_t bad = size_check(ctx, width, height)) return bad;
     if (n_parts == 0 || part >= n_parts) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "part >= n_parts");
     Camera cam;
     Window win;

@@ -2,7 +2,7 @@
 // mean radiance over the cosine-weighted hemisphere of its normal, resolved to the texels of a chart and dilated past the chart's edge.
 // The rays are radiance entries and are traced by the radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue); the skeleton
 // of a bake export, its chunk loop, the cached direction table, streams, ordering behind ev_q and the staging rule are those of every
-// list call (brt_frame.h: bake_call, bake_call_host, bake_chunks, cached_table, staged, list_step_run, device_aligned); the stats are
+// list call (brt_frame.h: bake_call, bake_call_host, bake_chunks, cached_table, staged, list_step_run, device_aligned, flags_check); the stats are
 // the probe bakes' (bake_stats).  Here: the checks, the direction table's maths, the argument packing, the pass loop and the host twins.
 #include "brt_frame.h"
 #include "brt_lightmap.h"
@@ -37,11 +37,6 @@ int32_t image_check(brt_ctx* ctx, uint32_t width, uint32_t height, uint32_t pass
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width and height must be in [1, 16384]");
     if (passes > kLightmapMaxPasses) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "passes must be in [0, 64]");
     if (wrap_u > 1u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "wrap_u must be 0 or 1");
-    return BRT_OK;
-}
-
-int32_t out_flags_check(brt_ctx* ctx, uint32_t flags, uint32_t allowed, const char* what) {
-    if (flags & ~allowed) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, what);
     return BRT_OK;
 }
 
@@ -268,7 +263,7 @@ int32_t brt_lightmap_rays_device(brt_ctx* ctx, const void* d_points, uint32_t n_
 int32_t brt_lightmap_resolve_device(brt_ctx* ctx, const void* d_results, const void* d_points, uint32_t n_points, uint32_t n_dirs, void* d_out,
                                     void* d_info_or_null, void* hip_stream, uint32_t flags) {
     return ctx_guard(ctx, [&]() -> int32_t {
-    int32_t rc = out_flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
+    int32_t rc = flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
     if (rc == BRT_OK) rc = list_check(ctx, n_points, n_dirs);
     if (rc != BRT_OK || n_points == 0u) return rc;
     if (!d_results || !d_points || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null device pointer");
@@ -288,7 +283,7 @@ int32_t brt_lightmap_resolve_device(brt_ctx* ctx, const void* d_results, const v
 int32_t brt_lightmap_dilate_device(brt_ctx* ctx, const void* d_texels_f32, uint32_t width, uint32_t height, uint32_t passes, uint32_t wrap_u,
                                    void* d_out, void* hip_stream, uint32_t flags) {
     return ctx_guard(ctx, [&]() -> int32_t {
-    int32_t rc = out_flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
+    int32_t rc = flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
     if (rc == BRT_OK) rc = image_check(ctx, width, height, passes, wrap_u);
     if (rc != BRT_OK) return rc;
     if (!d_texels_f32 || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "null device pointer");
@@ -313,7 +308,7 @@ int32_t brt_bake_lightmap_device(brt_ctx* ctx, const void* d_points, uint32_t wi
                                  uint32_t passes, uint32_t wrap_u, float origin_bound, void* d_out, void* d_info_or_null, void* hip_stream,
                                  uint32_t flags, uint64_t* out_stats8) {
     return ctx_guard(ctx, [&]() -> int32_t {
-    int32_t rc = out_flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
+    int32_t rc = flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_RGBA16F only");
     if (rc == BRT_OK) rc = lightmap_bake_check(ctx, d_points, width, height, n_dirs, bounces, passes, wrap_u, origin_bound, d_out, d_info_or_null, flags);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_points, d_out, d_info_or_null});
     if (rc != BRT_OK) return rc;
@@ -328,7 +323,7 @@ int32_t brt_bake_lightmap_device(brt_ctx* ctx, const void* d_points, uint32_t wi
 int32_t brt_bake_lightmap(brt_ctx* ctx, const void* points, uint32_t width, uint32_t height, uint32_t n_dirs, uint32_t bounces, uint32_t passes,
                           uint32_t wrap_u, float origin_bound, void* out, void* info_or_null, uint32_t flags, uint64_t* out_stats8) {
     return ctx_guard(ctx, [&]() -> int32_t {
-    int32_t rc = out_flags_check(ctx, flags, BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_OUT_RGBA16F only");
+    int32_t rc = flags_check(ctx, flags, BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_OUT_RGBA16F only");
     if (rc == BRT_OK) rc = lightmap_bake_check(ctx, points, width, height, n_dirs, bounces, passes, wrap_u, origin_bound, out, info_or_null, flags);
     if (rc != BRT_OK) return rc;
     // the points, the texels and the info records on the device: one buffer

@@ -36,12 +36,6 @@ int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const 
     return BRT_OK;
 }
 
-int32_t size_check(brt_ctx* ctx, uint32_t width, uint32_t height) {
-    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
-    return BRT_OK;
-}
-
 int32_t list_check(brt_ctx* ctx, const void* pixels, uint32_t n_pixels, const void* out) {
     if (n_pixels > 0x7fff0000u) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "n_pixels too large");
     if (n_pixels != 0u && (!pixels || !out)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "pixels / out is null");
@@ -51,7 +45,7 @@ int32_t list_check(brt_ctx* ctx, const void* pixels, uint32_t n_pixels, const vo
 // the control words of the first device (DeviceCtx::d_pxbuf), for work behind ev_q
 static int32_t pixels_ctl(brt_ctx* ctx, DeviceCtx& dc) {
     if (dc.d_pxbuf) return BRT_OK;
-    return ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, 32u);
+    return ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, kPxListWord * 4u);
 }
 
 static int32_t call_enqueue(brt_ctx* ctx, DeviceCtx& dc, const PixelsCall& pc, const uint32_t* d_pixels, const PixelsTarget& target,

@@ -1,4 +1,7 @@
 // brt_api_post.cpp -- the post-passes on the first device: denoiser (brt_denoise.hip), temporal accumulation (brt_temporal.hip), blend-post.
+// The skeleton of an export (tree, device, stream, synchronisation, stats) is that of every call on a whole frame (brt_frame.h frame_call),
+// and so are the flag and size checks (flags_check, size_check).  Here: the denoiser's scratch and its ordering behind ev_dn
+// (denoise_begin), the temporal history, the pass sequence (run_denoise), the post-pass flags of a render, the settings and debug reads.
 #include "brt_frame.h"
 
 using namespace brt;
@@ -152,32 +155,19 @@ namespace {
 // brt_denoise_device, and brt_blend_post_device (bp.on: d_frame_rgba is a coverage frame)
 int32_t denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, const float* d_frame_rgba,
                        void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats, const BlendPost& bp) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!d_frame_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, bp.on ? "d_coverage_rgba / d_out is null" : "d_frame_rgba / d_out is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only");
+    if (const int32_t bad = flags_check(ctx, flags, kOutPostFlags, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only"))
+        return bad;
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
-    uint32_t rebuilt = 0u;
-    int32_t rc = ensure_tree_reach(ctx, camera80, &rebuilt);    // (the guides walk the tree the frame was traced in)
-    if (rc != BRT_OK) return rc;
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    const auto [own_stream, stream] = stream_of(dc, hip_stream, flags);
-    FrameParams fp;
-    DenoiseScratch ds;
-    rc = denoise_begin(ctx, dc, camera80, window16, width, height, stream, &fp, &ds);
-    // without BRT_FLAG_TEMPORAL the call denoises (BRT_FLAG_DENOISE implied); with it, it accumulates, and filters if BRT_FLAG_DENOISE is set too
-    const uint32_t post = (flags & BRT_FLAG_TEMPORAL) ? flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL) : (uint32_t)BRT_FLAG_DENOISE;
-    if (rc == BRT_OK) rc = run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, stream, post, bp);
-    if (rc == BRT_OK && own_stream) HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->total_ms = ms_since(t0);
-        tree_stats(ctx, rebuilt, stats);
-    }
-    return BRT_OK;
+    return frame_call(ctx, camera80, hip_stream, flags, stats, FRAME_STATS_CLEAR, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        FrameParams fp;
+        DenoiseScratch ds;
+        const int32_t rc = denoise_begin(ctx, dc, camera80, window16, width, height, sc.stream, &fp, &ds);
+        if (rc != BRT_OK) return rc;
+        // without BRT_FLAG_TEMPORAL the call denoises (BRT_FLAG_DENOISE implied); with it, it accumulates, and filters if BRT_FLAG_DENOISE is set too
+        const uint32_t post = (flags & BRT_FLAG_TEMPORAL) ? flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL) : (uint32_t)BRT_FLAG_DENOISE;
+        return run_denoise(ctx, dc, fp, ds, d_frame_rgba, d_out, flags & BRT_FLAG_OUT_MASK, sc.stream, post, bp);
+    });
 }
 
 }  // namespace
@@ -199,7 +189,7 @@ int32_t brt_set_denoise(brt_ctx* ctx, uint32_t iterations, float sigma_luminance
 
 int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                            const float* d_frame_rgba, void* d_out, void* hip_stream, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    return ctx_guard(ctx, [&]() -> int32_t {
     return denoise_device(ctx, camera80, window16, width, height, d_frame_rgba, d_out, hip_stream, flags, stats, BlendPost());
     });
 }
@@ -207,7 +197,7 @@ int32_t brt_denoise_device(brt_ctx* ctx, const void* camera80, const void* windo
 int32_t brt_blend_post_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                               const float* d_coverage_rgba, const float* d_raster_rgba, void* d_out, void* hip_stream, uint32_t flags,
                               brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    return ctx_guard(ctx, [&]() -> int32_t {
     BlendPost bp;
     bp.on = true;
     bp.d_raster_rgba = d_raster_rgba;
@@ -219,22 +209,18 @@ int32_t brt_debug_denoise_guides(brt_ctx* ctx, const void* camera80, const void*
     return ctx_guard(ctx, [&]() -> int32_t {
     if (!out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out8 is null");
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
-    uint32_t rebuilt = 0u;
-    int32_t rc = ensure_tree_reach(ctx, camera80, &rebuilt);
-    if (rc != BRT_OK) return rc;
-    DeviceCtx& dc = ctx->devs[0];
-    HIP_TRY(ctx, hipSetDevice(dc.device));
-    FrameParams fp;
-    DenoiseScratch ds;
-    rc = denoise_begin(ctx, dc, camera80, window16, width, height, dc.stream, &fp, &ds);
-    if (rc != BRT_OK) return rc;
-    HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, dc.stream));
-    const size_t n = (size_t)width * height;
-    HIP_TRY(ctx, hipMemcpy2DAsync(out8, 32, ds.g0, 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
-    HIP_TRY(ctx, hipMemcpy2DAsync(out8 + 4, 32, ds.g1, 16, 16, n, hipMemcpyDeviceToHost, dc.stream));
-    HIP_TRY(ctx, hipEventRecord(dc.ev_dn, dc.stream));
-    HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-    return BRT_OK;
+    return frame_call(ctx, camera80, nullptr, 0u, nullptr, FRAME_STATS_KEEP, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        FrameParams fp;
+        DenoiseScratch ds;
+        const int32_t rc = denoise_begin(ctx, dc, camera80, window16, width, height, sc.stream, &fp, &ds);
+        if (rc != BRT_OK) return rc;
+        HIP_TRY(ctx, launch_denoise_guides(dc.view, fp, ds, sc.stream));
+        const size_t n = (size_t)width * height;
+        HIP_TRY(ctx, hipMemcpy2DAsync(out8, 32, ds.g0, 16, 16, n, hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(ctx, hipMemcpy2DAsync(out8 + 4, 32, ds.g1, 16, 16, n, hipMemcpyDeviceToHost, sc.stream));
+        HIP_TRY(ctx, hipEventRecord(dc.ev_dn, sc.stream));
+        return BRT_OK;
+    });
     });
 }
 
@@ -257,8 +243,7 @@ int32_t brt_reset_temporal(brt_ctx* ctx) {
 int32_t brt_debug_temporal_state(brt_ctx* ctx, uint32_t width, uint32_t height, float* out8) {
     return ctx_guard(ctx, [&]() -> int32_t {
     if (!out8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "out8 is null");
-    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    if (const int32_t bad = size_check(ctx, width, height)) return bad;
     const auto& tp = ctx->temporal;
     const size_t n = (size_t)width * height;
     if (!tp.valid) {                                 // an empty history: n = 0, nothing reprojected

@@ -1,35 +1,13 @@
 // brt_api_upscale.cpp -- guide-buffer upsampling on the first device (brt_upscale.hip): of a low frame the caller holds, and of one the
 // call traces (and post-processes) itself.  DESIGN.md "Guide-buffer upsampling"; with a level and the full-size raster inputs
-// (brt_upscale_blend_device, brt_render_upscaled_blend_device): "Upsampling blended frames".
+// (brt_upscale_blend_device, brt_render_upscaled_blend_device): "Upsampling blended frames"; with the selected pixels traced again at
+// full size: "Refined upsampling".  The skeleton of an export, the low frame the context keeps (context_frame, ordered by ev_dn), the
+// selection list and its re-trace (refine_list, trace_selected, ordered by ev_q) and the flag, level and overlap helpers are those of
+// every call on a whole frame (brt_frame.h); the scratch and ev_dn are the denoiser's (brt_api_post.cpp denoise_begin).  Here: the size
+// rule of a pair of frames, the low window, the checks of each export in their order, and the enqueue of the upsampling kernel.
 #include "brt_frame.h"
 
 using namespace brt;
-
-namespace brt {
-
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const char* pa = static_cast<const char*>(a);
-    const char* pb = static_cast<const char*>(b);
-    return a && b && pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
-size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt) {
-    return (size_t)width * height * (fmt == BRT_FLAG_OUT_RGBA32F ? 16u : fmt == BRT_FLAG_OUT_RGBA16F ? 8u : 4u);
-}
-
-// The control words and the list of a width x height refinement or adaptive frame (DeviceCtx::d_pxbuf) for work on `stream`: a larger
-// one is allocated only once the last user of the old one has ended; the control words are zeroed behind that user
-int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream) {
-    const size_t bytes = 32u + (size_t)width * height * 4u;
-    if (dc.pxbuf_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    const int32_t rc = ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, bytes);
-    if (rc != BRT_OK) return rc;
-    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    HIP_TRY(ctx, hipMemsetAsync(dc.d_pxbuf, 0, 32, stream));
-    return BRT_OK;
-}
-
-}  // namespace brt
 
 namespace {
 
@@ -65,9 +43,7 @@ struct Blend {
 
 // the level of a blended call: 3 is the call without a level (the raster inputs are not read), 0 traces nothing
 int32_t level_check(brt_ctx* ctx, Blend* bl) {
-    if (bl->level == BRT_LEVEL_SKIP) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "level 0 traces nothing: there is no frame to upsample");
-    if (bl->level != BRT_LEVEL_FALLBACK_RASTER && bl->level != BRT_LEVEL_FALLBACK_RAYTRACED && bl->level != BRT_LEVEL_PURE)
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "level must be 1, 2 or 3");
+    if (const int32_t bad = frame_level_check(ctx, bl->level, "level 0 traces nothing: there is no frame to upsample")) return bad;
     if (!bl->on()) bl->d_raster_rgba = bl->d_raster_depth = nullptr;
     return BRT_OK;
 }
@@ -100,12 +76,9 @@ int32_t upscale_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const
 int32_t upscale_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                        const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, void* hip_stream, uint32_t flags,
                        brt_stats* stats, Blend bl) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
     if (!d_low_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_low_rgba / d_out is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only");
+    if (const int32_t bad = flags_check(ctx, flags, kOutFlags, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only")) return bad;
     if (const int32_t bad = level_check(ctx, &bl)) return bad;
     if (const int32_t bad = sizes_check(ctx, low_width, low_height, width, height)) return bad;
     const uint32_t fmt = flags & BRT_FLAG_OUT_MASK;
@@ -113,60 +86,46 @@ int32_t upscale_device(brt_ctx* ctx, const void* camera80, const void* window16,
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out overlaps d_low_rgba");
     if (const int32_t bad = raster_overlap_check(ctx, bl, d_out, width, height, fmt)) return bad;
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
-    DeviceCtx& dc = ctx->devs[0];
-    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {     // (the guides walk the tree of the frame)
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        const int32_t r = upscale_enqueue(ctx, dc, camera80, window16, low_width, low_height, d_low_rgba, window16, width, height, d_out, fmt,
-                                          sc.stream, false, bl);
-        if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        if (r == BRT_OK && stats) std::memset(stats, 0, sizeof *stats);      // (total_ms only, and the tree)
-        return r;
+    return frame_call(ctx, camera80, hip_stream, flags, stats, FRAME_STATS_CLEAR, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        return upscale_enqueue(ctx, dc, camera80, window16, low_width, low_height, d_low_rgba, window16, width, height, d_out, fmt, sc.stream,
+                               false, bl);
     });
-    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
-    return rc;
+}
+
+// The low frame of a call that traces it, into the context's frame (context_frame) on the call's stream: exactly brt_render_device's
+// low_width x low_height Pure frame (every device of the context) with the post-passes `post` on it, whatever the level of the presented
+// frame -- its raster blend is decided per output pixel by the upsampling.  Leaves the first device current.
+int32_t low_frame(brt_ctx* ctx, DeviceCtx& dc, const StreamChoice& sc, const void* camera80, const void* low_window16, uint32_t low_width,
+                  uint32_t low_height, void* hip_stream, uint32_t flags, uint32_t post, brt_stats* stats) {
+    int32_t r = context_frame(ctx, dc, (size_t)low_width * low_height * 16u, sc.stream);
+    if (r == BRT_OK)
+        r = render_frame_device(ctx, camera80, low_window16, BRT_LEVEL_PURE, low_width, low_height, nullptr, nullptr, dc.d_uplow, hip_stream,
+                                (flags & BRT_FLAG_CALLER_STREAM) | post, stats);
+    if (r != BRT_OK) return r;
+    HIP_TRY(ctx, hipSetDevice(dc.device));
+    return BRT_OK;
 }
 
 int32_t render_upscaled_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                                uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats,
                                Blend bl) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
     if (!camera80 || !window16) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "camera/window is null");
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK | BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only");
+    if (const int32_t bad = flags_check(ctx, flags, kOutPostFlags, "flags: BRT_FLAG_CALLER_STREAM, BRT_FLAG_OUT_*, BRT_FLAG_DENOISE and BRT_FLAG_TEMPORAL only"))
+        return bad;
     if (const int32_t bad = level_check(ctx, &bl)) return bad;
     if (const int32_t bad = sizes_check(ctx, low_width, low_height, width, height)) return bad;
     if (const int32_t bad = raster_overlap_check(ctx, bl, d_frame, width, height, flags & BRT_FLAG_OUT_MASK)) return bad;
     if (!ctx->has_scene) return ctx_fail(ctx, BRT_ERR_NO_SCENE, "brt_upload_scene has not succeeded yet");
     char low_win[16];
     low_window(window16, height, low_height, low_win);
-    DeviceCtx& dc = ctx->devs[0];
     const uint32_t post = flags & (BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL);
-    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        // the low frame lives in the context: a larger one is allocated only once the last upsampling has read the old one, and the
-        // trace writes it behind that upsampling on whatever stream it ran
-        const size_t bytes = (size_t)low_width * low_height * 16u;
-        if (dc.uplow_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
-        int32_t r = ensure(ctx, &dc.d_uplow, &dc.uplow_cap, bytes);
+    return frame_call(ctx, camera80, hip_stream, flags, stats, FRAME_STATS_KEEP, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        const int32_t r = low_frame(ctx, dc, sc, camera80, low_win, low_width, low_height, hip_stream, flags, post, stats);
         if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_dn, 0));
-        // exactly brt_render_device's low_width x low_height Pure frame (every device of the context), post-passes on the low frame;
-        // whatever the level of the presented frame: its raster blend is decided per output pixel by the upsampling
-        r = render_frame_device(ctx, camera80, low_win, BRT_LEVEL_PURE, low_width, low_height, nullptr, nullptr, dc.d_uplow, hip_stream,
-                                (flags & BRT_FLAG_CALLER_STREAM) | post, stats);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        r = upscale_enqueue(ctx, dc, camera80, low_win, low_width, low_height, dc.d_uplow, window16, width, height, d_frame,
-                            flags & BRT_FLAG_OUT_MASK, sc.stream, post != 0u, bl);  // (the post-passes cast the low guides: not cast twice)
-        if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return r;
+        return upscale_enqueue(ctx, dc, camera80, low_win, low_width, low_height, dc.d_uplow, window16, width, height, d_frame,
+                               flags & BRT_FLAG_OUT_MASK, sc.stream, post != 0u, bl);  // (the post-passes cast the low guides: not cast twice)
     });
-    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
-    return rc;
 }
 
 // ---- refined upsampling (DESIGN.md "Refined upsampling") ------------------------------------------------------------------------------
@@ -188,19 +147,14 @@ int32_t refine_check(brt_ctx* ctx, const void* camera80, const void* window16, u
 int32_t refine_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, const void* low_window16, uint32_t low_width,
                        uint32_t low_height, const float* d_low, uint32_t width, uint32_t height, void* d_out, uint32_t out_format,
                        uint32_t classes, uint32_t* d_count, hipStream_t stream) {
-    int32_t rc = refine_list(ctx, dc, width, height, stream);
+    SelectList sl;
+    int32_t rc = refine_list(ctx, dc, width, height, stream, &sl);
     if (rc != BRT_OK) return rc;
-    const UpscaleSelect us = {classes, dc.d_pxbuf + 5, dc.d_pxbuf + 8, nullptr};
+    const UpscaleSelect us = {classes, sl.count, sl.list, nullptr};
     rc = upscale_enqueue(ctx, dc, camera80, low_window16, low_width, low_height, d_low, window16, width, height, d_out, out_format, stream,
                          false, Blend(), &us);
     if (rc != BRT_OK) return rc;
-    PixelsLaunch pl{};
-    rc = pixels_enqueue(ctx, dc, camera80, window16, width, height, us.list, width * height, us.count, {d_out, true, out_format}, dc.d_pxbuf,
-                        stream, false, &pl);
-    if (rc != BRT_OK) return rc;
-    if (d_count) HIP_TRY(ctx, hipMemcpyAsync(d_count, us.count, 4, hipMemcpyDeviceToDevice, stream));
-    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-    return BRT_OK;
+    return trace_selected(ctx, dc, camera80, window16, width, height, sl, d_out, out_format, d_count, stream);
 }
 
 }  // namespace
@@ -210,69 +164,41 @@ extern "C" {
 int32_t brt_upscale_refine_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                                   const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, uint32_t classes,
                                   uint32_t* d_refined_count_or_null, void* hip_stream, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_low_rgba || !d_out) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_low_rgba / d_out is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only");
+    if (const int32_t bad = flags_check(ctx, flags, kOutFlags, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only")) return bad;
     if (const int32_t bad = refine_check(ctx, camera80, window16, low_width, low_height, width, height, classes)) return bad;
     const uint32_t fmt = flags & BRT_FLAG_OUT_MASK;
     if (overlaps(d_out, out_bytes(width, height, fmt), d_low_rgba, (size_t)low_width * low_height * 16u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out overlaps d_low_rgba");
     if (overlaps(d_out, out_bytes(width, height, fmt), d_refined_count_or_null, 4u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_out overlaps d_refined_count");
-    DeviceCtx& dc = ctx->devs[0];
-    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        const int32_t r = refine_enqueue(ctx, dc, camera80, window16, window16, low_width, low_height, d_low_rgba, width, height, d_out, fmt,
-                                         classes, d_refined_count_or_null, sc.stream);
-        if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        if (r == BRT_OK && stats) std::memset(stats, 0, sizeof *stats);      // (total_ms only, and the tree)
-        return r;
+    return frame_call(ctx, camera80, hip_stream, flags, stats, FRAME_STATS_CLEAR, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        return refine_enqueue(ctx, dc, camera80, window16, window16, low_width, low_height, d_low_rgba, width, height, d_out, fmt, classes,
+                              d_refined_count_or_null, sc.stream);
     });
-    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
-    return rc;
     });
 }
 
 int32_t brt_render_upscaled_refined_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width,
                                            uint32_t low_height, uint32_t width, uint32_t height, void* d_frame, uint32_t classes,
                                            uint32_t* d_refined_count_or_null, void* hip_stream, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!ctx) return fail(BRT_ERR_INVALID_ARGUMENT, "ctx is null");
+    return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_frame) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame is null");
-    if (flags & ~(uint32_t)(BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK))
-        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only (refined pixels are raw samples: no post-pass)");
+    if (const int32_t bad = flags_check(ctx, flags, kOutFlags, "flags: BRT_FLAG_CALLER_STREAM and BRT_FLAG_OUT_* only (refined pixels are raw samples: no post-pass)"))
+        return bad;
     if (const int32_t bad = refine_check(ctx, camera80, window16, low_width, low_height, width, height, classes)) return bad;
     const uint32_t fmt = flags & BRT_FLAG_OUT_MASK;
     if (overlaps(d_frame, out_bytes(width, height, fmt), d_refined_count_or_null, 4u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_frame overlaps d_refined_count");
     char low_win[16];
     low_window(window16, height, low_height, low_win);
-    DeviceCtx& dc = ctx->devs[0];
-    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
-        // the low frame of the context, as brt_render_upscaled_device keeps it
-        const size_t bytes = (size_t)low_width * low_height * 16u;
-        if (dc.uplow_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
-        int32_t r = ensure(ctx, &dc.d_uplow, &dc.uplow_cap, bytes);
+    return frame_call(ctx, camera80, hip_stream, flags, stats, FRAME_STATS_KEEP, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+        const int32_t r = low_frame(ctx, dc, sc, camera80, low_win, low_width, low_height, hip_stream, flags, 0u, stats);
         if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_dn, 0));
-        r = render_frame_device(ctx, camera80, low_win, BRT_LEVEL_PURE, low_width, low_height, nullptr, nullptr, dc.d_uplow, hip_stream,
-                                flags & BRT_FLAG_CALLER_STREAM, stats);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        r = refine_enqueue(ctx, dc, camera80, window16, low_win, low_width, low_height, dc.d_uplow, width, height, d_frame, fmt, classes,
-                           d_refined_count_or_null, sc.stream);
-        if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return r;
+        return refine_enqueue(ctx, dc, camera80, window16, low_win, low_width, low_height, dc.d_uplow, width, height, d_frame, fmt, classes,
+                              d_refined_count_or_null, sc.stream);
     });
-    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
-    return rc;
     });
 }
 
@@ -281,20 +207,15 @@ int32_t brt_upscale_refine_mask_device(brt_ctx* ctx, const void* camera80, const
                                        uint32_t flags) {
     return ctx_guard(ctx, [&]() -> int32_t {
     if (!d_low_rgba || !d_mask_u8) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_low_rgba / d_mask_u8 is null");
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
+    if (const int32_t bad = caller_stream_flags_check(ctx, flags)) return bad;
     if (const int32_t bad = refine_check(ctx, camera80, window16, low_width, low_height, width, height, BRT_REFINE_EDGES | BRT_REFINE_SPECULAR))
         return bad;
     if (overlaps(d_mask_u8, (size_t)width * height, d_low_rgba, (size_t)low_width * low_height * 16u))
         return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "d_mask_u8 overlaps d_low_rgba");
-    DeviceCtx& dc = ctx->devs[0];
-    return with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, nullptr, [&]() -> int32_t {
-        HIP_TRY(ctx, hipSetDevice(dc.device));
-        const StreamChoice sc = stream_of(dc, hip_stream, flags);
+    return frame_call(ctx, camera80, hip_stream, flags, nullptr, FRAME_STATS_KEEP, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         const UpscaleSelect us = {BRT_REFINE_EDGES | BRT_REFINE_SPECULAR, nullptr, nullptr, static_cast<uint8_t*>(d_mask_u8)};
-        const int32_t r = upscale_enqueue(ctx, dc, camera80, window16, low_width, low_height, d_low_rgba, window16, width, height, nullptr,
-                                          BRT_FLAG_OUT_RGBA32F, sc.stream, false, Blend(), &us);
-        if (r == BRT_OK && sc.own) HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return r;
+        return upscale_enqueue(ctx, dc, camera80, window16, low_width, low_height, d_low_rgba, window16, width, height, nullptr,
+                               BRT_FLAG_OUT_RGBA32F, sc.stream, false, Blend(), &us);
     });
     });
 }
@@ -302,7 +223,7 @@ int32_t brt_upscale_refine_mask_device(brt_ctx* ctx, const void* camera80, const
 int32_t brt_upscale_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                            const float* d_low_rgba, uint32_t width, uint32_t height, void* d_out, void* hip_stream, uint32_t flags,
                            brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    return ctx_guard(ctx, [&]() -> int32_t {
     return upscale_device(ctx, camera80, window16, low_width, low_height, d_low_rgba, width, height, d_out, hip_stream, flags, stats, Blend());
     });
 }
@@ -311,18 +232,15 @@ int32_t brt_upscale_blend_device(brt_ctx* ctx, const void* camera80, const void*
                                  uint32_t low_height, const float* d_low_rgba, uint32_t width, uint32_t height,
                                  const float* d_raster_rgba_or_null, const float* d_raster_depth_or_null, void* d_out, void* hip_stream,
                                  uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    Blend bl;
-    bl.level = level;
-    bl.d_raster_rgba = d_raster_rgba_or_null;
-    bl.d_raster_depth = d_raster_depth_or_null;
-    return upscale_device(ctx, camera80, window16, low_width, low_height, d_low_rgba, width, height, d_out, hip_stream, flags, stats, bl);
+    return ctx_guard(ctx, [&]() -> int32_t {
+    return upscale_device(ctx, camera80, window16, low_width, low_height, d_low_rgba, width, height, d_out, hip_stream, flags, stats,
+                          Blend{level, d_raster_rgba_or_null, d_raster_depth_or_null});
     });
 }
 
 int32_t brt_render_upscaled_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t low_width, uint32_t low_height,
                                    uint32_t width, uint32_t height, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
+    return ctx_guard(ctx, [&]() -> int32_t {
     return render_upscaled_device(ctx, camera80, window16, low_width, low_height, width, height, d_frame, hip_stream, flags, stats, Blend());
     });
 }
@@ -331,12 +249,9 @@ int32_t brt_render_upscaled_blend_device(brt_ctx* ctx, const void* camera80, con
                                          uint32_t low_height, uint32_t width, uint32_t height, const float* d_raster_rgba_or_null,
                                          const float* d_raster_depth_or_null, void* d_frame, void* hip_stream, uint32_t flags,
                                          brt_stats* stats) {
-    return guard(ctx ? &ctx->last_error : nullptr, [&]() -> int32_t {
-    Blend bl;
-    bl.level = level;
-    bl.d_raster_rgba = d_raster_rgba_or_null;
-    bl.d_raster_depth = d_raster_depth_or_null;
-    return render_upscaled_device(ctx, camera80, window16, low_width, low_height, width, height, d_frame, hip_stream, flags, stats, bl);
+    return ctx_guard(ctx, [&]() -> int32_t {
+    return render_upscaled_device(ctx, camera80, window16, low_width, low_height, width, height, d_frame, hip_stream, flags, stats,
+                                  Blend{level, d_raster_rgba_or_null, d_raster_depth_or_null});
     });
 }
 
@@ -345,9 +260,7 @@ int32_t brt_render_upscaled_blend_device(brt_ctx* ctx, const void* camera80, con
 int32_t brt_host_blend_covered(const void* camera80, uint32_t level, float t, float raster_depth, uint32_t* out_covered) {
     return guard(nullptr, [&]() -> int32_t {
     if (!camera80 || !out_covered) return fail(BRT_ERR_INVALID_ARGUMENT, "null pointer");
-    if (level == BRT_LEVEL_SKIP) return fail(BRT_ERR_UNSUPPORTED, "level 0 traces nothing");
-    if (level != BRT_LEVEL_FALLBACK_RASTER && level != BRT_LEVEL_FALLBACK_RAYTRACED && level != BRT_LEVEL_PURE)
-        return fail(BRT_ERR_INVALID_ARGUMENT, "level must be 1, 2 or 3");
+    if (const int32_t bad = frame_level_check(nullptr, level, "level 0 traces nothing")) return bad;
     Camera cam;
     std::memcpy(&cam, camera80, sizeof cam);
     *out_covered = 0u;

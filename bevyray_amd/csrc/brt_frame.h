@@ -50,6 +50,41 @@ struct PartStrips {
     uint64_t total_rows() const { return (uint64_t)n_full * BRT_STRIP_ROWS + tail_rows; }
 };
 
+// ---- argument checks and sizes that more than one family states (the list calls; post, upscale, adaptive, G-buffer, lightmap) ----
+// `text` names what the export allows, in its own words
+inline int32_t flags_check(brt_ctx* ctx, uint32_t flags, uint32_t allowed, const char* text) {
+    if (flags & ~allowed) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, text);
+    return BRT_OK;
+}
+// what a call that writes a frame in a BRT_FLAG_OUT_* format allows, and with the post-passes of a frame it traces itself
+constexpr uint32_t kOutFlags = BRT_FLAG_CALLER_STREAM | BRT_FLAG_OUT_MASK;
+constexpr uint32_t kOutPostFlags = kOutFlags | BRT_FLAG_DENOISE | BRT_FLAG_TEMPORAL;
+inline int32_t caller_stream_flags_check(brt_ctx* ctx, uint32_t flags) {
+    return flags_check(ctx, flags, BRT_FLAG_CALLER_STREAM, "flags: BRT_FLAG_CALLER_STREAM only");
+}
+// the size of a frame (a host twin without a context passes nullptr, as to every check here)
+inline int32_t size_check(brt_ctx* ctx, uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0 || width > 32768u || height > 32768u)
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "width/height must be in [1, 32768]");
+    return BRT_OK;
+}
+// the level of a frame that is presented: 0 traces nothing (`nothing`: the call's words for it), else 1, 2 or 3
+inline int32_t frame_level_check(brt_ctx* ctx, uint32_t level, const char* nothing) {
+    if (level == BRT_LEVEL_SKIP) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, nothing);
+    if (level != BRT_LEVEL_FALLBACK_RASTER && level != BRT_LEVEL_FALLBACK_RAYTRACED && level != BRT_LEVEL_PURE)
+        return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "level must be 1, 2 or 3");
+    return BRT_OK;
+}
+inline bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const char* pa = static_cast<const char*>(a);
+    const char* pb = static_cast<const char*>(b);
+    return a && b && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+// of a width x height frame in the BRT_FLAG_OUT_* format fmt
+inline size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt) {
+    return (size_t)width * height * (fmt == BRT_FLAG_OUT_RGBA32F ? 16u : fmt == BRT_FLAG_OUT_RGBA16F ? 8u : 4u);
+}
+
 // ---- brt_api.cpp ----
 // brt_upload_scene; with `rebuild`, the resident scene's bytes again in a callee-built SAH tree of reach level `level`
 int32_t upload_scene(brt_ctx* ctx, const void* models, uint32_t n_models, const void* materials, uint32_t n_materials,
@@ -164,10 +199,9 @@ struct PixelsTarget {
 int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                        const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
                        hipStream_t stream, bool force_plain, PixelsLaunch* pl, const LensView* lens = nullptr);
-// What brt_render_pixels* and brt_render_lens* (brt_api_lens.cpp) share.  The two checks of a frame size and of a list with its output;
-// a call behind its checks, of n_pixels > 0 entries; its two bodies, which run once the tree is settled; and the launch fields of its
-// stats (counts2 null: not counted; kernel_variant 32 / 33, under a lens 34 / 35).
-int32_t size_check(brt_ctx* ctx, uint32_t width, uint32_t height);
+// What brt_render_pixels* and brt_render_lens* (brt_api_lens.cpp) share.  The check of a list with its output; a call behind its checks,
+// of n_pixels > 0 entries; its two bodies, which run once the tree is settled; and the launch fields of its stats (counts2 null: not
+// counted; kernel_variant 32 / 33, under a lens 34 / 35).
 int32_t list_check(brt_ctx* ctx, const void* pixels, uint32_t n_pixels, const void* out);
 struct PixelsCall {
     const void *camera80, *window16;     // as pixels_enqueue takes them
@@ -198,13 +232,6 @@ int32_t pixels_call(brt_ctx* ctx, const PixelsCall& pc, brt_stats* stats, Reach&
     return rc;
 }
 
-// ---- brt_api_upscale.cpp ----
-bool overlaps(const void* a, size_t a_bytes, const void* b, size_t b_bytes);
-size_t out_bytes(uint32_t width, uint32_t height, uint32_t fmt);
-// The control words and the list of a width x height refinement or adaptive frame (DeviceCtx::d_pxbuf) for work on `stream`: a larger
-// one is allocated only once the last user of the old one has ended; the control words are zeroed behind that user
-int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream);
-
 // ---- brt_api_post.cpp ----
 // the guides' frame parameters (one part, level 3) and the denoiser's scratch of a width x height frame for work on `stream`
 int32_t denoise_begin(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
@@ -214,12 +241,77 @@ int32_t run_denoise(brt_ctx* ctx, DeviceCtx& dc, const FrameParams& fp, const De
 bool blend_post_on(uint32_t level, uint32_t flags);
 int32_t post_flags_check(brt_ctx* ctx, uint32_t level, uint32_t flags);
 
-// ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp,
-// brt_api_envmap.cpp, brt_api_lightmap.cpp, brt_api_pixels.cpp) ----
-inline int32_t caller_stream_flags_check(brt_ctx* ctx, uint32_t flags) {
-    if (flags & ~(uint32_t)BRT_FLAG_CALLER_STREAM) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "flags: BRT_FLAG_CALLER_STREAM only");
+// ---- what the calls on a whole frame behind the tracer share (brt_api_post.cpp, brt_api_upscale.cpp, brt_api_adaptive.cpp) ----
+// What a successful call leaves in its brt_stats besides total_ms and the tree: what render_frame_device filled in, or nothing; and on the
+// context's own stream the rays of the re-trace (trace_selected) added to either.
+enum FrameStats : uint32_t { FRAME_STATS_KEEP = 0u, FRAME_STATS_CLEAR = 1u, FRAME_STATS_ADD_RETRACE = 2u };
+// A call behind its argument checks: the tree settled for the camera (with_tree_reach: a failed call leaves nothing in flight on the
+// context's own streams), then body(dc, sc) on the first device with the call's stream; an own stream is synchronised; the stats rule;
+// total_ms.
+template <class Body>
+int32_t frame_call(brt_ctx* ctx, const void* camera80, void* hip_stream, uint32_t flags, brt_stats* stats, uint32_t stats_rule, Body&& body) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t rc = with_tree_reach(ctx, camera80, BRT_LEVEL_PURE, stats, [&]() -> int32_t {     // (the guides walk the tree of the frame)
+        DeviceCtx& dc = ctx->devs[0];
+        HIP_TRY(ctx, hipSetDevice(dc.device));
+        const StreamChoice sc = stream_of(dc, hip_stream, flags);
+        const int32_t r = body(dc, sc);
+        if (r != BRT_OK) return r;
+        unsigned long long rays = 0u;
+        if (sc.own) {
+            if (stats_rule & FRAME_STATS_ADD_RETRACE) HIP_TRY(ctx, hipMemcpyAsync(&rays, dc.d_pxbuf, sizeof rays, hipMemcpyDeviceToHost, sc.stream));
+            HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+        }
+        if (stats && (stats_rule & FRAME_STATS_CLEAR)) std::memset(stats, 0, sizeof *stats);
+        if (stats) stats->rays += rays;
+        return BRT_OK;
+    });
+    if (rc == BRT_OK && stats) stats->total_ms = ms_since(t0);
+    return rc;
+}
+
+// The frame the context keeps between two stages of one call (DeviceCtx::d_uplow: the low frame of an upsampling that traces it, the base
+// frame of adaptive sampling), of at least `bytes`, for work on `stream`.  Its last reader recorded ev_dn: the frame grows only once
+// ev_dn has passed, and the stream waits for ev_dn before the trace writes it.
+inline int32_t context_frame(brt_ctx* ctx, DeviceCtx& dc, size_t bytes, hipStream_t stream) {
+    if (dc.uplow_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_dn));
+    const int32_t rc = ensure(ctx, &dc.d_uplow, &dc.uplow_cap, bytes);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_dn, 0));
     return BRT_OK;
 }
+
+// DeviceCtx::d_pxbuf: kPxListWord control words -- the {u64 rays, u64 refused, u32 batch counter} pixels_enqueue zeroes, at kPxCountWord
+// the number of selected pixels, two spare -- then the list of a selecting call, one word per pixel of its frame.
+constexpr uint32_t kPxCountWord = 5u, kPxListWord = 8u;
+struct SelectList { uint32_t *ctl, *count, *list; };
+// The list of a width x height refinement or adaptive frame for work on `stream`, ordered by ev_q: a larger one is allocated only once the
+// last user of the old one has ended; the control words are zeroed behind that user
+inline int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream, SelectList* sl) {
+    const size_t bytes = ((size_t)width * height + kPxListWord) * 4u;
+    if (dc.pxbuf_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
+    const int32_t rc = ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, bytes);
+    if (rc != BRT_OK) return rc;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    HIP_TRY(ctx, hipMemsetAsync(dc.d_pxbuf, 0, kPxListWord * 4u, stream));
+    *sl = {dc.d_pxbuf, dc.d_pxbuf + kPxCountWord, dc.d_pxbuf + kPxListWord};
+    return BRT_OK;
+}
+// Behind the kernel that selected into sl on `stream`: the selected pixels of the width x height frame traced into d_out, the count copied
+// to d_count (or nullptr), and ev_q recorded, which frees the list for the next selecting call
+inline int32_t trace_selected(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                              const SelectList& sl, void* d_out, uint32_t out_format, uint32_t* d_count, hipStream_t stream) {
+    PixelsLaunch pl{};
+    const int32_t rc = pixels_enqueue(ctx, dc, camera80, window16, width, height, sl.list, width * height, sl.count, {d_out, true, out_format},
+                                      sl.ctl, stream, false, &pl);
+    if (rc != BRT_OK) return rc;
+    if (d_count) HIP_TRY(ctx, hipMemcpyAsync(d_count, sl.count, 4, hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+    return BRT_OK;
+}
+
+// ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp,
+// brt_api_envmap.cpp, brt_api_lightmap.cpp, brt_api_pixels.cpp) ----
 inline int32_t origin_bound_check(brt_ctx* ctx, float origin_bound) {
     if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
     return BRT_OK;

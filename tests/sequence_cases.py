@@ -309,6 +309,52 @@ def generate(spec, oracle):
     return seq
 
 
+# ---- what the contexts' buffers of the frame-level calls see ----------------------------------------------------------------------
+ADAPTIVE_BASE_SPP = 8           # RaytracePlugin.set_adaptive's default: a sequence of spp <= 8 traces the plain frame, no base frame
+
+
+def _context_frame_bytes(step):
+    """what a step needs of the frame the context keeps between two stages of a call (the low frame of an upscaled step, the base frame
+    of an adaptive one; brt_frame.h context_frame)"""
+    if step.family == "upscaled":
+        return step.v["pair"][2] * step.v["pair"][3] * 16
+    return ADAPTIVE_SIZE[0] * ADAPTIVE_SIZE[1] * 16 if step.family == "adaptive" else 0
+
+
+def frame_grows_on_a_caller_stream(seq):
+    """-> the adaptive steps on a caller's stream at which the context's frame, last used by an upscaled step, has to grow"""
+    if seq.spp <= ADAPTIVE_BASE_SPP:
+        return []
+    out, have, last = [], 0, None
+    for s in seq.steps:
+        need = _context_frame_bytes(s)
+        if need:
+            if s.family == "adaptive" and last == "upscaled" and need > have and s.stream != "own":
+                out.append(s.index)
+            have, last = max(have, need), s.family
+    return out
+
+
+def refined_follows_adaptive(seq):
+    """-> the refined upscaled steps behind an adaptive step that selected: the selection list (DeviceCtx::d_pxbuf) serves both tails"""
+    if seq.spp <= ADAPTIVE_BASE_SPP:
+        return []
+    first = next((s.index for s in seq.steps if s.family == "adaptive"), None)
+    return [s.index for s in seq.steps if first is not None and s.index > first and s.family == "upscaled" and s.v["call"] == "refined"]
+
+
+def fixed_frame_grows(oracle):
+    """One fixed sequence at the module's sizes, which the drawn ones lack: an upscaled frame (low frame 32x18) on one caller stream, the
+    adaptive frame (base frame 64x36: the context's frame grows) on another, then a refined upscaled frame on the first."""
+    seq = generate(("fixed_frame_grows", "fixed", 4242, ("upscaled", "adaptive", "upscaled"), 0.0), oracle)
+    seq.spp = 32
+    for s, stream, v in zip(seq.steps, ("s1", "s2", "s1"), ({"call": "plain"}, {}, {"call": "refined"})):
+        s.stream = stream
+        if v:
+            s.v, s.inp = dict(v, pair=UPSCALE_PAIRS[0], level=3), {}
+    return seq
+
+
 def description(seq):
     """The whole sequence as bytes-comparable text: the determinism test compares two of these"""
     lines = [f"{seq.name} {seq.w}x{seq.h} spp {seq.spp} tile {seq.tile} spread {seq.spread}"]

@@ -108,6 +108,19 @@ def test_every_variant_and_every_event_is_drawn():
     assert raises >= 4
 
 
+def test_the_context_frame_and_the_selection_list_are_reused_across_families(oracle):
+    """Two reuses of the buffers the frame-level calls share (brt_frame.h context_frame, refine_list): the context's frame grows between
+    an upscaled and an adaptive call on a caller's stream -- no drawn sequence has that, so one fixed sequence adds it -- and a refined
+    call follows an adaptive one."""
+    drawn = [_sequence(n) for n in NAMES]
+    fixed = sc.fixed_frame_grows(oracle)
+    assert not any(sc.frame_grows_on_a_caller_stream(q) for q in drawn)      # (if a drawn one gains it, the fixed one can go)
+    assert sc.frame_grows_on_a_caller_stream(fixed) == [1]
+    assert sum(1 for q in drawn if sc.refined_follows_adaptive(q)) >= 1 and sc.refined_follows_adaptive(fixed) == [2]
+    assert sc.description(fixed) == sc.description(sc.fixed_frame_grows(oracle))
+    assert [(s.family, s.stream, s.event) for s in fixed.steps] == [("upscaled", "s1", None), ("adaptive", "s2", None), ("upscaled", "s1", None)]
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_the_reference_only_inputs_are_non_trivial(oracle, name):
     seq = _sequence(name)
@@ -575,6 +588,10 @@ def test_stepwise(oracle, name):
 def test_in_flight(oracle, name):
     seq = _sequence(name)
     want = _stepwise(name)
+    _compare_in_flight(seq, want)
+
+
+def _compare_in_flight(seq, want):
     got = _run_in_flight(seq)
     compared = 0
     for s, g, w in zip(seq.steps, got, want):
@@ -583,6 +600,15 @@ def test_in_flight(oracle, name):
             _bits_equal(g[k], w[k], f"{seq.name} (seed {seq.seed}) in flight, {s.describe()}: {k} against the stepwise run")
         compared += 1
     assert compared == len(seq.steps)
+
+
+@pytest.mark.gpu
+def test_the_fixed_sequence_stepwise_and_in_flight(oracle):
+    """sequence_cases.fixed_frame_grows: every step bit for bit against its control context, then in flight against the stepwise run"""
+    seq = sc.fixed_frame_grows(oracle)
+    want, report = _run_stepwise(seq, oracle)
+    assert report["compared"] == len(want) == 3
+    _compare_in_flight(seq, want)
 
 
 @pytest.mark.gpu
