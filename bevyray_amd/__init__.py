@@ -12,6 +12,7 @@ from .raytracing import (  # noqa: F401
     SCENE_COVER, SCENE_RTIOW_FINAL, SCENE_STRESS_GRID, STRIP_ROWS, WINDOW_DTYPE, Buffers, CameraExtract,
     OrthographicProjection, PerspectiveProjection, RaytracedCamera, RaytracedSphere, RaytraceMaterial, RaytracePlugin,
     Raytracing, RayTracingNode, StandardMaterial, Transform, WindowExtract, build_bvh, build_bvh_sah, cover_camera, generate_scene, tree_reach,
+    PROG_DEFAULT_THRESHOLD, PROG_PIXEL_DTYPE, PROG_SELECTED, progressive_accumulate, progressive_class,
     ADAPT_DEFAULT_THRESHOLD, ADAPT_NOISY, ADAPT_SPARSE, HIT_DTYPE, REFINE_EDGES, REFINE_SPECULAR, adaptive_class, QUERY_ANY, QUERY_CLOSEST, QUERY_NONE, QUERY_STATUS_FRONT_FACE, QUERY_STATUS_HIT, QUERY_STATUS_INVALID, QUERY_STATUS_MISS,
     QUERY_STATUS_OUT_OF_REACH, RADIANCE_DTYPE, RADIANCE_RAY_DTYPE, RAY_DTYPE, pixel_ray,
     PROBE_AMBIENT_CUBE, PROBE_DTYPE, PROBE_RECORD_DTYPE, PROBE_SH9, probe_directions, probe_irradiance,

@@ -163,6 +163,14 @@ _PROTOTYPES = {
     "brt_adaptive_refine_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _VP, _U32, C.POINTER(BrtStats)]),
     "brt_adaptive_mask_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U32]),
     "brt_host_adaptive_class": (_I32, [_F, _U32, _VP, _VP, _VP, _VP, _F, _U32, C.POINTER(_U32)]),
+    "brt_set_progressive": (_I32, [_VP, _U32, _U32, _F, _U32]),
+    "brt_progressive_sample_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _U32, _VP, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_progressive_sample": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _U32, _U32, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_progressive_select_device": (_I32, [_VP, _U32, _U32, _VP, _U32, _VP, _VP, _VP, _VP, _U32]),
+    "brt_render_progressive_device": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_render_progressive": (_I32, [_VP, _VP, _VP, _U32, _U32, _VP, _VP, _U32, C.POINTER(BrtStats)]),
+    "brt_host_progressive_accumulate": (_I32, [_VP, _VP]),
+    "brt_host_progressive_class": (_I32, [_VP, _VP, _U32, _F, _U32, C.POINTER(_U32)]),
     "brt_debug_profile": (_I32, [_VP, C.POINTER(C.c_uint64)]),
     "brt_debug_tile_order": (_I32, [_VP, _VP, _VP, _U32, _U32, C.c_uint64, _U32, _U32, _U32, _VP, _VP]),
     "brt_build_bvh": (_I32, [_VP, _U32, _VP, _U32, C.POINTER(_U32)]),

@@ -15,6 +15,7 @@
 #include "brt_host.h"
 #include "brt_kernels.h"
 #include "brt_pixels.h"
+#include "brt_progressive.h"
 #include "brt_query.h"
 #include "brt_radiance.h"
 #include "brt_upscale.h"
@@ -196,7 +197,7 @@ struct DeviceCtx {
 enum Knob : int {
     K_BOTTOM_UP, K_REFILL_MIN, K_WALK_EXIT, K_LEAF_VOTE, K_DRAIN_DONATE, K_POOL_ADOPT, K_WGQ_BATCH, K_LPT_LANE_PERMILLE, K_TUNABLE,
     K_FORCE_GLOBAL_SCENE, K_FORCE_LDS_TOP, K_BLOCK_THREADS, K_WG_PER_CU, K_POOL_CAP, K_LPT, K_LPT_SORT, K_LPT_SKY_SLACK, K_CRIT,
-    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_PIXELS_FORM, K_RADIANCE_FORM, K_PROBE_CHUNK_RAYS, K_COUNT
+    K_ORDER_ON_HOST, K_NO_LEAN, K_PREPASS_SPP, K_NO_DIRTY_TRACKING, K_CPU_BVH, K_PLOC_ONE_BLOCK_MAX, K_BVH_QUALITY, K_POOL_FORCE, K_LPT_REFRESH_EVERY, K_LEAN_MEASURE, K_LPT_DILATE, K_SPLIT_TAIL, K_SPLIT_FORCE, K_HOT_RECORDS, K_TEST_THROW, K_QUERY_FORM, K_QUERY_STREAM_MIN, K_PIXELS_FORM, K_RADIANCE_FORM, K_PROBE_CHUNK_RAYS, K_PROGRESSIVE_ORDER, K_COUNT
 };
 struct KnobDef { const char* name; uint32_t dflt; };
 constexpr KnobDef kKnobs[K_COUNT] = {
@@ -213,7 +214,10 @@ constexpr KnobDef kKnobs[K_COUNT] = {
     // radiance queries: the form of a call (0: streaming from kRadianceStreamMin entries on where the scene has an LDS form, 1 plain, 2 streaming)
     {"BRT_RADIANCE_FORM", 0},
     // light probes: the entries of one chunk of a bake (whole probes, at least one; 64 bytes of staging per entry)
-    {"BRT_PROBE_CHUNK_RAYS", 1u << 21}};
+    {"BRT_PROBE_CHUNK_RAYS", 1u << 21},
+    // progressive frames: the order of a whole-frame pass (0: raster order, 1: entries in 8x8 tiles, so that a wave's FIRST fetch is one
+    // tile -- the streaming form's later refills take single entries; measured 0.25 % faster at 1080p, inside the spread)
+    {"BRT_PROGRESSIVE_ORDER", 1}};
 struct Knobs {
     uint32_t v[K_COUNT];
     Knobs() { for (int i = 0; i < K_COUNT; i++) v[i] = kKnobs[i].dflt; }
@@ -266,6 +270,11 @@ struct brt_ctx {
         float threshold = brt::kAdaptDefaultThreshold;
         uint32_t min_taps = 6;
     } adaptive;
+    struct Progressive {            // brt_set_progressive
+        uint32_t first_spp = 8, max_spp = 64;
+        float threshold = brt::kProgDefaultThreshold;
+        uint32_t radius = 1;
+    } progressive;
     struct Temporal {               // BRT_FLAG_TEMPORAL
         uint32_t max_history = 32;  // brt_set_temporal
         bool valid = false;         // the history holds a frame (false: n = 0 everywhere)

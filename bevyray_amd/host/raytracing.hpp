@@ -288,6 +288,33 @@ public:
                               void* d_mask_u8, void* hip_stream = nullptr, uint32_t flags = 0) {
         check(brt_adaptive_mask_device(ctx_, &camera, &window, width, height, d_base, d_mask_u8, hip_stream, flags), ctx_);
     }
+    // Progressive frames (include/bevyray_amd.h "progressive frames"): a plane of 32-byte pixel records (ProgressivePixel) the caller holds;
+    // the listed pixels (d_pixels nullptr: every pixel, n_pixels = width * height) continued to `target` samples, each named at most once;
+    // the pixels a target is still worth selected from the records' own moments; and the one-call form under RaytracePlugin::set_progressive.
+    struct ProgressivePixel { float sum[3]; float m1, m2; uint32_t rng, n, rays; };
+    void progressive_sample_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, void* d_state,
+                                   const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, uint32_t target, void* d_frame = nullptr,
+                                   void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_progressive_sample_device(ctx_, &camera, &window, width, height, d_state, d_pixels, n_pixels, d_count, target, d_frame, hip_stream,
+                                            flags, stats), ctx_);
+    }
+    void progressive_sample(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, ProgressivePixel* state,
+                            const uint32_t* pixels, uint32_t n_pixels, uint32_t target, void* frame = nullptr, uint32_t flags = 0,
+                            brt_stats* stats = nullptr) {
+        check(brt_progressive_sample(ctx_, &camera, &window, width, height, state, pixels, n_pixels, target, frame, flags, stats), ctx_);
+    }
+    void progressive_select_device(uint32_t width, uint32_t height, const void* d_state, uint32_t target, uint32_t* d_list, uint32_t* d_count,
+                                   void* d_mask_u8 = nullptr, void* hip_stream = nullptr, uint32_t flags = 0) {
+        check(brt_progressive_select_device(ctx_, width, height, d_state, target, d_list, d_count, d_mask_u8, hip_stream, flags), ctx_);
+    }
+    void render_progressive_device(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, void* d_state,
+                                   void* d_destination, void* hip_stream = nullptr, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_progressive_device(ctx_, &camera, &window, width, height, d_state, d_destination, hip_stream, flags, stats), ctx_);
+    }
+    void render_progressive(const CameraExtract& camera, const WindowExtract& window, uint32_t width, uint32_t height, ProgressivePixel* state,
+                            void* frame, uint32_t flags = 0, brt_stats* stats = nullptr) {
+        check(brt_render_progressive(ctx_, &camera, &window, width, height, state, frame, flags, stats), ctx_);
+    }
     // the window a low_height frame is traced with when it is presented at `height` rows
     static WindowExtract upscale_window(const WindowExtract& window, uint32_t height, uint32_t low_height) {
         WindowExtract w{};
@@ -366,6 +393,10 @@ public:
     // the settings of adaptive frames (brt_set_adaptive; the defaults are the library's)
     void set_adaptive(uint32_t base_spp = 8, float threshold = 0.025f, uint32_t min_taps = 6) {
         check(brt_set_adaptive(ctx_, base_spp, threshold, min_taps), ctx_);
+    }
+    // the settings of progressive frames (brt_set_progressive; the defaults are the library's)
+    void set_progressive(uint32_t first_spp = 8, uint32_t max_spp = 64, float threshold = 0.05f, uint32_t radius = 1) {
+        check(brt_set_progressive(ctx_, first_spp, max_spp, threshold, radius), ctx_);
     }
     // the temporal history of BRT_FLAG_TEMPORAL frames (brt_set_temporal: 1..65535, empties it; brt_reset_temporal: on a camera cut)
     void set_temporal(uint32_t max_history = 32) { check(brt_set_temporal(ctx_, max_history), ctx_); }

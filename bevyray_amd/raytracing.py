@@ -331,6 +331,33 @@ def adaptive_class(t, material_id, rgb, taps_inside, taps_id, taps_rgb, threshol
     return int(c.value)
 
 
+# progressive frames: brt_*progressive* (include/bevyray_amd.h): the 32-byte record of a pixel between two of its samples
+PROG_SELECTED = 1
+PROG_DEFAULT_THRESHOLD = 0.05
+PROG_PIXEL_DTYPE = np.dtype([("sum", np.float32, 3), ("m1", np.float32), ("m2", np.float32), ("rng", np.uint32), ("n", np.uint32),
+                             ("rays", np.uint32)])
+assert PROG_PIXEL_DTYPE.itemsize == 32
+
+
+def progressive_accumulate(record, rgb) -> np.ndarray:
+    """brt_host_progressive_accumulate: one PROG_PIXEL_DTYPE record with one more sample of colour rgb (a new array; rng and rays stay)."""
+    rec = np.array(record, PROG_PIXEL_DTYPE).reshape(1).copy()
+    col = np.ascontiguousarray(rgb, np.float32).reshape(-1)[:3].copy()
+    _lib.check(_lib.load().brt_host_progressive_accumulate(rec.ctypes.data, col.ctypes.data))
+    return rec
+
+
+def progressive_class(records9, inside9, target: int, threshold: float = PROG_DEFAULT_THRESHOLD, radius: int = 1) -> int:
+    """brt_host_progressive_class: PROG_SELECTED or 0 for one pixel from the PROG_PIXEL_DTYPE records of its 3x3 window (dy outer, dx
+    inner, -1 .. 1: the pixel itself is records9[4]) and whether each lies inside the frame."""
+    recs = np.ascontiguousarray(records9, PROG_PIXEL_DTYPE).reshape(9)
+    inside = np.ascontiguousarray(inside9, np.uint32).reshape(9)
+    c = C.c_uint32(0)
+    _lib.check(_lib.load().brt_host_progressive_class(recs.ctypes.data, inside.ctypes.data, int(target), float(threshold), int(radius),
+                                                      C.byref(c)))
+    return int(c.value)
+
+
 def upscale_window(window, height: int, low_height: int) -> np.ndarray:
     """brt_host_upscale_window: the window a low_height frame is traced with when it is to be upsampled to `height` rows -- the seed of
     `window`, its height scaled to max(1, window.height * low_height // height).  Host arithmetic."""
@@ -712,6 +739,11 @@ class RaytracePlugin:
         """brt_set_adaptive: the settings of RayTracingNode.render_adaptive_device & co. (base_spp 1..65535, threshold finite and > 0,
         min_taps 1..25).  Invalid values raise BrtError and leave the settings as they were."""
         _lib.check(self._lib.brt_set_adaptive(self._ctx, int(base_spp), float(threshold), int(min_taps)), self._ctx)
+
+    def set_progressive(self, first_spp: int = 8, max_spp: int = 64, threshold: float = PROG_DEFAULT_THRESHOLD, radius: int = 1) -> None:
+        """brt_set_progressive: the settings of RayTracingNode.render_progressive* and progressive_select_device (2 <= first_spp <=
+        max_spp <= 65535, threshold finite and > 0, radius 0 or 1).  Invalid values raise BrtError and leave the settings as they were."""
+        _lib.check(self._lib.brt_set_progressive(self._ctx, int(first_spp), int(max_spp), float(threshold), int(radius)), self._ctx)
 
     def debug_denoise_guides(self, camera, window, width: int, height: int) -> np.ndarray:
         """brt_debug_denoise_guides: (height, width, 8) f32 -- normal.xyz, t (inf: sky), a.rgb, material id as bits
@@ -1202,6 +1234,71 @@ class RayTracingNode:
         p = self._p
         _lib.check(p._lib.brt_adaptive_mask_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_base or None,
                                                    d_mask or None, *_stream_args(stream)), p._ctx)
+
+    # -- progressive frames (include/bevyray_amd.h "progressive frames") -----------------------------
+
+    def progressive_sample_device(self, camera, window, width: int, height: int, d_state: int, target: int, d_pixels: int = 0,
+                                  n_pixels: Optional[int] = None, d_count: int = 0, d_frame: int = 0, stream: Optional[int] = None,
+                                  out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_progressive_sample_device: the listed pixels (d_pixels 0: every pixel) of the state plane at d_state (PROG_PIXEL_DTYPE,
+        width x height) continued to `target` samples; their values scattered into the frame at d_frame (0: none).  A pixel may be
+        named at most once per call.  flags: FLAG_KERNEL_SIMPLE for the plain form."""
+        p = self._p
+        stats = BrtStats()
+        n = width * height if n_pixels is None else int(n_pixels)
+        _lib.check(p._lib.brt_progressive_sample_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_state or None,
+                                                        d_pixels or None, n, d_count or None, int(target), d_frame or None,
+                                                        *_stream_args(stream, out_format | flags), C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def progressive_sample(self, camera, window, width: int, height: int, state: np.ndarray, target: int, pixels=None,
+                           frame: Optional[np.ndarray] = None, out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_progressive_sample: progressive_sample_device for host arrays, in place: `state` (PROG_PIXEL_DTYPE, height x width,
+        C-contiguous), `pixels` (uint32 or None: every pixel) and `frame` (or None)."""
+        p = self._p
+        stats = BrtStats()
+        assert state.dtype == PROG_PIXEL_DTYPE and state.size == width * height and state.flags.c_contiguous
+        lst = None if pixels is None else np.ascontiguousarray(pixels, np.uint32)
+        if lst is not None and lst.size == 0:       # (a null list means every pixel: an empty one is nothing to do)
+            self.last_stats = BrtStats().as_dict()
+            return self.last_stats
+        n = width * height if lst is None else lst.size
+        _lib.check(p._lib.brt_progressive_sample(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, state.ctypes.data,
+                                                 None if lst is None else lst.ctypes.data, n, int(target),
+                                                 None if frame is None else frame.ctypes.data, out_format | flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def progressive_select_device(self, width: int, height: int, d_state: int, target: int, d_list: int = 0, d_count: int = 0,
+                                  d_mask: int = 0, stream: Optional[int] = None) -> None:
+        """brt_progressive_select_device: the pixels of the state plane that `target` is still worth under the context's threshold and
+        radius (RaytracePlugin.set_progressive): appended to d_list with their number in d_count, class bytes to d_mask (0: none)."""
+        p = self._p
+        _lib.check(p._lib.brt_progressive_select_device(p._ctx, width, height, d_state or None, int(target), d_list or None, d_count or None,
+                                                        d_mask or None, *_stream_args(stream)), p._ctx)
+
+    def render_progressive_device(self, camera, window, width: int, height: int, d_state: int, d_frame: int, stream: Optional[int] = None,
+                                  out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_progressive_device: the one-call form -- every pixel to first_spp, then selection and continuation for the targets
+        doubling up to max_spp (RaytracePlugin.set_progressive).  The state at d_state is not cleared."""
+        p = self._p
+        stats = BrtStats()
+        _lib.check(p._lib.brt_render_progressive_device(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, d_state or None,
+                                                        d_frame or None, *_stream_args(stream, out_format | flags), C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
+
+    def render_progressive(self, camera, window, width: int, height: int, state: np.ndarray, frame: np.ndarray,
+                           out_format: int = FLAG_OUT_RGBA32F, flags: int = 0) -> dict:
+        """brt_render_progressive: render_progressive_device for host arrays, in place."""
+        p = self._p
+        stats = BrtStats()
+        assert state.dtype == PROG_PIXEL_DTYPE and state.size == width * height and state.flags.c_contiguous
+        _lib.check(p._lib.brt_render_progressive(p._ctx, camera.ctypes.data, window.ctypes.data, width, height, state.ctypes.data,
+                                                 frame.ctypes.data, out_format | flags, C.byref(stats)), p._ctx)
+        self.last_stats = stats.as_dict()
+        return self.last_stats
 
     # -- ray queries (include/bevyray_amd.h "ray queries") ------------------------------------------
 

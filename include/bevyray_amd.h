@@ -1117,6 +1117,71 @@ int32_t brt_adaptive_mask_device(brt_ctx* ctx, const void* camera80, const void*
 int32_t brt_host_adaptive_class(float t, uint32_t material_id, const float* rgb, const uint32_t* taps_inside25, const uint32_t* taps_id25,
                                 const float* taps_rgb75, float threshold, uint32_t min_taps, uint32_t* out_class);
 
+/* ---- progressive frames ---------------------------------------------------------------------------------------------------------------
+ * A Pure (level 3) frame that gains samples call after call, and whose pixels can stop at different sample counts.  A pixel's samples
+ * share one RNG state and the sample count enters only the final division, so between two samples a pixel is fully described by a
+ * RECORD the caller holds, 32 bytes per pixel, width x height of them (the STATE plane):
+ *   { float sum[3]; float m1; float m2; uint32_t rng; uint32_t n; uint32_t rays; }
+ * An all-zero record is a pixel without samples (rng is ignored while n == 0).  One sample of colour c: sum += c, then
+ * l = (0.2126 r + 0.7152 g) + 0.0722 b, m1 += l, m2 += l * l, n += 1; rays gains the sample's raycasts.  The value of the pixel is
+ * {sum / (float)n, 1}, four zeros at n == 0: a pixel continued to n samples holds exactly what brt_render_device stores there at
+ * sample_count n, whatever its neighbours got.  The rule, every operation a separately rounded f32 one:
+ *   OWN FLAG of a pixel with n >= 2 (fewer: quiet): m = m1 / n, v = max(0, m2 / n - m * m), e = v / n, t = threshold * max(m, 0.01);
+ *   NOISY iff e > t * t  (max(a, b) = a > b ? a : b).  Non-finite moments: a NaN moment, or m1 and m2 both +INF (INF - INF = NaN, v = 0),
+ *   compares false and the pixel is quiet.  The one non-finite case the rule selects: m2 ALONE overflowing while m * m stays finite
+ *   (luminances of about 1e19) gives e = +INF, which is noisy at every threshold whose t * t is finite.  The flag does not read `sum`.
+ *   CLASS for a target T: BRT_PROG_SELECTED iff n_p < T and a pixel of the (2 radius + 1)^2 window around p, clipped to the frame, is
+ *   noisy (radius 0 or 1).
+ * Kernels, costs and quality: DESIGN.md "Progressive frames".
+ *   brt_set_progressive             2 <= first_spp <= max_spp <= 65535 (defaults 8, 64), threshold finite and > 0 (default 0.05), radius 0
+ *                                   or 1 (default 1); anything else BRT_ERR_INVALID_ARGUMENT and the settings stay as they were.
+ *   brt_progressive_sample_device   continues the listed pixels (DEVICE list of n_pixels entries p = y * width + x; d_count_or_null: a
+ *                                   DEVICE word that holds the number of entries, n_pixels is then the capacity) to `target` samples:
+ *                                   records in d_state, values scattered into d_frame_or_null (width x height, BRT_FLAG_OUT_* format).
+ *                                   A record with n >= target is left byte for byte, its value is still stored; an entry outside the
+ *                                   frame is refused and touches nothing; pixels not listed are not touched.  A PIXEL MAY BE NAMED AT MOST
+ *                                   ONCE PER CALL (two entries of one pixel race).  d_pixels_or_null null: every pixel (n_pixels = width *
+ *                                   height, no count word).  camera.sample_count is not read.  flags: BRT_FLAG_OUT_*,
+ *                                   BRT_FLAG_CALLER_STREAM, BRT_FLAG_KERNEL_SIMPLE (the plain form).  stats_or_null as brt_render_pixels*
+ *                                   (rays, paths = samples run, reserved = entries refused on the context's own stream); kernel_variant
+ *                                   36 (streaming form) / 37 (plain form).
+ *   brt_progressive_sample          the same for host buffers (no count word), synchronous; pixels of `frame` that are not listed keep
+ *                                   what the caller's frame held.
+ *   brt_progressive_select_device   the class of every pixel for `target` under the context's threshold and radius: the selected pixels
+ *                                   appended to d_list (width * height words) with their number in d_count (zeroed here; only the list's
+ *                                   order is not deterministic), the class bytes to d_mask_u8_or_null.  d_list and d_count both null: the
+ *                                   mask alone.  Traces nothing.  flags: BRT_FLAG_CALLER_STREAM only.
+ *   brt_render_progressive_device   the one-call form: every pixel to first_spp, then for the targets first_spp * 2, * 4, ... (the last one
+ *                                   max_spp) a selection and the selected pixels continued, the count taken from the device word: no host
+ *                                   round trip, a fixed number of passes.  The state is NOT cleared: a zeroed plane starts a new frame, a
+ *                                   held plane with a larger max_spp carries a finished frame on.  d_frame holds every pixel's value.
+ *   brt_render_progressive          the same for host buffers, synchronous.
+ *   brt_host_progressive_accumulate one sample's colour rgb added to the record at record32, on the host (the code the kernels compile).
+ *   brt_host_progressive_class      the class of ONE pixel from the records of its 3x3 window (dy outer, dx inner, both -1 .. 1: the pixel
+ *                                   itself is records9[4]; inside9[k] = 0: outside the frame), on the host.
+ * Any other flag bit is BRT_ERR_INVALID_ARGUMENT, BRT_FLAG_DENOISE / BRT_FLAG_TEMPORAL included.  A non-default policy (brt_set_policy)
+ * and orthographic projection: BRT_ERR_UNSUPPORTED; BRT_ERR_NO_SCENE before an upload; null pointers, a target of 0 or above 65535,
+ * sizes outside [1, 32768] and a state plane that overlaps the frame: BRT_ERR_INVALID_ARGUMENT.  DEVICE planes are 16-byte aligned.  A
+ * refused call leaves the context usable.  Calls of one context run one behind the other with its pixel lists, ray queries and
+ * adaptive calls, on whatever streams they come; plain frames and their dispatch history are not touched. */
+#define BRT_PROG_SELECTED 1u
+int32_t brt_set_progressive(brt_ctx* ctx, uint32_t first_spp, uint32_t max_spp, float threshold, uint32_t radius);
+int32_t brt_progressive_sample_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                      void* d_state, const uint32_t* d_pixels_or_null, uint32_t n_pixels, const uint32_t* d_count_or_null,
+                                      uint32_t target, void* d_frame_or_null, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_progressive_sample(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* state,
+                               const uint32_t* pixels_or_null, uint32_t n_pixels, uint32_t target, void* frame_or_null, uint32_t flags,
+                               brt_stats* stats_or_null);
+int32_t brt_progressive_select_device(brt_ctx* ctx, uint32_t width, uint32_t height, const void* d_state, uint32_t target, uint32_t* d_list,
+                                      uint32_t* d_count, void* d_mask_u8_or_null, void* hip_stream, uint32_t flags);
+int32_t brt_render_progressive_device(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height,
+                                      void* d_state, void* d_frame, void* hip_stream, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_render_progressive(brt_ctx* ctx, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* state,
+                               void* frame, uint32_t flags, brt_stats* stats_or_null);
+int32_t brt_host_progressive_accumulate(void* record32, const float* rgb);
+int32_t brt_host_progressive_class(const void* records9, const uint32_t* inside9, uint32_t target, float threshold, uint32_t radius,
+                                   uint32_t* out_class);
+
 /* Diagnostic: the 64 raw control words of the last launch on the context's first device: out64[0..4]
  * = the brt_stats counters; after a BRT_FLAG_COUNTERS launch out64[8+2k], out64[9+2k] = how
  * often the waves executed code section k and the sum of active lanes over those executions
