@@ -12,6 +12,7 @@
 
 #include "brt_adaptive.h"
 #include "brt_store.h"
+#include "brt_wave.h"
 
 namespace brt {
 
@@ -31,19 +32,6 @@ struct AdaptiveArgs {
     uint32_t* list;
     uint8_t* mask;
 };
-
-// k_upscale's select_append (brt_upscale.hip): the lanes of the wave with `sel` set append p to the list -- one ballot, one atomicAdd of
-// the wave on the count word, plain vector stores.  Every lane of the wave calls it.
-BRT_DEV void adaptive_append(const AdaptiveArgs& aa, bool sel, uint32_t p) {
-    const uint64_t m = __ballot(sel);
-    if (m == 0ull) return;
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const uint32_t leader = (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
-    uint32_t first = 0u;
-    if (lane == leader) first = atomicAdd(aa.count, (uint32_t)__popcll(m));
-    first = (uint32_t)__builtin_amdgcn_readlane((int)first, (int)leader);
-    if (sel) aa.list[first + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = p;
-}
 
 template <uint32_t FMT, bool MASK_ONLY>
 __global__ __launch_bounds__(256) void k_adaptive_select(AdaptiveArgs aa, typename OutPixel<FMT>::type* __restrict__ out) {
@@ -80,7 +68,7 @@ __global__ __launch_bounds__(256) void k_adaptive_select(AdaptiveArgs aa, typena
         if (inside) aa.mask[p] = (uint8_t)cls;
     } else {
         if (inside) out[p] = OutPixel<FMT>::make(aa.base[p]);
-        adaptive_append(aa, cls != 0u, p);
+        wave_append(aa.count, aa.list, cls != 0u, p);
     }
 }
 

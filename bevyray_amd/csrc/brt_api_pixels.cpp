@@ -1,7 +1,8 @@
 // brt_api_pixels.cpp -- the sparse pixel tracer (brt_pixels.hip; DESIGN.md "Refined upsampling") on the first device: a list of pixels
 // of a Pure frame, each traced alone to the value the whole frame holds there.  The tree follows the call's camera (with_tree_reach),
 // not an origin bound; the launch plan is that of every list kernel (plan_list).  The lens exports (brt_api_lens.cpp) are the same
-// calls with a lens attached: the enqueue, the two bodies of a call and its stats are here for both.
+// calls with a lens attached: the enqueue, the two bodies of a call and its stats are here for both.  A pass of a progressive frame
+// (brt_api_progressive.cpp) is the same enqueue with the progressive terms attached.
 #include "brt_frame.h"
 
 using namespace brt;
@@ -12,14 +13,14 @@ namespace brt {
 // goes to it here: every representation and tree), else the streaming form (plan_list).
 int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                        const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
-                       hipStream_t stream, bool force_plain, PixelsLaunch* pl, const LensView* lens) {
+                       hipStream_t stream, bool force_plain, PixelsLaunch* pl, const LensView* lens, const ProgPass* prog) {
     int32_t rc = make_frame_params(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, 0u, 1u, &pl->frame);
     if (rc != BRT_OK) return rc;
     if (pl->frame.policy_flags != 0u)
         return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, lens ? "lens frames implement the default policy only (brt_set_policy)"
                                                        : "the pixel tracer implements the default policy only (brt_set_policy)");
     const uint32_t form = ctx->knobs[K_PIXELS_FORM];
-    // waves per SIMD where nothing is staged (make usage-lens): 114 VGPRs with the hand-written loop (4), 80-94 without (5)
+    // waves per SIMD where nothing is staged (make usage-lens, usage-progressive): 114 VGPRs with the hand-written loop (4), 74-94 without (5)
     plan_list(ctx, dc, n_pixels, !(form == 1u || (force_plain && form != 2u)), 4u, 5u, false, pl);
     PixelsArgs& pa = pl->args;
     pa.pixels = d_pixels;
@@ -31,8 +32,10 @@ int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const 
     pa.stat = reinterpret_cast<unsigned long long*>(d_ctl);
     pa.counter = d_ctl + 4;
     pl->stream = stream;
-    HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 20, stream));
-    HIP_TRY(ctx, lens ? launch_trace_lens(*pl, *lens) : launch_trace_pixels(*pl));
+    if (prog && !prog->first) HIP_TRY(ctx, hipMemsetAsync(pa.counter, 0, 4, stream));
+    else HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 20, stream));
+    if (prog && prog->first) HIP_TRY(ctx, hipMemsetAsync(prog->sample.samples, 0, 8, stream));
+    HIP_TRY(ctx, prog ? launch_prog_sample(*pl, prog->sample) : lens ? launch_trace_lens(*pl, *lens) : launch_trace_pixels(*pl));
     return BRT_OK;
 }
 
@@ -99,12 +102,7 @@ void pixels_stats(const PixelsCall& pc, const PixelsRun& run, double total_ms, b
     stats->rays = run.counted ? run.counts[0] : 0u;
     stats->reserved = run.counted ? (uint32_t)std::min<unsigned long long>(run.counts[1], 0xffffffffull) : 0u;      // entries refused
     stats->paths = run.counted ? ((uint64_t)pc.n_pixels - run.counts[1]) * pl.frame.sample_count : 0u;
-    stats->n_workgroups = list_groups(pl, pc.n_pixels);
-    stats->threads_per_workgroup = pl.form == LIST_STREAM ? pl.block : 256u;
-    stats->lds_bytes = (uint32_t)pl.lds_bytes;
-    stats->scene_in_lds = pl.form != LIST_STREAM ? 0u : pl.scene_mode == SCENE_LDS ? 1u : (pl.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
-    // (the persistent kernel's variants are below 32)
-    stats->kernel_variant = (pc.lens ? 34u : 32u) + (pl.form == LIST_STREAM ? 0u : 1u);
+    list_launch_stats(pl, pc.n_pixels, pc.lens ? 34u : 32u, stats);
     stats->total_ms = total_ms;
 }
 

@@ -1,8 +1,8 @@
 // brt_api_progressive.cpp -- progressive frames on the first device (brt_progressive.hip; DESIGN.md "Progressive frames"): a plane of
-// 32-byte pixel records the caller holds, pixels of it continued to a target sample count by the progressive forms of the sparse pixel
-// tracer, and the pixels worth a higher target selected from the records' own moments (brt_progressive.h).  The skeleton of an export is
-// frame_call's (brt_frame.h); every call runs behind the context's other list work (ev_q) and records it; the launch plan is that of
-// every list kernel (plan_list).  No call here goes through render_frame_device: the dispatch-order and lean history of plain frames,
+// 32-byte pixel records the caller holds, pixels of it continued to a target sample count by the sparse pixel tracer under the
+// progressive rule, and the pixels worth a higher target selected from the records' own moments (brt_progressive.h).  The skeleton of an
+// export is frame_call's (brt_frame.h); every call runs behind the context's other list work (ev_q) and records it; a pass is enqueued
+// by pixels_enqueue (brt_api_pixels.cpp).  No call here goes through render_frame_device: the dispatch-order and lean history of plain frames,
 // and the base-frame slot of adaptive frames, are never looked at.  Here: the checks of each export in their order, the settings, the
 // enqueue of a pass, the passes of the one-call form, and the host twins of the record and the rule.
 #include "brt_frame.h"
@@ -58,55 +58,21 @@ struct ProgRun {
     bool counted = false;
 };
 
-// One pass on `stream`: the entries of d_pixels (null: every pixel, in the order of BRT_PROGRESSIVE_ORDER) continued to `target`.  d_ctl:
-// DeviceCtx::d_pxbuf's control words; `first`: they are zeroed, else the batch counter alone (the counts of a call's passes add up).
+// One pass on `stream`: the entries of d_pixels (null: every pixel, in the order of BRT_PROGRESSIVE_ORDER, the tile order padded to whole
+// 8x8 tiles) continued to `target` -- pixels_enqueue under the progressive rule, on DeviceCtx::d_pxbuf's control words.
 int32_t prog_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* d_state,
                      const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, uint32_t target, void* d_frame, uint32_t fmt,
                      bool first, hipStream_t stream, uint32_t flags, ProgRun* run) {
-    PixelsLaunch* pl = &run->pl;
-    const int32_t rc = make_frame_params(ctx, camera80, window16, BRT_LEVEL_PURE, width, height, 0u, 1u, &pl->frame);
-    if (rc != BRT_OK) return rc;
-    if (pl->frame.policy_flags != 0u) return ctx_fail(ctx, BRT_ERR_UNSUPPORTED, "the pixel tracer implements the default policy only (brt_set_policy)");
-    ProgSample pg{};
-    pg.state = static_cast<ProgPixel*>(d_state);
-    pg.target = target;
-    pg.order = (!d_pixels && ctx->knobs[K_PROGRESSIVE_ORDER] != 0u) ? 1u : 0u;
-    if (pg.order) n_pixels = pl->frame.tiles_x * ((height + 7u) / 8u) * 64u;
-    uint32_t* d_ctl = dc.d_pxbuf;
-    pg.samples = reinterpret_cast<unsigned long long*>(d_ctl + kPxSamplesWord);
-    const uint32_t form = ctx->knobs[K_PIXELS_FORM];
-    const bool force_plain = (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u;
-    // waves per SIMD where nothing is staged (make usage-progressive)
-    plan_list(ctx, dc, n_pixels, !(form == 1u || (force_plain && form != 2u)), 4u, 5u, false, pl);
-    PixelsArgs& pa = pl->args;
-    pa.pixels = d_pixels;
-    pa.n_pixels = n_pixels;
-    pa.count = d_count;
-    pa.out = d_frame;
-    pa.scatter = 1u;
-    pa.out_format = fmt;
-    pa.stat = reinterpret_cast<unsigned long long*>(d_ctl);
-    pa.counter = d_ctl + 4;
-    pl->stream = stream;
+    ProgPass pp{};
+    pp.first = first;
+    pp.sample.state = static_cast<ProgPixel*>(d_state);
+    pp.sample.target = target;
+    pp.sample.order = (!d_pixels && ctx->knobs[K_PROGRESSIVE_ORDER] != 0u) ? 1u : 0u;
+    if (pp.sample.order) n_pixels = ((width + 7u) / 8u) * ((height + 7u) / 8u) * 64u;
+    pp.sample.samples = reinterpret_cast<unsigned long long*>(dc.d_pxbuf + kPxSamplesWord);
     run->entries = n_pixels;
-    if (first) {
-        HIP_TRY(ctx, hipMemsetAsync(d_ctl, 0, 20, stream));
-        HIP_TRY(ctx, hipMemsetAsync(d_ctl + kPxSamplesWord, 0, 8, stream));
-    } else {
-        HIP_TRY(ctx, hipMemsetAsync(d_ctl + 4, 0, 4, stream));
-    }
-    HIP_TRY(ctx, launch_prog_sample(*pl, pg));
-    return BRT_OK;
-}
-
-// d_pxbuf with room for the list of a width x height frame (list_words 0: the control words alone), for work on `stream` behind ev_q
-int32_t prog_buffers(brt_ctx* ctx, DeviceCtx& dc, size_t list_words, hipStream_t stream) {
-    const size_t bytes = (list_words + kPxListWord) * 4u;
-    if (dc.pxbuf_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
-    const int32_t rc = ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, bytes);
-    if (rc != BRT_OK) return rc;
-    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-    return BRT_OK;
+    return pixels_enqueue(ctx, dc, camera80, window16, width, height, d_pixels, n_pixels, d_count, {d_frame, true, fmt}, dc.d_pxbuf, stream,
+                          (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u, &run->pl, nullptr, &pp);
 }
 
 int32_t select_enqueue(brt_ctx* ctx, uint32_t width, uint32_t height, const void* d_state, uint32_t target, float threshold, uint32_t radius,
@@ -129,7 +95,7 @@ int32_t select_enqueue(brt_ctx* ctx, uint32_t width, uint32_t height, const void
 int32_t passes_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* d_state,
                        void* d_frame, uint32_t fmt, hipStream_t stream, uint32_t flags, ProgRun* run) {
     const uint32_t px = width * height;
-    int32_t r = prog_buffers(ctx, dc, px, stream);
+    int32_t r = list_buffer(ctx, dc, px, stream);
     if (r != BRT_OK) return r;
     uint32_t* count = dc.d_pxbuf + kPxCountWord;
     uint32_t* list = dc.d_pxbuf + kPxListWord;
@@ -159,7 +125,6 @@ int32_t prog_call(brt_ctx* ctx, const void* camera80, void* hip_stream, uint32_t
         return body(dc, sc);
     });
     if (rc != BRT_OK || !stats) return rc;
-    const PixelsLaunch& pl = run->pl;
     if (run->counted) {      // (the own stream has been synchronised, and nothing of this context has run since)
         uint32_t ctl[kPxListWord];
         HIP_TRY(ctx, hipMemcpy(ctl, ctx->devs[0].d_pxbuf, sizeof ctl, hipMemcpyDeviceToHost));
@@ -169,11 +134,7 @@ int32_t prog_call(brt_ctx* ctx, const void* camera80, void* hip_stream, uint32_t
         stats->reserved = (uint32_t)std::min<unsigned long long>(refused, 0xffffffffull);      // entries refused
         stats->paths = samples;
     }
-    stats->n_workgroups = list_groups(pl, run->entries);
-    stats->threads_per_workgroup = pl.form == LIST_STREAM ? pl.block : 256u;
-    stats->lds_bytes = (uint32_t)pl.lds_bytes;
-    stats->scene_in_lds = pl.form != LIST_STREAM ? 0u : pl.scene_mode == SCENE_LDS ? 1u : (pl.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
-    stats->kernel_variant = 36u + (pl.form == LIST_STREAM ? 0u : 1u);      // (the pixel lists' are 32 .. 35)
+    list_launch_stats(run->pl, run->entries, 36u, stats);      // (the pixel lists' variants are 32 .. 35)
     return rc;
 }
 
@@ -210,7 +171,7 @@ int32_t brt_progressive_sample_device(brt_ctx* ctx, const void* camera80, const 
     if (n_pixels == 0u) return BRT_OK;
     ProgRun run;
     return prog_call(ctx, camera80, hip_stream, flags, stats, &run, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = prog_buffers(ctx, dc, 0u, sc.stream);
+        int32_t r = list_buffer(ctx, dc, 0u, sc.stream);
         if (r == BRT_OK)
             r = prog_enqueue(ctx, dc, camera80, window16, width, height, d_state, d_pixels_or_null, n_pixels, d_count_or_null, target,
                              d_frame_or_null, fmt, true, sc.stream, flags, &run);
@@ -239,7 +200,7 @@ int32_t brt_progressive_sample(brt_ctx* ctx, const void* camera80, const void* w
     return prog_call(ctx, camera80, nullptr, flags, stats, &run, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
         int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, state_bytes}, {&dc.d_pxlist, &dc.pxlist_cap, std::max<size_t>(list_bytes, 16u)},
                                      {&dc.d_pxout, &dc.pxout_cap, std::max<size_t>(frame_bytes, 16u)}});
-        if (r == BRT_OK) r = prog_buffers(ctx, dc, 0u, sc.stream);
+        if (r == BRT_OK) r = list_buffer(ctx, dc, 0u, sc.stream);
         if (r != BRT_OK) return r;
         HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, state, state_bytes, hipMemcpyHostToDevice, sc.stream));
         if (pixels_or_null) HIP_TRY(ctx, hipMemcpyAsync(dc.d_pxlist, pixels_or_null, list_bytes, hipMemcpyHostToDevice, sc.stream));

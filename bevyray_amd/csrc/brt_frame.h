@@ -195,10 +195,15 @@ struct PixelsTarget {
 // first device.  d_count: a device word holding the number of entries (nullptr: n_pixels, which is else the list's capacity).  ctl: 8
 // words of the caller's {u64 rays, u64 refused, u32 batch counter, ...}, zeroed here.  Refuses a non-default policy.  lens: the list
 // under the lens rule (brt_lens.hip), where a null d_pixels means that entry i is pixel i; camera80 is then the pinhole camera of the
-// frame terms.
+// frame terms.  prog: the list under the progressive rule (brt_progressive.hip), a pass of a call (brt_api_progressive.cpp): the first
+// pass zeroes the samples word as well, a later one the batch counter alone, so that the counts of a call's passes add up.
+struct ProgPass {
+    ProgSample sample;
+    bool first;
+};
 int32_t pixels_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height,
                        const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, const PixelsTarget& target, uint32_t* d_ctl,
-                       hipStream_t stream, bool force_plain, PixelsLaunch* pl, const LensView* lens = nullptr);
+                       hipStream_t stream, bool force_plain, PixelsLaunch* pl, const LensView* lens = nullptr, const ProgPass* prog = nullptr);
 // What brt_render_pixels* and brt_render_lens* (brt_api_lens.cpp) share.  The check of a list with its output; a call behind its checks,
 // of n_pixels > 0 entries; its two bodies, which run once the tree is settled; and the launch fields of its stats (counts2 null: not
 // counted; kernel_variant 32 / 33, under a lens 34 / 35).
@@ -285,14 +290,20 @@ inline int32_t context_frame(brt_ctx* ctx, DeviceCtx& dc, size_t bytes, hipStrea
 // the number of selected pixels, two spare -- then the list of a selecting call, one word per pixel of its frame.
 constexpr uint32_t kPxCountWord = 5u, kPxListWord = 8u;
 struct SelectList { uint32_t *ctl, *count, *list; };
-// The list of a width x height refinement or adaptive frame for work on `stream`, ordered by ev_q: a larger one is allocated only once the
-// last user of the old one has ended; the control words are zeroed behind that user
-inline int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream, SelectList* sl) {
-    const size_t bytes = ((size_t)width * height + kPxListWord) * 4u;
+// d_pxbuf with room for a list of list_words entries (0: the control words alone) for work on `stream`, ordered by ev_q: a larger one is
+// allocated only once the last user of the old one has ended, and the stream is put behind that user
+inline int32_t list_buffer(brt_ctx* ctx, DeviceCtx& dc, size_t list_words, hipStream_t stream) {
+    const size_t bytes = (list_words + kPxListWord) * 4u;
     if (dc.pxbuf_cap < bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
     const int32_t rc = ensure(ctx, &dc.d_pxbuf, &dc.pxbuf_cap, bytes);
     if (rc != BRT_OK) return rc;
     HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    return BRT_OK;
+}
+// The list of a width x height refinement or adaptive frame: list_buffer, and the control words zeroed behind the last user
+inline int32_t refine_list(brt_ctx* ctx, DeviceCtx& dc, uint32_t width, uint32_t height, hipStream_t stream, SelectList* sl) {
+    const int32_t rc = list_buffer(ctx, dc, (size_t)width * height, stream);
+    if (rc != BRT_OK) return rc;
     HIP_TRY(ctx, hipMemsetAsync(dc.d_pxbuf, 0, kPxListWord * 4u, stream));
     *sl = {dc.d_pxbuf, dc.d_pxbuf + kPxCountWord, dc.d_pxbuf + kPxListWord};
     return BRT_OK;
@@ -446,8 +457,16 @@ int32_t bake_call_host(brt_ctx* ctx, float origin_bound, size_t io_bytes, const 
 }
 
 // The out_stats8 of a list call: three counts (nullptr: not gathered), tree rebuilt, the callee-built tree's reach (bits), the form, and
-// the family's word 6.  list_groups: the workgroups of a launch over n items.
+// the family's word 6.  list_groups: the workgroups of a launch over n items.  list_launch_stats: the launch fields of the brt_stats of a
+// list of pixels; variant: the streaming form's kernel_variant (the plain form's is one more; the persistent kernel's are below 32).
 inline uint32_t list_groups(const StreamLaunch& sl, uint32_t n) { return sl.form == LIST_STREAM ? sl.grid : (n + 255u) / 256u; }
+inline void list_launch_stats(const StreamLaunch& sl, uint32_t n, uint32_t variant, brt_stats* stats) {
+    stats->n_workgroups = list_groups(sl, n);
+    stats->threads_per_workgroup = sl.form == LIST_STREAM ? sl.block : 256u;
+    stats->lds_bytes = (uint32_t)sl.lds_bytes;
+    stats->scene_in_lds = sl.form != LIST_STREAM ? 0u : sl.scene_mode == SCENE_LDS ? 1u : (sl.scene_mode == SCENE_LDS_TOP ? 2u : 0u);
+    stats->kernel_variant = variant + (sl.form == LIST_STREAM ? 0u : 1u);
+}
 template <class Count>
 void list_stats8(const brt_ctx* ctx, const Count* counts3, uint32_t rebuilt, int form, uint64_t word6, uint64_t* out8) {
     if (!out8) return;

@@ -1,17 +1,33 @@
 // brt_pixels_dev.h -- the two forms of the kernel that traces a list of pixels, and what they are made of: a list's length, an entry's
 // store and refusal, the wave's counts, a pixel's begin and value; and their launch (launch_list).  Device code: included by
-// brt_pixels.hip and brt_lens.hip only, which each instantiate the kernels with a start rule of their own (PinholeStart,
-// LensStart<LENS>):
-//   Start::pixel_of(pa, i)                       the pixel entry i names (whether a null list means "entry i is pixel i")
-//   Start::sample(fp, ps, rng, o, d, extra...)   one sample's primary ray on the RNG state of its pixel
-// extra: what the rule takes beyond the frame, as trailing kernel arguments (scalar registers) -- nothing, or the lens terms.  (A rule
-// passed as an empty struct would take kernel-argument space, and a shared body behind thin __global__ wrappers changes the
-// instruction selection of pixels_store: with the rule a type and the terms a pack, every instantiation keeps its instructions.  A
-// rule holds functions only: with a static data member in it, the kernels' hand-written walk loops do not compile for the host.)
+// brt_pixels.hip, brt_lens.hip and brt_progressive.hip only, which each instantiate the kernels with a rule of their own that says WHAT A
+// PIXEL IS (PinholeStart, LensStart<LENS>, ProgStart).  A rule is a type of static functions:
+//   Rule::Lane                                        what a lane keeps for its pixel beyond PixelState (empty, or the record's moments)
+//   Rule::pixel_of(fp, pa, i, extra...)               the pixel entry i names (whether a null list means "entry i is pixel i")
+//   Rule::pads()                                      whether pixel_of answers kListPad for an entry of a null list that names no pixel and is
+//                                                     passed over: not traced, not refused (a constant, and the test is the kernel's own: behind
+//                                                     a hook the progressive kernels' round is laid out differently)
+//   Rule::refuse(pa, i, extra...)                     entry i names no pixel of the frame
+//   Rule::begin(fp, pa, i, p, ps, lane, extra...)     pixel p before its next sample; false: it has ended already and has been dealt with
+//   Rule::begins_ended(fp, extra...)                  whether a pixel that began may have no sample to run (the round then ends it at once)
+//   Rule::target(fp, extra...)                        the pixel ends once ps.sample has reached it
+//   Rule::sample(fp, ps, rng, o, d, extra...)         one sample's primary ray on the RNG state of its pixel
+//   Rule::walked(lane) / Rule::sampled(lane, color)   one more walk / one more sample of the lane's pixel
+//   Rule::end(fp, p, ps, lane, extra...)              the pixel's samples have ended: what the rule keeps of it besides its value
+//   Rule::stores(pa) / Rule::value(fp, ps, extra...)  whether the call wants the value of an ended pixel (host and device: a launch that
+//                                                     does needs an output plane), and the value.  The kernel calls pixels_store with it
+//                                                     itself: behind a hook of the rule pixels_store's format switch is selected differently.
+//   Rule::count(pa, rays, refused, lane, extra...)    the wave's counts (all lanes of the wave call it)
+// WholePixel is the rule of brt_pixels.h's list but for pixel_of and sample: a pixel from pixel_begin's seed to fp.sample_count samples.
+// extra: what the rule takes beyond the frame, as trailing kernel arguments (scalar registers) -- nothing, the lens terms, or the
+// progressive terms.  (A rule passed as an empty struct would take kernel-argument space, and a shared body behind thin __global__
+// wrappers changes the instruction selection of pixels_store: with the rule a type and the terms a pack, every instantiation keeps its
+// instructions.  A rule holds functions only: with a static data member in it, the kernels' hand-written walk loops do not compile for
+// the host.)
 //
-// k_list_plain<Start, D16, Extra...>                one thread per entry: k_trace_simple's loop over a list, the scene in global memory, a
+// k_list_plain<Rule, D16, Extra...>                 one thread per entry: k_trace_simple's loop over a list, the scene in global memory, a
 //                                                   private stack.  Every scene representation and tree.
-// k_list_stream<Start, MODE, D16, SIMPLE, Extra...> persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged
+// k_list_stream<Rule, MODE, D16, SIMPLE, Extra...>  persistent workgroups: the scene (SCENE_LDS) or the top of the tree (SCENE_LDS_TOP) staged
 //                                                   in LDS (stream_stage, brt_stream.h), the stacks in LDS, so the hand-written walk loops
 //                                                   serve it.  A lane carries one path.  A round: the wave takes entries from the batch
 //                                                   counter (one fetch-add) for the lanes whose pixel has ended, walk_run for all lanes, and
@@ -27,6 +43,8 @@
 #include "brt_stream.h"
 
 namespace brt {
+
+constexpr uint32_t kListPad = 0xffffffffu;      // a slot of a null list that names no pixel (Rule::pads)
 
 // the wave's counts into pa.stat (all lanes of the wave call it)
 BRT_DEV void pixels_count(const PixelsArgs& pa, uint32_t rays, uint32_t refused) {
@@ -59,11 +77,6 @@ BRT_DEV void pixels_store(const PixelsArgs& pa, uint32_t i, uint32_t p, float4 v
     }
 }
 
-// entry i names no pixel of the frame
-BRT_DEV void pixels_refuse(const PixelsArgs& pa, uint32_t i) {
-    if (!pa.scatter) reinterpret_cast<float4*>(pa.out)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
 BRT_DEV void pixels_begin(const FrameParams& fp, uint32_t p, PixelState& ps) {
     PixelCoord c;
     c.py = p / fp.width;
@@ -80,26 +93,56 @@ BRT_DEV float4 pixels_value(const FrameParams& fp, const PixelState& ps) {
     return make_float4(ps.sum.x / fp.spp_f, ps.sum.y / fp.spp_f, ps.sum.z / fp.spp_f, 1.0f);
 }
 
+// A whole pixel of the Pure frame: from pixel_begin's seed through fp.sample_count samples to the frame's value.  An entry that names no
+// pixel of the frame stores four zeros where the list is packed.
+struct WholePixel {
+    struct Lane {};
+    static constexpr bool pads() { return false; }
+    template <class... Extra>
+    static BRT_DEV void refuse(const PixelsArgs& pa, uint32_t i, const Extra&...) {
+        if (!pa.scatter) reinterpret_cast<float4*>(pa.out)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    template <class... Extra>
+    static BRT_DEV bool begin(const FrameParams& fp, const PixelsArgs&, uint32_t, uint32_t p, PixelState& ps, Lane&, const Extra&...) {
+        pixels_begin(fp, p, ps);
+        return true;
+    }
+    template <class... Extra>
+    static BRT_DEV bool begins_ended(const FrameParams& fp, const Extra&...) { return fp.sample_count == 0u; }      // (the average of nothing)
+    template <class... Extra>
+    static BRT_DEV uint32_t target(const FrameParams& fp, const Extra&...) { return fp.sample_count; }
+    static BRT_DEV void walked(Lane&) {}
+    static BRT_DEV void sampled(Lane&, f3) {}
+    template <class... Extra>
+    static BRT_DEV void end(const FrameParams&, uint32_t, const PixelState&, Lane&, const Extra&...) {}
+    static constexpr bool stores(const PixelsArgs&) { return true; }
+    template <class... Extra>
+    static BRT_DEV float4 value(const FrameParams& fp, const PixelState& ps, const Extra&...) { return pixels_value(fp, ps); }
+    template <class... Extra>
+    static BRT_DEV void count(const PixelsArgs& pa, uint32_t rays, uint32_t refused, Lane&, const Extra&...) { pixels_count(pa, rays, refused); }
+};
+
 // ---- plain form ----------------------------------------------------------------------------------------------------------------------
 
-template <class Start, bool D16, class... Extra>
+template <class Rule, bool D16, class... Extra>
 __global__ __launch_bounds__(256) void k_list_plain(DeviceSceneView sv, FrameParams fp, PixelsArgs pa, Extra... extra) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     uint32_t n_rays = 0u, refused = 0u;
+    typename Rule::Lane lane{};
     if (i < pixels_n(pa)) {
-        const uint32_t p = Start::pixel_of(pa, i);
-        if (p >= fp.width * fp.height) {
-            pixels_refuse(pa, i);
+        const uint32_t p = Rule::pixel_of(fp, pa, i, extra...);
+        PixelState ps;
+        if (Rule::pads() && p == kListPad && !pa.pixels) {
+        } else if (p >= fp.width * fp.height) {
+            Rule::refuse(pa, i, extra...);
             refused = 1u;
-        } else {
+        } else if (Rule::begin(fp, pa, i, p, ps, lane, extra...)) {
             const ScenePtrs sc = scene_global(sv);
             HitCounters hc = {};
-            PixelState ps;
-            pixels_begin(fp, p, ps);
             uint32_t stack[34];   // DONE sentinel + 32 entries + one spare
-            for (uint32_t s = 0; s < fp.sample_count; s++) {          // raytrace.wgsl:161
+            for (const uint32_t target = Rule::target(fp, extra...); ps.sample < target; ps.sample++) {          // raytrace.wgsl:161
                 f3 o, d;
-                Start::sample(fp, ps, ps.rng, o, d, extra...);
+                Rule::sample(fp, ps, ps.rng, o, d, extra...);
                 f3 tput = mk3(1.0f, 1.0f, 1.0f);
                 float first_depth = kInf;
                 uint32_t bounce = 0;
@@ -109,19 +152,22 @@ __global__ __launch_bounds__(256) void k_list_plain(DeviceSceneView sv, FramePar
                     uint32_t idx;
                     raycast<1, false, D16, false>(sc, sv.root_desc, stack, o, d, t, idx, hc);
                     n_rays++;
+                    Rule::walked(lane);
                     if (shade_segment<false>(sc, fp, o, d, tput, bounce, first_depth, t, idx, ps.rng, color, hc)) break;
                 }
                 ps.sum = ps.sum + color;
+                Rule::sampled(lane, color);
             }
-            pixels_store(pa, i, p, pixels_value(fp, ps));
+            Rule::end(fp, p, ps, lane, extra...);
+            if (Rule::stores(pa)) pixels_store(pa, i, p, Rule::value(fp, ps, extra...));
         }
     }
-    pixels_count(pa, n_rays, refused);
+    Rule::count(pa, n_rays, refused, lane, extra...);
 }
 
 // ---- streaming form ------------------------------------------------------------------------------------------------------------------
 
-template <class Start, int MODE, bool D16, bool SIMPLE, class... Extra>
+template <class Rule, int MODE, bool D16, bool SIMPLE, class... Extra>
 __global__ __launch_bounds__(BRT_BLOCK) void k_list_stream(DeviceSceneView sv, FrameParams fp, PixelsArgs pa, Extra... extra) {
     static_assert(MODE == SCENE_GLOBAL || D16, "a scene staged in LDS always uses 16-bit descriptors");
     using StackT = typename std::conditional<D16, int16_t, int32_t>::type;   // sign-extending loads: brt_layout.h
@@ -138,6 +184,7 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_list_stream(DeviceSceneView sv, F
     f3 o = mk3(0.0f, 0.0f, 0.0f), d = mk3(0.0f, 0.0f, 1.0f), tput = mk3(1.0f, 1.0f, 1.0f);
     uint32_t bounce = 0u;
     float first_depth = kInf;
+    typename Rule::Lane own{};
     uint32_t entry = 0u, pixel = 0u;
     bool in_flight = false;          // this lane holds a pixel whose samples have not ended
     bool exhausted = false;          // wave-uniform: the batch counter has passed the last entry
@@ -154,18 +201,19 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_list_stream(DeviceSceneView sv, F
             exhausted = base >= n || n - base <= cnt;
             const uint32_t mine = base + mbcnt64(idle);
             if (!in_flight && base < n && mine < n) {
-                const uint32_t p = Start::pixel_of(pa, mine);
-                if (p >= frame_px) {
-                    pixels_refuse(pa, mine);
+                const uint32_t p = Rule::pixel_of(fp, pa, mine, extra...);
+                if (Rule::pads() && p == kListPad && !pa.pixels) {
+                } else if (p >= frame_px) {
+                    Rule::refuse(pa, mine, extra...);
                     refused++;
-                } else {
+                } else if (Rule::begin(fp, pa, mine, p, ps, own, extra...)) {
                     entry = mine;
                     pixel = p;
-                    pixels_begin(fp, p, ps);
-                    if (fp.sample_count == 0u) {                       // (no sample: the average of nothing)
-                        pixels_store(pa, entry, pixel, pixels_value(fp, ps));
+                    if (Rule::begins_ended(fp, extra...)) {
+                        Rule::end(fp, pixel, ps, own, extra...);
+                        if (Rule::stores(pa)) pixels_store(pa, entry, pixel, Rule::value(fp, ps, extra...));
                     } else {
-                        Start::sample(fp, ps, ps.rng, o, d, extra...);
+                        Rule::sample(fp, ps, ps.rng, o, d, extra...);
                         tput = mk3(1.0f, 1.0f, 1.0f);
                         first_depth = kInf;
                         bounce = 0u;
@@ -178,17 +226,20 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_list_stream(DeviceSceneView sv, F
         walk_run<64, false, D16, SIMPLE, MODE, StackT>(sc, walk, stk, o, d, kWalkExitLanes, kLeafVote, hc);
         if (in_flight && !walk_pending<D16, SIMPLE>(walk)) {
             n_rays++;
+            Rule::walked(own);
             f3 color;
             if (shade_segment<false>(sc, fp, o, d, tput, bounce, first_depth, walk.closest, walk.closest_idx, ps.rng, color, hc)) {
                 ps.sum = ps.sum + color;                                // :165
+                Rule::sampled(own, color);
                 ps.sample++;
-                if (ps.sample < fp.sample_count) {
-                    Start::sample(fp, ps, ps.rng, o, d, extra...);
+                if (ps.sample < Rule::target(fp, extra...)) {
+                    Rule::sample(fp, ps, ps.rng, o, d, extra...);
                     tput = mk3(1.0f, 1.0f, 1.0f);
                     first_depth = kInf;
                     bounce = 0u;
                 } else {
-                    pixels_store(pa, entry, pixel, pixels_value(fp, ps));
+                    Rule::end(fp, pixel, ps, own, extra...);
+                    if (Rule::stores(pa)) pixels_store(pa, entry, pixel, Rule::value(fp, ps, extra...));
                     in_flight = false;
                 }
             }
@@ -197,29 +248,29 @@ __global__ __launch_bounds__(BRT_BLOCK) void k_list_stream(DeviceSceneView sv, F
         }
         if (exhausted && __ballot(in_flight) == 0ull) break;
     }
-    pixels_count(pa, n_rays, refused);
+    Rule::count(pa, n_rays, refused, own, extra...);
 }
 
 // ---- host-callable launcher ----------------------------------------------------------------------------------------------------------
 
-template <class Start, class... Extra>
+template <class Rule, class... Extra>
 struct ListStream {
     template <int MODE, bool D16, bool SIMPLE>
-    static auto kernel() { return k_list_stream<Start, MODE, D16, SIMPLE, Extra...>; }
+    static auto kernel() { return k_list_stream<Rule, MODE, D16, SIMPLE, Extra...>; }
 };
 
-// The list of pl under the rule Start, in the form pl names.  null_list: a null list means "entry i is pixel i" (else it is refused).
-template <class Start, class... Extra>
+// The list of pl under the rule Rule, in the form pl names.  null_list: a null list means "entry i is pixel i" (else it is refused).
+template <class Rule, class... Extra>
 static hipError_t launch_list(const PixelsLaunch& pl, bool null_list, const Extra&... extra) {
     if (pl.args.n_pixels == 0u) return hipSuccess;
-    if ((!pl.args.pixels && !null_list) || !pl.args.out || pl.frame.policy_flags != 0u) return hipErrorInvalidValue;
+    if ((!pl.args.pixels && !null_list) || (Rule::stores(pl.args) && !pl.args.out) || pl.frame.policy_flags != 0u) return hipErrorInvalidValue;
     if (pl.form == LIST_PLAIN) {
         const dim3 grid((pl.args.n_pixels + 255u) / 256u);
-        if (pl.scene.desc16) hipLaunchKernelGGL((k_list_plain<Start, true, Extra...>), grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args, extra...);
-        else hipLaunchKernelGGL((k_list_plain<Start, false, Extra...>), grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args, extra...);
+        if (pl.scene.desc16) hipLaunchKernelGGL((k_list_plain<Rule, true, Extra...>), grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args, extra...);
+        else hipLaunchKernelGGL((k_list_plain<Rule, false, Extra...>), grid, dim3(256), 0, pl.stream, pl.scene, pl.frame, pl.args, extra...);
         return hipGetLastError();
     }
-    return launch_stream<ListStream<Start, Extra...>>(pl, pl.args.counter, pl.frame, pl.args, extra...);
+    return launch_stream<ListStream<Rule, Extra...>>(pl, pl.args.counter, pl.frame, pl.args, extra...);
 }
 
 }  // namespace brt

@@ -10,6 +10,7 @@
 
 #include "brt_device.h"
 #include "brt_kernels.h"
+#include "brt_wave.h"      // lane_id, mbcnt64, wave_sum
 
 #ifndef BRT_PHASE_PRIO_AT
 #define BRT_PHASE_PRIO_AT 2   // 0: no phase priorities; 1: raised for the walk; 2: raised from the top of the round (walk begin included)
@@ -45,17 +46,6 @@ BRT_DEV PixelCoord slot_to_pixel(const FrameParams& fp, uint32_t q, uint32_t til
     c.t = t;
     c.inside = (c.px < fp.width) && (c.py < fp.height);
     return c;
-}
-
-BRT_DEV uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-BRT_DEV uint32_t mbcnt64(uint64_t mask) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-BRT_DEV uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
 }
 
 // Per-pixel state of a lane

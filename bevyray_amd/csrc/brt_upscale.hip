@@ -19,6 +19,7 @@
 
 #include "brt_store.h"
 #include "brt_upscale.h"
+#include "brt_wave.h"
 
 namespace brt {
 
@@ -72,18 +73,8 @@ BRT_DEV float4 blend_texel(uint32_t p, const UpscaleBlend& b) { return raster_te
 BRT_DEV uint8_t* select_mask(const UpscaleSelect& us) { return us.mask; }
 BRT_DEV uint32_t select_classes(const UpscaleSelect& us) { return us.classes; }
 
-// the lanes of the wave that are here and have `sel` set append p to the list: one ballot, one atomicAdd of the wave on the count word,
-// plain vector stores
-BRT_DEV void select_append(const UpscaleSelect& us, bool sel, uint32_t p) {
-    const uint64_t m = __ballot(sel);
-    if (m == 0ull) return;
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const uint32_t leader = (uint32_t)__builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
-    uint32_t base = 0u;
-    if (lane == leader) base = atomicAdd(us.count, (uint32_t)__popcll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)leader);
-    if (sel) us.list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = p;
-}
+// the lanes of the wave that are here and have `sel` set append p to the call's list (wave_append, brt_wave.h)
+BRT_DEV void select_append(const UpscaleSelect& us, bool sel, uint32_t p) { wave_append(us.count, us.list, sel, p); }
 
 // whether the kernel's optional pack holds a T
 template <typename T, typename... Opt> constexpr bool opt_is() { return (std::is_same<T, Opt>::value || ...); }

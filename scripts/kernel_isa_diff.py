@@ -9,7 +9,8 @@ directives and the numbering of local labels are ignored; an empty template para
 instantiation of a kernel template that gained an optional trailing argument), and a seventh argument `false` of k_trace_persistent
 counts as no argument (the template lost that parameter; its `true` instantiation has no namesake and is reported missing), and
 k_trace_pixels_{plain,stream}<...> and k_lens_{plain,stream}<LENS, ...> count as their namesakes k_list_*<PinholeStart, ...> and
-k_list_*<LensStart<LENS>, ..., LensView> (the two families became one pair of templates under a start rule).  Exit
+k_list_*<LensStart<LENS>, ..., LensView> (the two families became one pair of templates under a start rule), and k_prog_plain<D16> and
+k_prog_stream<MODE, D16, SIMPLE> as k_list_*<ProgStart, ..., ProgSample> (the progressive kernels became a third rule of that pair).  Exit
 status 1 if a kernel is DIFF or missing."""
 import re
 import sys
@@ -36,6 +37,8 @@ def kernels(path, info=None):
             cur = re.sub(r"(k_trace_persistentI(?:L[ib]\dE){6})Lb0E(EEv)", r"\1\2", cur)
             cur = re.sub(r"\d\dk_trace_pixels_(plain|stream)I", lambda g: f"{len(g.group(1)) + 7}k_list_{g.group(1)}INS_12PinholeStartE", cur)
             cur = re.sub(r"k_lens_(plain|stream)I(Lj\dE)((?:L[ib]\dE)+)EEv(\w+)NS_8LensViewE$", r"k_list_\1INS_9LensStartI\2EE\3JNS_8LensViewEEEEv\4", cur)
+            cur = re.sub(r"12_GLOBAL__N_1\d\dk_prog_(plain|stream)I((?:L[ib]\dE)+)EEv(\w+)NS_10ProgSampleE$",
+                         lambda g: f"{len(g.group(1)) + 7}k_list_{g.group(1)}INS_9ProgStartE{g.group(2)}JNS_10ProgSampleEEEEv{g.group(3)}", cur)
             out[cur] = []
             last = cur
         elif cur is not None:
