@@ -22,7 +22,7 @@ void free_device(DeviceCtx& dc) {
     for (void* p : std::initializer_list<void*>{dc.d_scene, dc.d_ctrl, dc.d_strip_table, dc.d_tile, dc.d_gather, dc.d_pack, dc.d_raster_rgba,
              dc.d_raster_depth, dc.d_bvh_scratch, dc.d_tile_cost, dc.d_tile_order, dc.d_order_meta, dc.d_order_scratch, dc.d_slice_state,
              dc.d_record_hits, dc.d_bvh_models, dc.d_denoise, dc.d_temporal, dc.d_tsph, dc.d_uplow, dc.d_qctl, dc.d_qmap, dc.d_qrays, dc.d_qhits,
-             dc.d_pxbuf, dc.d_pxlist, dc.d_pxout, dc.d_radctl, dc.probe_dirs.d, dc.d_list_io, dc.d_volume_probes,
+             dc.d_pxbuf, dc.d_radctl, dc.probe_dirs.d, dc.d_list_io, dc.d_volume_probes,
              dc.d_envmap, dc.envmap_taps.d, dc.d_lightmap, dc.lightmap_dirs.d})
         if (p) (void)hipFree(p);
     if (dc.h_stage) (void)hipHostFree(dc.h_stage);

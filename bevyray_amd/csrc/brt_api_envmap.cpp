@@ -1,8 +1,8 @@
 // brt_api_envmap.cpp -- reflection probes (brt_envmap.h, brt_envmap.hip; DESIGN.md "Reflection probes") on the first device: a cube map
 // traced from one position and its mip chain prefiltered by roughness.  The texels' rays are radiance entries and are traced by the
 // radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue); the skeleton of a bake export, its chunk loop, the cached tap
-// tables, streams, ordering behind ev_q and the staging rule are those of every list call (brt_frame.h: bake_call, bake_call_host,
-// bake_chunks, cached_table, staged, list_step_run, device_aligned); the stats are the probe bakes' (bake_stats).  Here: the checks, the
+// tables, streams, ordering behind ev_q, the staging rule and the round trip of the host form's buffer are those of every list call
+// (brt_frame.h: bake_call, bake_call_host over host_round_trip, bake_chunks, cached_table, staged, list_step_run, device_aligned); the stats are the probe bakes' (bake_stats).  Here: the checks, the
 // tap tables' maths, the argument packing, the level loop and the host twins.
 #include "brt_envmap.h"
 #include "brt_frame.h"
@@ -356,9 +356,9 @@ int32_t brt_bake_envmap(brt_ctx* ctx, const float* position3, uint32_t seed, uin
     if (rc != BRT_OK) return rc;
     const float pos[3] = {position3[0], position3[1], position3[2]};
     const size_t bytes = (size_t)envmap_level_offset(size, levels) * (flags == BRT_FLAG_OUT_RGBA16F ? 8u : 16u);
-    return bake_call_host(ctx, origin_bound, bytes, {0u, out, bytes}, out_stats8,
-                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
-        return envmap_bake_enqueue(ctx, dc, stream, pos, seed, size, levels, samples, bounces, n_taps, dc.d_list_io, flags, counted, run);
+    return bake_call_host(ctx, origin_bound, {{nullptr, out, bytes}}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run, char* const* d) {
+        return envmap_bake_enqueue(ctx, dc, stream, pos, seed, size, levels, samples, bounces, n_taps, d[0], flags, counted, run);
     }, [&] { return position_reach_check(ctx, pos); });
     });
 }

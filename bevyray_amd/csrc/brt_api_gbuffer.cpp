@@ -2,7 +2,9 @@
 // list call in everything but its shape: the tree follows the camera (ensure_tree_reach, as for a render), the kernel runs behind the
 // previous query or list of the context (ev_q, which it records, so uploads and tree rebuilds wait for it as they do for queries), with the
 // queries' resident -> caller sphere map (query_rmap) and their control words (d_qctl).  It keeps nothing in the context: no frame, no
-// dispatch history, no temporal history, no denoiser scratch.  The host twin of the rule (brt_host_gbuffer_pixel) needs no context.
+// dispatch history, no temporal history, no denoiser scratch.  The skeleton of a call is written once for both forms (gbuffer_call); the
+// host form is the device form's enqueue inside the round trip of the caller's planes (brt_frame.h host_round_trip), its stats are
+// list_stats8's.  The host twin of the rule (brt_host_gbuffer_pixel) needs no context.
 #include "brt_frame.h"
 #include "brt_gbuffer_launch.h"
 
@@ -49,7 +51,6 @@ GbufferCam cam_of(const Camera& c) {
     return gbuffer_cam_of(c.position, c.direction, c.up, c.aspect, tan_half_fov(c.fov), c.near_, c.far_);
 }
 
-size_t round16(size_t n) { return (n + 15u) & ~(size_t)15u; }
 size_t normal_bytes(const brt_gbuffer& d, size_t n) { return n * (d.normal_format == BRT_GBUFFER_NORMAL_RGBA32F ? 16u : 4u); }
 size_t motion_bytes(const brt_gbuffer& d, size_t n) { return n * (d.motion_format == BRT_GBUFFER_MOTION_UV16F ? 4u : 8u); }
 
@@ -96,20 +97,26 @@ int32_t gbuffer_call_check(brt_ctx* ctx, const void* camera80, const void* windo
     return BRT_OK;
 }
 
-// out_stats8: pixels cast, hits, covered (counted calls), tree rebuilt, the callee-built tree's reach (bits), moved, no-previous, 0
-void gbuffer_stats(const brt_ctx* ctx, const uint32_t* counts5, uint32_t rebuilt, uint64_t* out8) {
-    if (!out8) return;
-    const float reach = ctx->tree_callee_sah ? ctx->tree_reach : 0.0f;
-    uint32_t reach_bits;
-    std::memcpy(&reach_bits, &reach, 4);
-    out8[0] = counts5[0];
-    out8[1] = counts5[1];
-    out8[2] = counts5[2];
-    out8[3] = rebuilt;
-    out8[4] = reach_bits;
-    out8[5] = counts5[3];
-    out8[6] = counts5[4];
-    out8[7] = 0u;
+// A call behind its argument checks, both forms: the tree a frame of this camera is traced in; a call without a plane reports its stats
+// and enqueues nothing; else enqueue(dc, stream, counted) on the call's stream -- the host form's is the device form's inside
+// host_round_trip; the own stream copies the five counts out and synchronises (a caller's stream is not waited for: its counts stay 0).
+// out_stats8: pixels cast, hits, covered (counted calls), tree rebuilt, the callee-built tree's reach (bits), moved, no-previous, 0 (the
+// two are counts of pixels: below 1 << 31)
+template <class Enqueue>
+int32_t gbuffer_call(brt_ctx* ctx, const void* camera80, bool any_plane, void* hip_stream, uint32_t flags, uint64_t* out_stats8, Enqueue&& enqueue) {
+    uint32_t rebuilt = 0u, counts[5] = {0u, 0u, 0u, 0u, 0u};
+    int32_t rc = ensure_tree_reach(ctx, camera80, &rebuilt);
+    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
+    if (any_plane)
+        rc = with_list_call(ctx, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+            const int32_t r = enqueue(dc, sc.stream, sc.own);
+            if (r != BRT_OK || !sc.own) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
+            HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+            return BRT_OK;
+        });
+    if (rc == BRT_OK) list_stats8(ctx, counts, rebuilt, (int)counts[3], counts[4], out_stats8);
+    return rc;
 }
 
 }  // namespace
@@ -125,20 +132,11 @@ int32_t brt_render_gbuffer_device(brt_ctx* ctx, const void* camera80, const void
     int32_t rc = gbuffer_call_check(ctx, camera80, window16, gbuffer32, prev_camera80_or_null, width, height, flags, &gc);
     if (rc == BRT_OK) rc = device_aligned(ctx, {d_prev_models_or_null, d_coverage_rgba_or_null, d_depth, d_normal, d_motion, d_ids, d_albedo});
     if (rc != BRT_OK) return rc;
-    uint32_t rebuilt = 0u, counts[5] = {0u, 0u, 0u, 0u, 0u};      // (a caller's stream is not waited for: its counts stay 0)
-    rc = ensure_tree_reach(ctx, camera80, &rebuilt);               // (the tree a frame of this camera is traced in)
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    if (!d_depth && !d_normal && !d_motion && !d_ids && !d_albedo) { gbuffer_stats(ctx, counts, rebuilt, out_stats8_or_null); return BRT_OK; }
-    rc = with_list_call(ctx, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        const int32_t r = gbuffer_enqueue(ctx, dc, sc.stream, gc, camera80, window16, width, height, d_prev_models_or_null,
-                                          d_coverage_rgba_or_null, d_depth, d_normal, d_motion, d_ids, d_albedo, sc.own);
-        if (r != BRT_OK || !sc.own) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
+    return gbuffer_call(ctx, camera80, d_depth || d_normal || d_motion || d_ids || d_albedo, hip_stream, flags, out_stats8_or_null,
+                        [&](DeviceCtx& dc, hipStream_t stream, bool counted) {
+        return gbuffer_enqueue(ctx, dc, stream, gc, camera80, window16, width, height, d_prev_models_or_null, d_coverage_rgba_or_null, d_depth,
+                               d_normal, d_motion, d_ids, d_albedo, counted);
     });
-    if (rc == BRT_OK) gbuffer_stats(ctx, counts, rebuilt, out_stats8_or_null);
-    return rc;
     });
 }
 
@@ -147,44 +145,21 @@ int32_t brt_render_gbuffer(brt_ctx* ctx, const void* camera80, const void* windo
                            void* depth, void* normal, void* motion, void* ids, void* albedo, uint64_t* out_stats8_or_null) {
     return ctx_guard(ctx, [&]() -> int32_t {
     GbufferCall gc{};
-    int32_t rc = gbuffer_call_check(ctx, camera80, window16, gbuffer32, prev_camera80_or_null, width, height, 0u, &gc);
+    const int32_t rc = gbuffer_call_check(ctx, camera80, window16, gbuffer32, prev_camera80_or_null, width, height, 0u, &gc);
     if (rc != BRT_OK) return rc;
-    uint32_t rebuilt = 0u, counts[5] = {0u, 0u, 0u, 0u, 0u};
-    rc = ensure_tree_reach(ctx, camera80, &rebuilt);
-    if (rc != BRT_OK) { drain_all_streams(ctx); return rc; }
-    if (!depth && !normal && !motion && !ids && !albedo) { gbuffer_stats(ctx, counts, rebuilt, out_stats8_or_null); return BRT_OK; }
-    rc = with_list_call(ctx, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        // the staging buffer: previous models, coverage, then the planes, each at a multiple of 16 bytes
-        const size_t n = (size_t)width * height, m = dc.view.n_models;
-        struct Part { const void* in; void* out; size_t bytes; size_t off; };
-        Part parts[7] = {{prev_models_or_null, nullptr, prev_models_or_null ? m * 32u : 0u, 0u},
-                         {coverage_rgba_or_null, nullptr, coverage_rgba_or_null ? n * 16u : 0u, 0u},
-                         {depth, depth, depth ? n * 4u : 0u, 0u},
-                         {normal, normal, normal ? normal_bytes(gc.desc, n) : 0u, 0u},
-                         {motion, motion, motion ? motion_bytes(gc.desc, n) : 0u, 0u},
-                         {ids, ids, ids ? n * 16u : 0u, 0u},
-                         {albedo, albedo, albedo ? n * 16u : 0u, 0u}};
-        size_t total = 0u;
-        for (Part& q : parts) { q.off = total; total += round16(q.bytes); }
-        int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, total}});
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
+    return gbuffer_call(ctx, camera80, depth || normal || motion || ids || albedo, nullptr, 0u, out_stats8_or_null,
+                        [&](DeviceCtx& dc, hipStream_t stream, bool counted) {
         // a covered pixel keeps what the caller's plane holds: the planes go in as well as out when a coverage frame is bound
-        for (int i = 0; i < 7; i++)
-            if (parts[i].bytes && (i < 2 || coverage_rgba_or_null))
-                HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io + parts[i].off, parts[i].in, parts[i].bytes, hipMemcpyHostToDevice, dc.stream));
-        auto at = [&](int i) -> void* { return parts[i].bytes ? dc.d_list_io + parts[i].off : nullptr; };
-        r = gbuffer_enqueue(ctx, dc, dc.stream, gc, camera80, window16, width, height, at(0), at(1), at(2), at(3), at(4), at(5), at(6), true);
-        if (r != BRT_OK) return r;
-        for (int i = 2; i < 7; i++)
-            if (parts[i].bytes) HIP_TRY(ctx, hipMemcpyAsync(parts[i].out, dc.d_list_io + parts[i].off, parts[i].bytes, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copies out read the staging buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
+        const size_t n = (size_t)width * height, m = dc.view.n_models;
+        auto plane = [&](void* p, size_t bytes) { return HostPlane{coverage_rgba_or_null ? p : nullptr, p, p ? bytes : 0u}; };
+        return host_round_trip(ctx, dc, stream, {{prev_models_or_null, nullptr, prev_models_or_null ? m * 32u : 0u},
+                                                 {coverage_rgba_or_null, nullptr, coverage_rgba_or_null ? n * 16u : 0u},
+                                                 plane(depth, n * 4u), plane(normal, normal_bytes(gc.desc, n)),
+                                                 plane(motion, motion_bytes(gc.desc, n)), plane(ids, n * 16u), plane(albedo, n * 16u)},
+                               [&](char* const* d) {
+            return gbuffer_enqueue(ctx, dc, stream, gc, camera80, window16, width, height, d[0], d[1], d[2], d[3], d[4], d[5], d[6], counted);
+        });
     });
-    if (rc == BRT_OK) gbuffer_stats(ctx, counts, rebuilt, out_stats8_or_null);
-    return rc;
     });
 }
 

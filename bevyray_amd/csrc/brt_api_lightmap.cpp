@@ -1,9 +1,9 @@
 // brt_api_lightmap.cpp -- lightmaps (brt_lightmap.h, brt_lightmap.hip; DESIGN.md "Lightmaps") on the first device: per surface point the
 // mean radiance over the cosine-weighted hemisphere of its normal, resolved to the texels of a chart and dilated past the chart's edge.
 // The rays are radiance entries and are traced by the radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue); the skeleton
-// of a bake export, its chunk loop, the cached direction table, streams, ordering behind ev_q and the staging rule are those of every
-// list call (brt_frame.h: bake_call, bake_call_host, bake_chunks, cached_table, staged, list_step_run, device_aligned, flags_check); the stats are
-// the probe bakes' (bake_stats).  Here: the checks, the direction table's maths, the argument packing, the pass loop and the host twins.
+// of a bake export, its chunk loop, the cached direction table, streams, ordering behind ev_q, the staging rule and the round trip of the
+// host form's buffers are those of every list call (brt_frame.h: bake_call, bake_call_host over host_round_trip, bake_chunks,
+// cached_table, staged, list_step_run, device_aligned, flags_check); the stats are the probe bakes' (bake_stats).  Here: the checks, the direction table's maths, the argument packing, the pass loop and the host twins.
 #include "brt_frame.h"
 #include "brt_lightmap.h"
 
@@ -326,18 +326,11 @@ int32_t brt_bake_lightmap(brt_ctx* ctx, const void* points, uint32_t width, uint
     int32_t rc = flags_check(ctx, flags, BRT_FLAG_OUT_RGBA16F, "flags: BRT_FLAG_OUT_RGBA16F only");
     if (rc == BRT_OK) rc = lightmap_bake_check(ctx, points, width, height, n_dirs, bounces, passes, wrap_u, origin_bound, out, info_or_null, flags);
     if (rc != BRT_OK) return rc;
-    // the points, the texels and the info records on the device: one buffer
     const size_t n = (size_t)width * height;
-    const size_t in_bytes = align256(n * 32u), tex_bytes = n * texel_bytes(flags), info_at = in_bytes + align256(tex_bytes);
-    return bake_call_host(ctx, origin_bound, info_at + n * 8u, {in_bytes, out, tex_bytes}, out_stats8,
-                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) -> int32_t {
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, points, n * 32u, hipMemcpyHostToDevice, stream));
-        const int32_t r = lightmap_bake_enqueue(ctx, dc, stream, dc.d_list_io, width, height, n_dirs, bounces, passes, wrap_u,
-                                                dc.d_list_io + in_bytes, info_or_null ? dc.d_list_io + info_at : nullptr, flags, counted, run);
-        if (r != BRT_OK || !info_or_null) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(info_or_null, dc.d_list_io + info_at, n * 8u, hipMemcpyDeviceToHost, stream));
-        return BRT_OK;
+    return bake_call_host(ctx, origin_bound, {{points, nullptr, n * 32u}, {nullptr, out, n * texel_bytes(flags)},
+                                              {nullptr, info_or_null, info_or_null ? n * 8u : 0u}}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run, char* const* d) {
+        return lightmap_bake_enqueue(ctx, dc, stream, d[0], width, height, n_dirs, bounces, passes, wrap_u, d[1], d[2], flags, counted, run);
     });
     });
 }

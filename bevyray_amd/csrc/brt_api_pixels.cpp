@@ -1,7 +1,8 @@
 // brt_api_pixels.cpp -- the sparse pixel tracer (brt_pixels.hip; DESIGN.md "Refined upsampling") on the first device: a list of pixels
 // of a Pure frame, each traced alone to the value the whole frame holds there.  The tree follows the call's camera (with_tree_reach),
 // not an origin bound; the launch plan is that of every list kernel (plan_list).  The lens exports (brt_api_lens.cpp) are the same
-// calls with a lens attached: the enqueue, the two bodies of a call and its stats are here for both.  A pass of a progressive frame
+// calls with a lens attached: the enqueue, the two bodies of a call and its stats are here for both; the host body is the device body's
+// enqueue inside the round trip of its buffers (brt_frame.h host_round_trip).  A pass of a progressive frame
 // (brt_api_progressive.cpp) is the same enqueue with the progressive terms attached.
 #include "brt_frame.h"
 
@@ -78,20 +79,15 @@ int32_t pixels_run_host(brt_ctx* ctx, const PixelsCall& pc, PixelsRun* run) {
     DeviceCtx& dc = ctx->devs[0];
     HIP_TRY(ctx, hipSetDevice(dc.device));
     run->counted = true;
-    const size_t list_bytes = pc.pixels ? (size_t)pc.n_pixels * 4u : 0u, out_bytes = (size_t)pc.n_pixels * 16u;
-    // (the staging rule of `staged`, written out: the control words are allocated between the wait and the buffers)
-    if (dc.pxlist_cap < list_bytes || dc.pxout_cap < out_bytes) HIP_TRY(ctx, hipEventSynchronize(dc.ev_q));
     int32_t r = pixels_ctl(ctx, dc);
-    if (r == BRT_OK && pc.pixels) r = ensure(ctx, &dc.d_pxlist, &dc.pxlist_cap, list_bytes);
-    if (r == BRT_OK) r = ensure(ctx, &dc.d_pxout, &dc.pxout_cap, out_bytes);
     if (r != BRT_OK) return r;
-    HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-    if (pc.pixels) HIP_TRY(ctx, hipMemcpyAsync(dc.d_pxlist, pc.pixels, list_bytes, hipMemcpyHostToDevice, dc.stream));
-    r = call_enqueue(ctx, dc, pc, pc.pixels ? reinterpret_cast<const uint32_t*>(dc.d_pxlist) : nullptr, {dc.d_pxout, false, 0u}, dc.stream, run);
+    // (a lens call without a list has no list plane: entry i is pixel i)
+    r = host_round_trip(ctx, dc, dc.stream, {{pc.pixels, nullptr, pc.pixels ? (size_t)pc.n_pixels * 4u : 0u},
+                                             {nullptr, pc.out_rgba32f, (size_t)pc.n_pixels * 16u}}, [&](char* const* d) {
+        return call_enqueue(ctx, dc, pc, reinterpret_cast<const uint32_t*>(d[0]), {d[1], false, 0u}, dc.stream, run);
+    });
     if (r != BRT_OK) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(pc.out_rgba32f, dc.d_pxout, out_bytes, hipMemcpyDeviceToHost, dc.stream));
     HIP_TRY(ctx, hipMemcpyAsync(run->counts, dc.d_pxbuf, sizeof run->counts, hipMemcpyDeviceToHost, dc.stream));
-    HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
     HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
     return BRT_OK;
 }

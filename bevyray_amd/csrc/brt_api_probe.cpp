@@ -1,8 +1,9 @@
 // brt_api_probe.cpp -- light probes (brt_probe.hip; DESIGN.md "Light probes") on the first device: irradiance records for a list of
 // positions.  The rays are radiance entries and are traced by the radiance kernels as they are (brt_api_radiance.cpp radiance_enqueue);
-// reach, refusal bound and staging buffers are the ray queries' (brt_api_query.cpp); the skeleton of a bake export, its chunk loop, the
-// cached direction table and the runner of a step export are brt_frame.h's (bake_call, bake_call_host, bake_chunks, cached_table,
-// staged, list_step_run, list_stats8).  Here: the checks, the direction table's maths, the argument packing and the host twins.
+// reach and refusal bound are the ray queries' (brt_api_query.cpp); the skeleton of a bake export, its chunk loop, the cached direction
+// table, the round trip of the host form's buffers and the runner of a step export are brt_frame.h's (bake_call, bake_call_host over
+// host_round_trip, bake_chunks, cached_table, staged, list_step_run, list_stats8).  Here: the checks, the direction table's maths, the
+// argument packing and the host twins.
 #include "brt_frame.h"
 #include "brt_probe.h"
 
@@ -228,13 +229,9 @@ int32_t brt_bake_probes(brt_ctx* ctx, const void* probes, uint32_t n_probes, uin
     int32_t rc = bake_check(ctx, probes, n_probes, n_dirs, bounces, basis, origin_bound, out);
     if (rc != BRT_OK) return rc;
     if (n_probes == 0u) { bake_stats(ctx, BakeRun(), 0u, out_stats8); return BRT_OK; }
-    // the probes and the records on the device: one buffer, 16 + 128 bytes per probe
-    const size_t in_bytes = align256((size_t)n_probes * 16u), out_bytes_ = (size_t)n_probes * 128u;
-    return bake_call_host(ctx, origin_bound, in_bytes + out_bytes_, {in_bytes, out, out_bytes_}, out_stats8,
-                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) -> int32_t {
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, probes, (size_t)n_probes * 16u, hipMemcpyHostToDevice, stream));
-        return bake_enqueue(ctx, dc, stream, dc.d_list_io, n_probes, n_dirs, bounces, basis, dc.d_list_io + in_bytes, counted, run);
+    return bake_call_host(ctx, origin_bound, {{probes, nullptr, (size_t)n_probes * 16u}, {nullptr, out, (size_t)n_probes * 128u}}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run, char* const* d) {
+        return bake_enqueue(ctx, dc, stream, d[0], n_probes, n_dirs, bounces, basis, d[1], counted, run);
     });
     });
 }

@@ -2,7 +2,8 @@
 // 32-byte pixel records the caller holds, pixels of it continued to a target sample count by the sparse pixel tracer under the
 // progressive rule, and the pixels worth a higher target selected from the records' own moments (brt_progressive.h).  The skeleton of an
 // export is frame_call's (brt_frame.h); every call runs behind the context's other list work (ev_q) and records it; a pass is enqueued
-// by pixels_enqueue (brt_api_pixels.cpp).  No call here goes through render_frame_device: the dispatch-order and lean history of plain frames,
+// by pixels_enqueue (brt_api_pixels.cpp); a host form is its device form's enqueue inside the round trip of the caller's planes
+// (host_round_trip).  No call here goes through render_frame_device: the dispatch-order and lean history of plain frames,
 // and the base-frame slot of adaptive frames, are never looked at.  Here: the checks of each export in their order, the settings, the
 // enqueue of a pass, the passes of the one-call form, and the host twins of the record and the rule.
 #include "brt_frame.h"
@@ -73,6 +74,18 @@ int32_t prog_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const vo
     run->entries = n_pixels;
     return pixels_enqueue(ctx, dc, camera80, window16, width, height, d_pixels, n_pixels, d_count, {d_frame, true, fmt}, dc.d_pxbuf, stream,
                           (flags & BRT_FLAG_KERNEL_SIMPLE) != 0u, &run->pl, nullptr, &pp);
+}
+
+// the one pass of brt_progressive_sample* on DEVICE planes: behind ev_q on the control words (list_buffer), and recorded in it
+int32_t sample_enqueue(brt_ctx* ctx, DeviceCtx& dc, const void* camera80, const void* window16, uint32_t width, uint32_t height, void* d_state,
+                       const uint32_t* d_pixels, uint32_t n_pixels, const uint32_t* d_count, uint32_t target, void* d_frame, uint32_t fmt,
+                       hipStream_t stream, uint32_t flags, ProgRun* run) {
+    int32_t r = list_buffer(ctx, dc, 0u, stream);
+    if (r == BRT_OK)
+        r = prog_enqueue(ctx, dc, camera80, window16, width, height, d_state, d_pixels, n_pixels, d_count, target, d_frame, fmt, true, stream, flags, run);
+    if (r != BRT_OK) return r;
+    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
+    return BRT_OK;
 }
 
 int32_t select_enqueue(brt_ctx* ctx, uint32_t width, uint32_t height, const void* d_state, uint32_t target, float threshold, uint32_t radius,
@@ -170,14 +183,9 @@ int32_t brt_progressive_sample_device(brt_ctx* ctx, const void* camera80, const 
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_pixels == 0u) return BRT_OK;
     ProgRun run;
-    return prog_call(ctx, camera80, hip_stream, flags, stats, &run, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = list_buffer(ctx, dc, 0u, sc.stream);
-        if (r == BRT_OK)
-            r = prog_enqueue(ctx, dc, camera80, window16, width, height, d_state, d_pixels_or_null, n_pixels, d_count_or_null, target,
-                             d_frame_or_null, fmt, true, sc.stream, flags, &run);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));
-        return BRT_OK;
+    return prog_call(ctx, camera80, hip_stream, flags, stats, &run, [&](DeviceCtx& dc, const StreamChoice& sc) {
+        return sample_enqueue(ctx, dc, camera80, window16, width, height, d_state, d_pixels_or_null, n_pixels, d_count_or_null, target,
+                              d_frame_or_null, fmt, sc.stream, flags, &run);
     });
     });
 }
@@ -195,25 +203,15 @@ int32_t brt_progressive_sample(brt_ctx* ctx, const void* camera80, const void* w
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_pixels == 0u) return BRT_OK;
     ProgRun run;
-    const size_t state_bytes = (size_t)width * height * sizeof(ProgPixel), frame_bytes = frame_or_null ? out_bytes(width, height, fmt) : 0u;
-    const size_t list_bytes = pixels_or_null ? (size_t)n_pixels * 4u : 0u;
     return prog_call(ctx, camera80, nullptr, flags, stats, &run, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, state_bytes}, {&dc.d_pxlist, &dc.pxlist_cap, std::max<size_t>(list_bytes, 16u)},
-                                     {&dc.d_pxout, &dc.pxout_cap, std::max<size_t>(frame_bytes, 16u)}});
-        if (r == BRT_OK) r = list_buffer(ctx, dc, 0u, sc.stream);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, state, state_bytes, hipMemcpyHostToDevice, sc.stream));
-        if (pixels_or_null) HIP_TRY(ctx, hipMemcpyAsync(dc.d_pxlist, pixels_or_null, list_bytes, hipMemcpyHostToDevice, sc.stream));
-        // (a frame holds the listed pixels' values and, elsewhere, what the caller's frame held)
-        if (frame_or_null) HIP_TRY(ctx, hipMemcpyAsync(dc.d_pxout, frame_or_null, frame_bytes, hipMemcpyHostToDevice, sc.stream));
-        r = prog_enqueue(ctx, dc, camera80, window16, width, height, dc.d_list_io,
-                         pixels_or_null ? reinterpret_cast<const uint32_t*>(dc.d_pxlist) : nullptr, n_pixels, nullptr, target,
-                         frame_or_null ? dc.d_pxout : nullptr, fmt, true, sc.stream, flags, &run);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(state, dc.d_list_io, state_bytes, hipMemcpyDeviceToHost, sc.stream));
-        if (frame_or_null) HIP_TRY(ctx, hipMemcpyAsync(frame_or_null, dc.d_pxout, frame_bytes, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));           // (the copies out read the staging buffers)
-        return BRT_OK;
+        // (a frame holds the listed pixels' values and, elsewhere, what the caller's frame held: it goes in as well as out)
+        return host_round_trip(ctx, dc, sc.stream, {{state, state, (size_t)width * height * sizeof(ProgPixel)},
+                                                    {pixels_or_null, nullptr, pixels_or_null ? (size_t)n_pixels * 4u : 0u},
+                                                    {frame_or_null, frame_or_null, frame_or_null ? out_bytes(width, height, fmt) : 0u}},
+                               [&](char* const* d) {
+            return sample_enqueue(ctx, dc, camera80, window16, width, height, d[0], reinterpret_cast<const uint32_t*>(d[1]), n_pixels, nullptr,
+                                  target, d[2], fmt, sc.stream, flags, &run);
+        });
     });
     });
 }
@@ -265,18 +263,12 @@ int32_t brt_render_progressive(brt_ctx* ctx, const void* camera80, const void* w
     if (const int32_t bad = plane_check(ctx, width, height, state, frame, fmt)) return bad;
     if (stats) std::memset(stats, 0, sizeof *stats);
     ProgRun run;
-    const size_t state_bytes = (size_t)width * height * sizeof(ProgPixel), frame_bytes = out_bytes(width, height, fmt);
     return prog_call(ctx, camera80, nullptr, flags, stats, &run, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, state_bytes}, {&dc.d_pxout, &dc.pxout_cap, frame_bytes}});
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(sc.stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, state, state_bytes, hipMemcpyHostToDevice, sc.stream));
-        r = passes_enqueue(ctx, dc, camera80, window16, width, height, dc.d_list_io, dc.d_pxout, fmt, sc.stream, flags, &run);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(state, dc.d_list_io, state_bytes, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(frame, dc.d_pxout, frame_bytes, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, sc.stream));           // (the copies out read the staging buffers)
-        return BRT_OK;
+        // (the first pass writes every pixel of the frame: it goes out only)
+        return host_round_trip(ctx, dc, sc.stream, {{state, state, (size_t)width * height * sizeof(ProgPixel)},
+                                                    {nullptr, frame, out_bytes(width, height, fmt)}}, [&](char* const* d) {
+            return passes_enqueue(ctx, dc, camera80, window16, width, height, d[0], d[1], fmt, sc.stream, flags, &run);
+        });
     });
     });
 }

@@ -1,6 +1,6 @@
 // brt_api_query.cpp -- ray queries (brt_query.hip; DESIGN.md "Ray queries") on the first device, and the launch plan of every list
-// kernel (plan_list).  The skeleton of a list call -- flags, staging, reach, stream, drain, stats -- is brt_frame.h's (with_reach,
-// staged, list_stats8).
+// kernel (plan_list).  The skeleton of a call -- reach, stream, counts, drain, stats -- and the round trip of the host form's buffers are
+// brt_frame.h's (ray_list_call, host_round_trip).
 #include "brt_frame.h"
 
 using namespace brt;
@@ -202,10 +202,6 @@ int32_t query_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mo
     return BRT_OK;
 }
 
-void query_stats(const brt_ctx* ctx, const QueryLaunch& ql, uint32_t rebuilt, const uint32_t* counts3, uint64_t* out8) {
-    list_stats8(ctx, counts3, rebuilt, ql.form, list_groups(ql, ql.args.n_rays), out8);
-}
-
 }  // namespace
 
 extern "C" {
@@ -216,44 +212,24 @@ int32_t brt_query_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_rays,
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = query_check(ctx, d_rays, n_rays, mode, origin_bound, d_hits);
     if (rc != BRT_OK) return rc;
-    QueryLaunch ql{};
-    uint32_t rebuilt = 0u, counts[3] = {0u, 0u, 0u};      // (a caller's stream is not waited for: its counts stay 0)
-    if (n_rays == 0u) { query_stats(ctx, ql, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = query_enqueue(ctx, dc, sc.stream, d_rays, n_rays, mode, d_hits, sc.own, &ql);
-        if (r != BRT_OK || !sc.own) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
+    return ray_list_call<uint32_t, QueryLaunch>(ctx, n_rays, origin_bound, hip_stream, flags, &DeviceCtx::d_qctl, out_stats8,
+                                                [&](DeviceCtx& dc, hipStream_t stream, bool counted, QueryLaunch* ql) {
+        return query_enqueue(ctx, dc, stream, d_rays, n_rays, mode, d_hits, counted, ql);
     });
-    if (rc == BRT_OK) query_stats(ctx, ql, rebuilt, counts, out_stats8);
-    return rc;
     });
 }
 
 int32_t brt_query_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t mode, float origin_bound, void* hits, uint64_t* out_stats8) {
     return ctx_guard(ctx, [&]() -> int32_t {
-    int32_t rc = query_check(ctx, rays, n_rays, mode, origin_bound, hits);
+    const int32_t rc = query_check(ctx, rays, n_rays, mode, origin_bound, hits);
     if (rc != BRT_OK) return rc;
-    QueryLaunch ql{};
-    uint32_t rebuilt = 0u, counts[3] = {0u, 0u, 0u};
-    if (n_rays == 0u) { query_stats(ctx, ql, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        const size_t bytes = (size_t)n_rays * 32u;
-        int32_t r = staged(ctx, dc, {{&dc.d_qrays, &dc.qrays_cap, bytes}, {&dc.d_qhits, &dc.qhits_cap, bytes}});
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_qrays, rays, bytes, hipMemcpyHostToDevice, dc.stream));
-        r = query_enqueue(ctx, dc, dc.stream, dc.d_qrays, n_rays, mode, dc.d_qhits, true, &ql);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(hits, dc.d_qhits, bytes, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_qctl, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
+    const size_t bytes = (size_t)n_rays * 32u;
+    return ray_list_call<uint32_t, QueryLaunch>(ctx, n_rays, origin_bound, nullptr, 0u, &DeviceCtx::d_qctl, out_stats8,
+                                                [&](DeviceCtx& dc, hipStream_t stream, bool counted, QueryLaunch* ql) {
+        return host_round_trip(ctx, dc, stream, {{rays, nullptr, bytes}, {nullptr, hits, bytes}}, [&](char* const* d) {
+            return query_enqueue(ctx, dc, stream, d[0], n_rays, mode, d[1], counted, ql);
+        });
     });
-    if (rc == BRT_OK) query_stats(ctx, ql, rebuilt, counts, out_stats8);
-    return rc;
     });
 }
 

@@ -1,6 +1,6 @@
 // brt_api_radiance.cpp -- radiance queries (brt_radiance.hip; DESIGN.md "Radiance queries") on the first device: path-traced colour
-// for a list of the caller's rays.  Reach, refusal bound, sphere numbering, staging buffers and launch plan are the ray queries'
-// (brt_api_query.cpp); the skeleton of a list call is brt_frame.h's (with_reach, staged, list_stats8).
+// for a list of the caller's rays.  Reach, refusal bound, sphere numbering and launch plan are the ray queries' (brt_api_query.cpp); the
+// skeleton of a call and the round trip of the host form's buffers are brt_frame.h's (ray_list_call, host_round_trip).
 #include "brt_frame.h"
 
 using namespace brt;
@@ -68,10 +68,6 @@ int32_t radiance_check(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t
     return BRT_OK;
 }
 
-void radiance_stats(const brt_ctx* ctx, const RadianceLaunch& rl, uint32_t rebuilt, const unsigned long long* counts3, uint64_t* out8) {
-    list_stats8(ctx, counts3, rebuilt, rl.form, list_groups(rl, rl.args.n_rays), out8);
-}
-
 }  // namespace
 
 extern "C" {
@@ -82,47 +78,25 @@ int32_t brt_radiance_rays_device(brt_ctx* ctx, const void* d_rays, uint32_t n_ra
     int32_t rc = caller_stream_flags_check(ctx, flags);
     if (rc == BRT_OK) rc = radiance_check(ctx, d_rays, n_rays, samples, bounces, origin_bound, d_out);
     if (rc != BRT_OK) return rc;
-    RadianceLaunch rl{};
-    uint32_t rebuilt = 0u;
-    unsigned long long counts[3] = {0u, 0u, 0u};      // (a caller's stream is not waited for: its counts stay 0)
-    if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
-        int32_t r = radiance_enqueue(ctx, dc, sc.stream, d_rays, n_rays, samples, bounces, d_out, sc.own, &rl);
-        if (r != BRT_OK || !sc.own) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_radctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
-        HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
-        return BRT_OK;
+    return ray_list_call<unsigned long long, RadianceLaunch>(ctx, n_rays, origin_bound, hip_stream, flags, &DeviceCtx::d_radctl, out_stats8,
+                                                             [&](DeviceCtx& dc, hipStream_t stream, bool counted, RadianceLaunch* rl) {
+        return radiance_enqueue(ctx, dc, stream, d_rays, n_rays, samples, bounces, d_out, counted, rl);
     });
-    if (rc == BRT_OK) radiance_stats(ctx, rl, rebuilt, counts, out_stats8);
-    return rc;
     });
 }
 
 int32_t brt_radiance_rays(brt_ctx* ctx, const void* rays, uint32_t n_rays, uint32_t samples, uint32_t bounces, float origin_bound, void* out,
                           uint64_t* out_stats8) {
     return ctx_guard(ctx, [&]() -> int32_t {
-    int32_t rc = radiance_check(ctx, rays, n_rays, samples, bounces, origin_bound, out);
+    const int32_t rc = radiance_check(ctx, rays, n_rays, samples, bounces, origin_bound, out);
     if (rc != BRT_OK) return rc;
-    RadianceLaunch rl{};
-    uint32_t rebuilt = 0u;
-    unsigned long long counts[3] = {0u, 0u, 0u};
-    if (n_rays == 0u) { radiance_stats(ctx, rl, 0u, nullptr, out_stats8); return BRT_OK; }
-    rc = with_reach(ctx, origin_bound, &rebuilt, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        const size_t bytes = (size_t)n_rays * 32u;
-        int32_t r = staged(ctx, dc, {{&dc.d_qrays, &dc.qrays_cap, bytes}, {&dc.d_qhits, &dc.qhits_cap, bytes}});
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_qrays, rays, bytes, hipMemcpyHostToDevice, dc.stream));
-        r = radiance_enqueue(ctx, dc, dc.stream, dc.d_qrays, n_rays, samples, bounces, dc.d_qhits, true, &rl);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_qhits, bytes, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(counts, dc.d_radctl, sizeof counts, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));           // (the copy out reads the staging buffer)
-        HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
-        return BRT_OK;
+    const size_t bytes = (size_t)n_rays * 32u;
+    return ray_list_call<unsigned long long, RadianceLaunch>(ctx, n_rays, origin_bound, nullptr, 0u, &DeviceCtx::d_radctl, out_stats8,
+                                                             [&](DeviceCtx& dc, hipStream_t stream, bool counted, RadianceLaunch* rl) {
+        return host_round_trip(ctx, dc, stream, {{rays, nullptr, bytes}, {nullptr, out, bytes}}, [&](char* const* d) {
+            return radiance_enqueue(ctx, dc, stream, d[0], n_rays, samples, bounces, d[1], counted, rl);
+        });
     });
-    if (rc == BRT_OK) radiance_stats(ctx, rl, rebuilt, counts, out_stats8);
-    return rc;
     });
 }
 

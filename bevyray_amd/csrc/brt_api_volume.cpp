@@ -1,8 +1,9 @@
 // brt_api_volume.cpp -- irradiance volumes (brt_volume.h, brt_volume.hip; DESIGN.md "Irradiance volumes") on the first device: a regular
 // lattice of light probes baked in one call, and lists of {position, normal} shaded from the baked records.  The bake is the light
 // probes' (brt_api_probe.cpp bake_enqueue) over probes that k_volume_probes writes; the skeleton of a bake export, streams, ordering
-// behind ev_q and the staging rule are those of every list call (brt_frame.h: bake_call, bake_call_host, with_list_call, staged,
-// list_step_run, device_aligned).  Here: the descriptor's checks, the argument packing and the host twins.
+// behind ev_q, the staging rule and the round trip of the host forms' buffers are those of every list call (brt_frame.h: bake_call,
+// bake_call_host, host_round_trip, with_list_call, staged, list_step_run, device_aligned).  Here: the descriptor's checks, the argument
+// packing and the host twins.
 #include "brt_frame.h"
 #include "brt_volume.h"
 
@@ -169,10 +170,9 @@ int32_t brt_bake_volume(brt_ctx* ctx, const void* volume48, uint32_t n_dirs, uin
     uint32_t n_probes = 0u;
     const int32_t rc = volume_bake_check(ctx, volume48, n_dirs, bounces, origin_bound, records, &v, &n_probes);
     if (rc != BRT_OK) return rc;
-    const size_t bytes = (size_t)n_probes * 128u;
-    return bake_call_host(ctx, origin_bound, bytes, {0u, records, bytes}, out_stats8,
-                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) {
-        return volume_bake_enqueue(ctx, dc, stream, v, n_probes, n_dirs, bounces, dc.d_list_io, counted, run);
+    return bake_call_host(ctx, origin_bound, {{nullptr, records, (size_t)n_probes * 128u}}, out_stats8,
+                          [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run, char* const* d) {
+        return volume_bake_enqueue(ctx, dc, stream, v, n_probes, n_dirs, bounces, d[0], counted, run);
     });
     });
 }
@@ -201,18 +201,11 @@ int32_t brt_sample_volume(brt_ctx* ctx, const void* volume48, const void* record
     if (rc == BRT_OK) rc = sample_check(ctx, n_probes, records, points, n_points, out);
     if (rc != BRT_OK || n_points == 0u) return rc;
     return with_list_call(ctx, nullptr, 0u, [&](DeviceCtx& dc, const StreamChoice&) -> int32_t {
-        // the records, the points and the samples on the device: one buffer
-        const size_t rec_bytes = (size_t)n_probes * 128u, pt_bytes = (size_t)n_points * 32u, out_bytes_ = (size_t)n_points * 16u;
-        const size_t pt_off = align256(rec_bytes), out_off = pt_off + align256(pt_bytes), bytes = out_off + out_bytes_;
-        int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, bytes}});
+        const int32_t r = host_round_trip(ctx, dc, dc.stream, {{records, nullptr, (size_t)n_probes * 128u}, {points, nullptr, (size_t)n_points * 32u},
+                                                               {nullptr, out, (size_t)n_points * 16u}}, [&](char* const* d) {
+            return volume_sample_enqueue(ctx, dc.stream, v, d[0], d[1], n_points, d[2]);
+        });
         if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipStreamWaitEvent(dc.stream, dc.ev_q, 0));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io, records, rec_bytes, hipMemcpyHostToDevice, dc.stream));
-        HIP_TRY(ctx, hipMemcpyAsync(dc.d_list_io + pt_off, points, pt_bytes, hipMemcpyHostToDevice, dc.stream));
-        r = volume_sample_enqueue(ctx, dc.stream, v, dc.d_list_io, dc.d_list_io + pt_off, n_points, dc.d_list_io + out_off);
-        if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out, dc.d_list_io + out_off, out_bytes_, hipMemcpyDeviceToHost, dc.stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, dc.stream));
         HIP_TRY(ctx, hipStreamSynchronize(dc.stream));
         return BRT_OK;
     });

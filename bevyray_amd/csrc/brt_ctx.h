@@ -131,14 +131,14 @@ struct DeviceCtx {
     float* d_uplow = nullptr;
     size_t uplow_cap = 0;
     // ray queries (brt_query.h), first device only.  Queries of the context run one behind the other (every one waits for ev_q and
-    // records it), so the batch counter, the resident -> caller map and the staging buffers of brt_query_rays have one user at a time
+    // records it), so the batch counter, the resident -> caller map and the lists of the bakes have one user at a time
     hipEvent_t ev_q = nullptr;      // end of the last query (any stream): uploads, rebuilds and the hot-order renumbering wait for it
     uint32_t* d_qctl = nullptr;     // [0..2] rays walked, hits, refused; [4] the streaming form's batch counter
     uint32_t* d_qmap = nullptr;     // resident sphere index -> the caller's, when the hot order has renumbered the spheres
     size_t qmap_cap = 0;
     uint32_t qmap_tree = 0, qmap_serial = 0;   // the tree_epoch / hot_serial d_qmap was made for (0: none)
     uint32_t hot_serial = 0;        // bumped by every renumbering of the resident spheres (apply_hot_order)
-    char* d_qrays = nullptr;        // brt_query_rays: the host batch on the device, and its results
+    char* d_qrays = nullptr;        // the probe, envmap and lightmap bakes: the rays of a chunk, and their results
     size_t qrays_cap = 0;
     char* d_qhits = nullptr;
     size_t qhits_cap = 0;
@@ -148,23 +148,19 @@ struct DeviceCtx {
     // Its users run one behind the other, ordered by ev_q like the queries (so uploads and renumberings wait for them too)
     uint32_t* d_pxbuf = nullptr;
     size_t pxbuf_cap = 0;
-    char* d_pxlist = nullptr;       // brt_render_pixels, brt_render_lens*: the host list on the device, and its results
-    size_t pxlist_cap = 0;
-    char* d_pxout = nullptr;
-    size_t pxout_cap = 0;
     // radiance queries (brt_radiance.h), first device only: 3 x u64 {walks performed, entries whose own ray hit, entries refused}, then
     // the streaming form's batch counter at word 8.  A radiance list runs behind ev_q and records it, like the ray queries and the pixel
-    // lists (so they all run one behind the other, and uploads, rebuilds and renumberings wait for them); brt_radiance_rays stages in
-    // d_qrays / d_qhits, which therefore have one user at a time
+    // lists (so they all run one behind the other, and uploads, rebuilds and renumberings wait for them)
     uint32_t* d_radctl = nullptr;
     size_t radctl_cap = 0;
     // light probes (brt_probe.h), first device only: the direction table {x, y, z, 0}, kept by n_dirs.  A bake stages its lists in
     // d_qrays / d_qhits and is ordered by ev_q like the radiance lists it launches; the table is rewritten only once every list of the
     // context has ended (brt_frame.h cached_table)
     DeviceTable probe_dirs;
-    // the device side of the host forms brt_bake_probes (probes and records), brt_bake_volume (records), brt_sample_volume (records,
-    // points and samples) and brt_bake_envmap (the chain).  Every user is synchronous on `stream` and reaches the buffer through `staged`
-    // (brt_frame.h): it grows only once every list of the context has ended, and a call has returned before the next one takes it over
+    // the device side of every export that takes host buffers of the list families (queries, radiance, bakes, volume samples, pixel and
+    // lens lists, progressive frames, the G-buffer): the caller's planes of one call, laid out by host_round_trip (brt_frame.h), and
+    // nothing else.  Every user is synchronous on `stream` and reaches the buffer through `staged`: it grows only once every list of the
+    // context has ended, and a call has returned before the next one takes it over
     char* d_list_io = nullptr;
     size_t list_io_cap = 0;
     // irradiance volumes (brt_volume.h), first device only: the probes k_volume_probes generates for a bake.  Ordered by ev_q like the

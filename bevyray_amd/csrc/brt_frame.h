@@ -322,7 +322,7 @@ inline int32_t trace_selected(brt_ctx* ctx, DeviceCtx& dc, const void* camera80,
 }
 
 // ---- what the list entry points share (brt_api_query.cpp, brt_api_radiance.cpp, brt_api_probe.cpp, brt_api_volume.cpp,
-// brt_api_envmap.cpp, brt_api_lightmap.cpp, brt_api_pixels.cpp) ----
+// brt_api_envmap.cpp, brt_api_lightmap.cpp, brt_api_pixels.cpp, brt_api_progressive.cpp, brt_api_gbuffer.cpp) ----
 inline int32_t origin_bound_check(brt_ctx* ctx, float origin_bound) {
     if (!(origin_bound >= 0.0f) || !std::isfinite(origin_bound)) return ctx_fail(ctx, BRT_ERR_INVALID_ARGUMENT, "origin_bound must be finite and >= 0");
     return BRT_OK;
@@ -344,6 +344,35 @@ inline int32_t staged(brt_ctx* ctx, DeviceCtx& dc, std::initializer_list<StagedB
         const int32_t rc = ensure(ctx, b.ptr, b.cap, b.bytes);
         if (rc != BRT_OK) return rc;
     }
+    return BRT_OK;
+}
+
+// The round trip of a host form: the caller's host planes laid out in d_list_io, each at a multiple of 256 bytes (`staged`: at least 16
+// bytes), `stream` put behind ev_q, the planes with an `in` copied to the device, body(d) -- d[i]: plane i on the device, null for an
+// absent one -- which enqueues what the device form enqueues, the planes with an `out` copied back, and ev_q recorded behind them: the
+// copies out read the buffer.  Nothing is synchronised and no count is read: that is the call's around it.  d_list_io holds nothing else.
+struct HostPlane {
+    const void* in;      // copied to the device before the body (null: not copied in)
+    void* out;           // copied back after it (null: not copied out)
+    size_t bytes;        // 0: the plane is absent
+};
+template <size_t N, class Body>
+int32_t host_round_trip(brt_ctx* ctx, DeviceCtx& dc, hipStream_t stream, const HostPlane (&planes)[N], Body&& body) {
+    size_t at[N], total = 0u;
+    for (size_t i = 0; i < N; i++) { at[i] = total; total += align256(planes[i].bytes); }
+    int32_t r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, std::max<size_t>(total, 16u)}});
+    if (r != BRT_OK) return r;
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, dc.ev_q, 0));
+    char* d[N];
+    for (size_t i = 0; i < N; i++) {
+        d[i] = planes[i].bytes ? dc.d_list_io + at[i] : nullptr;
+        if (d[i] && planes[i].in) HIP_TRY(ctx, hipMemcpyAsync(d[i], planes[i].in, planes[i].bytes, hipMemcpyHostToDevice, stream));
+    }
+    r = body(d);
+    if (r != BRT_OK) return r;
+    for (size_t i = 0; i < N; i++)
+        if (d[i] && planes[i].out) HIP_TRY(ctx, hipMemcpyAsync(planes[i].out, d[i], planes[i].bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
     return BRT_OK;
 }
 
@@ -438,21 +467,15 @@ int32_t bake_call(brt_ctx* ctx, float origin_bound, void* hip_stream, uint32_t f
     if (rc == BRT_OK) bake_stats(ctx, run, rebuilt, out_stats8);
     return rc;
 }
-// The host form: the bake on the context's own stream into d_list_io (io_bytes of it: `staged`), whose `bytes` at `offset` are then
-// copied to `host`; the copy reads the buffer, so ev_q is recorded behind it.  reached(): what the call checks once the tree is
-// settled, before anything is staged.
-struct BakeCopyOut { size_t offset; void* host; size_t bytes; };
-template <class Enqueue, class Reached = int32_t (*)()>
-int32_t bake_call_host(brt_ctx* ctx, float origin_bound, size_t io_bytes, const BakeCopyOut& out, uint64_t* out_stats8, Enqueue&& enqueue,
+// The host form: the bake on the context's own stream over the caller's planes (host_round_trip), enqueue(dc, stream, counted, &run, d)
+// with the planes' device addresses.  reached(): what the call checks once the tree is settled, before anything is staged.
+template <size_t N, class Enqueue, class Reached = int32_t (*)()>
+int32_t bake_call_host(brt_ctx* ctx, float origin_bound, const HostPlane (&planes)[N], uint64_t* out_stats8, Enqueue&& enqueue,
                        Reached reached = [] { return (int32_t)BRT_OK; }) {
     return bake_call(ctx, origin_bound, nullptr, 0u, out_stats8, [&](DeviceCtx& dc, hipStream_t stream, bool counted, BakeRun* run) -> int32_t {
-        int32_t r = reached();
-        if (r == BRT_OK) r = staged(ctx, dc, {{&dc.d_list_io, &dc.list_io_cap, io_bytes}});
-        if (r == BRT_OK) r = enqueue(dc, stream, counted, run);
+        const int32_t r = reached();
         if (r != BRT_OK) return r;
-        HIP_TRY(ctx, hipMemcpyAsync(out.host, dc.d_list_io + out.offset, out.bytes, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipEventRecord(dc.ev_q, stream));
-        return BRT_OK;
+        return host_round_trip(ctx, dc, stream, planes, [&](char* const* d) { return enqueue(dc, stream, counted, run, d); });
     });
 }
 
@@ -479,6 +502,30 @@ void list_stats8(const brt_ctx* ctx, const Count* counts3, uint32_t rebuilt, int
     out8[5] = (uint64_t)form;
     out8[6] = word6;
     out8[7] = 0u;
+}
+
+// A list of caller rays behind its argument checks, both forms (ray queries: QueryLaunch, u32 counts in d_qctl; radiance queries:
+// RadianceLaunch, u64 counts in d_radctl).  An empty list reports its stats and touches nothing; else the tree's reach (with_reach), then
+// enqueue(dc, stream, counted, &launch) on the call's stream -- the host form's is the device form's inside host_round_trip; the own
+// stream copies the three counts out and synchronises (a caller's stream is not waited for: its counts stay 0); the stats (list_stats8,
+// word 6: the workgroups of the launch).
+template <class Count, class Launch, class Enqueue>
+int32_t ray_list_call(brt_ctx* ctx, uint32_t n_rays, float origin_bound, void* hip_stream, uint32_t flags, uint32_t* DeviceCtx::*ctl,
+                      uint64_t* out_stats8, Enqueue&& enqueue) {
+    Launch l{};
+    uint32_t rebuilt = 0u;
+    Count counts[3] = {0u, 0u, 0u};
+    int32_t rc = BRT_OK;
+    if (n_rays != 0u)
+        rc = with_reach(ctx, origin_bound, &rebuilt, hip_stream, flags, [&](DeviceCtx& dc, const StreamChoice& sc) -> int32_t {
+            const int32_t r = enqueue(dc, sc.stream, sc.own, &l);
+            if (r != BRT_OK || !sc.own) return r;
+            HIP_TRY(ctx, hipMemcpyAsync(counts, dc.*ctl, sizeof counts, hipMemcpyDeviceToHost, sc.stream));
+            HIP_TRY(ctx, hipStreamSynchronize(sc.stream));
+            return BRT_OK;
+        });
+    if (rc == BRT_OK) list_stats8(ctx, counts, rebuilt, l.form, list_groups(l, l.args.n_rays), out_stats8);
+    return rc;
 }
 
 }  // namespace brt

@@ -341,7 +341,7 @@ def test_camera_beyond_the_callee_trees_reach(plugin, oracle):
 @pytest.mark.gpu
 def test_a_host_list_behind_a_held_one_grows_the_staging_buffers(oracle, cover):
     """A device-entry list of 700 is held on a caller's stream; the host entry point then stages 5 000 entries, which a new context has
-    no room for: d_pxlist and d_pxout are allocated behind the held list (whose control words the new one shares).  No host
+    no room for: the host forms' staging buffer is allocated behind the held list (whose control words the new one shares).  No host
     synchronisation between the two calls; the held list's output is read last."""
     import torch
     b, lvl, cam, win, want = cover
