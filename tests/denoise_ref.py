@@ -18,9 +18,11 @@ def strength(spp):
     return F32(1.0) if spp <= STRENGTH_SPP else np.sqrt(F32(STRENGTH_SPP) / F32(spp))
 
 
-def pixel_center_rays(oracle, cam, w, h):
+def pixel_center_rays(oracle, cam, w, h, window=None):
     """(origin (3,), unit directions (h, w, 3)) of the pixel-centre primary rays: the camera ray of tests/helpers.py:sky_color with
-    rand_square = (0, 0), i.e. no jitter."""
+    rand_square = (0, 0), i.e. no jitter.  window: the jitter term the kernels keep (camera_ray_dir_center adds (1 / window size) * 0
+    to the pixel's position): +0.0 and no bit of any ray for a finite window size, INF * 0 = NaN in every ray under a window of
+    height 0 -- every ray then misses ("a window of height 0")."""
     c = cam[0]
     aspect = F32(c["aspect"])
     cd, cu = c["direction"].astype(F32), c["up"].astype(F32)
@@ -30,14 +32,20 @@ def pixel_center_rays(oracle, cam, w, h):
     uvy = (np.arange(h, dtype=F32) + F32(0.5)) / F32(h)
     ndc_x = (uvx * F32(2.0) - F32(1.0))[None, :, None]
     ndc_y = (F32(1.0) - uvy * F32(2.0))[:, None, None]
+    if window is not None:
+        with np.errstate(all="ignore"):
+            height = F32(window[0]["height"])
+            ndc_x = ndc_x + (F32(1.0) / (height * aspect)) * F32(0.0)
+            ndc_y = ndc_y + (F32(1.0) / height) * F32(0.0)
     d = (cd + ((ndc_x * aspect) * scale) * right) + (ndc_y * scale) * cu
     ln = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])[..., None]
     return c["position"].astype(F32), (d / ln).astype(F32), scale
 
 
-def guides(oracle, buffers, cam, w, h):
-    """(h, w, 8) f32: normal.xyz, t (inf: sky), a.rgb, material id as bits (0xFFFFFFFF: sky) -- brt_debug_denoise_guides' layout."""
-    o, dirs, _ = pixel_center_rays(oracle, cam, w, h)
+def guides(oracle, buffers, cam, w, h, window=None):
+    """(h, w, 8) f32: normal.xyz, t (inf: sky), a.rgb, material id as bits (0xFFFFFFFF: sky) -- brt_debug_denoise_guides' layout.
+    window: see pixel_center_rays."""
+    o, dirs, _ = pixel_center_rays(oracle, cam, w, h, window)
     models = np.ascontiguousarray(buffers.models)
     bvh = np.ascontiguousarray(buffers.bvh)
     mats = buffers.materials
